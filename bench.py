@@ -7,6 +7,12 @@ image; it never copies a frame to the host).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config A|B|C|D|E|Chard] [--mode exact|fast]
                   [--pose garden|train|bicycle] [--rows contiguous|interleaved|balanced] [--sort ...]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the headline (metric, value, unit, ms_per_step, ...); with
+--dump-outputs it also writes the frame of the last timed step.  Everything else below -- the per-stage buckets, the
+roofline with its rocprofv3 --pmc child runs, the CPU baseline, the extras and the N > 1 checks and guarded phases --
+runs only with --full.
 
 What `value` is: N_gaussians / ms_per_step with ONE frame slot -- frames run back to back on one HIP stream, nothing
 of frame f+1 overlaps frame f -- i.e. the GPU time of a frame, which is what the reference's "Total GPU time"
@@ -100,7 +106,16 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="multi-rank rehearsal on ONE GPU: every rank uses cuda:0 and the strip gather goes "
                          "through gloo on the host (RCCL needs one GPU per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the PMC child runs, the instrumented passes (buckets_ms, roofline), "
+                         "the stream-copy probe, the CPU baseline, the extras and, with N > 1, the sharded-frame check and the "
+                         "guarded phases.  Without it a run sets up, warms up, times --steps frames and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the RGBA8 frame, as float32) to "
+                         "DIR/<name>.npy; frames above 64 MB as float32 are written as a fixed, seeded sample of pixels")
     args = ap.parse_args(argv)
+    if args.extras or args.c_abi_gather:          # they ask for blocks only a --full run has
+        args.full = True
     if args.steps <= 20 and not args.extras:      # a short run is a smoke run of the headline: seconds, not minutes
         args.no_extras = True
     return args
@@ -320,7 +335,7 @@ def pmc_traffic(args):
         return "rocprofv3 not on PATH"
     tmp = tempfile.mkdtemp(prefix="gs_pmc_", dir="/tmp")
     child = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", "3", "--warmup", "1",
-             "--no-extras", "--no-cpu-baseline", "--no-pmc", "--mode", args.mode, "--sort", args.sort,
+             "--full", "--no-extras", "--no-cpu-baseline", "--no-pmc", "--mode", args.mode, "--sort", args.sort,
              "--render-kernel", args.render_kernel] + (["--pose", args.pose] if args.pose else [])
     env = dict(os.environ, TMPDIR="/tmp")
     env.pop(LINE_ENV, None)                               # the children's lines are not this run's line
@@ -455,6 +470,68 @@ def dry_run(args, world, rank, line):
     return 0 if ok else 1
 
 
+def generate_uniform(n, width, height, mu, seed, threads, chunk=None):
+    """synth.generate(n, width, height, mu, seed) of a uniform cloud -- the same records, bit for bit -- made by a pool of
+    threads (numpy leaves the GIL inside its array loops).  Record i of synth.generate draws the splitmix64 outputs of
+    seed + (128 i + k + 1) * golden, so its rows lo .. hi are rows 0 .. hi - lo of the cloud of seed + 128 lo * golden (mod
+    2^64): every thread makes chunks of synth.generate's own size that way, and the whole cloud is then put in Morton order."""
+    import inspect
+    from concurrent.futures import ThreadPoolExecutor
+    import numpy as np
+    from vk3dgaussiansplatting_amd import synth
+    chunk = chunk or inspect.signature(synth.generate).parameters["chunk"].default
+    out = np.empty((n, synth.FLOATS_PER_GAUSSIAN), dtype=np.float32)
+    step = int(synth._DRAWS_PER_SPLAT) * int(synth._GOLDEN)
+
+    def part(lo):
+        hi = min(n, lo + chunk)
+        out[lo:hi] = synth.generate(hi - lo, width, height, mu, (seed + lo * step) % (1 << 64), morton=False, chunk=chunk)
+    with ThreadPoolExecutor(max(1, threads)) as pool:
+        list(pool.map(part, range(0, n, chunk)))
+    return np.ascontiguousarray(out[np.argsort(synth.morton_codes(out[:, 0:3]), kind="stable")])
+
+
+def generate_cloud(name, pose, threads):
+    """synth.generate_config(name, pose=pose); the uniform clouds at the generator's own camera through generate_uniform."""
+    from vk3dgaussiansplatting_amd import synth
+    cfg = dict(synth.CONFIGS[name])
+    if pose is not None or cfg.get("kind", "uniform") != "uniform" or threads < 2:
+        return synth.generate_config(name, pose=pose)
+    aos = generate_uniform(cfg["n"], cfg["width"], cfg["height"], cfg["mu"], cfg["seed"], threads)
+    cfg["camera"] = ((0.0, 0.0, 0.0), 0.0, 0.0)
+    return aos, cfg
+
+
+def host_threads(world):
+    """CPU threads this process may use for host work: its share of at most 16 CPUs."""
+    try:
+        cpus = len(os.sched_getaffinity(0))
+    except AttributeError:
+        cpus = os.cpu_count() or 1
+    return max(1, min(16, cpus) // max(1, world))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240807
+
+
+def dump_outputs(path, frame):
+    """--dump-outputs: the frame a caller of the timed path receives ([H, W, 4] RGBA8) as float32 -- whole, or, above 64 MB,
+    a fixed seeded sample of its pixels (`image_sample`, [k, 4]) with their row-major pixel indices (`image_sample_index`)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    img = frame.astype(np.float32)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(path, "image.npy"), img)
+        return {"image": list(img.shape)}
+    flat = img.reshape(-1, img.shape[-1])
+    k = (DUMP_LIMIT_BYTES // 2) // (flat.shape[1] * 4 + 8)
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[0], k, replace=False))
+    np.save(os.path.join(path, "image_sample.npy"), flat[idx])
+    np.save(os.path.join(path, "image_sample_index.npy"), idx.astype(np.float64))
+    return {"image_sample": [int(k), int(flat.shape[1])], "image_sample_index": [int(k)]}
+
+
 def cpu_baseline(aos, cfg, oracle, camera=((0.0, 0.0, 0.0), 0.0, 0.0)):
     """The oracle (a scalar C port of the same four stages, oracle/gs_oracle.c -O2) timed on this box's host cores on
     the WHOLE workload: one frame on one thread (`value`), and the threaded port (gso_frame_mt) on the CPUs this
@@ -523,7 +600,7 @@ def main():
     pmc = "not measured (--no-pmc)" if args.no_pmc else "not measured (one-GPU runs of the radix sorters only)"
     if profiled:
         pmc = "not measured (this process already runs under rocprofv3)"
-    elif world == 1 and not args.no_pmc and not args.rehearse and args.sort != "bucket":
+    elif args.full and world == 1 and not args.no_pmc and not args.rehearse and args.sort != "bucket":
         pmc = pmc_traffic(args)
         if isinstance(pmc, str):
             log(f"[bench] roofline.traffic unavailable: {pmc}")
@@ -565,7 +642,7 @@ def main():
     cfg = dict(synth.CONFIGS[args.config])
     w, h, n = cfg["width"], cfg["height"], cfg["n"]
     t0 = time.time()
-    aos, cfg_gen = synth.generate_config(args.config, pose=args.pose)
+    aos, cfg_gen = generate_cloud(args.config, args.pose, host_threads(world))
     camera = cfg_gen["camera"]
     if rank == 0:
         log(f"[bench] config {args.config}{' pose ' + args.pose if args.pose else ''}: {n} gaussians @ {w}x{h} generated in {time.time() - t0:.1f}s")
@@ -738,7 +815,7 @@ def main():
     # N > 1: the assembled frame must equal what one GPU renders alone (checked once, untimed); the single-GPU
     # render of the same frame is also timed (a few frames), so the line carries its own strong-scaling reference
     sharded_ok, one_gpu_ms, gather_ms, full = None, None, None, None
-    if world > 1:
+    if world > 1 and args.full:
         with torch.cuda.stream(ring.streams[0]):
             ring.sf.wait(0)
             owner.drawDevice(scene, ring.ptrs[0], sync=False, compact_rows=interleaved)
@@ -771,6 +848,51 @@ def main():
         ring.barrier()
 
     ms_per_step = ring.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # the frame of the last timed step: its strip ((n - 1) mod S), gathered from the ranks when the frame is sharded
+        k_last = (ring.n - 1) % ring.S
+        frame_last = ring.sf.assemble([ring.sf.strips[k_last]] if world == 1 else ring.sf.gathered[k_last])
+        dumped = dump_outputs(args.dump_outputs, frame_last.cpu().numpy())
+        log(f"[bench] the last timed step's outputs written to {args.dump_outputs}: {dumped}")
+
+    def headline(config_extra=None):
+        """The line's headline fields; config_extra = what only the instrumented passes of --full know (sort elements ...)."""
+        value = n / ms_per_step / 1000.0            # Msplats/s, whole job
+        ref = REF_MS.get(args.config) if world == 1 else None
+        return {
+            "metric": "Msplats/s + total frame ms (InitSortList/RadixSort/FindRanges/Render split)",
+            "value": round(value, 2), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": round(value / (ref[0] / ref[1] / 1000.0), 3) if ref else None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {
+                "workload": WORKLOADS[args.config] + (f", viewed from the reference's {args.pose} benchmark camera (cloud moved rigidly, "
+                                                      "stored in Morton order of the moved positions)" if args.pose else ""),
+                "camera": {"position": [float(x) for x in camera[0]], "yaw": camera[1], "pitch": camera[2]},
+                "num_gaussians": n, "width": w, "height": h, **(config_extra or {}),
+                "render_mode": args.mode, "render_kernel": args.render_kernel,
+                "sort_algorithm": args.sort, "frames_in_flight": F, "gather_strips": ring.S if world > 1 else None,
+                "parallelism": (f"tile-row shard x{world} ({args.rows} rows), RGBA8 strips gathered to rank 0 over "
+                                f"{'gloo (rehearsal on one GPU)' if args.rehearse else 'RCCL'}") if world > 1 else "single GPU",
+                "baseline_note": "vs_baseline = the reference README's total GPU frame time on an RTX 3080 Ti for the real "
+                                 "scene of this shape (BASELINE.md) over ms_per_step; ours is a synthetic cloud with the "
+                                 "same N and E, one frame slot, so both sides are GPU time per frame",
+            },
+        }
+
+    if not args.full:
+        # a plain run: the headline and nothing else (--full adds the instrumented passes, roofline, CPU baseline, extras)
+        ring.close(keep_owner=True)
+        if rank == 0:
+            line.finish(dict(headline(), full=False))
+        owner.setStream(None)
+        owner.cleanup()
+        if world > 1:
+            tdist.barrier()
+            tdist.destroy_process_group()
+        return
+
     # every slot rendered the same camera: their strips must be identical
     slots_ok = all(bool(torch.equal(ring.sf.strips[0], ring.sf.strips[k])) for k in range(1, ring.S))
     sf_main = ring.sf
@@ -1199,8 +1321,6 @@ def main():
 
     if rank == 0:
         e_total = int(sum(float(s[0]) for s in allstats))
-        value = n / ms_per_step / 1000.0            # Msplats/s, whole job
-        ref = REF_MS.get(args.config) if world == 1 else None
         # Roofline of the dominant kernel, k_scatter's depth-word passes (they carry key + payload).  `achieved` / `frac`
         # describe what HBM sees: the PMC bytes of those launches measured in this run (pmc_traffic) over the mean launch
         # duration (HIP event pair around every such launch, on its stream), or -- when no PMC measurement could be made
@@ -1364,27 +1484,8 @@ def main():
                                    + f", E = {e_rank} sort elements, T = tiles, P = passes) and the HBM bytes rocprofv3 --pmc FETCH_SIZE x2 + "
                                    "WRITE_SIZE counted for the stage's kernels per frame, each over the stage's bucket of buckets_ms (hipEvents "
                                    "at the reference's timestamp points) and over the 8 TB/s peak")
-        out = {
-            "metric": "Msplats/s + total frame ms (InitSortList/RadixSort/FindRanges/Render split)",
-            "value": round(value, 2), "unit": "Msplats/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": round(value / (ref[0] / ref[1] / 1000.0), 3) if ref else None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {
-                "workload": WORKLOADS[args.config] + (f", viewed from the reference's {args.pose} benchmark camera (cloud moved rigidly, "
-                                                      "stored in Morton order of the moved positions)" if args.pose else ""),
-                "camera": {"position": [float(x) for x in camera[0]], "yaw": camera[1], "pitch": camera[2]},
-                "num_gaussians": n, "width": w, "height": h, "sort_elements": e_total,
-                "capacity": int(info.capacity), "radix_passes": passes_full + passes_tile, "render_mode": args.mode,
-                "render_kernel": args.render_kernel,
-                "sort_algorithm": args.sort, "frames_in_flight": F, "gather_strips": ring.S if world > 1 else None,
-                "parallelism": (f"tile-row shard x{world} ({args.rows} rows), RGBA8 strips gathered to rank 0 over "
-                                f"{'gloo (rehearsal on one GPU)' if args.rehearse else 'RCCL'}") if world > 1 else "single GPU",
-                "baseline_note": "vs_baseline = the reference README's total GPU frame time on an RTX 3080 Ti for the real "
-                                 "scene of this shape (BASELINE.md) over ms_per_step; ours is a synthetic cloud with the "
-                                 "same N and E, one frame slot, so both sides are GPU time per frame",
-            },
+        out = headline({"sort_elements": e_total, "capacity": int(info.capacity), "radix_passes": passes_full + passes_tile})
+        out.update({
             "buckets_ms": {k: round(float(v), 4) for k, v in zip(
                 ["init_sort_list", "radix_sort", "find_ranges", "render", "total"], allstats[0][2:7].tolist())},
             "buckets_note": "rank 0, hipEvents at the reference's 7 timestamp points (Renderer.cpp:557-622), mean of "
@@ -1395,7 +1496,8 @@ def main():
             "host_ms": host_t,
             "frame_slots_identical": slots_ok,
             "roofline": roofline,
-        }
+            "full": True,
+        })
         if world > 1:
             out["world_size"] = tdist.get_world_size()
             out["backend"] = tdist.get_backend()     # "nccl" = RCCL over xGMI; "gloo" only under --rehearse

@@ -123,3 +123,35 @@ def test_line_file_of_a_supervised_run_is_not_shared_with_profiler_children():
     src = open(BENCH).read()
     body = src[src.index("def pmc_traffic("):src.index("def all_ranks_ok(")]
     assert re.search(r"env\.pop\(LINE_ENV", body)
+
+
+def test_threaded_cloud_is_the_generators_cloud():
+    """bench.generate_uniform (the headline cloud on a pool of threads) against synth.generate: every record bit for bit,
+    over chunks that start anywhere in the splitmix64 streams."""
+    import numpy as np
+    import bench
+    from vk3dgaussiansplatting_amd import synth
+    a = bench.generate_uniform(10_000, 640, 360, -3.48486, 20240807, threads=4, chunk=3_000)
+    b = synth.generate(10_000, 640, 360, -3.48486, 20240807, chunk=3_000)
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_dumped_outputs(tmp_path):
+    """--dump-outputs: a frame that fits 64 MB as float32 whole; a larger one (4K) as a fixed seeded sample of pixels."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    small = rng.integers(0, 256, (1080, 1920, 4), dtype=np.uint8)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert np.array_equal(np.load(tmp_path / "s" / "image.npy"), small.astype(np.float32))
+    big = rng.integers(0, 256, (2160, 3840, 4), dtype=np.uint8)
+    for d in ("b1", "b2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "b1"))
+    assert files == ["image_sample.npy", "image_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b1" / f) for f in files) <= 64 << 20
+    px, idx = (np.load(tmp_path / "b1" / f) for f in files)
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(np.unique(idx)) == len(idx) == len(px)
+    assert np.array_equal(px, big.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b1" / f), np.load(tmp_path / "b2" / f))

@@ -9,7 +9,7 @@ for c in B C Chard D; do
 done
 cut -c1-140 $o/probe.txt
 for lib in "" build_variants/lib_nont.so; do
-  GS_LIB_OVERRIDE=${lib:+$PWD/$lib} timeout -k 10 500 python bench.py --config E --steps 100 --warmup 10 --no-extras --no-pmc --no-cpu-baseline > $o/bench_E_${lib:+nont}.json 2> $o/bench_E_${lib:+nont}.err; echo "E ${lib:-default} rc $?"
+  GS_LIB_OVERRIDE=${lib:+$PWD/$lib} timeout -k 10 500 python bench.py --full --config E --steps 100 --warmup 10 --no-extras --no-pmc --no-cpu-baseline > $o/bench_E_${lib:+nont}.json 2> $o/bench_E_${lib:+nont}.err; echo "E ${lib:-default} rc $?"
 done
 python - <<'PY'
 import json, glob

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?run this on the GPU box}
 o=gpurun_out/pose_sweep; rm -rf $o; mkdir -p $o
 for cfg in C Chard; do for pose in none garden train bicycle; do
   pa=""; [ $pose != none ] && pa="--pose $pose"
-  timeout -k 10 300 python bench.py --config $cfg $pa --steps 300 --warmup 30 --no-extras --no-cpu-baseline --no-pmc > $o/${cfg}_$pose.json 2> $o/${cfg}_$pose.err || { echo "FAIL $cfg $pose"; tail -3 $o/${cfg}_$pose.err; }
+  timeout -k 10 300 python bench.py --full --config $cfg $pa --steps 300 --warmup 30 --no-extras --no-cpu-baseline --no-pmc > $o/${cfg}_$pose.json 2> $o/${cfg}_$pose.err || { echo "FAIL $cfg $pose"; tail -3 $o/${cfg}_$pose.err; }
 done; done
 python - <<'PY'
 import json

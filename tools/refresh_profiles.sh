@@ -44,11 +44,11 @@ if [ "${1:-}" = "--radix8" ]; then
   cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?run this on the GPU box (gpurun sets GRAFT_REPO_ROOT)}"
   out=gpurun_out/refresh8; mkdir -p $out
   for k in radix8 radix8_splat_first; do
-    timeout -k 10 400 python bench.py --sort $k --no-cpu-baseline > $out/bench_C_$k.json 2> $out/bench_C_$k.err || { echo "FAIL bench C $k"; tail -5 $out/bench_C_$k.err; exit 1; }
-    timeout -k 10 400 python bench.py --config D --sort $k --no-cpu-baseline --no-pmc > $out/bench_D_$k.json 2> $out/bench_D_$k.err || echo "FAIL bench D $k"
+    timeout -k 10 400 python bench.py --full --sort $k --no-cpu-baseline > $out/bench_C_$k.json 2> $out/bench_C_$k.err || { echo "FAIL bench C $k"; tail -5 $out/bench_C_$k.err; exit 1; }
+    timeout -k 10 400 python bench.py --full --config D --sort $k --no-cpu-baseline --no-pmc > $out/bench_D_$k.json 2> $out/bench_D_$k.err || echo "FAIL bench D $k"
   done
   for k in radix4 radix8 radix8_splat_first; do
-    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_$k -o p -- python bench.py --sort $k --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_${k}_bench.json 2> $out/kstats_$k.err || { echo "FAIL kstats $k"; continue; }
+    timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_$k -o p -- python bench.py --full --sort $k --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_${k}_bench.json 2> $out/kstats_$k.err || { echo "FAIL kstats $k"; continue; }
     python tools/kstats.py "$(find $out/kstats_$k -name p_kernel_stats.csv | head -1)" > $out/kstats_$k.txt
   done
   python tools/pass_times.py "$(find $out/kstats_radix4 -name p_kernel_trace.csv | head -1)" > $out/passes_radix4.txt
@@ -70,15 +70,15 @@ if [ "${1:-}" = "--radix8" ]; then
 fi
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?run this on the GPU box (gpurun sets GRAFT_REPO_ROOT)}"
 out=gpurun_out/refresh; mkdir -p $out
-timeout -k 10 500 python bench.py --c-abi-gather > $out/bench_C.json 2> $out/bench_C.err || { echo "bench C failed"; tail -5 $out/bench_C.err; exit 1; }
-for c in A B D Chard E; do timeout -k 10 500 python bench.py --config $c > $out/bench_$c.json 2> $out/bench_$c.err || echo "FAIL bench $c"; done
-timeout -k 10 400 python bench.py --sort splat_first --no-cpu-baseline > $out/bench_C_sf.json 2> $out/bench_C_sf.err || echo "FAIL bench splat_first"
+timeout -k 10 500 python bench.py --full --c-abi-gather > $out/bench_C.json 2> $out/bench_C.err || { echo "bench C failed"; tail -5 $out/bench_C.err; exit 1; }
+for c in A B D Chard E; do timeout -k 10 500 python bench.py --full --config $c > $out/bench_$c.json 2> $out/bench_$c.err || echo "FAIL bench $c"; done
+timeout -k 10 400 python bench.py --full --sort splat_first --no-cpu-baseline > $out/bench_C_sf.json 2> $out/bench_C_sf.err || echo "FAIL bench splat_first"
 # the profiled runs measure nothing themselves (--no-pmc: no nested rocprofv3 children)
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats -o p -- python bench.py --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_bench.json 2> $out/kstats.err \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats -o p -- python bench.py --full --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_bench.json 2> $out/kstats.err \
   && python tools/kstats.py "$(find $out/kstats -name p_kernel_stats.csv | head -1)" > $out/kstats.txt
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_sf -o p -- python bench.py --sort splat_first --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_sf_bench.json 2> $out/kstats_sf.err \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_sf -o p -- python bench.py --full --sort splat_first --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_sf_bench.json 2> $out/kstats_sf.err \
   && python tools/kstats.py "$(find $out/kstats_sf -name p_kernel_stats.csv | head -1)" > $out/kstats_sf.txt
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_hard -o p -- python bench.py --config Chard --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_hard_bench.json 2> $out/kstats_hard.err \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kstats_hard -o p -- python bench.py --full --config Chard --steps 200 --warmup 20 --no-extras --no-cpu-baseline --no-pmc > $out/kstats_hard_bench.json 2> $out/kstats_hard.err \
   && python tools/kstats.py "$(find $out/kstats_hard -name p_kernel_stats.csv | head -1)" > $out/kstats_hard.txt
 EXTRA_ARGS=--no-pmc tools/pmc_frame.sh > $out/pmc_frame.txt 2>&1 && cp gpurun_out/pmc_frame/traffic.json $out/traffic.json
 EXTRA_ARGS=--no-pmc tools/pmc_sq.sh > $out/pmc_sq.txt 2>&1

@@ -7,10 +7,10 @@
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 o=gpurun_out/rehearse_abort; rm -rf $o; mkdir -p $o
 for r in 0 1; do
-  GS_BENCH_ABORT_IN_PHASES=$r timeout -k 10 400 python bench.py --gpus 2 --rehearse --steps 30 --warmup 5 > $o/abort_rank$r.json 2> $o/abort_rank$r.err; echo "own launcher, rank $r aborts: rc $?"
-  GS_BENCH_ABORT_IN_PHASES=$r timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29610 + r)) bench.py --gpus 2 --rehearse --steps 30 --warmup 5 > $o/abort_rank${r}_torchrun.json 2> $o/abort_rank${r}_torchrun.err; echo "foreign launcher, rank $r aborts: rc $?"
+  GS_BENCH_ABORT_IN_PHASES=$r timeout -k 10 400 python bench.py --full --gpus 2 --rehearse --steps 30 --warmup 5 > $o/abort_rank$r.json 2> $o/abort_rank$r.err; echo "own launcher, rank $r aborts: rc $?"
+  GS_BENCH_ABORT_IN_PHASES=$r timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29610 + r)) bench.py --full --gpus 2 --rehearse --steps 30 --warmup 5 > $o/abort_rank${r}_torchrun.json 2> $o/abort_rank${r}_torchrun.err; echo "foreign launcher, rank $r aborts: rc $?"
 done
-GS_BENCH_ABORT_IN_PHASES=0 timeout -k 10 400 python bench.py --steps 30 --warmup 5 --no-pmc > $o/abort_one_gpu.json 2> $o/abort_one_gpu.err; echo "one GPU, abort in the first extra: rc $?"
+GS_BENCH_ABORT_IN_PHASES=0 timeout -k 10 400 python bench.py --full --steps 30 --warmup 5 --no-pmc > $o/abort_one_gpu.json 2> $o/abort_one_gpu.err; echo "one GPU, abort in the first extra: rc $?"
 python - <<'PY'
 import json
 for f in ("abort_rank0", "abort_rank0_torchrun", "abort_rank1", "abort_rank1_torchrun", "abort_one_gpu"):

@@ -4,4 +4,4 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 o=gpurun_out/r04_inter; mkdir -p $o
 make -C tools/mock_rccl > /dev/null
 export GS_RCCL_LIBRARY=$PWD/tools/mock_rccl/librccl.so.1 MOCK_RCCL_DIR=/tmp
-for g in 2 4; do timeout -k 10 400 python bench.py --gpus $g --rehearse --steps 60 --warmup 10 > $o/c_$g.json 2> $o/c_$g.err; echo "rc $?"; done
+for g in 2 4; do timeout -k 10 400 python bench.py --full --gpus $g --rehearse --steps 60 --warmup 10 > $o/c_$g.json 2> $o/c_$g.err; echo "rc $?"; done

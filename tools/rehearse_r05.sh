@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 o=gpurun_out/rehearse_r05; rm -rf $o; mkdir -p $o
 make -C tools/mock_rccl > /dev/null
 export GS_RCCL_LIBRARY=$PWD/tools/mock_rccl/librccl.so.1 MOCK_RCCL_DIR=/tmp
-run() { tag=$1; shift; timeout -k 10 500 python bench.py "$@" --rehearse --steps 70 --warmup 5 > $o/$tag.json 2> $o/$tag.err; echo "$tag rc $?"; }
+run() { tag=$1; shift; timeout -k 10 500 python bench.py --full "$@" --rehearse --steps 70 --warmup 5 > $o/$tag.json 2> $o/$tag.err; echo "$tag rc $?"; }
 run contiguous_2 --gpus 2
 run contiguous_4 --gpus 4
 run interleaved_3 --gpus 3 --rows interleaved

@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}"
 o=gpurun_out/r04_inter; mkdir -p $o
 make -C tools/mock_rccl > /dev/null
 export GS_RCCL_LIBRARY=$PWD/tools/mock_rccl/librccl.so.1 MOCK_RCCL_DIR=/tmp
-for g in 2 3; do timeout -k 10 400 python bench.py --gpus $g --rehearse --rows interleaved --steps 30 --warmup 5 > $o/r_$g.json 2> $o/r_$g.err; echo "rc $?"; done
-timeout -k 10 400 python bench.py --gpus 4 --rehearse --steps 30 --warmup 5 > $o/r_4.json 2> $o/r_4.err; echo "rc $?"
+for g in 2 3; do timeout -k 10 400 python bench.py --full --gpus $g --rehearse --rows interleaved --steps 30 --warmup 5 > $o/r_$g.json 2> $o/r_$g.err; echo "rc $?"; done
+timeout -k 10 400 python bench.py --full --gpus 4 --rehearse --steps 30 --warmup 5 > $o/r_4.json 2> $o/r_4.err; echo "rc $?"
 python - <<'PY'
 import json
 for g in (2, 3, 4):
