@@ -63,7 +63,9 @@ extern "C" {
 
 /* render arithmetic */
 #define GS_RENDER_EXACT 0u      /* bit-identical to the CPU oracle (no contraction, pinned exp) */
-#define GS_RENDER_FAST 1u       /* fused multiply-adds + hardware exp2; <= 1 step per 8-bit channel */
+#define GS_RENDER_FAST 1u       /* fused multiply-adds + hardware exp2; <= 1 step per 8-bit channel, infinite colours
+                                   included (a lane that skips an entry leaves its colour untouched); the same pixels
+                                   in every launch shape */
 
 typedef struct gs_ctx gs_ctx;
 

@@ -72,8 +72,15 @@ def assert_frame_equals_oracle(r, img, ref, exact_pixels=True):
     if exact_pixels:
         assert np.array_equal(img, ref["image"])
     else:
-        d = np.abs(img.astype(np.int16) - ref["image"].astype(np.int16))
-        assert d.max() <= 1, f"max channel difference {d.max()} > 1 step"     # north_star tolerance
+        assert_within_one_step(img, ref["image"])
+
+
+def assert_within_one_step(img, ref_img, what=""):
+    """GS_RENDER_FAST's contract (north_star tolerance): every channel of every pixel within one 8-bit step -- no fraction
+    of channels, no wider bound.  A failure names the pixels (y, x) that are further off."""
+    d = np.abs(img.astype(np.int16) - ref_img.astype(np.int16))
+    bad = np.argwhere(d.max(axis=-1) > 1)
+    assert bad.size == 0, f"{what} max channel difference {d.max()} > 1 step at {len(bad)} pixels (y, x): {bad[:8].tolist()}"
 
 
 @pytest.mark.parametrize("w,h", [(320, 180), (250, 130), (64, 48), (1, 1), (17, 33)])
@@ -132,7 +139,8 @@ def test_frame_does_not_depend_on_stale_lds(pattern):
     """LDS is not cleared between workgroups: a kernel that reads a slot it never wrote finds what its previous tenant
     left there -- usually a plausible float of the same kernel, which hides the bug (round 4's blend loop multiplied
     the unused half of a batch's last pair by a zero weight: fine until that half held a NaN).  tools/probe fills the
-    LDS of every CU with NaNs / all ones / infinities; then the golden frame, all launch shapes and sorters."""
+    LDS of every CU with NaNs / all ones / infinities; then the golden frame, all launch shapes and sorters.  GS_RENDER_FAST
+    in every launch shape: the frame a context drew before its poisoning, bit for bit, after each."""
     import sys
     from conftest import ROOT
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -141,13 +149,21 @@ def test_frame_does_not_depend_on_stale_lds(pattern):
     g = np.load(os.path.join(GOLDEN, "small_scene.npz"))
     w, h = int(g["width"]), int(g["height"])
     sc = _scene_from_matrices(g["aos"], g["view"], g["proj"], g["cam_pos"], w, h)
-    for kernel in (gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_KERNEL_WAVE_4PX):
+    for kernel in (gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_KERNEL_WAVE_2PX,
+                   gs.GS_RENDER_KERNEL_WAVE_4PX):
         for sort in ALL_SORTS:
             r = make_renderer(sc, w, h, sort=sort, kernel=kernel)
             for _ in range(3):
                 assert P.gs_lds_poison(r._ctx.handle, pattern) == 0
                 assert np.array_equal(r.draw(sc), g["image_mode0"]), (kernel, sort)
             r.cleanup()
+        r = make_renderer(sc, w, h, mode=gs.GS_RENDER_FAST, kernel=kernel)
+        clean = r.draw(sc).copy()
+        assert_within_one_step(clean, g["image_mode0"], f"fast, kernel {kernel}:")
+        for _ in range(3):
+            assert P.gs_lds_poison(r._ctx.handle, pattern) == 0
+            assert np.array_equal(r.draw(sc), clean), ("fast", kernel)
+        r.cleanup()
 
 
 def test_common_glsl_cross_check_extreme():
@@ -846,46 +862,65 @@ def test_extreme_but_finite_inputs(oracle_mod):
         r.cleanup()
 
 
-@pytest.mark.parametrize("kernel", [gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_2PX,
-                                    gs.GS_RENDER_KERNEL_WAVE_1PX])
-def test_exponent_range_of_the_pinned_exp(oracle_mod, kernel):
-    """The blend loop evaluates the pinned exp in a cheaper form than oracle/gs_oracle.c's gso_exp (one max instead of
-    two clamps, round-to-nearest by a magic add, ldexp as an integer add to the exponent field): same bits wherever the
-    result is used.  Opacities far outside [0, 1] push that claim to its edges -- 1e30 keeps lanes live down to f = -74.6
-    (n = -108 in the exponent add), a negative opacity makes the skip threshold NaN so that EVERY f <= 0 is live,
-    including exponents of -1e10 that only the lower clamp keeps finite -- and the frame must still be the oracle's."""
+RENDER_SHAPES = (gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_KERNEL_WAVE_2PX, gs.GS_RENDER_KERNEL_WAVE_4PX,
+                 gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WORKGROUP_8X8)
+
+
+def _exponent_range_scene():
+    """Opacities far outside [0, 1] (test_exponent_range_of_the_pinned_exp)."""
     w, h = 208, 120
     aos = synth.generate(2500, w, h, -2.2, seed=41)
     rng = np.random.default_rng(3)
     aos[:, 15] = rng.choice(np.float32([0.9, 1e30, -0.5, 300.0, 3e-3, 1e-30]), aos.shape[0], p=[0.6, 0.01, 0.3, 0.01, 0.04, 0.04])
     aos[::5, 4:7] *= np.float32(0.02)                      # tiny footprints: exponents of -1e4 .. -1e10 a pixel away
-    sc = make_scene(aos, w, h, pos=(0.2, -0.1, -1.0), yaw=0.1, pitch=-0.05)
-    _, ref = oracle_run(oracle_mod, sc, w, h)
-    assert np.isfinite(ref["stage1"]["color"]).all()
-    r = make_renderer(sc, w, h, kernel=kernel)
-    img = r.draw(sc)
-    assert_frame_equals_oracle(r, img, ref)
-    r.cleanup()
+    return make_scene(aos, w, h, pos=(0.2, -0.1, -1.0), yaw=0.1, pitch=-0.05), w, h
 
 
-@pytest.mark.parametrize("kernel", [gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_2PX])
-def test_infinite_colours_take_the_select_form(oracle_mod, kernel):
-    """The blend loop adds `0 * colour` on lanes that skip an entry -- the same bits as not adding when the colour is
-    finite.  SH coefficients near FLT_MAX make some splats' colour +inf (no NaN): a batch that stages such an entry must
-    fall back to the select form, where a skipping lane's colour is not touched (0 * inf would be NaN): the frame stays
-    the oracle's."""
+def _infinite_colour_scene():
+    """Some splats' colour +inf, none NaN (test_infinite_colours_take_the_select_form)."""
     w, h = 208, 120
     aos = synth.generate(2500, w, h, -2.2, seed=43)
     for i in (0, 2, 6, 12):                                 # dc and three bands whose basis is positive in front of the camera
         aos[::17, 12 + 4 * i:15 + 4 * i] = np.float32(3.4e38)
-    sc = make_scene(aos, w, h, pos=(0.2, -0.1, -1.0), yaw=0.1, pitch=-0.05)
+    return make_scene(aos, w, h, pos=(0.2, -0.1, -1.0), yaw=0.1, pitch=-0.05), w, h
+
+
+@pytest.mark.parametrize("kernel", [gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_2PX,
+                                    gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_KERNEL_WAVE_4PX, gs.GS_RENDER_KERNEL_WORKGROUP_8X8])
+def test_exponent_range_of_the_pinned_exp(oracle_mod, kernel):
+    """The blend loop evaluates the pinned exp in a cheaper form than oracle/gs_oracle.c's gso_exp (one max instead of
+    two clamps, round-to-nearest by a magic add, ldexp as an integer add to the exponent field): same bits wherever the
+    result is used.  Opacities far outside [0, 1] push that claim to its edges -- 1e30 keeps lanes live down to f = -74.6
+    (n = -108 in the exponent add), a negative opacity makes the skip threshold NaN so that EVERY f <= 0 is live,
+    including exponents of -1e10 that only the lower clamp keeps finite -- and the frame must still be the oracle's.
+    GS_RENDER_FAST (hardware exp2) on the same scene: keys, ranges and counters exact, every channel within one step."""
+    sc, w, h = _exponent_range_scene()
+    _, ref = oracle_run(oracle_mod, sc, w, h)
+    assert np.isfinite(ref["stage1"]["color"]).all()
+    for mode in (gs.GS_RENDER_EXACT, gs.GS_RENDER_FAST):
+        r = make_renderer(sc, w, h, mode=mode, kernel=kernel)
+        img = r.draw(sc)
+        assert_frame_equals_oracle(r, img, ref, exact_pixels=(mode == gs.GS_RENDER_EXACT))
+        r.cleanup()
+
+
+@pytest.mark.parametrize("kernel", [gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WORKGROUP, gs.GS_RENDER_KERNEL_WAVE_2PX,
+                                    gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_KERNEL_WAVE_4PX, gs.GS_RENDER_KERNEL_WORKGROUP_8X8])
+def test_infinite_colours_take_the_select_form(oracle_mod, kernel):
+    """The blend loop adds `0 * colour` on lanes that skip an entry -- the same bits as not adding when the colour is
+    finite.  SH coefficients near FLT_MAX make some splats' colour +inf (no NaN): a batch that stages such an entry must
+    fall back to the select form, where a skipping lane's colour is not touched (0 * inf would be NaN, stored as 0): the
+    frame stays the oracle's -- bit for bit in GS_RENDER_EXACT, within one step in GS_RENDER_FAST, in every launch shape
+    (WAVE_4PX's exact blend is a packed path of its own)."""
+    sc, w, h = _infinite_colour_scene()
     _, ref = oracle_run(oracle_mod, sc, w, h)
     col = ref["stage1"]["color"]
     assert np.isinf(col).sum() > 20 and not np.isnan(col).any()
-    r = make_renderer(sc, w, h, kernel=kernel)
-    img = r.draw(sc)
-    assert_frame_equals_oracle(r, img, ref)
-    r.cleanup()
+    for mode in (gs.GS_RENDER_EXACT, gs.GS_RENDER_FAST):
+        r = make_renderer(sc, w, h, mode=mode, kernel=kernel)
+        img = r.draw(sc)
+        assert_frame_equals_oracle(r, img, ref, exact_pixels=(mode == gs.GS_RENDER_EXACT))
+        r.cleanup()
 
 
 def test_c_abi_call_order_status_codes(small_cloud):
@@ -1420,6 +1455,97 @@ def test_tile_dispatch_order_does_not_change_pixels(oracle_mod, kernel):
         for row in range(1, 12, 3):
             assert np.array_equal(img[row * 16:min(row * 16 + 16, h)], ref["image"][row * 16:min(row * 16 + 16, h)])
         r.cleanup()
+
+
+def _fast_shape_scene(name):
+    if name == "ragged":                                    # test_tile_dispatch_order_does_not_change_pixels' cloud
+        w, h = 333, 190
+        aos = synth.generate(6000, w, h, -3.0, seed=23)
+        aos[:40, 4:7] *= 30.0
+        return make_scene(aos, w, h), w, h
+    if name == "dense":                                     # tiles that saturate (test_every_render_launch_shape_is_bit_exact)
+        w, h = 160, 96
+        return make_scene(synth.generate(20000, w, h, -1.6, seed=29), w, h), w, h
+    if name == "extreme":
+        from conftest import extreme_cloud
+        w, h = 200, 120
+        return make_scene(extreme_cloud(4000, 500, w, h), w, h), w, h
+    return {"infinite_colours": _infinite_colour_scene, "exponent_range": _exponent_range_scene}[name]()
+
+
+@pytest.mark.parametrize("scene", ["ragged", "dense", "extreme", "infinite_colours", "exponent_range"])
+def test_fast_frames_identical_across_launch_shapes(oracle_mod, scene):
+    """GS_RENDER_FAST evaluates the same expression sequence per pixel in every launch shape -- the same fused f, the same
+    exp2(f log2 e), the same fma blend and transmittance update -- and stage_splat's margin keeps each wave's rectangle
+    cull unobservable for FAST's error as well.  So its frame is bit-identical across the five shapes and both tile
+    orders (and within one step of the oracle); a contiguous band, and interleaved rows written in real rows or packed,
+    reproduce the full frame's rows.  A difference is a bug in staging, LDS slots, lane mapping or the store."""
+    import torch
+    sc, w, h = _fast_shape_scene(scene)
+    _, ref = oracle_run(oracle_mod, sc, w, h)
+    gh = (h + 15) // 16
+    px_rows = lambda rows: np.concatenate([np.arange(t * 16, min(t * 16 + 16, h)) for t in rows])
+    band = range(1, gh - 1)
+    inter = list(range((gh - 1) % 3, gh, 3))                # every third tile row, the partial last one included
+    dev = torch.device("cuda:0")
+    full = None
+    for kernel in RENDER_SHAPES:
+        for order in (gs.GS_TILE_ORDER_LONGEST_FIRST, gs.GS_TILE_ORDER_RASTER):
+            what = f"kernel {kernel}, order {order}:"
+            r = make_renderer(sc, w, h, mode=gs.GS_RENDER_FAST, kernel=kernel, order=order)
+            img = r.draw(sc).copy()
+            if full is None:
+                assert_frame_equals_oracle(r, img, ref, exact_pixels=False)
+                full = img
+            assert np.array_equal(img, full), f"{what} {np.argwhere((img != full).any(axis=-1))[:8].tolist()}"
+            r.setTileRows(band.start, band.stop)
+            assert np.array_equal(r.draw(sc)[px_rows(band)], full[px_rows(band)]), what
+            r.setTileRowsInterleaved(inter[0], 3, compact_output=False)
+            frame = torch.zeros((h, w, 4), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()                        # the fill runs on torch's stream, the frame on the context's
+            r.drawDevice(sc, frame.data_ptr())
+            frame = frame.cpu().numpy()
+            assert np.array_equal(frame[px_rows(inter)], full[px_rows(inter)]), what
+            assert not np.delete(frame, px_rows(inter), axis=0).any(), what      # nothing outside the owned rows
+            r.setTileRowsInterleaved(inter[0], 3, compact_output=True)
+            strip = torch.zeros((len(inter) * 16, w, 4), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            r.drawDevice(sc, strip.data_ptr())
+            strip = strip.cpu().numpy()
+            assert np.array_equal(strip[:len(px_rows(inter))], full[px_rows(inter)]), what   # owned rows packed
+            assert not strip[len(px_rows(inter)):].any(), what
+            r.cleanup()
+
+
+@pytest.mark.parametrize("scene", ["small", "small_sh1", "small_sh2", "dense", "extreme"])
+def test_fast_mode_on_the_parity_envelope_scenes(scene):
+    """GS_RENDER_FAST on test_parity_envelope's scenes (tests/golden/ref_envelope.npz; no oracle code runs): the exact frame
+    hashes to the contract's dump; the fast one differs only in the blend, so its depth keys, tile boxes and emit flags
+    hash the same and every channel is within one step of the exact frame.  The fixture shows the fused and the
+    exp2(x log2 e) evaluations of the reference's own shader text within one step on these scenes -- the extreme cloud and
+    SH modes 1 and 2 included: the evidence behind FAST's bound."""
+    import hashlib
+    me = _golden_script("make_envelope")
+    z = np.load(os.path.join(GOLDEN, "ref_envelope.npz"))
+    inputs = dict(me.scenes(small_only=True))[scene]
+    aos, view, proj, pos, w, h = inputs[:6]
+    sc = _scene_from_matrices(aos, view, proj, pos, w, h)
+    sc.camera.setShMode(inputs[6] if len(inputs) > 6 else 0)
+    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+    contract = list(z[f"{scene}_contract_sha256"])
+    frames = []
+    for mode in (gs.GS_RENDER_EXACT, gs.GS_RENDER_FAST):
+        r = make_renderer(sc, w, h, mode=mode)
+        img = r.draw(sc).copy()
+        em, key, box = me.per_splat(_emitted_list(r, sc), aos.shape[0], (w + 15) // 16)
+        r.cleanup()
+        hashes = [sha(img), sha(key), sha(box), sha(em)]
+        if mode == gs.GS_RENDER_EXACT:
+            assert hashes == contract
+        else:
+            assert hashes[1:] == contract[1:]                # FAST touches the blend only
+        frames.append(img)
+    assert_within_one_step(frames[1], frames[0], f"{scene}:")
 
 
 def test_zero_determinant_splats(oracle_mod):

@@ -396,10 +396,10 @@ __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
                     col[k][1] = act ? col[k][1] + wgt * g1.z : col[k][1];
                     col[k][2] = act ? col[k][2] + wgt * g1.w : col[k][2];
                 } else {
-                    const float w0 = act ? wgt : 0.0f;
-                    col[k][0] = __builtin_fmaf(w0, g1.y, col[k][0]);
-                    col[k][1] = __builtin_fmaf(w0, g1.z, col[k][1]);
-                    col[k][2] = __builtin_fmaf(w0, g1.w, col[k][2]);
+                    // select form: a skipping lane's colour is not touched (0 * inf would be NaN, stored as 0)
+                    col[k][0] = act ? __builtin_fmaf(wgt, g1.y, col[k][0]) : col[k][0];
+                    col[k][1] = act ? __builtin_fmaf(wgt, g1.z, col[k][1]) : col[k][1];
+                    col[k][2] = act ? __builtin_fmaf(wgt, g1.w, col[k][2]) : col[k][2];
                 }
                 const float next_t = T[k] * (1.0f - alpha);            // :133
                 const bool fin = act && next_t < 0.0001f;              // :136-140, colour already added
@@ -464,11 +464,15 @@ __device__ __forceinline__ void blend_entry(uint64_t need, float alpha, float cr
                                             float& col2, float& T, uint64_t& done) {
     const uint64_t act = need & ~mask_of(alpha < 1.0f / 255.0f);      // :127
     const float wgt = T * alpha;                                       // :131
-    if constexpr (!EXACT) {
+    if constexpr (!EXACT && FINITE) {
         const float w0 = sel(act, wgt, 0.0f);
         col0 = __builtin_fmaf(w0, cr, col0);
         col1 = __builtin_fmaf(w0, cg, col1);
         col2 = __builtin_fmaf(w0, cb, col2);
+    } else if constexpr (!EXACT) {
+        col0 = sel(act, __builtin_fmaf(wgt, cr, col0), col0);
+        col1 = sel(act, __builtin_fmaf(wgt, cg, col1), col1);
+        col2 = sel(act, __builtin_fmaf(wgt, cb, col2), col2);
     } else if constexpr (FINITE) {
         const float w0 = sel(act, wgt, 0.0f);
         col0 = col0 + w0 * cr;
