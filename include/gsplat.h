@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 5   /* 5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
+#define GS_API_VERSION 6   /* 6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
                               gs_runtime_versions(), gs_dist_* / gs_gather_strips; 4: GS_ROWS_BALANCED + gs_dist_rebalance /
                               gs_dist_bands, gs_render_sharded_async / gs_sharded_frame / gs_sharded_read (two sharded
                               frames in flight, the assembled frame left in HBM), GS_BUF_COLOR for every non-culled splat */
@@ -358,6 +358,41 @@ int gs_get_host_timings(const gs_ctx* ctx, gs_host_timings* out);
 /* No reference counterpart (its buffers are only visible in a GPU debugger): copies one device
  * buffer of the last frame to dst; bytes must not exceed the buffer's size. */
 int gs_debug_read(gs_ctx* ctx, int which, void* dst, size_t bytes);
+
+/* Optional per-pixel outputs of a frame (no reference counterpart: RenderGaussians.comp:147-151 stores vec4(color, 1) and
+ * nothing else).  A per-context mask, empty by default; with it empty every frame is exactly what it is without it.
+ *   GS_OUTPUT_RGBA32F  float[H][W][4]: r, g, b = the pixel's accumulated colour sum_i T_i * alpha_i * c_i BEFORE the clamp
+ *                      (premultiplied); a = 1 - T_end, T_end = the transmittance after the last entry whose colour was added
+ *                      -- for a pixel that ends on the early-out of :136-140 (colour added, then break at nextT < 1e-4)
+ *                      that is the nextT of the entry, so colour and alpha describe the same entries.  A pixel nothing
+ *                      contributes to: (0, 0, 0, 0).
+ *   GS_OUTPUT_DEPTH    float[H][W]: sum_i T_i * alpha_i * z_i, z_i = -viewSpacePos.z of the splat (viewMat * vec4(pos, 1), the
+ *                      value getDepthKey quantises, InitSortList.comp:70-80: positive in front of the camera), blended
+ *                      exactly like a fourth colour channel -- same weights, same entries, same early-out.  The expected
+ *                      depth is depth / a, where a > 0 (the caller's division).
+ * Both buffers are addressed like the RGBA8 image of the frame: row-major, top row first; a tile-row band
+ * (gs_set_tile_rows*) writes the same rows as the image, compact rows under gs_set_tile_rows_interleaved(.., compact_output
+ * = 1) with gs_render_device*; rows the context does not own are left untouched (zero after gs_set_outputs or
+ * gs_set_resolution).  The RGBA8 frame is byte-identical with or without outputs, for every sorter, render mode and launch
+ * shape; quantising the float colour with the UNORM expression floor(clamp(c, 0, 1) * 255 + 0.5) gives its bytes.
+ * GS_RENDER_EXACT: alpha and depth use the colour's operation order (d = d + (T * alpha) * z, no contraction, 1 - T at
+ * the end): bit-reproducible against a CPU restatement.  GS_RENDER_FAST may contract them, like its colour.
+ *   gs_set_outputs   : mask = 0 (RGBA8 only) or any OR of GS_OUTPUT_*; waits for the context's stream, (re)allocates the
+ *                      buffers (again at every gs_set_resolution).  GS_ERR_INVALID for unknown bits.
+ *   gs_read_output   : which = one enabled GS_OUTPUT_* bit; waits for the context's stream and copies the last frame's
+ *                      buffer (H * W * 16 or H * W * 4 bytes) to dst on the HOST; bytes must be at least that.
+ *   gs_output_device : the device pointer of that buffer and its size (bytes may be NULL).  Valid until the next
+ *                      gs_set_outputs, gs_set_resolution, gs_set_tile_rows* or gs_destroy; it holds the last enqueued frame's
+ *                      values once gs_synchronize has returned (gs_render_device_async works).
+ * Both fail with GS_ERR_INVALID (message in gs_last_error) for a which that is unknown or not enabled, a bytes that is too
+ * small, and when no frame has been rendered since the outputs were enabled or resized.
+ * Sharded frames (gs_dist_shard_rows, gs_render_sharded*) do not gather these buffers: a sharded call on a context with a
+ * non-zero mask returns GS_ERR_INVALID and enqueues nothing. */
+#define GS_OUTPUT_RGBA32F 1u
+#define GS_OUTPUT_DEPTH 2u
+int gs_set_outputs(gs_ctx* ctx, uint32_t mask);
+int gs_read_output(gs_ctx* ctx, uint32_t which, void* dst, size_t bytes);
+int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes);
 
 /* Runs ONLY the InitSortList stage of a frame (project + count scan + emit) and waits; afterwards
  * GS_BUF_UNSORTED_*, GS_BUF_COLOR, GS_BUF_COV and GS_BUF_COUNT are readable (stage-level parity). */

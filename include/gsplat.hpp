@@ -129,6 +129,26 @@ public:
         return rc;
     }
 
+    // Optional per-pixel outputs of every later frame (gsplat.h, GS_OUTPUT_*): mask 0 = the RGBA8 frame alone (default).
+    int setOutputs(uint32_t mask) {
+        const int rc = gs_set_outputs(ctx_, mask);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    // host copy of the last frame's buffer `which` (one GS_OUTPUT_* bit): bytes >= H * W * 16 (RGBA32F) or H * W * 4 (DEPTH)
+    int readOutput(uint32_t which, void* dst, size_t bytes) {
+        const int rc = gs_read_output(ctx_, which, dst, bytes);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    // the device buffer itself (nullptr on failure, see lastError()); its contents are the last enqueued frame's once the
+    // context's stream has been waited for
+    void* outputDevice(uint32_t which, size_t* bytes = nullptr) {
+        void* dev = nullptr;
+        if (gs_output_device(ctx_, which, &dev, bytes) < 0) error_ = gs_last_error(ctx_);
+        return dev;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

@@ -33,6 +33,7 @@ GS_SORT_TILE_BUCKET = 1
 GS_SORT_RADIX4_SPLAT_FIRST = 2
 GS_SORT_RADIX8 = 3
 GS_SORT_RADIX8_SPLAT_FIRST = 4
+GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read_output `which`
 
 (BUF_SORTED_TILE, BUF_SORTED_DEPTH, BUF_SORTED_ID, BUF_RANGES, BUF_COLOR, BUF_COV, BUF_COUNT,
  BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE) = range(11)
@@ -116,9 +117,10 @@ EXPORTS = [
     "gs_get_host_timings", "gs_set_tile_rows_interleaved", "gs_api_version", "gs_runtime_versions",
     "gs_dist_unique_id", "gs_dist_init", "gs_gather_strips", "gs_dist_destroy", "gs_dist_shard_rows", "gs_render_sharded",
     "gs_render_sharded_async", "gs_sharded_frame", "gs_sharded_read", "gs_dist_rebalance", "gs_dist_bands", "gs_balance_rows",
+    "gs_set_outputs", "gs_read_output", "gs_output_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
-API_VERSION = 5            # GS_API_VERSION of include/gsplat.h this binding was written against
+API_VERSION = 6            # GS_API_VERSION of include/gsplat.h this binding was written against
 DIST_UNIQUE_ID_BYTES = 128
 
 
@@ -234,6 +236,9 @@ def lib() -> C.CDLL:
     L.gs_dist_rebalance.argtypes = [ctxp, C.POINTER(u32)]
     L.gs_dist_bands.argtypes = [ctxp, C.POINTER(u32), u32]
     L.gs_balance_rows.argtypes = [C.POINTER(C.c_double), u32, u32, C.POINTER(u32)]
+    L.gs_set_outputs.argtypes = [ctxp, u32]
+    L.gs_read_output.argtypes = [ctxp, u32, vp, C.c_size_t]
+    L.gs_output_device.argtypes = [ctxp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -61,6 +61,7 @@ void free_scene(gs_ctx* c) {
     free_dev(c->scratch.band_list);
     free_dev(c->scratch.block_flags); free_dev(c->scratch.flag_offsets);
     free_dev(c->scratch.sorted_sums); free_dev(c->scratch.aux_params);
+    free_dev(c->scratch.view_z);
     c->n = 0;
 }
 
@@ -81,6 +82,8 @@ void free_resolution(gs_ctx* c) {
     drop_sort_graph(c);
     free_sort(c->sort);
     free_dev(c->ranges); free_dev(c->tile_order); free_dev(c->framebuffer);
+    free_dev(c->out_rgba32f); free_dev(c->out_depth);
+    c->outputs_valid = false;
     // the strips of a sharded frame are sized by the resolution: gs_dist_shard_rows must be called again
     gsi_dist_free_buffers(c);
     c->capacity = 0; c->width = c->height = 0;
@@ -304,10 +307,12 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
         if (tm) HIP_TRY(c, hipEventRecord(c->alt_ev[1], st));
     }
     if (tm) HIP_TRY(c, hipEventRecord(c->ev[4], st));
-    // computeRenderGaussians (Subrenderer.cpp:218-346)
+    // computeRenderGaussians (Subrenderer.cpp:218-346), with the outputs of gs_set_outputs beside the image
+    const RenderOutputs outs{reinterpret_cast<float4*>(c->out_rgba32f), c->out_depth, c->scratch.view_z};
     launch_render(fp, c->scratch.raster, c->sort.id[c->sorted_index], c->ranges, ordered ? c->tile_order : nullptr,
-                  out_dev ? out_dev : c->framebuffer, c->cfg.render_mode, c->cfg.render_kernel, st);
+                  out_dev ? out_dev : c->framebuffer, c->cfg.render_mode, c->cfg.render_kernel, st, outs);
     if (int r = check_launch(c, "RenderGaussians")) return r;
+    if (c->outputs) c->outputs_valid = true;
     if (tm) { HIP_TRY(c, hipEventRecord(c->ev[5], st)); HIP_TRY(c, hipEventRecord(c->ev[6], st)); }
     c->have_frame = true;
     return GS_OK;
@@ -609,6 +614,10 @@ static int alloc_scratch(gs_ctx* c, uint32_t n) {
     HIP_TRY(c, hipMemsetAsync(c->scratch.help_count, 0, 4 * sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->scratch.help_list, 0, (size_t)kEmitHelpCap * sizeof(uint2), c->stream));
     HIP_TRY(c, hipMemsetAsync(c->scratch.help_slot, 0xFF, (size_t)c->num_blocks * sizeof(uint32_t), c->stream));
+    if (c->outputs & GS_OUTPUT_DEPTH) {   // k_project stores the view depths only while the depth output is on
+        HIP_TRY(c, hipMalloc((void**)&c->scratch.view_z, N * sizeof(float)));
+        HIP_TRY(c, hipMemsetAsync(c->scratch.view_z, 0, N * sizeof(float), c->stream));
+    }
     c->emit_parity = 0;
     if (sorts_splat_first(c->cfg.sort_algorithm)) {
         HIP_TRY(c, hipMalloc((void**)&c->scratch.block_flags, padded * sizeof(uint32_t)));
@@ -703,6 +712,8 @@ int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
     return GS_OK;
 }
 
+static hipError_t alloc_outputs(gs_ctx* c);
+
 int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     if (!c) return GS_ERR_INVALID;
     if (!c->n) return fail(c, GS_ERR_NO_SCENE, "gs_set_resolution: upload gaussians first");
@@ -729,10 +740,90 @@ int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     if (e == hipSuccess) e = hipMalloc((void**)&c->framebuffer, (size_t)width * height * 4);
     if (e == hipSuccess) e = hipMemset(c->ranges, 0, (size_t)gw * gh * 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->framebuffer, 0, (size_t)width * height * 4);
+    if (e == hipSuccess) e = alloc_outputs(c);
     if (e != hipSuccess) {
         free_resolution(c);
         return fail(c, GS_ERR_HIP, std::string("gs_set_resolution: ") + hipGetErrorString(e));
     }
+    return GS_OK;
+}
+
+// The output buffers of the mask at the current resolution, zero-filled (rows a context does not own stay zero)
+static hipError_t alloc_outputs(gs_ctx* c) {
+    const size_t px = (size_t)c->width * c->height;
+    hipError_t e = hipSuccess;
+    if (px && (c->outputs & GS_OUTPUT_RGBA32F)) {
+        e = hipMalloc((void**)&c->out_rgba32f, px * 4 * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(c->out_rgba32f, 0, px * 4 * sizeof(float));
+    }
+    if (e == hipSuccess && px && (c->outputs & GS_OUTPUT_DEPTH)) {
+        e = hipMalloc((void**)&c->out_depth, px * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(c->out_depth, 0, px * sizeof(float));
+    }
+    return e;
+}
+
+int gs_set_outputs(gs_ctx* c, uint32_t mask) {
+    if (!c) return GS_ERR_INVALID;
+    if (mask & ~(GS_OUTPUT_RGBA32F | GS_OUTPUT_DEPTH)) return fail(c, GS_ERR_INVALID, "gs_set_outputs: unknown output bit in the mask");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the buffers
+    // k_project and RenderGaussians are launched outside the captured graphs (enqueue_frame): no graph depends on the mask
+    free_dev(c->out_rgba32f); free_dev(c->out_depth); free_dev(c->scratch.view_z);
+    c->outputs = mask;
+    c->outputs_valid = false;
+    hipError_t e = hipSuccess;
+    if (c->n && (mask & GS_OUTPUT_DEPTH)) {
+        e = hipMalloc((void**)&c->scratch.view_z, (size_t)c->n * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(c->scratch.view_z, 0, (size_t)c->n * sizeof(float));
+    }
+    if (e == hipSuccess) e = alloc_outputs(c);
+    if (e != hipSuccess) {   // back to RGBA8-only frames rather than half set up
+        free_dev(c->out_rgba32f); free_dev(c->out_depth); free_dev(c->scratch.view_z);
+        c->outputs = 0;
+        return fail(c, GS_ERR_HIP, std::string("gs_set_outputs: ") + hipGetErrorString(e));
+    }
+    return GS_OK;
+}
+
+// which: one GS_OUTPUT_* bit that is enabled and allocated -> its buffer and size; else fails
+static int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** dev, size_t* size) {
+    if (which != GS_OUTPUT_RGBA32F && which != GS_OUTPUT_DEPTH)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": which must be GS_OUTPUT_RGBA32F or GS_OUTPUT_DEPTH");
+    if (!(c->outputs & which)) return fail(c, GS_ERR_INVALID, std::string(who) + ": that output is not enabled (gs_set_outputs)");
+    if (!c->capacity) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_set_resolution not called");
+    const size_t px = (size_t)c->width * c->height;
+    *dev = which == GS_OUTPUT_RGBA32F ? (void*)c->out_rgba32f : (void*)c->out_depth;
+    *size = px * (which == GS_OUTPUT_RGBA32F ? 4 * sizeof(float) : sizeof(float));
+    return GS_OK;
+}
+
+int gs_read_output(gs_ctx* c, uint32_t which, void* dst, size_t bytes) {
+    if (!c) return GS_ERR_INVALID;
+    if (!dst) return fail(c, GS_ERR_INVALID, "gs_read_output: dst is null");
+    void* dev = nullptr;
+    size_t size = 0;
+    if (int r = output_buffer(c, which, "gs_read_output", &dev, &size)) return r;
+    if (!c->outputs_valid)
+        return fail(c, GS_ERR_INVALID, "gs_read_output: no frame rendered since the outputs were enabled or resized");
+    if (bytes < size) return fail(c, GS_ERR_INVALID, "gs_read_output: bytes is smaller than the buffer (H * W * 16 or H * W * 4)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(dst, dev, size, hipMemcpyDeviceToHost));
+    return GS_OK;
+}
+
+int gs_output_device(gs_ctx* c, uint32_t which, void** dev_out, size_t* bytes) {
+    if (!c) return GS_ERR_INVALID;
+    if (!dev_out) return fail(c, GS_ERR_INVALID, "gs_output_device: dev_out is null");
+    *dev_out = nullptr;
+    void* dev = nullptr;
+    size_t size = 0;
+    if (int r = output_buffer(c, which, "gs_output_device", &dev, &size)) return r;
+    if (!c->outputs_valid)
+        return fail(c, GS_ERR_INVALID, "gs_output_device: no frame rendered since the outputs were enabled or resized");
+    *dev_out = dev;
+    if (bytes) *bytes = size;
     return GS_OK;
 }
 

@@ -55,6 +55,12 @@ struct gs_ctx {
     uint32_t band_sort_bits = 0;
     bool hi16 = false;   // the frame's sort list stores the compact tile ids as uint16 (at most 65535 owned tiles)
     gs::SortBuffers sort{};
+    // gs_set_outputs: the optional per-pixel outputs, addressed like the RGBA8 image (the view depths of the splats live in
+    // scratch.view_z, which follows the mask and the scene)
+    uint32_t outputs = 0;             // GS_OUTPUT_* mask
+    float* out_rgba32f = nullptr;     // [H][W][4] while GS_OUTPUT_RGBA32F is on and a resolution is set
+    float* out_depth = nullptr;       // [H][W] while GS_OUTPUT_DEPTH is on and a resolution is set
+    bool outputs_valid = false;       // a frame has been enqueued since the mask or the resolution last changed
     uint32_t* ranges = nullptr;
     uint32_t* tile_order = nullptr;   // [tiles] RenderGaussians' dispatch order (GS_TILE_ORDER_LONGEST_FIRST)
     uint8_t* framebuffer = nullptr;

@@ -317,6 +317,7 @@ int gs_dist_bands(const gs_ctx* c, uint32_t* edges_out, uint32_t count) {
 
 int gs_render_sharded_async(gs_ctx* c, const float view[16], const float proj[16], const float cam_pos[3], uint32_t sh_mode) {
     if (!c) return GS_ERR_INVALID;
+    if (c->outputs) return fail(c, GS_ERR_INVALID, "gs_render_sharded_async: sharded frames do not gather the outputs of gs_set_outputs: set the mask to 0 first");
     if (int rc = check_sharded(c, "gs_render_sharded_async")) return rc;
     DIST_TRY(c, hipSetDevice(c->device));
     const int slot = c->dist_next;
@@ -376,6 +377,7 @@ int gs_sharded_read(gs_ctx* c, uint32_t which, uint8_t* rgba_out) {
 int gs_render_sharded(gs_ctx* c, const float view[16], const float proj[16], const float cam_pos[3], uint32_t sh_mode,
                       uint8_t* rgba_out) {
     if (!c) return GS_ERR_INVALID;
+    if (c->outputs) return fail(c, GS_ERR_INVALID, "gs_render_sharded: sharded frames do not gather the outputs of gs_set_outputs: set the mask to 0 first");
     if (int rc = check_sharded(c, "gs_render_sharded")) return rc;
     if (c->dist_rank == 0 && !rgba_out) return fail(c, GS_ERR_INVALID, "gs_render_sharded: rank 0 needs rgba_out");
     const int rc_frame = gs_render_sharded_async(c, view, proj, cam_pos, sh_mode);

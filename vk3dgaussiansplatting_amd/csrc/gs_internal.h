@@ -143,6 +143,8 @@ struct SplatScratch {
     SortParams* aux_params;  // [2]: the splat list's dispatch record; scratch for the second scan
     uint32_t* elems_note;    // device alias of a pinned host word (or null): k_scan_blocks leaves the frame's element count + 1
                              // there, so that the host knows the length of recent lists without waiting for a frame
+    float* view_z;           // [N] while GS_OUTPUT_DEPTH is on (null otherwise): -viewSpacePos.z of the emitting splats, the
+                             //       value getDepthKey quantises (InitSortList.comp:70-80); what the depth output blends
 };
 #ifndef GS_EMIT_SLICE
 #define GS_EMIT_SLICE 4096
@@ -228,10 +230,17 @@ void launch_find_ranges(const FrameParams& fp, const uint32_t* sorted_tile, cons
 // order[k] = the k-th tile RenderGaussians dispatches, as an index among the context's own tiles, longest list first
 void launch_tile_order(const FrameParams& fp, const uint32_t* ranges, uint32_t* order, hipStream_t stream);
 size_t tile_order_words(uint32_t grid_w, uint32_t grid_h);   // words `order` must hold: the table and the kernels' scratch
+// The optional per-pixel outputs of a frame (gs_set_outputs), addressed like the RGBA8 image: rgba32f = premultiplied
+// colour before the clamp + 1 - T_end, depth = the colour's blend of view_z.  All null: the RGBA8 frame alone.
+struct RenderOutputs {
+    float4* rgba32f;         // [H][W] or null
+    float* depth;            // [H][W] or null
+    const float* view_z;     // SplatScratch::view_z (needed with depth)
+};
 // order == nullptr: raster order
 void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
                    const uint32_t* ranges, const uint32_t* order, uint8_t* rgba, uint32_t render_mode,
-                   uint32_t render_kernel, hipStream_t stream);
+                   uint32_t render_kernel, hipStream_t stream, const RenderOutputs& outs = RenderOutputs{});
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,
                        const SceneBuffers& s, hipStream_t stream);
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream);

@@ -347,7 +347,10 @@ __device__ __forceinline__ void splat_colour(const FrameParams& fp, const float*
 // NT_SH: the 48 spherical-harmonics planes (192 of the 236 bytes a splat's record takes) are loaded non-temporally -- a
 // frame reads each of them once, and a scene larger than the 256 MiB Infinity Cache cannot keep them from one frame to
 // the next anyway, while its other planes and the frame's lists can use the space (launch_project picks by scene size).
-template <bool NT_SH>
+// VIEW_Z (GS_OUTPUT_DEPTH on, SplatScratch::view_z allocated): also stores the view depth -viewSpacePos.z of every emitting
+// splat for the depth output -- an instantiation of its own, so that frames without it run the kernel as it was (a branch
+// in this kernel, at its SGPR limit, re-arranged the spills of the whole kernel).
+template <bool NT_SH, bool VIEW_Z>
 __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(const FrameParams fp,
                                                            const SceneBuffers scene,
                                                            const SplatScratch sc, const uint32_t num_blocks) {
@@ -471,6 +474,7 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                         splat_colour<NT_SH>(fp, scene.sh + g, n, px, py, pz, res);
                         rec1 = make_float4(inv_z, res[0], res[1], res[2]);
                         sc.depth_key[g] = depth_key;
+                        if constexpr (VIEW_Z) sc.view_z[g] = -vp[2];     // GS_OUTPUT_DEPTH: the z getDepthKey used
                         sc.extents[g] = make_uint2((uint32_t)min_x | ((uint32_t)k0 << 16),
                                                    (uint32_t)max_x | ((uint32_t)k1 << 16));
                     }
@@ -776,10 +780,14 @@ void launch_project(const FrameParams& fp, const SceneBuffers& scene, const Spla
 #ifndef GS_PROJECT_NT_SH_ABOVE
 #define GS_PROJECT_NT_SH_ABOVE ((size_t)256u << 20)       /* scene bytes above which the SH planes are loaded non-temporally */
 #endif
-    if ((size_t)fp.num_gaussians * 236u > GS_PROJECT_NT_SH_ABOVE)
-        hipLaunchKernelGGL(k_project<true>, dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-    else
-        hipLaunchKernelGGL(k_project<false>, dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    const bool nt_sh = (size_t)fp.num_gaussians * 236u > GS_PROJECT_NT_SH_ABOVE;
+    if (sc.view_z) {
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, true>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, true>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    } else {
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, false>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, false>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    }
 }
 
 // gs_debug_read(GS_BUF_COLOR), full-grid contexts: the reference stores a colour for EVERY splat that passes the two culls

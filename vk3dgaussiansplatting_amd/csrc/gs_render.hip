@@ -164,20 +164,24 @@ __device__ __forceinline__ float exp_pinned_live(float x) {            // the sc
 
 struct Fetched {
     float4 a, b, c;   // raw SplatRaster
+    float z;          // AUX: the splat's view depth (SplatScratch::view_z; 0 without GS_OUTPUT_DEPTH)
     bool valid;
 };
 
+template <bool AUX = false>
 __device__ __forceinline__ Fetched fetch_splat(const SplatRaster* __restrict__ raster,
                                                const uint32_t* __restrict__ sorted_id,
-                                               uint32_t idx, uint32_t end) {
+                                               uint32_t idx, uint32_t end, const float* __restrict__ view_z = nullptr) {
     Fetched f;
     f.valid = idx < end;
+    if constexpr (AUX) f.z = 0.0f;
     if (f.valid) {
         const uint32_t gi = sorted_id[idx];                            // RenderGaussians.comp:88
         const float4* rp = reinterpret_cast<const float4*>(raster + gi);
         f.a = rp[0];
         f.b = rp[1];
         f.c = rp[2];
+        if (AUX && view_z) f.z = view_z[gi];
     } else {
         f.a = f.b = f.c = make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -244,17 +248,22 @@ __device__ __forceinline__ bool stage_splat(Fetched& nxt, float tile_x0, float t
 // STATS is a tuning-only instantiation (gs_debug_render_stats): per tile {list length, splats
 // visited, splats with any pixel needing exp, clock ticks | entries staged before the tile was done, -, -, -}.
 // The product launches STATS = false.
+// AUX: the optional outputs of gs_set_outputs (RenderOutputs) beside the RGBA8 word -- the view depth rides in the free
+// slot of the staged entry and is blended with the colour's weight, and T also follows the entry that finishes a pixel
+// (the early-out of :136-140 adds that entry's colour, so 1 - T_end describes the same entries).  A finished lane is
+// masked out of every later blend: the colour chain is the one of AUX = false, bit for bit.
 // PX = pixels per lane: 4 -> one wave per tile (16 rows x 4 lanes), 2 -> two waves per tile (each
 // 8 rows x 8 lanes), 1 -> four waves per tile (each 4 rows x 16 lanes).  Waves of one tile are
 // independent workgroups: each gathers, culls (against its own pixel rectangle) and blends on its own.
-template <bool EXACT, int PX, bool STATS = false>
+template <bool EXACT, int PX, bool STATS = false, bool AUX = false>
 __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
                                                 const SplatRaster* __restrict__ raster,
                                                 const uint32_t* __restrict__ sorted_id,
                                                 const uint32_t* __restrict__ ranges,
                                                 const uint32_t* __restrict__ order,
-                                                uint32_t* __restrict__ rgba, uint4* __restrict__ stats = nullptr) {
-    // LDS image of the current batch: {sx, sy, inv.x, inv.y}, {inv.z, r, g, b}, {a, skip threshold, -, -}
+                                                uint32_t* __restrict__ rgba, uint4* __restrict__ stats,
+                                                const RenderOutputs aux) {
+    // LDS image of the current batch: {sx, sy, inv.x, inv.y}, {inv.z, r, g, b}, {a, skip threshold, z (AUX), -}
     __shared__ float4 s_batch[64][3];
 
     constexpr int WPT = 4 / PX;            // waves per tile
@@ -278,18 +287,20 @@ __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
     float fpx[PX];
     float col[PX][3];
     float T[PX];
+    float dep[PX];                                                     // AUX: sum of T * alpha * z
     bool done[PX];
 #pragma unroll
     for (int k = 0; k < PX; ++k) {
         fpx[k] = (float)(px0 + k);
         col[k][0] = col[k][1] = col[k][2] = 0.0f;
         T[k] = 1.0f;
+        dep[k] = 0.0f;
         done[k] = !(px0 + k < fp.width && py < fp.height);             // never stored (:147)
     }
 
     uint32_t st_visited = 0, st_need = 0, st_walked = 0;   // STATS: entries visited / needing an exp / staged before the tile was done
     const uint64_t st_t0 = STATS ? __builtin_amdgcn_s_memtime() : 0;
-    Fetched nxt = fetch_splat(raster, sorted_id, start + lane, end);
+    Fetched nxt = fetch_splat<AUX>(raster, sorted_id, start + lane, end, aux.view_z);
     for (uint32_t i = start; i < end; i += 64) {                       // :81
         // :86-108, one list entry per lane (the per-splat setup itself is k_project's)
         const bool keep = stage_splat(nxt, tile_x0, tile_y0, (float)(ROWS - 1));
@@ -300,16 +311,18 @@ __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
             const uint32_t slot = mbcnt(kmask);                        // order-preserving compaction
             s_batch[slot][0] = nxt.a;
             s_batch[slot][1] = nxt.b;
+            if (AUX) nxt.c.z = nxt.z;
             s_batch[slot][2] = nxt.c;
         }
         __syncthreads();                                               // :109 (single wave)
-        nxt = fetch_splat(raster, sorted_id, i + 64 + lane, end);      // prefetch next batch
+        nxt = fetch_splat<AUX>(raster, sorted_id, i + 64 + lane, end, aux.view_z);   // prefetch next batch
 
         for (uint32_t j = 0; j < n; ++j) {                             // :112
             const float4 g0 = s_batch[j][0];
             const float4 g1 = s_batch[j][1];
             const float2 g2 = *reinterpret_cast<const float2*>(&s_batch[j][2]);
             const float ga = g2.x, fthr = g2.y;
+            const float gz = AUX ? s_batch[j][2].z : 0.0f;
             float ey = g0.y - fpy;                                     // :119
             ey = -ey;                                                  // :120
             float f[PX];
@@ -374,13 +387,18 @@ __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
                     col[k1][1] = act1 ? cg.y : col[k1][1];
                     col[k0][2] = act0 ? cb.x : col[k0][2];
                     col[k1][2] = act1 ? cb.y : col[k1][2];
+                    if constexpr (AUX) {                                                     // depth: a fourth channel
+                        const v2f cz = (v2f){dep[k0], dep[k1]} + wgt * (v2f){gz, gz};
+                        dep[k0] = act0 ? cz.x : dep[k0];
+                        dep[k1] = act1 ? cz.y : dep[k1];
+                    }
                     const v2f next_t = Tv * ((v2f){1.0f, 1.0f} - alpha);                     // :133
                     const bool fin0 = act0 && next_t.x < 0.0001f;                            // :136-140
                     const bool fin1 = act1 && next_t.y < 0.0001f;
                     done[k0] = done[k0] || fin0;
                     done[k1] = done[k1] || fin1;
-                    T[k0] = (act0 && !fin0) ? next_t.x : T[k0];                              // :142
-                    T[k1] = (act1 && !fin1) ? next_t.y : T[k1];
+                    T[k0] = (act0 && (AUX || !fin0)) ? next_t.x : T[k0];                     // :142 (AUX: T_end)
+                    T[k1] = (act1 && (AUX || !fin1)) ? next_t.y : T[k1];
                 }
             } else
 #pragma unroll
@@ -395,16 +413,18 @@ __global__ __launch_bounds__(64) void k_render(const FrameParams fp,
                     col[k][0] = act ? col[k][0] + wgt * g1.y : col[k][0];
                     col[k][1] = act ? col[k][1] + wgt * g1.z : col[k][1];
                     col[k][2] = act ? col[k][2] + wgt * g1.w : col[k][2];
+                    if (AUX) dep[k] = act ? dep[k] + wgt * gz : dep[k];
                 } else {
                     // select form: a skipping lane's colour is not touched (0 * inf would be NaN, stored as 0)
                     col[k][0] = act ? __builtin_fmaf(wgt, g1.y, col[k][0]) : col[k][0];
                     col[k][1] = act ? __builtin_fmaf(wgt, g1.z, col[k][1]) : col[k][1];
                     col[k][2] = act ? __builtin_fmaf(wgt, g1.w, col[k][2]) : col[k][2];
+                    if (AUX) dep[k] = act ? __builtin_fmaf(wgt, gz, dep[k]) : dep[k];
                 }
                 const float next_t = T[k] * (1.0f - alpha);            // :133
                 const bool fin = act && next_t < 0.0001f;              // :136-140, colour already added
                 done[k] = done[k] || fin;
-                T[k] = (act && !fin) ? next_t : T[k];                  // :142
+                T[k] = (act && (AUX || !fin)) ? next_t : T[k];         // :142 (AUX: T_end)
             }
             bool all_done = true;
 #pragma unroll
@@ -443,6 +463,16 @@ finish:
             for (int k = 0; k < PX; ++k)
                 if (px0 + k < fp.width) row[px0 + k] = packed[k];
         }
+        if constexpr (AUX) {                                           // same addressing as the RGBA8 word
+            const size_t o = (size_t)out_y * fp.width + px0;
+#pragma unroll
+            for (int k = 0; k < PX; ++k) {
+                if (px0 + k < fp.width) {
+                    if (aux.rgba32f) aux.rgba32f[o + k] = make_float4(col[k][0], col[k][1], col[k][2], 1.0f - T[k]);
+                    if (aux.depth) aux.depth[o + k] = dep[k];
+                }
+            }
+        }
     }
 }
 
@@ -459,9 +489,12 @@ __device__ __forceinline__ float sel(uint64_t m, float a, float b) { return __bu
 // with the weight forced to zero on the lanes that skip -- col + 0 * c == col bit for bit when c is finite (colours are
 // max(x, 0), never negative) -- three selects less per entry; a batch with a non-finite colour takes the select form,
 // where a skipped lane's colour is not touched at all, as in the shader.
-template <bool EXACT, bool FINITE>
+// AUX (k_render_wg<.., AUX>): the view depth z is blended like a fourth colour channel into dep -- z is always finite, so
+// the zero-weight FINITE form is exact for it in both branches -- and T also takes the value of the entry that finishes a
+// lane (T_end); that lane is in `done` from then on, so no later blend of it reads T.
+template <bool EXACT, bool FINITE, bool AUX = false>
 __device__ __forceinline__ void blend_entry(uint64_t need, float alpha, float cr, float cg, float cb, float& col0, float& col1,
-                                            float& col2, float& T, uint64_t& done) {
+                                            float& col2, float& T, uint64_t& done, float z = 0.0f, float* dep = nullptr) {
     const uint64_t act = need & ~mask_of(alpha < 1.0f / 255.0f);      // :127
     const float wgt = T * alpha;                                       // :131
     if constexpr (!EXACT && FINITE) {
@@ -469,24 +502,29 @@ __device__ __forceinline__ void blend_entry(uint64_t need, float alpha, float cr
         col0 = __builtin_fmaf(w0, cr, col0);
         col1 = __builtin_fmaf(w0, cg, col1);
         col2 = __builtin_fmaf(w0, cb, col2);
+        if constexpr (AUX) *dep = __builtin_fmaf(w0, z, *dep);
     } else if constexpr (!EXACT) {
         col0 = sel(act, __builtin_fmaf(wgt, cr, col0), col0);
         col1 = sel(act, __builtin_fmaf(wgt, cg, col1), col1);
         col2 = sel(act, __builtin_fmaf(wgt, cb, col2), col2);
+        if constexpr (AUX) *dep = __builtin_fmaf(sel(act, wgt, 0.0f), z, *dep);
     } else if constexpr (FINITE) {
         const float w0 = sel(act, wgt, 0.0f);
         col0 = col0 + w0 * cr;
         col1 = col1 + w0 * cg;
         col2 = col2 + w0 * cb;
+        if constexpr (AUX) *dep = *dep + w0 * z;
     } else {
         col0 = sel(act, col0 + wgt * cr, col0);
         col1 = sel(act, col1 + wgt * cg, col1);
         col2 = sel(act, col2 + wgt * cb, col2);
+        if constexpr (AUX) *dep = *dep + sel(act, wgt, 0.0f) * z;
     }
     const float next_t = T * (1.0f - alpha);                           // :133
     const uint64_t fin = act & mask_of(next_t < 0.0001f);              // :136-140, colour already added
     done |= fin;
-    T = sel(act & ~fin, next_t, T);                                    // :142
+    if constexpr (AUX) T = sel(act, next_t, T);                        // :142, and T_end on the finishing entry
+    else T = sel(act & ~fin, next_t, T);                               // :142
 }
 
 // Two list entries (the pair `pair` of the staged batch; two == false when the batch ends on a single one: the second
@@ -498,11 +536,13 @@ __device__ __forceinline__ void blend_entry(uint64_t need, float alpha, float cr
 // iy_a, iy_b}, {iz_a, iz_b, alpha_a, alpha_b}, {thr_a, thr_b, r_a, r_b}, {g_a, g_b, b_a, b_b} -- so that five 16-byte
 // reads deliver every operand as the register pair a packed instruction wants (entry-major slots cost ten v_mov per
 // step to build those pairs: 8 % of the loop).
+// AUX: a sixth quad {z_a, z_b, -, -} per pair (the view depths, read only when a lane needs the pair).
 constexpr int kPairQuads = 5;
-template <bool EXACT, bool FINITE>
+template <bool EXACT, bool FINITE, bool AUX = false>
 __device__ __forceinline__ void blend_pair(const float4* pairs, int pair, bool two, float fpx, float fpy,
-                                           float& col0, float& col1, float& col2, float& T, uint64_t& done) {
-    const float4* q = pairs + pair * kPairQuads;
+                                           float& col0, float& col1, float& col2, float& T, uint64_t& done,
+                                           float* dep = nullptr) {
+    const float4* q = pairs + pair * (AUX ? kPairQuads + 1 : kPairQuads);
     const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
     const v2f ex = (v2f){q0.x, q0.y} - (v2f){fpx, fpx};                          // :119
     const v2f ey = -((v2f){q0.z, q0.w} - (v2f){fpy, fpy});                       // :119-120
@@ -525,8 +565,14 @@ __device__ __forceinline__ void blend_pair(const float4* pairs, int pair, bool t
         const v2f t = f * (v2f){0x1.715476p+0f, 0x1.715476p+0f};
         alpha = (v2f){q2.z, q2.w} * (v2f){__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
     }
-    blend_entry<EXACT, FINITE>(live_a & ~done, alpha.x, q3.z, q4.x, q4.z, col0, col1, col2, T, done);
-    blend_entry<EXACT, FINITE>(live_b & ~done, alpha.y, q3.w, q4.y, q4.w, col0, col1, col2, T, done);
+    if constexpr (AUX) {
+        const float4 q5 = q[5];
+        blend_entry<EXACT, FINITE, true>(live_a & ~done, alpha.x, q3.z, q4.x, q4.z, col0, col1, col2, T, done, q5.x, dep);
+        blend_entry<EXACT, FINITE, true>(live_b & ~done, alpha.y, q3.w, q4.y, q4.w, col0, col1, col2, T, done, q5.y, dep);
+    } else {
+        blend_entry<EXACT, FINITE>(live_a & ~done, alpha.x, q3.z, q4.x, q4.z, col0, col1, col2, T, done);
+        blend_entry<EXACT, FINITE>(live_b & ~done, alpha.y, q3.w, q4.y, q4.w, col0, col1, col2, T, done);
+    }
 }
 
 // One 256-thread workgroup per tile, one pixel per lane -- the reference's own launch shape (RenderGaussians.comp:
@@ -540,14 +586,16 @@ __device__ __forceinline__ void blend_pair(const float4* pairs, int pair, bool t
 // capture-like cloud and 15 - 22 % on the uniform one, although every entry is then gathered four times).
 // QUAD: wave w owns the 8 x 8 quadrant (w & 1, w >> 1) of the tile instead of the 16 x 4 strip w -- 20 % less perimeter,
 // so fewer list entries survive a wave's rectangle test (gs_config.render_kernel = GS_RENDER_KERNEL_WORKGROUP_8X8).
-template <bool EXACT, bool QUAD>
+// AUX: the optional outputs (RenderOutputs; blend_entry, blend_pair).
+template <bool EXACT, bool QUAD, bool AUX = false>
 __global__ __launch_bounds__(256) void k_render_wg(const FrameParams fp,
                                                     const SplatRaster* __restrict__ raster,
                                                     const uint32_t* __restrict__ sorted_id,
                                                     const uint32_t* __restrict__ ranges,
                                                     const uint32_t* __restrict__ order,
-                                                    uint32_t* __restrict__ rgba) {
-    __shared__ float4 s_batch[4][32 * kPairQuads];   // per wave: 32 pairs of staged entries, pair-interleaved (blend_pair)
+                                                    uint32_t* __restrict__ rgba, const RenderOutputs aux) {
+    constexpr int kQuads = AUX ? kPairQuads + 1 : kPairQuads;
+    __shared__ float4 s_batch[4][32 * kQuads];       // per wave: 32 pairs of staged entries, pair-interleaved (blend_pair)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t tile_in_band = order ? order[blockIdx.x] : blockIdx.x;   // longest lists first (k_tile_classes, k_tile_scatter)
@@ -567,10 +615,11 @@ __global__ __launch_bounds__(256) void k_render_wg(const FrameParams fp,
     constexpr float kRowsM1 = QUAD ? 7.0f : 3.0f, kColsM1 = QUAD ? 7.0f : 15.0f;
 
     float col0 = 0.0f, col1 = 0.0f, col2 = 0.0f, T = 1.0f;
+    float dep = 0.0f;                                                  // AUX: sum of T * alpha * z
     uint64_t done = mask_of(!(px < fp.width && py < fp.height));       // never stored (:147); a whole wave: 64 lanes
     if (done != ~0ull) {
         float4* wbatch = s_batch[wave];                                // this wave's quarter of the buffer
-        Fetched nxt = fetch_splat(raster, sorted_id, start + lane, end);
+        Fetched nxt = fetch_splat<AUX>(raster, sorted_id, start + lane, end, aux.view_z);
         for (uint32_t i = start; i < end; i += 64) {                   // :81
             const bool keep = stage_splat(nxt, tile_x0, wave_y0, kRowsM1, kColsM1);
             const uint64_t kmask = __ballot(keep);
@@ -579,7 +628,7 @@ __global__ __launch_bounds__(256) void k_render_wg(const FrameParams fp,
             const bool finite = mask_of(keep && !(fabsf(nxt.b.y) < INFINITY && fabsf(nxt.b.z) < INFINITY && fabsf(nxt.b.w) < INFINITY)) == 0ull;
             if (keep) {
                 const uint32_t slot = mbcnt(kmask);                    // order-preserving compaction
-                float* w = reinterpret_cast<float*>(wbatch + (slot >> 1) * kPairQuads) + (slot & 1u);
+                float* w = reinterpret_cast<float*>(wbatch + (slot >> 1) * kQuads) + (slot & 1u);
                 w[0] = nxt.a.x; w[2] = nxt.a.y;                        // screen position
                 w[4] = nxt.a.z; w[6] = nxt.a.w; w[8] = nxt.b.x;        // inverse 2x2 covariance
                 w[10] = nxt.c.x; w[12] = nxt.c.y;                      // alpha, skip threshold
@@ -588,24 +637,28 @@ __global__ __launch_bounds__(256) void k_render_wg(const FrameParams fp,
                 // the finite form multiplies its colour by a zero weight -- give it a colour that keeps 0 * c == 0
                 // (the slots may hold anything, uninitialised LDS included)
                 if ((n & 1) && slot == (uint32_t)n - 1u) { w[15] = 0.0f; w[17] = 0.0f; w[19] = 0.0f; }
+                if (AUX) {                                             // view depth, and the same for the other half
+                    w[20] = nxt.z;
+                    if ((n & 1) && slot == (uint32_t)n - 1u) w[21] = 0.0f;
+                }
             }
             // one wave writes and reads these slots and the DS operations of a wave execute in order: no barrier
             // instruction, only fences that keep the compiler from moving the reads below above the writes (:109)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            nxt = fetch_splat(raster, sorted_id, i + 64 + lane, end);  // prefetch next batch
+            nxt = fetch_splat<AUX>(raster, sorted_id, i + 64 + lane, end, aux.view_z);   // prefetch next batch
             bool finished = false;
             if (finite) {
 #pragma unroll 1
                 for (int j = 0; j < n; j += 2) {                       // :112, two entries per step
-                    blend_pair<EXACT, true>(wbatch, j >> 1, j + 1 < n, fpx, fpy, col0, col1, col2, T, done);
+                    blend_pair<EXACT, true, AUX>(wbatch, j >> 1, j + 1 < n, fpx, fpy, col0, col1, col2, T, done, AUX ? &dep : nullptr);
                     if (done == ~0ull) { finished = true; break; }     // this wave's rows are finished
                 }
             } else {
 #pragma unroll 1
                 for (int j = 0; j < n; j += 2) {
-                    blend_pair<EXACT, false>(wbatch, j >> 1, j + 1 < n, fpx, fpy, col0, col1, col2, T, done);
+                    blend_pair<EXACT, false, AUX>(wbatch, j >> 1, j + 1 < n, fpx, fpy, col0, col1, col2, T, done, AUX ? &dep : nullptr);
                     if (done == ~0ull) { finished = true; break; }
                 }
             }
@@ -623,6 +676,10 @@ __global__ __launch_bounds__(256) void k_render_wg(const FrameParams fp,
         v |= (uint32_t)(clampf(col2, 0.0f, 1.0f) * 255.0f + 0.5f) << 16;
         const uint32_t out_y = fp.compact_out ? krow * kTile + ly : py;
         rgba[(size_t)out_y * fp.width + px] = v;
+        if constexpr (AUX) {                                           // same addressing as the RGBA8 word
+            if (aux.rgba32f) aux.rgba32f[(size_t)out_y * fp.width + px] = make_float4(col0, col1, col2, 1.0f - T);
+            if (aux.depth) aux.depth[(size_t)out_y * fp.width + px] = dep;
+        }
     }
 }
 
@@ -773,23 +830,20 @@ void launch_render_stats(const FrameParams& fp, const SplatRaster* raster, const
     const uint32_t tiles = fp.rows_owned * fp.grid_w;
     if (tiles == 0) return;
     hipLaunchKernelGGL((k_render<true, 4, true>), dim3(tiles), dim3(64), 0, stream, fp, raster, sorted_id,
-                       ranges, (const uint32_t*)nullptr, reinterpret_cast<uint32_t*>(rgba), stats);
+                       ranges, (const uint32_t*)nullptr, reinterpret_cast<uint32_t*>(rgba), stats, RenderOutputs{});
 }
 #endif
 
-void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
-                   const uint32_t* ranges, const uint32_t* order, uint8_t* rgba, uint32_t render_mode,
-                   uint32_t render_kernel, hipStream_t stream) {
-    const uint32_t tiles = fp.rows_owned * fp.grid_w;
-    if (tiles == 0) return;
-    uint32_t* out = reinterpret_cast<uint32_t*>(rgba);
-    const uint32_t px = render_kernel != 0u ? render_kernel : 17u;
-#define GS_LAUNCH_RENDER(EXACT, PX)                                                                   \
-    hipLaunchKernelGGL((k_render<EXACT, PX, false>), dim3(tiles * (4 / PX)), dim3(64), 0, stream, fp, \
-                       raster, sorted_id, ranges, order, out, (uint4*)nullptr)
+template <bool AUX>
+static void launch_render_kernels(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
+                                  const uint32_t* ranges, const uint32_t* order, uint32_t* out, uint32_t render_mode,
+                                  uint32_t px, uint32_t tiles, hipStream_t stream, const RenderOutputs& outs) {
+#define GS_LAUNCH_RENDER(EXACT, PX)                                                                        \
+    hipLaunchKernelGGL((k_render<EXACT, PX, false, AUX>), dim3(tiles * (4 / PX)), dim3(64), 0, stream, fp, \
+                       raster, sorted_id, ranges, order, out, (uint4*)nullptr, outs)
     if (px == 16 || px == 17) {   // workgroup-per-tile kernel: four 16 x 4 strips, or four 8 x 8 quadrants
 #define GS_LAUNCH_WG(EXACT, QUAD) \
-    hipLaunchKernelGGL((k_render_wg<EXACT, QUAD>), dim3(tiles), dim3(256), 0, stream, fp, raster, sorted_id, ranges, order, out)
+    hipLaunchKernelGGL((k_render_wg<EXACT, QUAD, AUX>), dim3(tiles), dim3(256), 0, stream, fp, raster, sorted_id, ranges, order, out, outs)
         if (render_mode == 0u) { if (px == 17) GS_LAUNCH_WG(true, true); else GS_LAUNCH_WG(true, false); }
         else { if (px == 17) GS_LAUNCH_WG(false, true); else GS_LAUNCH_WG(false, false); }
 #undef GS_LAUNCH_WG
@@ -803,6 +857,20 @@ void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint3
         else GS_LAUNCH_RENDER(false, 4);
     }
 #undef GS_LAUNCH_RENDER
+}
+
+void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
+                   const uint32_t* ranges, const uint32_t* order, uint8_t* rgba, uint32_t render_mode,
+                   uint32_t render_kernel, hipStream_t stream, const RenderOutputs& outs) {
+    const uint32_t tiles = fp.rows_owned * fp.grid_w;
+    if (tiles == 0) return;
+    uint32_t* out = reinterpret_cast<uint32_t*>(rgba);
+    const uint32_t px = render_kernel != 0u ? render_kernel : 17u;
+    // the outputs of gs_set_outputs: the AUX instantiations, only when something asks for them
+    if (outs.rgba32f || outs.depth)
+        launch_render_kernels<true>(fp, raster, sorted_id, ranges, order, out, render_mode, px, tiles, stream, outs);
+    else
+        launch_render_kernels<false>(fp, raster, sorted_id, ranges, order, out, render_mode, px, tiles, stream, outs);
 }
 
 } // namespace gs

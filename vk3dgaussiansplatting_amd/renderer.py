@@ -538,6 +538,29 @@ class Renderer:
             self._ctx.check(L.gs_debug_read(self._ctx.handle, which, _p(a), a.nbytes))
         return a
 
+    # -- optional per-pixel outputs (no reference counterpart; include/gsplat.h, GS_OUTPUT_*)
+    def setOutputs(self, rgba32f: bool = False, depth: bool = False):
+        """What every later frame leaves beside the RGBA8 image: rgba32f = premultiplied colour before the clamp + alpha
+        (1 - final transmittance), depth = the blend of the splats' view depths with the colour's weights (expected depth =
+        depth / alpha).  Both off (the default) = the RGBA8 frame alone."""
+        mask = (_lib.GS_OUTPUT_RGBA32F if rgba32f else 0) | (_lib.GS_OUTPUT_DEPTH if depth else 0)
+        self._ctx.check(_lib.lib().gs_set_outputs(self._ctx.handle, mask))
+
+    def readOutput(self, which: int) -> np.ndarray:
+        """The last frame's GS_OUTPUT_RGBA32F (float32 (H, W, 4)) or GS_OUTPUT_DEPTH (float32 (H, W)) buffer."""
+        info = self.sceneInfo()
+        shape = (info.height, info.width, 4) if which == _lib.GS_OUTPUT_RGBA32F else (info.height, info.width)
+        a = np.zeros(shape, dtype=np.float32)
+        self._ctx.check(_lib.lib().gs_read_output(self._ctx.handle, int(which), _p(a), a.nbytes))
+        return a
+
+    def outputDevicePtr(self, which: int) -> int:
+        """Device address of that buffer (same layout as readOutput); valid until the next setOutputs, resolution or
+        tile-row change.  Its contents are the last enqueued frame's once synchronize() has returned."""
+        dev, size = C.c_void_p(), C.c_size_t()
+        self._ctx.check(_lib.lib().gs_output_device(self._ctx.handle, int(which), C.byref(dev), C.byref(size)))
+        return int(dev.value)
+
     # -- Renderer.cpp:230-270
     def cleanup(self):
         if self._ctx is not None:
