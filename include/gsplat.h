@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 6   /* 6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
+#define GS_API_VERSION 7   /* 7: gs_backward / gs_backward_device / gs_upload_gaussians_device.  6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
                               gs_runtime_versions(), gs_dist_* / gs_gather_strips; 4: GS_ROWS_BALANCED + gs_dist_rebalance /
                               gs_dist_bands, gs_render_sharded_async / gs_sharded_frame / gs_sharded_read (two sharded
                               frames in flight, the assembled frame left in HBM), GS_BUF_COLOR for every non-culled splat */
@@ -211,6 +211,12 @@ const char* gs_last_error(const gs_ctx* ctx);
  * GS_GAUSSIAN_RECORD_BYTES each, as ResourceManager::getGaussians() returns them
  * (ResourceManager.h:53).  Converted once to the device SoA layout. */
 int gs_upload_gaussians(gs_ctx* ctx, const void* aos336, uint32_t n);
+/* The same from DEVICE memory (e.g. a torch tensor's data_ptr, float32 [n][84]), converted by the upload kernel directly.
+ * With the n of the scene the context holds, the planes are rewritten in place: enqueued on the context's stream, no host
+ * sync; every context sharing the scene (gs_share_scene) renders the new values; resolution, scratch and captured graphs
+ * stay.  The caller orders the writes of aos336_dev before this call (e.g. synchronises the stream that wrote it).  With
+ * another n it behaves like gs_upload_gaussians: a new scene (waits), gs_set_resolution must follow. */
+int gs_upload_gaussians_device(gs_ctx* ctx, const void* aos336_dev, uint32_t n);
 /* Frames in flight (the reference keeps GfxSettings::FRAMES_IN_FLIGHT = 3 command buffers, GfxSettings.h:15,
  * Renderer.cpp:304-310, 514): `ctx` renders the gaussians already uploaded to `owner` -- the read-only arrays
  * are shared, everything a frame writes (sort lists, ranges, raster records, image, stream, timings) stays per
@@ -393,6 +399,32 @@ int gs_debug_read(gs_ctx* ctx, int which, void* dst, size_t bytes);
 int gs_set_outputs(gs_ctx* ctx, uint32_t mask);
 int gs_read_output(gs_ctx* ctx, uint32_t which, void* dst, size_t bytes);
 int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes);
+
+/* Gradients of a frame (no reference counterpart): how the last frame enqueued on the context changes with its gaussians.
+ * Input: dL/dRGBA32F float[H][W][4] (the quantities of GS_OUTPUT_RGBA32F: premultiplied colour before the clamp and
+ * alpha = 1 - T_end; the outputs themselves need not be enabled) and dL/dDEPTH float[H][W] (GS_OUTPUT_DEPTH's quantity;
+ * NULL = zero), in real rows, top row first.  Output: dL/d(record) float[N][84] in the 336-byte layout and record order of
+ * gs_upload_gaussians.  Gradients go to the 59 fields a frame reads -- position.xyz, scale.xyz, rot (all four, used
+ * unnormalised as getRotMat uses it), shCoeffs[k].rgb for the coefficients the frame's sh_mode uses (0: all 16, 1: 1..15,
+ * 2: 0 only) and shCoeffs[0].a (opacity); every other float is 0, and so is the whole record of a splat that was culled or
+ * emitted no element.  Camera gradients are not computed.
+ * Boundary convention: the frame is piecewise smooth, and the gradient is the derivative of the branch the frame took with
+ * every discrete decision held fixed -- the near-plane and NDC culls, tile boxes, depth keys and the sorted order; which
+ * entries a pixel blends (f > 0 or alpha < 1/255 skip) and the entry it stops on (nextT < 1e-4, RenderGaussians.comp:127-140);
+ * det == 0 (opacity 0: no gradient); max(colour, 0) in getShColor (no derivative where the colour is below 0); the
+ * IN_VIEW_LIMIT clamp of x/z and y/z in getCovarianceMatrix (Common.glsl:60-63: a clamped ratio passes no derivative).  A
+ * frame whose list overflowed (GS_WARN_OVERFLOW) is differentiated as drawn, truncated.  The frame's sorted list, ranges
+ * and raster records must still be in HBM (they are until the next frame on the context); the scene's current planes are
+ * read.  Bitwise reproducible: no float atomics, the rows of a splat summed in a fixed order -- the same gradients for
+ * every sorter, launch shape, tile order and GS_COUNT_* mode.  Scratch: 40 bytes per list element of capacity + 44 bytes
+ * per gaussian, allocated on the first call and freed with the resolution.
+ *   gs_backward        : HOST pointers; synchronous (grad_records is written when it returns).
+ *   gs_backward_device : the same arguments as DEVICE pointers; enqueued on the context's stream, no host sync.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued: a NULL grad_rgba32f or grad_records, no frame since the
+ * last gs_set_resolution, gs_set_tile_rows*, gs_debug_init_sort_list or upload, a GS_RENDER_FAST context, a context that
+ * owns a subset of the tile rows, a sharded context (gs_dist_shard_rows). */
+int gs_backward(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
+int gs_backward_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
 
 /* Runs ONLY the InitSortList stage of a frame (project + count scan + emit) and waits; afterwards
  * GS_BUF_UNSORTED_*, GS_BUF_COLOR, GS_BUF_COV and GS_BUF_COUNT are readable (stage-level parity). */

@@ -149,6 +149,15 @@ public:
         return dev;
     }
 
+    // Gradients of the last frame (gsplat.h, gs_backward): HOST dL/dRGBA32F [H][W][4], dL/dDEPTH [H][W] (may be nullptr)
+    // -> dL/d(record) [N][84]; device = true: the same as device pointers, enqueued without waiting.
+    int backward(const float* grad_rgba32f, const float* grad_depth, float* grad_records, bool device = false) {
+        const int rc = device ? gs_backward_device(ctx_, grad_rgba32f, grad_depth, grad_records)
+                              : gs_backward(ctx_, grad_rgba32f, grad_depth, grad_records);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

@@ -118,9 +118,10 @@ EXPORTS = [
     "gs_dist_unique_id", "gs_dist_init", "gs_gather_strips", "gs_dist_destroy", "gs_dist_shard_rows", "gs_render_sharded",
     "gs_render_sharded_async", "gs_sharded_frame", "gs_sharded_read", "gs_dist_rebalance", "gs_dist_bands", "gs_balance_rows",
     "gs_set_outputs", "gs_read_output", "gs_output_device",
+    "gs_backward", "gs_backward_device", "gs_upload_gaussians_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
-API_VERSION = 6            # GS_API_VERSION of include/gsplat.h this binding was written against
+API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
 DIST_UNIQUE_ID_BYTES = 128
 
 
@@ -239,6 +240,9 @@ def lib() -> C.CDLL:
     L.gs_set_outputs.argtypes = [ctxp, u32]
     L.gs_read_output.argtypes = [ctxp, u32, vp, C.c_size_t]
     L.gs_output_device.argtypes = [ctxp, u32, C.POINTER(vp), C.POINTER(C.c_size_t)]
+    L.gs_backward.argtypes = [ctxp, vp, vp, vp]
+    L.gs_backward_device.argtypes = [ctxp, vp, vp, vp]
+    L.gs_upload_gaussians_device.argtypes = [ctxp, vp, u32]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -1,0 +1,91 @@
+"""Differentiable GS_RENDER_EXACT frames for PyTorch (include/gsplat.h, gs_backward*).
+
+    r = make_renderer(width, height)                         # one context, reused frame after frame
+    rgba = render(records, view, proj, cam_pos, sh_mode, renderer=r)            # float32 [H, W, 4]
+    rgba, depth = render(records, ..., depth=True, renderer=r)                  # + float32 [H, W]
+
+records: float32 [N, 84] on the renderer's GPU, in the record layout of ResourceManager.setGaussians.  The outputs are the
+GS_OUTPUT_RGBA32F and GS_OUTPUT_DEPTH quantities of the frame (premultiplied colour before the clamp + 1 - T_end, blended
+view depth); their backward is dL/d(records) from the library's HIP kernels.  The records reach the library through
+gs_upload_gaussians_device (no host copy of the scene); the outputs come back through the host.
+
+This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib
+from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager
+
+
+def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
+    """A Renderer for render(): a context on `device` without a scene (the first render uploads one).  kw: Renderer's
+    options (sort_algorithm, render_kernel, ...); render_mode must stay GS_RENDER_EXACT."""
+    r = Renderer(width, height, device=device, record_timings=False, **kw)
+    r.init(ResourceManager())
+    r._autograd_mask = None
+    r._autograd_frame = 0
+    return r
+
+
+def _draw(r: Renderer, records: torch.Tensor, view, proj, cam_pos, sh_mode: int, want_depth: bool):
+    """Upload records (device to device) and draw one frame; returns the host outputs."""
+    mask = _lib.GS_OUTPUT_RGBA32F | (_lib.GS_OUTPUT_DEPTH if want_depth else 0)
+    torch.cuda.current_stream(records.device).synchronize()     # the library works on a stream of its own
+    r.uploadDevice(records.data_ptr(), records.shape[0])
+    if getattr(r, "_autograd_mask", None) != mask:
+        r.setOutputs(rgba32f=True, depth=want_depth)
+        r._autograd_mask = mask
+    v = np.ascontiguousarray(view, dtype=np.float32).reshape(16)
+    p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
+    c = np.ascontiguousarray(cam_pos, dtype=np.float32).reshape(3)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    r._ctx.check(_lib.lib().gs_render_device(r._ctx.handle, ptr(v), ptr(p), ptr(c), int(sh_mode), None))
+    r._autograd_frame = getattr(r, "_autograd_frame", 0) + 1
+    rgba = r.readOutput(_lib.GS_OUTPUT_RGBA32F)
+    depth = r.readOutput(_lib.GS_OUTPUT_DEPTH) if want_depth else None
+    return rgba, depth, r._autograd_frame
+
+
+class _Frame(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, records, renderer, view, proj, cam_pos, sh_mode, want_depth):
+        rgba, depth, frame = _draw(renderer, records, view, proj, cam_pos, sh_mode, want_depth)
+        ctx.renderer, ctx.frame, ctx.args = renderer, frame, (view, proj, cam_pos, sh_mode, want_depth)
+        ctx.save_for_backward(records)
+        out = torch.from_numpy(rgba).to(records.device)
+        if want_depth:
+            return out, torch.from_numpy(depth).to(records.device)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_rgba, grad_depth=None):
+        (records,) = ctx.saved_tensors
+        r = ctx.renderer
+        if r._autograd_frame != ctx.frame:          # another frame was drawn since: draw this one again
+            _draw(r, records.detach(), *ctx.args)
+        g = (grad_rgba if grad_rgba is not None else torch.zeros(r.height, r.width, 4, device=records.device))
+        g = g.to(device=records.device, dtype=torch.float32).contiguous()
+        d = None
+        if ctx.args[4] and grad_depth is not None:
+            d = grad_depth.to(device=records.device, dtype=torch.float32).contiguous()
+        out = torch.empty(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
+        torch.cuda.current_stream(records.device).synchronize()
+        r.backwardDevice(g.data_ptr(), None if d is None else d.data_ptr(), out.data_ptr())
+        r.synchronize()
+        return out, None, None, None, None, None, None
+
+
+def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: bool = False, *, renderer: Renderer):
+    """The frame of `records` (float32 [N, 84], CUDA/HIP, on the renderer's device) under the camera (view, proj: 4 x 4
+    column-major as Camera.getViewMatrix / getProjectionMatrix give them, cam_pos: 3): rgba32f [H, W, 4], and depth [H, W]
+    if asked, both differentiable w.r.t. records."""
+    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
+        raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
+    if not records.is_cuda:
+        raise ValueError("records must be on the GPU")
+    return _Frame.apply(records.contiguous(), renderer, view, proj, cam_pos, int(sh_mode), bool(depth))

@@ -78,7 +78,14 @@ void drop_sort_graph(gs_ctx* c) {
     c->sort_graph_failed = false;
 }
 
+void free_backward(gs_ctx* c) {
+    free_dev(c->bwd.rows); free_dev(c->bwd.offsets); free_dev(c->bwd.block_sums); free_dev(c->bwd.block_offsets);
+    free_dev(c->bwd.sums); free_dev(c->bwd_host_in); free_dev(c->bwd_host_out);
+    c->bwd_frame = false;
+}
+
 void free_resolution(gs_ctx* c) {
+    free_backward(c);
     drop_sort_graph(c);
     free_sort(c->sort);
     free_dev(c->ranges); free_dev(c->tile_order); free_dev(c->framebuffer);
@@ -315,6 +322,7 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     if (c->outputs) c->outputs_valid = true;
     if (tm) { HIP_TRY(c, hipEventRecord(c->ev[5], st)); HIP_TRY(c, hipEventRecord(c->ev[6], st)); }
     c->have_frame = true;
+    c->bwd_frame = true;
     return GS_OK;
 }
 
@@ -652,15 +660,14 @@ int gs_share_scene(gs_ctx* c, gs_ctx* owner) {
     return GS_OK;
 }
 
-int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
-    if (!c) return GS_ERR_INVALID;
-    if (!aos336 || n == 0) return fail(c, GS_ERR_INVALID, "gs_upload_gaussians: empty input");
+// A fresh scene of n records on c: the arrays (shared with nobody yet) and the per-splat scratch; no resolution.
+static int new_scene(gs_ctx* c, uint32_t n, const char* who) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     free_resolution(c);   // capacity depends on n (Renderer.cpp:725)
     free_scene(c);        // contexts that share the previous arrays keep them
     c->shared = new (std::nothrow) SharedScene();
-    if (!c->shared) return fail(c, GS_ERR_INVALID, "gs_upload_gaussians: out of host memory");
+    if (!c->shared) return fail(c, GS_ERR_INVALID, std::string(who) + ": out of host memory");
     c->shared->n = n;
     const size_t N = n;
     {
@@ -674,11 +681,18 @@ int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
         if (e == hipSuccess) e = hipMalloc((void**)&b.block_bounds, ((size_t)(n + 63u) / 64u + 4u) * 8 * sizeof(float));
         if (e != hipSuccess) {
             free_scene(c);
-            return fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians: ") + hipGetErrorString(e));
+            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
         }
         c->scene = b;
     }
     if (int r = alloc_scratch(c, n)) { free_scene(c); return r; }
+    return GS_OK;
+}
+
+int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
+    if (!c) return GS_ERR_INVALID;
+    if (!aos336 || n == 0) return fail(c, GS_ERR_INVALID, "gs_upload_gaussians: empty input");
+    if (int r = new_scene(c, n, "gs_upload_gaussians")) return r;
 
     // AoS -> SoA on the device, through a bounded staging buffer
     const uint32_t chunk = n < (1u << 20) ? n : (1u << 20);
@@ -708,6 +722,33 @@ int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
         if (e != hipSuccess) rc = fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians: ") + hipGetErrorString(e));
     }
     if (rc != GS_OK) { free_scene(c); return rc; }
+    c->n = n;
+    return GS_OK;
+}
+
+int gs_upload_gaussians_device(gs_ctx* c, const void* aos336_dev, uint32_t n) {
+    if (!c) return GS_ERR_INVALID;
+    if (!aos336_dev || n == 0) return fail(c, GS_ERR_INVALID, "gs_upload_gaussians_device: empty input");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const float* src = static_cast<const float*>(aos336_dev);
+    if (c->shared && c->n == n) {
+        // the same scene size: the planes are rewritten in place behind whatever is enqueued on the stream, and every
+        // context that shares them renders the new values; resolution, scratch and captured graphs stay
+        launch_aos_to_soa(src, 0, n, n, c->scene, c->stream);
+        launch_block_bounds(n, c->scene, c->stream);
+        c->bwd_frame = false;
+        HIP_TRY(c, hipGetLastError());
+        return GS_OK;
+    }
+    if (int r = new_scene(c, n, "gs_upload_gaussians_device")) return r;
+    launch_aos_to_soa(src, 0, n, n, c->scene, c->stream);
+    launch_block_bounds(n, c->scene, c->stream);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        free_scene(c);
+        return fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians_device: ") + hipGetErrorString(e));
+    }
     c->n = n;
     return GS_OK;
 }
@@ -827,12 +868,68 @@ int gs_output_device(gs_ctx* c, uint32_t which, void** dev_out, size_t* bytes) {
     return GS_OK;
 }
 
+// gs_backward*: the refusals (nothing enqueued), then the scratch of the first call
+static int backward_prepare(gs_ctx* c, const char* who) {
+    if (c->cfg.render_mode != GS_RENDER_EXACT)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": only GS_RENDER_EXACT frames can be differentiated");
+    if (c->dist_sharded)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": a sharded context (gs_dist_shard_rows) cannot be differentiated");
+    if (!c->capacity || !c->n || !c->bwd_frame)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": no frame since the last gs_set_resolution, gs_set_tile_rows* or upload");
+    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->bwd.rows) {
+        const uint32_t blocks = (c->n + 255u) / 256u;
+        hipError_t e = hipMalloc((void**)&c->bwd.rows, backward_row_bytes(c->capacity));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.offsets, (size_t)c->n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_sums, (size_t)blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_offsets, (size_t)blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.sums, backward_sum_bytes(c->n));
+        if (e != hipSuccess) {
+            const bool frame = c->bwd_frame;
+            free_backward(c);
+            c->bwd_frame = frame;
+            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        }
+    }
+    return GS_OK;
+}
+
+int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
+    if (!c) return GS_ERR_INVALID;
+    if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward_device: null gradient pointer");
+    if (int r = backward_prepare(c, "gs_backward_device")) return r;
+    launch_backward(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, grad_rgba32f, grad_depth,
+                    c->bwd, grad_records, c->stream);
+    return check_launch(c, "gs_backward_device");
+}
+
+int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
+    if (!c) return GS_ERR_INVALID;
+    if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward: null gradient pointer");
+    if (int r = backward_prepare(c, "gs_backward")) return r;
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
+    if (!c->bwd_host_out) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
+    float* din = c->bwd_host_in;
+    HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    launch_backward(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, din,
+                    grad_depth ? din + px * 4 : nullptr, c->bwd, c->bwd_host_out, c->stream);
+    if (int r = check_launch(c, "gs_backward")) return r;
+    HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
 static int apply_tile_rows(gs_ctx* c, uint32_t row_begin, uint32_t row_end, uint32_t stride, uint32_t phase,
                            bool compact_out) {
     c->row_begin = row_begin; c->row_end = row_end; c->row_stride = stride;
     c->first_row = row_begin + phase;
     c->rows_owned = c->first_row < row_end ? (row_end - c->first_row + stride - 1u) / stride : 0u;
     c->compact_out = compact_out;
+    c->bwd_frame = false;
     if (c->elems_note) {           // another band: another list length (GS_COUNT_AUTO learns it from the next frame)
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the old one
         *(volatile uint32_t*)c->elems_note = 0u;
@@ -917,6 +1014,7 @@ int gs_debug_init_sort_list(gs_ctx* c, const float view[16], const float proj[16
     FrameParams fp = make_frame_params(c, view, proj, cam_pos, sh_mode);
     fp.parity = (c->emit_parity ^= 1u);
     c->last_fp = fp;
+    c->bwd_frame = false;
     launch_project(fp, c->scene, c->scratch, c->stream);
     launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, c->stream);
     launch_emit(fp, c->scratch, c->sort, c->stream);

@@ -1,0 +1,546 @@
+// gs_backward.hip -- gradients of the last GS_RENDER_EXACT frame w.r.t. the uploaded gaussians (gs_backward*,
+// include/gsplat.h), as five launches after the frame's own kernels:
+//   k_bwd_block_sums + k_bwd_scan_blocks + k_bwd_offsets : offset[g] = sum of tiles_touched over the splats before g, the
+//                   splat-order position of g's first element -- the position InitSortList's truncation goes by
+//                   (k_emit, k_gather_sorted), so an element of the list has offset[g] + (its tile's index in g's box)
+//                   below the capacity, and every such slot is an element of the list;
+//   k_bwd_blend   : per tile, the blend of RenderGaussians.comp:112-142 replayed front to back in the EXACT arithmetic
+//                   (same expressions, same pinned exp: the same entries contribute and each pixel stops on the same
+//                   entry K with the same T_K), then walked back to front with the colour behind every entry as a running
+//                   sum; the 256 pixels' derivatives of each list entry are reduced on chip in a fixed tree and stored as
+//                   one 10-float row in the slot of the entry, with plain stores;
+//   k_bwd_rowsum  : per splat, its rows summed in slot order (= tile raster order inside its box);
+//   k_bwd_chain   : per splat, the summed row through the per-splat part of the frame (conic <- 2-D covariance <- scale,
+//                   rotation; screen position and depth <- position; colour <- SH coefficients and position), written in
+//                   the 336-byte record layout of gs_upload_gaussians.
+// No float atomics anywhere: the gradients are bitwise reproducible, and the same for every sorter and launch shape of
+// the forward (they depend on the sorted list and the pixels only).
+#include "gs_device_utils.h"
+#include "gs_internal.h"
+
+namespace gs {
+
+constexpr int kBwdBatch = 64;             // list entries staged per step of k_bwd_blend
+constexpr int kRowFloats = 10;            // dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} of one list element
+constexpr int kRecordFloats = 84;         // GS_GAUSSIAN_RECORD_BYTES / 4
+
+// ---- per-splat slot offsets ---------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void k_bwd_block_sums(const uint32_t* __restrict__ touched, uint32_t n,
+                                                         uint32_t* __restrict__ block_sums) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t t = wave_sum_to_lane63(g < n ? touched[g] : 0u);   // < 256 * tiles: no overflow
+    if (lane_id() == 63) s_w[wave_id()] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+// One workgroup: exclusive scan of the block sums with a 64-bit running total, stored saturated at 2^32 - 1 (beyond any
+// capacity: the slots of such splats are not elements of the list).
+__global__ __launch_bounds__(1024) void k_bwd_scan_blocks(const uint32_t* __restrict__ block_sums, uint32_t blocks,
+                                                           uint32_t* __restrict__ block_offsets) {
+    __shared__ uint64_t s_w[16];
+    const uint32_t per = (blocks + 1023u) / 1024u;
+    const uint32_t b0 = threadIdx.x * per;
+    uint64_t mine = 0;
+    for (uint32_t k = 0; k < per; ++k)
+        if (b0 + k < blocks) mine += block_sums[b0 + k];
+    const uint64_t inc = wave_inclusive_scan64(mine);
+    if (lane_id() == 63) s_w[wave_id()] = inc;
+    __syncthreads();
+    uint64_t run = inc - mine;
+    for (int w = 0; w < wave_id(); ++w) run += s_w[w];
+    for (uint32_t k = 0; k < per; ++k) {
+        if (b0 + k < blocks) {
+            block_offsets[b0 + k] = run < 0xFFFFFFFFull ? (uint32_t)run : 0xFFFFFFFFu;
+            run += block_sums[b0 + k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bwd_offsets(const uint32_t* __restrict__ touched, uint32_t n,
+                                                      const uint32_t* __restrict__ block_offsets,
+                                                      uint32_t* __restrict__ offsets) {
+    __shared__ uint32_t s_w[4];
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t cnt = g < n ? touched[g] : 0u;
+    const uint32_t inc = wave_inclusive_scan(cnt);
+    if (lane_id() == 63) s_w[wave_id()] = inc;
+    __syncthreads();
+    uint32_t before = inc - cnt;
+    for (int w = 0; w < wave_id(); ++w) before += s_w[w];
+    const uint64_t off = (uint64_t)block_offsets[blockIdx.x] + before;
+    if (g < n) offsets[g] = off < 0xFFFFFFFFull ? (uint32_t)off : 0xFFFFFFFFu;
+}
+
+// ---- blend backward -----------------------------------------------------------------------------------------------
+
+struct BwdBlendArgs {
+    const SplatRaster* raster;
+    const uint32_t* sorted_id;
+    const uint32_t* ranges;
+    const float* pos;               // SceneBuffers::pos (the view depth of an entry, with grad_depth)
+    const float4* grad_rgba;        // [H][W] dL/dRGBA32F
+    const float* grad_depth;        // [H][W] dL/dDEPTH or null
+    const uint32_t* offsets;        // [N] k_bwd_offsets
+    const uint2* extents;           // SplatScratch::extents
+    float* rows;                    // [capacity][kRowFloats]
+    uint32_t capacity;
+};
+
+// The exponent of RenderGaussians.comp:119-123 in the operand order of k_render / blend_pair (contraction is off)
+__device__ __forceinline__ float blend_exponent(float sx, float sy, float ix, float iy, float iz, float fpx, float fpy,
+                                                float& ex, float& ey) {
+    ex = sx - fpx;
+    ey = -(sy - fpy);
+    return -0.5f * (ix * ex * ex + iz * ey * ey) - iy * ex * ey;
+}
+
+// One 256-thread workgroup per tile, one pixel per lane (wave w: pixel rows 4 w .. 4 w + 3).
+__global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const BwdBlendArgs a) {
+    // staged entries: sx, sy, ix, iy, iz, alpha0, r, g, b, z, slot (bits), -
+    __shared__ float s_e[kBwdBatch][12];
+    __shared__ float s_part[4][kBwdBatch][kRowFloats];   // per-wave sums of an entry's row
+    __shared__ uint32_t s_kend;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tile = blockIdx.x;                                // a full grid: compact id == global id
+    const uint32_t ty = tile / fp.grid_w, tx = tile % fp.grid_w;
+    const uint32_t start = a.ranges[tile * 2 + 0], end = a.ranges[tile * 2 + 1];
+    const uint32_t px = tx * kTile + (uint32_t)(tid & 15), py = ty * kTile + (uint32_t)(tid >> 4);
+    const bool inside = px < fp.width && py < fp.height;
+    const float fpx = (float)px, fpy = (float)py;
+    const bool want_z = a.grad_depth != nullptr;
+    if (tid == 0) s_kend = 0u;
+
+    // stages entries [i0, i0 + count) of the list into s_e (threads 0 .. count - 1)
+    auto stage = [&](uint32_t i0, uint32_t count) {
+        if ((uint32_t)tid < count) {
+            const uint32_t gi = a.sorted_id[i0 + tid];
+            const float4* rp = reinterpret_cast<const float4*>(a.raster + gi);
+            const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
+            float z = 0.0f;
+            if (want_z) {   // -viewSpacePos.z as k_project computes it (mat4_mul_vec4, row 2)
+                const size_t n = fp.num_gaussians;
+                float acc = fp.view[2] * a.pos[gi];
+                acc = acc + fp.view[6] * a.pos[n + gi];
+                acc = acc + fp.view[10] * a.pos[2 * n + gi];
+                acc = acc + fp.view[14] * 1.0f;
+                z = -acc;
+            }
+            const uint2 ext = a.extents[gi];
+            const uint32_t min_x = ext.x & 0xFFFFu, k0 = ext.x >> 16, max_x = ext.y & 0xFFFFu;
+            const uint64_t slot = (uint64_t)a.offsets[gi] + (uint64_t)(ty - k0) * (max_x - min_x) + (tx - min_x);
+            float* e = s_e[tid];
+            e[0] = r0.x; e[1] = r0.y; e[2] = r0.z; e[3] = r0.w; e[4] = r1.x;
+            e[5] = r2.x; e[6] = r1.y; e[7] = r1.z; e[8] = r1.w; e[9] = z;
+            e[10] = __uint_as_float(slot < a.capacity ? (uint32_t)slot : 0xFFFFFFFFu);
+        }
+    };
+    // the entry's test and alpha, bit for bit those of the forward: contributes = !(f > 0) && !(alpha < 1/255)
+    auto entry_alpha = [&](const float* e, float& ex, float& ey, float& expf_, bool& contributes) {
+        const float f = blend_exponent(e[0], e[1], e[2], e[3], e[4], fpx, fpy, ex, ey);
+        expf_ = exp_pinned_live(f);
+        const float alpha = e[5] * expf_;
+        contributes = !(f > 0.0f) && !(alpha < 1.0f / 255.0f);
+        return alpha;
+    };
+
+    // 1. forward replay: the last contributing entry K of the pixel and the transmittance T_K in front of it
+    uint32_t last = 0xFFFFFFFFu;
+    float T = 1.0f, TK = 0.0f;
+    bool done = !inside;
+    for (uint32_t i0 = start; i0 < end; i0 += kBwdBatch) {
+        const uint32_t cnt = end - i0 < (uint32_t)kBwdBatch ? end - i0 : (uint32_t)kBwdBatch;
+        stage(i0, cnt);
+        __syncthreads();
+        if (!done) {
+            for (uint32_t j = 0; j < cnt; ++j) {
+                float ex, ey, ef;
+                bool contributes;
+                const float alpha = entry_alpha(s_e[j], ex, ey, ef, contributes);
+                if (!contributes) continue;
+                const float next_t = T * (1.0f - alpha);                       // :133
+                last = i0 + j;
+                TK = T;
+                if (next_t < 0.0001f) { done = true; break; }                  // :136-140, colour already added
+                T = next_t;
+            }
+        }
+        if (__syncthreads_and(done)) break;                                    // also: s_e is free again
+    }
+    if (last != 0xFFFFFFFFu) atomicMax(&s_kend, last + 1u);                  // entries at or after s_kend: zero rows
+    __syncthreads();
+    const uint32_t kend = s_kend > start ? s_kend : start;
+
+    // 2. back to front over [start, kend)
+    float4 gc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float gd = 0.0f;
+    if (inside && last != 0xFFFFFFFFu) {
+        gc = a.grad_rgba[(size_t)py * fp.width + px];
+        if (want_z) gd = a.grad_depth[(size_t)py * fp.width + px];
+    }
+    float Tcur = TK;                                  // T in front of the entry processed last (walking back)
+    float Sr = 0.f, Sg = 0.f, Sb = 0.f, Sa = 0.f, Sz = 0.f;   // colour, alpha, depth behind it (divided by its T)
+    for (uint32_t i1 = kend; i1 > start;) {
+        const uint32_t i0 = i1 - start > (uint32_t)kBwdBatch ? i1 - (uint32_t)kBwdBatch : start;
+        const uint32_t cnt = i1 - i0;
+        stage(i0, cnt);
+        __syncthreads();
+        for (int j = (int)cnt - 1; j >= 0; --j) {
+            const uint32_t i = i0 + (uint32_t)j;
+            const float* e = s_e[j];
+            float ex, ey, ef;
+            bool contributes;
+            const float alpha = entry_alpha(e, ex, ey, ef, contributes);
+            contributes = contributes && last != 0xFFFFFFFFu && i <= last;
+            float v[kRowFloats];
+#pragma unroll
+            for (int k = 0; k < kRowFloats; ++k) v[k] = 0.0f;
+            if (contributes) {
+                const float one_m = 1.0f - alpha;                              // the forward's own (1 - alpha)
+                const float Ti = i == last ? TK : Tcur / one_m;                // T_{i+1} >= 1e-4 here: no early-out before K
+                const float cr = e[6], cg = e[7], cb = e[8], z = e[9];
+                const float dalpha = Ti * (gc.x * (cr - Sr) + gc.y * (cg - Sg) + gc.z * (cb - Sb) + gc.w * (1.0f - Sa) +
+                                           gd * (z - Sz));
+                const float w = Ti * alpha;
+                const float df = dalpha * alpha;                               // alpha = a * exp(f)
+                const float ix = e[2], iy = e[3], iz = e[4];
+                v[0] = df * (-(ix * ex) - iy * ey);                            // d f / d sx  (ex = sx - px)
+                v[1] = df * (iz * ey + iy * ex);                               // d f / d sy  (ey = py - sy)
+                v[2] = df * (-0.5f * ex * ex);
+                v[3] = df * (-ex * ey);
+                v[4] = df * (-0.5f * ey * ey);
+                v[5] = gc.x * w; v[6] = gc.y * w; v[7] = gc.z * w;
+                v[8] = dalpha * ef;
+                v[9] = gd * w;
+                Sr = alpha * cr + one_m * Sr;
+                Sg = alpha * cg + one_m * Sg;
+                Sb = alpha * cb + one_m * Sb;
+                Sa = alpha + one_m * Sa;
+                Sz = alpha * z + one_m * Sz;
+                Tcur = Ti;
+            }
+            // the wave's sum in a fixed butterfly (every lane ends with the same bits), then one lane parks it
+            if (__ballot(contributes) != 0ull) {
+#pragma unroll
+                for (int k = 0; k < kRowFloats; ++k) {
+#pragma unroll
+                    for (int off = 1; off < 64; off <<= 1) v[k] += __shfl_xor(v[k], off, 64);
+                }
+            }
+            if (lane == 0) {
+#pragma unroll
+                for (int k = 0; k < kRowFloats; ++k) s_part[wave][j][k] = v[k];
+            }
+        }
+        __syncthreads();
+        // the four waves' sums in a fixed order -> the entry's row, in its slot
+        for (uint32_t q = (uint32_t)tid; q < cnt * kRowFloats; q += 256u) {
+            const uint32_t j = q / kRowFloats, k = q % kRowFloats;
+            const uint32_t slot = __float_as_uint(s_e[j][10]);
+            const float sum = ((s_part[0][j][k] + s_part[1][j][k]) + s_part[2][j][k]) + s_part[3][j][k];
+            if (slot != 0xFFFFFFFFu) a.rows[(size_t)slot * kRowFloats + k] = sum;
+        }
+        __syncthreads();
+        i1 = i0;
+    }
+    // 3. entries no pixel of the tile reaches: zero rows
+    for (uint32_t i0 = kend; i0 < end; i0 += kBwdBatch) {
+        const uint32_t cnt = end - i0 < (uint32_t)kBwdBatch ? end - i0 : (uint32_t)kBwdBatch;
+        stage(i0, cnt);
+        __syncthreads();
+        for (uint32_t q = (uint32_t)tid; q < cnt * kRowFloats; q += 256u) {
+            const uint32_t slot = __float_as_uint(s_e[q / kRowFloats][10]);
+            if (slot != 0xFFFFFFFFu) a.rows[(size_t)slot * kRowFloats + q % kRowFloats] = 0.0f;
+        }
+        __syncthreads();
+    }
+}
+
+// ---- per splat ----------------------------------------------------------------------------------------------------
+
+// Sum of the splat's rows in slot order; zero for a splat that emits nothing.
+__global__ __launch_bounds__(256) void k_bwd_rowsum(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
+                                                     const float* __restrict__ rows, uint32_t n, uint32_t capacity,
+                                                     float* __restrict__ sums) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n) return;
+    float acc[kRowFloats];
+#pragma unroll
+    for (int k = 0; k < kRowFloats; ++k) acc[k] = 0.0f;
+    const uint64_t o = offsets[g];
+    const uint64_t e = o + touched[g];
+    const uint64_t stop = e < capacity ? e : capacity;
+    for (uint64_t s = o; s < stop; ++s) {
+        const float* r = rows + s * kRowFloats;
+#pragma unroll
+        for (int k = 0; k < kRowFloats; ++k) acc[k] += r[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kRowFloats; ++k) sums[(size_t)g * kRowFloats + k] = acc[k];
+}
+
+// GLSL `M * v`, M column-major, in the reference's operand order
+__device__ __forceinline__ void bwd_mat4_vec4(const float* m, float vx, float vy, float vz, float vw, float out[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float acc = m[0 * 4 + r] * vx;
+        acc = acc + m[1 * 4 + r] * vy;
+        acc = acc + m[2 * 4 + r] * vz;
+        acc = acc + m[3 * 4 + r] * vw;
+        out[r] = acc;
+    }
+}
+
+// Common.glsl:94-138 as a function of (X, Y, Z) = (-dx, -dy, dz), with its partial derivatives
+__device__ __forceinline__ void sh_basis_grad(float X, float Y, float Z, float b[16], float bx[16], float by[16], float bz[16]) {
+    const float S1 = 2.0f * X * Y, C1 = X * X - Y * Y;
+    const float S2 = X * S1 + Y * C1, C2 = X * C1 - Y * S1;
+    const float Z2 = Z * Z;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { bx[k] = 0.0f; by[k] = 0.0f; bz[k] = 0.0f; }
+    b[0] = 0.2820947917738781f;
+    b[1] = -0.48860251190292f * Y;                  by[1] = -0.48860251190292f;
+    b[2] = 0.4886025119029199f * Z;                 bz[2] = 0.4886025119029199f;
+    b[3] = -0.48860251190292f * X;                  bx[3] = -0.48860251190292f;
+    b[4] = 0.5462742152960395f * S1;                bx[4] = 0.5462742152960395f * 2.0f * Y; by[4] = 0.5462742152960395f * 2.0f * X;
+    b[5] = -1.092548430592079f * Z * Y;             by[5] = -1.092548430592079f * Z; bz[5] = -1.092548430592079f * Y;
+    b[6] = 0.9461746957575601f * Z2 + -0.31539156525252f;   bz[6] = 0.9461746957575601f * 2.0f * Z;
+    b[7] = -1.092548430592079f * Z * X;             bx[7] = -1.092548430592079f * Z; bz[7] = -1.092548430592079f * X;
+    b[8] = 0.5462742152960395f * C1;                bx[8] = 0.5462742152960395f * 2.0f * X; by[8] = 0.5462742152960395f * -2.0f * Y;
+    b[9] = -0.5900435899266435f * S2;               bx[9] = -0.5900435899266435f * 6.0f * X * Y;
+                                                    by[9] = -0.5900435899266435f * 3.0f * (X * X - Y * Y);
+    b[10] = 1.445305721320277f * Z * S1;            bx[10] = 1.445305721320277f * Z * 2.0f * Y; by[10] = 1.445305721320277f * Z * 2.0f * X;
+                                                    bz[10] = 1.445305721320277f * S1;
+    const float tc = -2.285228997322329f * Z2 + 0.4570457994644658f, dtc = -2.285228997322329f * 2.0f * Z;
+    b[11] = tc * Y;                                 by[11] = tc; bz[11] = dtc * Y;
+    b[12] = Z * (1.865881662950577f * Z2 + -1.119528997770346f);
+                                                    bz[12] = 3.0f * 1.865881662950577f * Z2 + -1.119528997770346f;
+    b[13] = tc * X;                                 bx[13] = tc; bz[13] = dtc * X;
+    b[14] = 1.445305721320277f * Z * C1;            bx[14] = 1.445305721320277f * Z * 2.0f * X; by[14] = 1.445305721320277f * Z * -2.0f * Y;
+                                                    bz[14] = 1.445305721320277f * C1;
+    b[15] = -0.5900435899266435f * C2;              bx[15] = -0.5900435899266435f * 3.0f * (X * X - Y * Y);
+                                                    by[15] = -0.5900435899266435f * -6.0f * X * Y;
+}
+
+// From the summed row of a splat to dL/d(record).  The branch the forward took is held fixed: the clamp of x/z, y/z in
+// getCovarianceMatrix (a clamped component passes no derivative to the ratio), max(colour, 0) (no derivative below 0),
+// det == 0 (opacity 0: the splat never contributes, all zero).
+__global__ __launch_bounds__(256) void k_bwd_chain(const FrameParams fp, const SceneBuffers scene,
+                                                    const uint32_t* __restrict__ touched, const float* __restrict__ sums,
+                                                    float* __restrict__ out) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t n = fp.num_gaussians;
+    if (g >= n) return;
+    float4* o = reinterpret_cast<float4*>(out + (size_t)g * kRecordFloats);
+    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* rs = sums + (size_t)g * kRowFloats;
+    float row[kRowFloats];
+#pragma unroll
+    for (int k = 0; k < kRowFloats; ++k) row[k] = rs[k];
+    bool any = touched[g] != 0u;
+    if (any) {
+        bool nz = false;
+#pragma unroll
+        for (int k = 0; k < kRowFloats; ++k) nz = nz || row[k] != 0.0f;
+        any = nz;
+    }
+    if (!any) {
+#pragma unroll
+        for (int k = 0; k < kRecordFloats / 4; ++k) o[k] = zero4;
+        return;
+    }
+    const float dsx = row[0], dsy = row[1], dix = row[2], diy = row[3], diz = row[4];
+    const float dcol[3] = {row[5], row[6], row[7]};
+    const float dop = row[8], dz = row[9];
+    const float p[3] = {scene.pos[g], scene.pos[(size_t)n + g], scene.pos[2 * (size_t)n + g]};
+    float s[3], q[4];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = scene.scale[(size_t)k * n + g];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = scene.rot[(size_t)k * n + g];
+    const float qr = q[0], qx = q[1], qy = q[2], qz = q[3];
+
+    float vp[4], cp[4];
+    bwd_mat4_vec4(fp.view, p[0], p[1], p[2], 1.0f, vp);
+    bwd_mat4_vec4(fp.proj, vp[0], vp[1], vp[2], vp[3], cp);
+    float dvp[4] = {0.f, 0.f, 0.f, 0.f};
+
+    // screen position (Common.glsl:80-89): s = ((+-ndc + 1) / 2) * extent, ndc = clip.xy / clip.w
+    {
+        const float dnx = dsx * 0.5f * (float)fp.width, dny = -dsy * 0.5f * (float)fp.height;
+        const float rw = 1.0f / cp[3];
+        const float dc[4] = {dnx * rw, dny * rw, 0.0f, -(dnx * cp[0] + dny * cp[1]) * rw * rw};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            dvp[c] += fp.proj[c * 4 + 0] * dc[0] + fp.proj[c * 4 + 1] * dc[1] + fp.proj[c * 4 + 3] * dc[3];
+    }
+    dvp[2] += -dz;                                          // depth = -viewSpacePos.z
+
+    // 2-D covariance (Common.glsl:32-78) and its inverse (RenderGaussians.comp:94-107)
+    float R[3][3];                                          // R[row][col] of getRotMat
+    R[0][0] = 1.0f - 2.0f * qy * qy - 2.0f * qz * qz; R[1][0] = 2.0f * qx * qy - 2.0f * qr * qz; R[2][0] = 2.0f * qx * qz + 2.0f * qr * qy;
+    R[0][1] = 2.0f * qx * qy + 2.0f * qr * qz; R[1][1] = 1.0f - 2.0f * qx * qx - 2.0f * qz * qz; R[2][1] = 2.0f * qy * qz - 2.0f * qr * qx;
+    R[0][2] = 2.0f * qx * qz - 2.0f * qr * qy; R[1][2] = 2.0f * qy * qz + 2.0f * qr * qx; R[2][2] = 1.0f - 2.0f * qx * qx - 2.0f * qy * qy;
+    float M[3][3], Sg[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) M[i][k] = R[i][k] * s[k];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Sg[i][j] = M[i][0] * M[j][0] + M[i][1] * M[j][1] + M[i][2] * M[j][2];
+    const float wdt = (float)fp.width, hgt = (float)fp.height;
+    const float tfy = fp.tan_fov_y, tfx = tfy * wdt / hgt;
+    const float fx = wdt / (2.0f * tfx), fy = hgt / (2.0f * tfy);
+    const float lim_x = tfx * fp.in_view_limit, lim_y = tfy * fp.in_view_limit;
+    const float tz = vp[2];
+    const float rx = vp[0] / tz, ry = vp[1] / tz;
+    const bool clamp_x = rx < -lim_x || rx > lim_x, clamp_y = ry < -lim_y || ry > lim_y;
+    const float ux = clampf(rx, -lim_x, lim_x), uy = clampf(ry, -lim_y, lim_y);
+    const float pvx = ux * tz, pvy = uy * tz;
+    const float J00 = fx / tz, J11 = fy / tz, J02 = -(fx * pvx) / (tz * tz), J12 = -(fy * pvy) / (tz * tz);
+    float W[3][3], Tm[2][3];                                // W[row][col] = view; T = J W (its third row is zero)
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W[r][c] = fp.view[c * 4 + r];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { Tm[0][c] = J00 * W[0][c] + J02 * W[2][c]; Tm[1][c] = J11 * W[1][c] + J12 * W[2][c]; }
+    float TS[2][3];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) TS[r][c] = Tm[r][0] * Sg[0][c] + Tm[r][1] * Sg[1][c] + Tm[r][2] * Sg[2][c];
+    const float ca = TS[0][0] * Tm[0][0] + TS[0][1] * Tm[0][1] + TS[0][2] * Tm[0][2] + 0.3f;
+    const float cb = TS[1][0] * Tm[0][0] + TS[1][1] * Tm[0][1] + TS[1][2] * Tm[0][2];
+    const float cc = TS[1][0] * Tm[1][0] + TS[1][1] * Tm[1][1] + TS[1][2] * Tm[1][2] + 0.3f;
+    const float det = ca * cc - cb * cb;
+
+    float dpos[3] = {0.f, 0.f, 0.f}, dscale[3] = {0.f, 0.f, 0.f}, drot[4] = {0.f, 0.f, 0.f, 0.f};
+    if (det != 0.0f) {
+        const float rd = 1.0f / det;
+        const float ix = cc * rd, iy = -cb * rd, iz = ca * rd;
+        const float ddet = -(dix * ix + diy * iy + diz * iz) * rd;
+        const float da = diz * rd + ddet * cc, db = -diy * rd - 2.0f * cb * ddet, dcc = dix * rd + ddet * ca;
+        const float Gs[2][2] = {{2.0f * da, db}, {db, 2.0f * dcc}};   // dL/dSigma' + its transpose (upper 2 x 2)
+        float GT[2][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) GT[r][c] = Gs[r][0] * Tm[0][c] + Gs[r][1] * Tm[1][c];
+        // dL/dT = Gs T Sigma;  dL/dM = (T^T Gs T) M
+        float dT[2][3], dSs[3][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dT[r][c] = GT[r][0] * Sg[0][c] + GT[r][1] * Sg[1][c] + GT[r][2] * Sg[2][c];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) dSs[i][j] = Tm[0][i] * GT[0][j] + Tm[1][i] * GT[1][j];
+        float dR[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float dM = dSs[i][0] * M[0][k] + dSs[i][1] * M[1][k] + dSs[i][2] * M[2][k];
+                dR[i][k] = dM * s[k];
+                dscale[k] += dM * R[i][k];
+            }
+        // getRotMat's entries as functions of (r, x, y, z)
+        drot[0] = 2.0f * (-qz * dR[1][0] + qy * dR[2][0] + qz * dR[0][1] - qx * dR[2][1] - qy * dR[0][2] + qx * dR[1][2]);
+        drot[1] = 2.0f * (qy * dR[1][0] + qz * dR[2][0] + qy * dR[0][1] - 2.0f * qx * dR[1][1] - qr * dR[2][1] +
+                          qz * dR[0][2] + qr * dR[1][2] - 2.0f * qx * dR[2][2]);
+        drot[2] = 2.0f * (-2.0f * qy * dR[0][0] + qx * dR[1][0] + qr * dR[2][0] + qx * dR[0][1] + qz * dR[2][1] -
+                          qr * dR[0][2] + qz * dR[1][2] - 2.0f * qy * dR[2][2]);
+        drot[3] = 2.0f * (-2.0f * qz * dR[0][0] - qr * dR[1][0] + qx * dR[2][0] + qr * dR[0][1] - 2.0f * qz * dR[1][1] +
+                          qy * dR[2][1] + qx * dR[0][2] + qy * dR[1][2]);
+        // dL/dJ = dL/dT W^T, then J's dependence on the view-space position
+        float dJ[2][3];
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) dJ[r][k] = dT[r][0] * W[k][0] + dT[r][1] * W[k][1] + dT[r][2] * W[k][2];
+        const float tz2 = tz * tz, tz3 = tz2 * tz;
+        float dtz = -fx / tz2 * dJ[0][0] - fy / tz2 * dJ[1][1] + 2.0f * fx * pvx / tz3 * dJ[0][2] + 2.0f * fy * pvy / tz3 * dJ[1][2];
+        const float dpvx = -fx / tz2 * dJ[0][2], dpvy = -fy / tz2 * dJ[1][2];
+        // pv.x = clamp(x / z) * z: d/dx = 1, d/dz = 0 inside the limits; d/dx = 0, d/dz = +-limit on the clamp
+        if (clamp_x) dtz += dpvx * ux; else dvp[0] += dpvx;
+        if (clamp_y) dtz += dpvy * uy; else dvp[1] += dpvy;
+        dvp[2] += dtz;
+    }
+
+    // colour (Common.glsl:141-170, InitSortList.comp:124-126)
+    const float ddx = p[0] - fp.cam_pos[0], ddy = p[1] - fp.cam_pos[1], ddz = p[2] - fp.cam_pos[2];
+    const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+    const float dir[3] = {ddx / len, ddy / len, ddz / len};
+    float b[16], bx[16], by[16], bz[16];
+    sh_basis_grad(-dir[0], -dir[1], dir[2], b, bx, by, bz);
+    const int k_lo = fp.sh_mode == 1u ? 1 : 0, k_hi = fp.sh_mode == 2u ? 1 : 16;
+    float dres[3];
+    {
+        const float* shp = scene.sh + g;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float res = 0.0f;
+            for (int k = k_lo; k < k_hi; ++k) res += shp[(size_t)(k * 3 + c) * n] * b[k];
+            if (fp.sh_mode == 1u) res -= 0.5f;
+            res += 0.5f;
+            dres[c] = res >= 0.0f ? dcol[c] : 0.0f;                     // max(colour, 0)
+        }
+        float dX = 0.f, dY = 0.f, dZ = 0.f;
+        if (fp.sh_mode != 2u) {
+            for (int k = k_lo; k < k_hi; ++k) {
+                const float db_k = dres[0] * shp[(size_t)(k * 3 + 0) * n] + dres[1] * shp[(size_t)(k * 3 + 1) * n] +
+                                   dres[2] * shp[(size_t)(k * 3 + 2) * n];
+                dX += db_k * bx[k]; dY += db_k * by[k]; dZ += db_k * bz[k];
+            }
+        }
+        const float dd[3] = {-dX, -dY, dZ};                              // d/d(dir)
+        const float dot = dd[0] * dir[0] + dd[1] * dir[1] + dd[2] * dir[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dpos[k] += (dd[k] - dir[k] * dot) / len;
+    }
+    // view-space position <- world position
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        dpos[k] += fp.view[k * 4 + 0] * dvp[0] + fp.view[k * 4 + 1] * dvp[1] + fp.view[k * 4 + 2] * dvp[2] + fp.view[k * 4 + 3] * dvp[3];
+
+    o[0] = make_float4(dpos[0], dpos[1], dpos[2], 0.0f);
+    o[1] = make_float4(dscale[0], dscale[1], dscale[2], 0.0f);
+    o[2] = make_float4(drot[0], drot[1], drot[2], drot[3]);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const bool used = k >= k_lo && k < k_hi;
+        o[3 + k] = make_float4(used ? dres[0] * b[k] : 0.0f, used ? dres[1] * b[k] : 0.0f, used ? dres[2] * b[k] : 0.0f,
+                               k == 0 ? dop : 0.0f);
+    }
+    o[19] = zero4;                                                       // color
+    o[20] = zero4;                                                       // covariance
+}
+
+void launch_backward(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, const uint32_t* sorted_id,
+                     const uint32_t* ranges, const float* grad_rgba, const float* grad_depth, const BackwardBuffers& bb,
+                     float* grad_records, hipStream_t stream) {
+    const uint32_t n = fp.num_gaussians;
+    const uint32_t blocks = (n + 255u) / 256u;
+    const uint32_t tiles = fp.grid_w * fp.grid_h;
+    hipLaunchKernelGGL(k_bwd_block_sums, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_sums);
+    hipLaunchKernelGGL(k_bwd_scan_blocks, dim3(1), dim3(1024), 0, stream, bb.block_sums, blocks, bb.block_offsets);
+    hipLaunchKernelGGL(k_bwd_offsets, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_offsets, bb.offsets);
+    const BwdBlendArgs args{sc.raster, sorted_id, ranges, scene.pos, reinterpret_cast<const float4*>(grad_rgba),
+                            grad_depth, bb.offsets, sc.extents, bb.rows, fp.capacity};
+    hipLaunchKernelGGL(k_bwd_blend, dim3(tiles), dim3(256), 0, stream, fp, args);
+    hipLaunchKernelGGL(k_bwd_rowsum, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, bb.offsets, bb.rows, n,
+                       fp.capacity, bb.sums);
+    hipLaunchKernelGGL(k_bwd_chain, dim3(blocks), dim3(256), 0, stream, fp, scene, sc.tiles_touched, bb.sums, grad_records);
+}
+
+size_t backward_row_bytes(uint32_t capacity) { return (size_t)capacity * kRowFloats * sizeof(float); }
+size_t backward_sum_bytes(uint32_t n) { return (size_t)n * kRowFloats * sizeof(float); }
+
+} // namespace gs

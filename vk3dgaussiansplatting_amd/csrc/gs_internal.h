@@ -241,6 +241,21 @@ struct RenderOutputs {
 void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
                    const uint32_t* ranges, const uint32_t* order, uint8_t* rgba, uint32_t render_mode,
                    uint32_t render_kernel, hipStream_t stream, const RenderOutputs& outs = RenderOutputs{});
+// gs_backward* (gs_backward.hip): scratch of a backward pass, allocated on the first call
+struct BackwardBuffers {
+    float* rows;              // [capacity][10]  dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} per element, in its slot
+    uint32_t* offsets;        // [N]  first slot of a splat: its tiles_touched summed over the splats before it (saturated)
+    uint32_t* block_sums;     // [ceil(N / 256)]
+    uint32_t* block_offsets;  // [ceil(N / 256)]
+    float* sums;              // [N][10]  a splat's rows summed in slot order
+};
+size_t backward_row_bytes(uint32_t capacity);
+size_t backward_sum_bytes(uint32_t n);
+// dL/d(record) [N][84] of the last frame (fp = its FrameParams, full grid, GS_RENDER_EXACT), from dL/dRGBA32F [H][W][4] and
+// dL/dDEPTH [H][W] (may be null).
+void launch_backward(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, const uint32_t* sorted_id,
+                     const uint32_t* ranges, const float* grad_rgba, const float* grad_depth, const BackwardBuffers& bb,
+                     float* grad_records, hipStream_t stream);
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,
                        const SceneBuffers& s, hipStream_t stream);
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream);

@@ -141,19 +141,6 @@ __device__ __forceinline__ v2f exp_pinned2_live(v2f x) {
                  __uint_as_float(__float_as_uint(p.y) + (__float_as_uint(tn.y) << 23))};
 }
 
-__device__ __forceinline__ float exp_pinned_live(float x) {            // the scalar form of exp_pinned2_live
-    const float t = __builtin_fmaxf(x * 0x1.715476p+0f, -126.0f);
-    const float tn = t + 12582912.0f;
-    const float r = t - (tn - 12582912.0f);
-    float p = 0x1.42059ap-13f;
-    p = __builtin_fmaf(p, r, 0x1.5f3e12p-10f);
-    p = __builtin_fmaf(p, r, 0x1.3b2d40p-7f);
-    p = __builtin_fmaf(p, r, 0x1.c6aeeap-5f);
-    p = __builtin_fmaf(p, r, 0x1.ebfbdcp-3f);
-    p = __builtin_fmaf(p, r, 0x1.62e430p-1f);
-    p = __builtin_fmaf(p, r, 1.0f);
-    return __uint_as_float(__float_as_uint(p) + (__float_as_uint(tn) << 23));
-}
 #ifdef GS_RENDER_EXP_CLAMPS
 #define GS_EXP1 exp_pinned
 #define GS_EXP2 exp_pinned2

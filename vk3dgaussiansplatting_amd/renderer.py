@@ -561,6 +561,41 @@ class Renderer:
         self._ctx.check(_lib.lib().gs_output_device(self._ctx.handle, int(which), C.byref(dev), C.byref(size)))
         return int(dev.value)
 
+    # -- gradients of a frame (no reference counterpart; include/gsplat.h, gs_backward*)
+    def backward(self, grad_rgba32f: np.ndarray, grad_depth: np.ndarray | None = None) -> np.ndarray:
+        """dL/d(record), float32 (N, 84) in the record layout of setGaussians, of the last frame drawn (GS_RENDER_EXACT, whole
+        frame) from dL/dRGBA32F (float32 (H, W, 4)) and optionally dL/dDEPTH (float32 (H, W)): the quantities of
+        setOutputs(rgba32f=True, depth=True), whether or not they are enabled."""
+        info = self.sceneInfo()
+        g = np.ascontiguousarray(grad_rgba32f, dtype=np.float32)
+        if g.shape != (info.height, info.width, 4):
+            raise ValueError(f"grad_rgba32f must have shape {(info.height, info.width, 4)}, not {g.shape}")
+        d = None
+        if grad_depth is not None:
+            d = np.ascontiguousarray(grad_depth, dtype=np.float32)
+            if d.shape != (info.height, info.width):
+                raise ValueError(f"grad_depth must have shape {(info.height, info.width)}, not {d.shape}")
+        out = np.zeros((info.num_gaussians, FLOATS_PER_GAUSSIAN), dtype=np.float32)
+        self._ctx.check(_lib.lib().gs_backward(self._ctx.handle, _p(g), None if d is None else _p(d), _p(out)))
+        return out
+
+    def backwardDevice(self, grad_rgba32f_ptr: int, grad_depth_ptr: int | None, grad_records_ptr: int):
+        """The same with device addresses (float32 (H, W, 4), (H, W) or None, (N, 84)); enqueued on the context's stream
+        without waiting (synchronize() waits)."""
+        self._ctx.check(_lib.lib().gs_backward_device(self._ctx.handle, C.c_void_p(grad_rgba32f_ptr),
+                                                      C.c_void_p(grad_depth_ptr) if grad_depth_ptr else None,
+                                                      C.c_void_p(grad_records_ptr)))
+
+    def uploadDevice(self, ptr: int, n: int):
+        """Gaussian records (float32 (n, 84)) from device memory.  With the scene's n: rewritten in place on the context's
+        stream, resolution kept; with another n: a new scene, and the resolution is set again here."""
+        same = self.sceneInfo().num_gaussians == int(n)
+        self._ctx.check(_lib.lib().gs_upload_gaussians_device(self._ctx.handle, C.c_void_p(int(ptr)), int(n)))
+        if not same:
+            self._ctx.check(_lib.lib().gs_set_resolution(self._ctx.handle, self.width, self.height))
+            info = self.sceneInfo()
+            self.numGaussians, self.numSortElements = info.num_gaussians, info.capacity
+
     # -- Renderer.cpp:230-270
     def cleanup(self):
         if self._ctx is not None:
