@@ -21,7 +21,8 @@ static void mat4_mul_vec4(const float* m, const float v[4], float out[4]) {
 }
 
 /* flags: [E][256], flags[e * 256 + ly * 16 + lx] = 1 when entry e (of its tile's range) adds its colour to the pixel
- * (lx, ly) of the tile; 0 otherwise (also for the entries after the pixel's early-out and for pixels outside the frame). */
+ * (lx, ly) of the tile, 2 when it does and the pixel stops on it (nextT < 1e-4); 0 otherwise (also for the entries after
+ * the pixel's early-out and for pixels outside the frame). */
 void gsb_blend_trace(const gso_params* p, const float* aos, const float* color, const float* cov, const uint32_t* sorted_id,
                      const uint32_t* ranges, uint8_t* flags) {
     const uint32_t ts = p->tile_size;
@@ -74,8 +75,8 @@ void gsb_blend_trace(const gso_params* p, const float* aos, const float* color, 
                         const float f = -0.5f * (o[3] * ex_x * ex_x + o[5] * ex_y * ex_y) - o[4] * ex_x * ex_y;
                         const float alpha = o[2] * gso_exp(f);
                         if (f > 0.0f || alpha < 1.0f / 255.0f) continue;
-                        flags[(size_t)(start + k) * 256u + ly * 16u + lx] = 1;
                         const float next_t = Ti * (1.0f - alpha);
+                        flags[(size_t)(start + k) * 256u + ly * 16u + lx] = next_t < 0.0001f ? 2 : 1;
                         if (next_t < 0.0001f) break;
                         Ti = next_t;
                     }

@@ -91,6 +91,50 @@ def scene_zero_det():
 
 SCENES = {"ragged": scene_ragged, "dense": scene_dense, "zero_det": scene_zero_det}
 
+# Camera poses (pos, yaw, pitch) for the posed scenes: one generic pose, and GardenScene.cpp's benchmark pose
+POSES = {"pose": ((0.7, -0.4, 1.5), 0.6, -0.35), "garden": gs.PlyScene.POSES["garden"]}
+
+
+def camera(pose, w, h):
+    """The renderer's Camera at POSES[pose] (its matrices are those of oracle.camera_matrices, bit for bit)."""
+    pos, yaw, pitch = POSES[pose]
+    cam = gs.Camera(w / h)
+    cam.setPosition(pos)
+    cam.setRotation(yaw, pitch)
+    cam.recalculate()
+    return cam
+
+
+def in_front_of(aos, w, h, pose):
+    """A cloud made for the origin camera (in front of it along +z) moved in front of the camera at POSES[pose], as
+    test_parity_gpu.test_reference_benchmark_camera_poses does: the same view-space positions under that camera."""
+    view = camera(pose, w, h).getViewMatrix().reshape(4, 4).T.astype(np.float64)      # row-major 4 x 4
+    inv = np.linalg.inv(view)
+    out = np.array(aos, np.float32, copy=True)
+    p = out[:, 0:3].astype(np.float64) * np.array([-1.0, 1.0, -1.0])                # origin camera: view (-x, y, -z)
+    out[:, 0:3] = ((inv[:3, :3] @ p.T).T + inv[:3, 3]).astype(np.float32)
+    return out
+
+
+def load_scene(name):
+    """A scene of SCENES by name, or 'scene@pose' for that cloud moved in front of the camera at POSES[pose]: (aos, w, h,
+    cam) with cam the keyword arguments of oracle_params / make_scene (empty: the origin camera)."""
+    scene, _, pose = name.partition("@")
+    aos, w, h = SCENES[scene]()
+    if not pose:
+        return aos, w, h, {}
+    pos, yaw, pitch = POSES[pose]
+    return in_front_of(aos, w, h, pose), w, h, dict(pos=pos, yaw=yaw, pitch=pitch)
+
+
+def assert_posed(p):
+    """The camera of params p is not the origin camera in disguise: its 3 x 3 view block is not symmetric, it sits away
+    from the origin, and the view depth row (view[2], view[6], view[10], view[14]) has more than its z term."""
+    W = np.array(p.view, np.float64).reshape(4, 4).T[:3, :3]
+    assert np.abs(W - W.T).max() > 0.1, W
+    assert np.linalg.norm(np.array(p.cam_pos, np.float64)) > 0.5
+    assert any(p.view[k] != 0 for k in (2, 6, 14)), list(p.view)
+
 
 def known_answer_scene(depths, w=64, h=48, opacity=0.5):
     """Splats of opacity `opacity` on the camera axis at view depths `depths` (origin camera: world (0, 0, z) has view
@@ -100,19 +144,32 @@ def known_answer_scene(depths, w=64, h=48, opacity=0.5):
     return np.stack(rec).astype(np.float32), w, h
 
 
-def oracle_params(oracle, w, h, sh_mode=0, **kw):
-    view, proj = oracle.camera_matrices(np.zeros(3, np.float32), 0.0, 0.0, w / h)
-    return oracle.make_params(w, h, view, proj, (0.0, 0.0, 0.0), sh_mode=sh_mode, **kw)
+def oracle_params(oracle, w, h, sh_mode=0, pos=(0.0, 0.0, 0.0), yaw=0.0, pitch=0.0, **kw):
+    pos = np.asarray(pos, np.float32)
+    view, proj = oracle.camera_matrices(pos, yaw, pitch, w / h)
+    return oracle.make_params(w, h, view, proj, pos, sh_mode=sh_mode, **kw)
+
+
+def camera_params(oracle, sc, w, h, **kw):
+    """Params from a Scene's own camera (its view, projection, position and SH mode), as test_parity_gpu.oracle_run."""
+    cam = sc.getCamera()
+    return oracle.make_params(w, h, cam.getViewMatrix(), cam.getProjectionMatrix(), cam.getPosition(),
+                              sh_mode=int(cam.getShMode()), **kw)
 
 
 # ---- tests ----------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("scene,sh_mode", [("ragged", 0), ("ragged", 1), ("ragged", 2), ("dense", 0), ("zero_det", 0)])
+@pytest.mark.parametrize("scene,sh_mode", [("ragged", 0), ("ragged", 1), ("ragged", 2), ("dense", 0), ("zero_det", 0),
+                                           ("ragged@pose", 0), ("ragged@pose", 1), ("ragged@garden", 0),
+                                           ("ragged@garden", 1)])
 def test_restatement_reproduces_the_oracle_frame(oracle_mod, tmp_path, scene, sh_mode):
     """Byte for byte the oracle's RGBA8 frame, and the same bytes again from quantising its float colour -- the condition
-    under which its alpha and depth are the reference for the GPU's."""
-    aos, w, h = SCENES[scene]()
-    p = oracle_params(oracle_mod, w, h, sh_mode)
+    under which its alpha and depth are the reference for the GPU's.  Also at posed cameras (a rotated, translated view:
+    the depth row and the SH direction's camera position count)."""
+    aos, w, h, cam = load_scene(scene)
+    p = oracle_params(oracle_mod, w, h, sh_mode, **cam)
+    if cam:
+        assert_posed(p)
     out = reference_outputs(tmp_path, p, aos)
     assert np.array_equal(out["rgba"], out["ref"]["image"])
     assert np.array_equal(quantise(out["rgba32f"]), out["rgba"])

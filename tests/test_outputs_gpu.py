@@ -10,7 +10,8 @@ import pytest
 import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib, synth
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
-from test_outputs_cpu import SCENES, known_answer_scene, oracle_params, quantise, reference_outputs
+from test_outputs_cpu import (SCENES, assert_posed, camera_params, known_answer_scene, load_scene, quantise,
+                              reference_outputs)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,9 +77,12 @@ def test_rgba8_frame_is_unchanged_by_the_outputs(sort):
             r.cleanup()
 
 
-def _exact_against_restatement(oracle_mod, tmp_path, aos, w, h, sh_mode=0, kernels=(gs.GS_RENDER_KERNEL_AUTO,)):
-    sc = make_scene(aos, w, h, sh_mode=sh_mode)
-    ref = reference_outputs(tmp_path, oracle_params(oracle_mod, w, h, sh_mode), aos)
+def _exact_against_restatement(oracle_mod, tmp_path, aos, w, h, sh_mode=0, kernels=(gs.GS_RENDER_KERNEL_AUTO,), cam=None):
+    sc = make_scene(aos, w, h, sh_mode=sh_mode, **(cam or {}))
+    p = camera_params(oracle_mod, sc, w, h)
+    if cam:
+        assert_posed(p)
+    ref = reference_outputs(tmp_path, p, aos)
     for kernel in kernels:
         r = make_renderer(sc, w, h, kernel=kernel)
         r.setOutputs(rgba32f=True, depth=True)
@@ -91,12 +95,16 @@ def _exact_against_restatement(oracle_mod, tmp_path, aos, w, h, sh_mode=0, kerne
     return sc, ref
 
 
-@pytest.mark.parametrize("scene,sh_mode", [("ragged", 0), ("ragged", 1), ("ragged", 2), ("dense", 0), ("zero_det", 0)])
+@pytest.mark.parametrize("scene,sh_mode", [("ragged", 0), ("ragged", 1), ("ragged", 2), ("dense", 0), ("zero_det", 0),
+                                           ("ragged@pose", 0), ("ragged@pose", 1), ("ragged@garden", 0),
+                                           ("ragged@garden", 1)])
 def test_exact_outputs_equal_the_restatement(oracle_mod, tmp_path, scene, sh_mode):
     """GS_RENDER_EXACT: colour, alpha and depth bit-identical to the C restatement over the oracle's intermediates -- the
-    whole frame in every launch shape; all three SH modes, the dense early-out cloud, zero-determinant splats."""
-    aos, w, h = SCENES[scene]()
-    _exact_against_restatement(oracle_mod, tmp_path, aos, w, h, sh_mode, KERNELS if sh_mode == 0 else (gs.GS_RENDER_KERNEL_AUTO,))
+    whole frame in every launch shape; all three SH modes, the dense early-out cloud, zero-determinant splats, and the
+    ragged cloud in front of rotated, translated cameras (the depth row's every term counts)."""
+    aos, w, h, cam = load_scene(scene)
+    kernels = KERNELS if sh_mode == 0 else (gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WAVE_2PX)
+    _exact_against_restatement(oracle_mod, tmp_path, aos, w, h, sh_mode, kernels if cam or sh_mode == 0 else kernels[:1], cam)
 
 
 def test_exact_outputs_bands_and_compact_rows(oracle_mod, tmp_path):
