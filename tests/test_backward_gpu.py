@@ -1,6 +1,8 @@
 """Gradients of an EXACT frame on the MI355X (include/gsplat.h, gs_backward*): a known answer, the float64 reference of
 tests/test_backward_cpu.py, central differences of the GPU's own forward, bitwise determinism across sorters and launch
-shapes, no interference with the frames, the C-ABI's refusals, the torch autograd binding and a full-size run."""
+shapes, no interference with the frames, the C-ABI's refusals, the torch autograd binding and a full-size run.  The
+values at full size (configs C, D, C-hard, a 2^32 list, a 65 k-tile grid) are checked on sampled tiles in
+tests/test_backward_fullsize_gpu.py."""
 import ctypes as C
 
 import numpy as np
