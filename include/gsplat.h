@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 7   /* 7: gs_backward / gs_backward_device / gs_upload_gaussians_device.  6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
+#define GS_API_VERSION 7   /* 7: gs_backward / gs_backward_device / gs_upload_gaussians_device.  7 (later): gs_visible_count / gs_backward_visible / gs_backward_visible_device (same version: detect them by the presence of the symbols).  6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
                               gs_runtime_versions(), gs_dist_* / gs_gather_strips; 4: GS_ROWS_BALANCED + gs_dist_rebalance /
                               gs_dist_bands, gs_render_sharded_async / gs_sharded_frame / gs_sharded_read (two sharded
                               frames in flight, the assembled frame left in HBM), GS_BUF_COLOR for every non-culled splat */
@@ -417,7 +417,8 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * and raster records must still be in HBM (they are until the next frame on the context); the scene's current planes are
  * read.  Bitwise reproducible: no float atomics, the rows of a splat summed in a fixed order -- the same gradients for
  * every sorter, launch shape, tile order and GS_COUNT_* mode.  Scratch: 40 bytes per list element of capacity + 44 bytes
- * per gaussian, allocated on the first call and freed with the resolution.
+ * per gaussian (+ 4 bytes per gaussian and 8 bytes per 256 gaussians for the visible form below), allocated on the first call
+ * and freed with the resolution.
  *   gs_backward        : HOST pointers; synchronous (grad_records is written when it returns).
  *   gs_backward_device : the same arguments as DEVICE pointers; enqueued on the context's stream, no host sync.
  * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued: a NULL grad_rgba32f or grad_records, no frame since the
@@ -425,6 +426,30 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * owns a subset of the tile rows, a sharded context (gs_dist_shard_rows). */
 int gs_backward(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
 int gs_backward_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
+
+/* Visible-splat form of gs_backward.  V = the splats g with tiles_touched != 0 in the last frame (they passed both culls and
+ * their tile box is not empty -- including splats whose elements were all cut by an overflowed list: their rows are zero),
+ * in ascending g.  ids_out[i] = the i-th such g; grad_rows_out[i][84] = bit for bit row ids_out[i] of what gs_backward
+ * writes for the same frame and the same dL/d(outputs).  Rows of splats outside V are never written anywhere: no
+ * N-sized output exists on this path.
+ *   gs_visible_count           : |V| of the last frame (HOST uint32); waits for the context's stream.
+ *   gs_backward_visible        : HOST pointers, synchronous.  *count_out = |V| always (not clamped).  At most max_rows
+ *                                ids / rows are written (the first max_rows of V); nothing beyond them is touched.
+ *                                Returns GS_WARN_OVERFLOW when |V| > max_rows, else GS_OK.
+ *   gs_backward_visible_device : all pointers DEVICE (count_out: one uint32 on the device); enqueued on the context's
+ *                                stream, no host sync; always GS_OK once enqueued -- the caller compares *count_out with
+ *                                max_rows after synchronising (or sizes with gs_visible_count first).
+ * |V| == 0: GS_OK, count 0, nothing written.  max_rows == 0 is legal (count only; ids_out / grad_rows_out may be NULL, and
+ * with both NULL the call is a count query: GS_OK).
+ * Refusals: those of gs_backward (same messages, nothing enqueued), plus a NULL count_out, and NULL ids_out /
+ * grad_rows_out with max_rows > 0.  Bitwise reproducible like gs_backward; the same for every sorter, launch shape, tile
+ * order and GS_COUNT_* mode.  Scratch: that of gs_backward with its visible part (4 bytes per gaussian for the ids of V and
+ * two block arrays of 4 bytes per 256 gaussians); gs_backward_visible also stages min(|V|, max_rows) rows on the device. */
+int gs_visible_count(gs_ctx* ctx, uint32_t* count_out);
+int gs_backward_visible(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth,
+                        uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
+int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth,
+                               uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
 
 /* Runs ONLY the InitSortList stage of a frame (project + count scan + emit) and waits; afterwards
  * GS_BUF_UNSORTED_*, GS_BUF_COLOR, GS_BUF_COV and GS_BUF_COUNT are readable (stage-level parity). */

@@ -158,6 +158,24 @@ public:
         return rc;
     }
 
+    // |V| of the last frame: the splats it rasterised (gsplat.h, gs_visible_count); 0 with error() set on a refusal.
+    uint32_t visibleCount() {
+        uint32_t count = 0;
+        if (gs_visible_count(ctx_, &count) < 0) error_ = gs_last_error(ctx_);
+        return count;
+    }
+
+    // The visible form of backward (gsplat.h, gs_backward_visible): the ids of V ascending and one [84] row for each, at
+    // most max_rows of them; *count_out = |V|.  GS_WARN_OVERFLOW: |V| > max_rows (host form).  device = true: every
+    // pointer is a device pointer and the call is enqueued without waiting.
+    int backwardVisible(const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out, float* grad_rows_out,
+                        uint32_t max_rows, uint32_t* count_out, bool device = false) {
+        const int rc = device ? gs_backward_visible_device(ctx_, grad_rgba32f, grad_depth, ids_out, grad_rows_out, max_rows, count_out)
+                              : gs_backward_visible(ctx_, grad_rgba32f, grad_depth, ids_out, grad_rows_out, max_rows, count_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

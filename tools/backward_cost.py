@@ -2,10 +2,12 @@
 (gs_get_timings, hipEvents) and the backward's host-measured time (enqueue + gs_synchronize), medians of --iters runs after
 3 warm-up runs; then the same backward again under `rocprofv3 --kernel-trace --stats` (a child process) for its split into
 the blend backward (k_bwd_blend, with the three small slot-offset kernels before it), the row sum (k_bwd_rowsum) and the
-chain (k_bwd_chain).  One JSON line per config.
+chain (k_bwd_chain).  The visible form (gs_backward_visible_device with max_rows = |V|) is timed in the same window, dense
+and visible iterations alternating in one process so that both see the same neighbours, and its own kernels (the k_bwd_vis_*
+scan and the fused row sum + chain, picked by their exact names) are split out of the same trace.  One JSON line per config.
 
     python tools/backward_cost.py [C Chard ...] [--iters 20]"""
-import argparse, csv, glob, json, os, shutil, subprocess, sys, tempfile, time
+import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -44,25 +46,49 @@ def backward_ms(r, gr, gd, out):
     return (time.perf_counter() - t0) * 1e3
 
 
+def visible_buffers(r, sc):
+    """|V| of the frame and device buffers of exactly that size: ids, rows, the count word."""
+    r.drawDevice(sc, None, sync=True)
+    v = r.visibleCount()
+    ids = torch.empty(max(v, 1), dtype=torch.int32, device="cuda")
+    rows = torch.empty(max(v, 1), 84, device="cuda")
+    count = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    return v, ids, rows, count
+
+
+def visible_ms(r, gr, gd, vis):
+    v, ids, rows, count = vis
+    t0 = time.perf_counter()
+    r.backwardVisibleDevice(gr.data_ptr(), gd.data_ptr(), ids.data_ptr(), rows.data_ptr(), v, count.data_ptr())
+    r.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
 if a.child:
     for name in a.configs:
         r, sc, gr, gd, out, n, w, h = setup(name)
-        r.drawDevice(sc, None, sync=True)
+        vis = visible_buffers(r, sc)
         for _ in range(a.iters):
             backward_ms(r, gr, gd, out)
+            visible_ms(r, gr, gd, vis)
         r.cleanup()
     sys.exit(0)
 
 for name in a.configs:
     r, sc, gr, gd, out, n, w, h = setup(name)
-    fwd, bwd = [], []
+    vis = visible_buffers(r, sc)
+    fwd, bwd, bvis = [], [], []
     for _ in range(3):
         r.drawDevice(sc, None, sync=True)
         backward_ms(r, gr, gd, out)
+        visible_ms(r, gr, gd, vis)
     for _ in range(a.iters):
         r.drawDevice(sc, None, sync=True)
         fwd.append(r.timings().total_ms)
         bwd.append(backward_ms(r, gr, gd, out))
+        bvis.append(visible_ms(r, gr, gd, vis))
+    assert int(vis[3].item()) == vis[0]
     elems = r.timings().num_sort_elements
     r.cleanup()
     split = {}
@@ -77,12 +103,17 @@ for name in a.configs:
             for row in csv.DictReader(open(files[0])):
                 us[row["Name"]] = float(row["AverageNs"]) / 1e3
             pick = lambda key: sum(v for k, v in us.items() if key in k)
+            base = lambda k: re.sub(r"^(void )?(gs::)?", "", k).split("(")[0].split("<")[0]
+            exact = lambda key: sum(v for k, v in us.items() if base(k) == key)
             split = {"blend_backward_ms": round((pick("k_bwd_blend") + pick("k_bwd_block_sums") + pick("k_bwd_scan_blocks") +
                                                  pick("k_bwd_offsets")) / 1e3, 4),
                      "row_sum_ms": round(pick("k_bwd_rowsum") / 1e3, 4), "chain_ms": round(pick("k_bwd_chain") / 1e3, 4),
-                     "slot_offsets_ms": round((pick("k_bwd_block_sums") + pick("k_bwd_scan_blocks") + pick("k_bwd_offsets")) / 1e3, 4)}
+                     "slot_offsets_ms": round((pick("k_bwd_block_sums") + pick("k_bwd_scan_blocks") + pick("k_bwd_offsets")) / 1e3, 4),
+                     "visible_scan_ms": round((exact("k_bwd_vis_block_sums") + exact("k_bwd_vis_scan_blocks") +
+                                               exact("k_bwd_vis_offsets")) / 1e3, 4),
+                     "visible_rowsum_chain_ms": round(exact("k_bwd_vis_rowsum_chain") / 1e3, 4)}
         shutil.rmtree(d, ignore_errors=True)
-    fm, bm = float(np.median(fwd)), float(np.median(bwd))
+    fm, bm, vm = float(np.median(fwd)), float(np.median(bwd)), float(np.median(bvis))
     print(json.dumps({"config": name, "width": w, "height": h, "gaussians": n, "elements": int(elems), "iters": a.iters,
-                      "forward_total_ms_median": round(fm, 4), "backward_ms_median": round(bm, 4),
-                      "backward_vs_forward": round(bm / fm, 3), **split}), flush=True)
+                      "visible": vis[0], "forward_total_ms_median": round(fm, 4), "backward_ms_median": round(bm, 4),
+                      "backward_vs_forward": round(bm / fm, 3), "backward_visible_ms_median": round(vm, 4), **split}), flush=True)

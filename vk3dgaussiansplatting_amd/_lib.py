@@ -119,6 +119,7 @@ EXPORTS = [
     "gs_render_sharded_async", "gs_sharded_frame", "gs_sharded_read", "gs_dist_rebalance", "gs_dist_bands", "gs_balance_rows",
     "gs_set_outputs", "gs_read_output", "gs_output_device",
     "gs_backward", "gs_backward_device", "gs_upload_gaussians_device",
+    "gs_visible_count", "gs_backward_visible", "gs_backward_visible_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -243,6 +244,9 @@ def lib() -> C.CDLL:
     L.gs_backward.argtypes = [ctxp, vp, vp, vp]
     L.gs_backward_device.argtypes = [ctxp, vp, vp, vp]
     L.gs_upload_gaussians_device.argtypes = [ctxp, vp, u32]
+    L.gs_visible_count.argtypes = [ctxp, vp]
+    L.gs_backward_visible.argtypes = [ctxp, vp, vp, vp, vp, u32, vp]
+    L.gs_backward_visible_device.argtypes = [ctxp, vp, vp, vp, vp, u32, vp]
     _lib = L
     _check_hip_runtime(L)
     return L

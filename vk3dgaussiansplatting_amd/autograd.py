@@ -9,6 +9,11 @@ GS_OUTPUT_RGBA32F and GS_OUTPUT_DEPTH quantities of the frame (premultiplied col
 view depth); their backward is dL/d(records) from the library's HIP kernels.  The records reach the library through
 gs_upload_gaussians_device (no host copy of the scene); the outputs come back through the host.
 
+render(..., sparse_grad=True) returns dL/d(records) as a sparse COO tensor [N, 84] that lists only the splats the frame
+rasterised (gs_backward_visible_device): no N-sized gradient is written, and torch.optim.SparseAdam moves only those rows.
+It is meant for a leaf `records`.  torch's backward formulas of the ops a non-leaf `records` comes from (cat, slicing) do
+not take sparse gradients, so a non-leaf input receives the same rows scattered into a dense [N, 84] tensor.
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -53,9 +58,10 @@ def _draw(r: Renderer, records: torch.Tensor, view, proj, cam_pos, sh_mode: int,
 
 class _Frame(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, records, renderer, view, proj, cam_pos, sh_mode, want_depth):
+    def forward(ctx, records, renderer, view, proj, cam_pos, sh_mode, want_depth, sparse_grad):
         rgba, depth, frame = _draw(renderer, records, view, proj, cam_pos, sh_mode, want_depth)
         ctx.renderer, ctx.frame, ctx.args = renderer, frame, (view, proj, cam_pos, sh_mode, want_depth)
+        ctx.sparse_grad = sparse_grad
         ctx.save_for_backward(records)
         out = torch.from_numpy(rgba).to(records.device)
         if want_depth:
@@ -73,19 +79,39 @@ class _Frame(torch.autograd.Function):
         d = None
         if ctx.args[4] and grad_depth is not None:
             d = grad_depth.to(device=records.device, dtype=torch.float32).contiguous()
+        if ctx.sparse_grad:
+            count = r.visibleCount()
+            # int32 storage for the library's uint32 ids (N < 2^31)
+            ids = torch.empty(count, dtype=torch.int32, device=records.device)
+            rows = torch.empty(count, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
+            seen = torch.empty(1, dtype=torch.int32, device=records.device)
+            torch.cuda.current_stream(records.device).synchronize()
+            r.backwardVisibleDevice(g.data_ptr(), None if d is None else d.data_ptr(), ids.data_ptr() if count else None,
+                                    rows.data_ptr() if count else None, count, seen.data_ptr())
+            r.synchronize()
+            if ctx.sparse_grad == "scatter":      # a non-leaf input
+                out = torch.zeros(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
+                out.index_copy_(0, ids.long(), rows)
+            else:
+                out = torch.sparse_coo_tensor(ids.long()[None], rows, size=(records.shape[0], FLOATS_PER_GAUSSIAN))
+            return out, None, None, None, None, None, None, None
         out = torch.empty(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
         torch.cuda.current_stream(records.device).synchronize()
         r.backwardDevice(g.data_ptr(), None if d is None else d.data_ptr(), out.data_ptr())
         r.synchronize()
-        return out, None, None, None, None, None, None
+        return out, None, None, None, None, None, None, None
 
 
-def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: bool = False, *, renderer: Renderer):
+def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: bool = False, *, renderer: Renderer,
+           sparse_grad: bool = False):
     """The frame of `records` (float32 [N, 84], CUDA/HIP, on the renderer's device) under the camera (view, proj: 4 x 4
     column-major as Camera.getViewMatrix / getProjectionMatrix give them, cam_pos: 3): rgba32f [H, W, 4], and depth [H, W]
-    if asked, both differentiable w.r.t. records."""
+    if asked, both differentiable w.r.t. records.  sparse_grad=True: records (meant to be a leaf) receives a sparse COO
+    gradient over the splats the frame rasterised, with the values of the dense one; a non-leaf records receives those
+    rows in a dense tensor."""
     if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
         raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
     if not records.is_cuda:
         raise ValueError("records must be on the GPU")
-    return _Frame.apply(records.contiguous(), renderer, view, proj, cam_pos, int(sh_mode), bool(depth))
+    mode = ("sparse" if records.grad_fn is None else "scatter") if sparse_grad else None
+    return _Frame.apply(records.contiguous(), renderer, view, proj, cam_pos, int(sh_mode), bool(depth), mode)

@@ -81,6 +81,8 @@ void drop_sort_graph(gs_ctx* c) {
 void free_backward(gs_ctx* c) {
     free_dev(c->bwd.rows); free_dev(c->bwd.offsets); free_dev(c->bwd.block_sums); free_dev(c->bwd.block_offsets);
     free_dev(c->bwd.sums); free_dev(c->bwd_host_in); free_dev(c->bwd_host_out);
+    free_dev(c->bwd.vis_ids); free_dev(c->bwd.vis_block_sums); free_dev(c->bwd.vis_block_offsets); free_dev(c->bwd_vis_out);
+    c->bwd_vis_rows = 0;
     c->bwd_frame = false;
 }
 
@@ -886,6 +888,9 @@ static int backward_prepare(gs_ctx* c, const char* who) {
         if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_sums, (size_t)blocks * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_offsets, (size_t)blocks * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.sums, backward_sum_bytes(c->n));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_sums, (size_t)blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_offsets, ((size_t)blocks + 1) * sizeof(uint32_t));
         if (e != hipSuccess) {
             const bool frame = c->bwd_frame;
             free_backward(c);
@@ -921,6 +926,76 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GS_OK;
+}
+
+int gs_visible_count(gs_ctx* c, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!count_out) return fail(c, GS_ERR_INVALID, "gs_visible_count: null count_out");
+    if (int r = backward_prepare(c, "gs_visible_count")) return r;
+    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, nullptr, 0u, nullptr, c->stream);
+    if (int r = check_launch(c, "gs_visible_count")) return r;
+    const uint32_t blocks = (c->n + 255u) / 256u;
+    HIP_TRY(c, hipMemcpyAsync(count_out, c->bwd.vis_block_offsets + blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+static int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba32f, const uint32_t* ids_out,
+                                     const float* grad_rows_out, uint32_t max_rows, const uint32_t* count_out) {
+    if (!grad_rgba32f) return fail(c, GS_ERR_INVALID, std::string(who) + ": null gradient pointer");
+    if (!count_out) return fail(c, GS_ERR_INVALID, std::string(who) + ": null count_out");
+    if (max_rows && (!ids_out || !grad_rows_out))
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": null ids_out or grad_rows_out with max_rows > 0");
+    return backward_prepare(c, who);
+}
+
+int gs_backward_visible_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
+                               float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_visible_refusals(c, "gs_backward_visible_device", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
+        return r;
+    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, ids_out, max_rows, count_out, c->stream);
+    if (max_rows)
+        launch_backward_visible_rows(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, grad_rgba32f,
+                                     grad_depth, c->bwd, max_rows, grad_rows_out, c->stream);
+    return check_launch(c, "gs_backward_visible_device");
+}
+
+int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
+                        float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_visible_refusals(c, "gs_backward_visible", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
+        return r;
+    // V and its size first (the count has to reach the host anyway), then exactly min(|V|, max_rows) rows
+    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, nullptr, 0u, nullptr, c->stream);
+    if (int r = check_launch(c, "gs_backward_visible")) return r;
+    const uint32_t blocks = (c->n + 255u) / 256u;
+    uint32_t count = 0;
+    HIP_TRY(c, hipMemcpyAsync(&count, c->bwd.vis_block_offsets + blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *count_out = count;
+    const uint32_t k = count < max_rows ? count : max_rows;
+    if (k) {
+        const size_t px = (size_t)c->width * c->height;
+        if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
+        if (c->bwd_vis_rows < k) {
+            free_dev(c->bwd_vis_out);
+            c->bwd_vis_rows = 0;
+            HIP_TRY(c, hipMalloc((void**)&c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
+            c->bwd_vis_rows = k;
+        }
+        float* din = c->bwd_host_in;
+        HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        launch_backward_visible_rows(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, din,
+                                     grad_depth ? din + px * 4 : nullptr, c->bwd, k, c->bwd_vis_out, c->stream);
+        if (int r = check_launch(c, "gs_backward_visible")) return r;
+        HIP_TRY(c, hipMemcpyAsync(ids_out, c->bwd.vis_ids, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(grad_rows_out, c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const bool count_only = !max_rows && !ids_out && !grad_rows_out;      // asked for no row: none is missing
+    return count > max_rows && !count_only ? GS_WARN_OVERFLOW : GS_OK;
 }
 
 static int apply_tile_rows(gs_ctx* c, uint32_t row_begin, uint32_t row_end, uint32_t stride, uint32_t phase,

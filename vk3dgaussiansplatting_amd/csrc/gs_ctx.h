@@ -67,6 +67,8 @@ struct gs_ctx {
     gs::BackwardBuffers bwd{};
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
     float* bwd_host_out = nullptr;    // ... and the record gradients [N][84]
+    float* bwd_vis_out = nullptr;     // gs_backward_visible (host pointers): bwd_vis_rows record gradients, grown on demand
+    uint32_t bwd_vis_rows = 0;
     bool bwd_frame = false;
     uint32_t* ranges = nullptr;
     uint32_t* tile_order = nullptr;   // [tiles] RenderGaussians' dispatch order (GS_TILE_ORDER_LONGEST_FIRST)

@@ -586,6 +586,47 @@ class Renderer:
                                                       C.c_void_p(grad_depth_ptr) if grad_depth_ptr else None,
                                                       C.c_void_p(grad_records_ptr)))
 
+    def visibleCount(self) -> int:
+        """|V|: how many splats the last frame rasterised (tiles_touched != 0); waits for the context's stream."""
+        count = C.c_uint32()
+        self._ctx.check(_lib.lib().gs_visible_count(self._ctx.handle, C.byref(count)))
+        return int(count.value)
+
+    def backwardVisible(self, grad_rgba32f: np.ndarray, grad_depth: np.ndarray | None = None, max_rows: int | None = None):
+        """backward() for the splats the frame rasterised alone: (ids uint32 (k,), rows float32 (k, 84), count) with ids
+        ascending, rows[i] = backward()[ids[i]] bit for bit, count = |V| and k = min(count, max_rows).  max_rows=None sizes
+        with visibleCount().  lastStatus is GS_WARN_OVERFLOW when count > max_rows."""
+        info = self.sceneInfo()
+        g = np.ascontiguousarray(grad_rgba32f, dtype=np.float32)
+        if g.shape != (info.height, info.width, 4):
+            raise ValueError(f"grad_rgba32f must have shape {(info.height, info.width, 4)}, not {g.shape}")
+        d = None
+        if grad_depth is not None:
+            d = np.ascontiguousarray(grad_depth, dtype=np.float32)
+            if d.shape != (info.height, info.width):
+                raise ValueError(f"grad_depth must have shape {(info.height, info.width)}, not {d.shape}")
+        if max_rows is None:
+            max_rows = self.visibleCount()
+        max_rows = int(max_rows)
+        ids = np.zeros(max_rows, dtype=np.uint32)
+        rows = np.zeros((max_rows, FLOATS_PER_GAUSSIAN), dtype=np.float32)
+        count = C.c_uint32()
+        self.lastStatus = self._ctx.check(_lib.lib().gs_backward_visible(
+            self._ctx.handle, _p(g), None if d is None else _p(d), _p(ids) if max_rows else None,
+            _p(rows) if max_rows else None, max_rows, C.byref(count)))
+        k = min(int(count.value), max_rows)
+        return ids[:k], rows[:k], int(count.value)
+
+    def backwardVisibleDevice(self, grad_rgba32f_ptr: int, grad_depth_ptr: int | None, ids_ptr: int | None,
+                              rows_ptr: int | None, max_rows: int, count_ptr: int):
+        """The same with device addresses (ids: uint32 (max_rows,), rows: float32 (max_rows, 84), count: one uint32);
+        enqueued on the context's stream without waiting.  The caller compares the count with max_rows after
+        synchronize()."""
+        self._ctx.check(_lib.lib().gs_backward_visible_device(
+            self._ctx.handle, C.c_void_p(grad_rgba32f_ptr), C.c_void_p(grad_depth_ptr) if grad_depth_ptr else None,
+            C.c_void_p(ids_ptr) if ids_ptr else None, C.c_void_p(rows_ptr) if rows_ptr else None, int(max_rows),
+            C.c_void_p(count_ptr) if count_ptr else None))
+
     def uploadDevice(self, ptr: int, n: int):
         """Gaussian records (float32 (n, 84)) from device memory.  With the scene's n: rewritten in place on the context's
         stream, resolution kept; with another n: a new scene, and the resolution is set again here."""
