@@ -416,7 +416,7 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * frame whose list overflowed (GS_WARN_OVERFLOW) is differentiated as drawn, truncated.  The frame's sorted list, ranges
  * and raster records must still be in HBM (they are until the next frame on the context); the scene's current planes are
  * read.  Bitwise reproducible: no float atomics, the rows of a splat summed in a fixed order -- the same gradients for
- * every sorter, launch shape, tile order and GS_COUNT_* mode.  Scratch: 40 bytes per list element of capacity + 44 bytes
+ * every sorter, launch shape, tile order and GS_COUNT_* mode.  Scratch: 40 bytes per list element of capacity + 4 bytes
  * per gaussian (+ 4 bytes per gaussian and 8 bytes per 256 gaussians for the visible form below), allocated on the first call
  * and freed with the resolution.
  *   gs_backward        : HOST pointers; synchronous (grad_records is written when it returns).

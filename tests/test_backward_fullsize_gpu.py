@@ -8,7 +8,7 @@ restricted to them (sampled_reference_gradient; test_sampled_reference_equals_th
 reference).  Every splat outside the union of those lists must get exactly zero.  What this reaches that the small
 scenes of test_backward_gpu.py do not: k_bwd_scan_blocks with several blocks per thread, offsets saturated at 2^32 - 1,
 slots up to 2^24 / 2^26, tile lists of up to 24 063 entries (376 batches of k_bwd_blend), boxes of thousands of rows in
-k_bwd_rowsum, the half tile row of 1080 lines, the 4K grid, a grid of more than 65 535 tiles and the tiles_touched /
+k_bwd_rowsum_chain, the half tile row of 1080 lines, the 4K grid, a grid of more than 65 535 tiles and the tiles_touched /
 extents the splat-first sorters leave.  The tolerance is compare_with_reference's, unchanged.
 
 Measured on an MI355X, worst |gpu - ref| / tolerance over the read fields (the bound is 1): C 0.003, C under the garden
@@ -140,7 +140,7 @@ def test_compaction_invariance(filler, n):
     nothing (padded_cloud; n = 262 144: 1024 blocks, one per thread; 262 145: two; 524 545: three, the last block
     partial; 1 048 577: five) with live splats at 0, n - 1 and on both sides of thread and wave boundaries.  The sort is
     stable and the index map monotone, so the sorted list is the compact cloud's list (on the oracle:
-    test_padded_cloud_has_the_compact_list); rows are summed in slot order and k_bwd_chain is per splat: the live
+    test_padded_cloud_has_the_compact_list); rows are summed in slot order and the chain is per splat: the live
     splats' gradient equals the compact cloud's BIT FOR BIT and every filler row is exactly zero."""
     aos, w, h = SCENES["ragged"]()
     r, sc, base = frame_and_grad(aos, w, h, seed=1)

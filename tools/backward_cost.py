@@ -1,10 +1,11 @@
 """What a backward pass (gs_backward_device, include/gsplat.h) costs against the forward frame: the forward's total_ms
 (gs_get_timings, hipEvents) and the backward's host-measured time (enqueue + gs_synchronize), medians of --iters runs after
 3 warm-up runs; then the same backward again under `rocprofv3 --kernel-trace --stats` (a child process) for its split into
-the blend backward (k_bwd_blend, with the three small slot-offset kernels before it), the row sum (k_bwd_rowsum) and the
-chain (k_bwd_chain).  The visible form (gs_backward_visible_device with max_rows = |V|) is timed in the same window, dense
-and visible iterations alternating in one process so that both see the same neighbours, and its own kernels (the k_bwd_vis_*
-scan and the fused row sum + chain, picked by their exact names) are split out of the same trace.  One JSON line per config.
+the blend backward (k_bwd_blend, with the three small slot-offset kernels before it) and the row sum + chain
+(k_bwd_rowsum_chain).  The visible form (gs_backward_visible_device with max_rows = |V|) is timed in the same window, dense
+and visible iterations alternating in one process so that both see the same neighbours; it runs the <true> instantiations
+of the same kernels, which the trace tells from the dense <false> ones by the template argument in the kernel name
+(k_bwd_blend is one kernel for both).  One JSON line per config.
 
     python tools/backward_cost.py [C Chard ...] [--iters 20]"""
 import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile, time
@@ -102,16 +103,15 @@ for name in a.configs:
             us = {}
             for row in csv.DictReader(open(files[0])):
                 us[row["Name"]] = float(row["AverageNs"]) / 1e3
-            pick = lambda key: sum(v for k, v in us.items() if key in k)
-            base = lambda k: re.sub(r"^(void )?(gs::)?", "", k).split("(")[0].split("<")[0]
-            exact = lambda key: sum(v for k, v in us.items() if base(k) == key)
-            split = {"blend_backward_ms": round((pick("k_bwd_blend") + pick("k_bwd_block_sums") + pick("k_bwd_scan_blocks") +
-                                                 pick("k_bwd_offsets")) / 1e3, 4),
-                     "row_sum_ms": round(pick("k_bwd_rowsum") / 1e3, 4), "chain_ms": round(pick("k_bwd_chain") / 1e3, 4),
-                     "slot_offsets_ms": round((pick("k_bwd_block_sums") + pick("k_bwd_scan_blocks") + pick("k_bwd_offsets")) / 1e3, 4),
-                     "visible_scan_ms": round((exact("k_bwd_vis_block_sums") + exact("k_bwd_vis_scan_blocks") +
-                                               exact("k_bwd_vis_offsets")) / 1e3, 4),
-                     "visible_rowsum_chain_ms": round(exact("k_bwd_vis_rowsum_chain") / 1e3, 4)}
+            # "void gs::k_bwd_offsets<true>(unsigned int const*, ...)" -> "k_bwd_offsets<true>": the template argument tells the
+            # dense instantiation from the visible one
+            kname = lambda k: re.sub(r"^(void )?(gs::)?", "", k).split("(")[0].replace(" ", "")
+            ms = lambda key: sum(v for k, v in us.items() if kname(k) == key) / 1e3
+            scan = lambda vis: sum(ms(f"{k}<{vis}>") for k in ("k_bwd_block_sums", "k_bwd_scan_blocks", "k_bwd_offsets"))
+            split = {"blend_backward_ms": round(ms("k_bwd_blend") + scan("false"), 4),
+                     "rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<false>"), 4),
+                     "slot_offsets_ms": round(scan("false"), 4), "visible_scan_ms": round(scan("true"), 4),
+                     "visible_rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<true>"), 4)}
         shutil.rmtree(d, ignore_errors=True)
     fm, bm, vm = float(np.median(fwd)), float(np.median(bwd)), float(np.median(bvis))
     print(json.dumps({"config": name, "width": w, "height": h, "gaussians": n, "elements": int(elems), "iters": a.iters,

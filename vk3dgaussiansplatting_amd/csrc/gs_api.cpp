@@ -80,14 +80,14 @@ void drop_sort_graph(gs_ctx* c) {
 
 void free_backward(gs_ctx* c) {
     free_dev(c->bwd.rows); free_dev(c->bwd.offsets); free_dev(c->bwd.block_sums); free_dev(c->bwd.block_offsets);
-    free_dev(c->bwd.sums); free_dev(c->bwd_host_in); free_dev(c->bwd_host_out);
-    free_dev(c->bwd.vis_ids); free_dev(c->bwd.vis_block_sums); free_dev(c->bwd.vis_block_offsets); free_dev(c->bwd_vis_out);
+    free_dev(c->bwd.vis_ids); free_dev(c->bwd.vis_block_sums); free_dev(c->bwd.vis_block_offsets);
+    free_dev(c->bwd_host_in); free_dev(c->bwd_host_out); free_dev(c->bwd_vis_out);
     c->bwd_vis_rows = 0;
-    c->bwd_frame = false;
 }
 
 void free_resolution(gs_ctx* c) {
     free_backward(c);
+    c->bwd_frame = false;
     drop_sort_graph(c);
     free_sort(c->sort);
     free_dev(c->ranges); free_dev(c->tile_order); free_dev(c->framebuffer);
@@ -882,22 +882,46 @@ static int backward_prepare(gs_ctx* c, const char* who) {
         return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->bwd.rows) {
-        const uint32_t blocks = (c->n + 255u) / 256u;
+        const size_t blocks = backward_blocks(c->n);
         hipError_t e = hipMalloc((void**)&c->bwd.rows, backward_row_bytes(c->capacity));
         if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.offsets, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_sums, (size_t)blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_offsets, (size_t)blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.sums, backward_sum_bytes(c->n));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_sums, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_offsets, blocks * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_sums, (size_t)blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_offsets, ((size_t)blocks + 1) * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_sums, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_offsets, (blocks + 1) * sizeof(uint32_t));
         if (e != hipSuccess) {
-            const bool frame = c->bwd_frame;
             free_backward(c);
-            c->bwd_frame = frame;
             return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
         }
     }
+    return GS_OK;
+}
+
+// The last frame as the backward launchers take it
+static BackwardFrame backward_frame(const gs_ctx* c) {
+    return BackwardFrame{c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, c->bwd};
+}
+
+// Host gradients onto the device (bwd_host_in, allocated on first use), enqueued on the context's stream: the two host
+// pointers are replaced by their device copies (a null grad_depth stays null)
+static int stage_host_grads(gs_ctx* c, const float*& grad_rgba32f, const float*& grad_depth) {
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
+    float* din = c->bwd_host_in;
+    HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    grad_rgba32f = din;
+    if (grad_depth) grad_depth = din + px * 4;
+    return GS_OK;
+}
+
+// V of the last frame into bwd.vis_ids and |V| into *count, on the host: the scan, then a wait for the stream
+static int visible_count_sync(gs_ctx* c, const char* who, uint32_t* count) {
+    launch_backward_visible_scan(backward_frame(c), nullptr, 0u, nullptr, c->stream);
+    if (int r = check_launch(c, who)) return r;
+    HIP_TRY(c, hipMemcpyAsync(count, c->bwd.vis_block_offsets + backward_blocks(c->n), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GS_OK;
 }
 
@@ -905,8 +929,7 @@ int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_d
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward_device: null gradient pointer");
     if (int r = backward_prepare(c, "gs_backward_device")) return r;
-    launch_backward(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, grad_rgba32f, grad_depth,
-                    c->bwd, grad_records, c->stream);
+    launch_backward(backward_frame(c), grad_rgba32f, grad_depth, grad_records, c->stream);
     return check_launch(c, "gs_backward_device");
 }
 
@@ -914,14 +937,9 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward: null gradient pointer");
     if (int r = backward_prepare(c, "gs_backward")) return r;
-    const size_t px = (size_t)c->width * c->height;
-    if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
     if (!c->bwd_host_out) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
-    float* din = c->bwd_host_in;
-    HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    launch_backward(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, din,
-                    grad_depth ? din + px * 4 : nullptr, c->bwd, c->bwd_host_out, c->stream);
+    if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
+    launch_backward(backward_frame(c), grad_rgba32f, grad_depth, c->bwd_host_out, c->stream);
     if (int r = check_launch(c, "gs_backward")) return r;
     HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -932,12 +950,7 @@ int gs_visible_count(gs_ctx* c, uint32_t* count_out) {
     if (!c) return GS_ERR_INVALID;
     if (!count_out) return fail(c, GS_ERR_INVALID, "gs_visible_count: null count_out");
     if (int r = backward_prepare(c, "gs_visible_count")) return r;
-    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, nullptr, 0u, nullptr, c->stream);
-    if (int r = check_launch(c, "gs_visible_count")) return r;
-    const uint32_t blocks = (c->n + 255u) / 256u;
-    HIP_TRY(c, hipMemcpyAsync(count_out, c->bwd.vis_block_offsets + blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GS_OK;
+    return visible_count_sync(c, "gs_visible_count", count_out);
 }
 
 static int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba32f, const uint32_t* ids_out,
@@ -954,10 +967,9 @@ int gs_backward_visible_device(gs_ctx* c, const float* grad_rgba32f, const float
     if (!c) return GS_ERR_INVALID;
     if (int r = backward_visible_refusals(c, "gs_backward_visible_device", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
         return r;
-    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, ids_out, max_rows, count_out, c->stream);
-    if (max_rows)
-        launch_backward_visible_rows(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, grad_rgba32f,
-                                     grad_depth, c->bwd, max_rows, grad_rows_out, c->stream);
+    const BackwardFrame f = backward_frame(c);
+    launch_backward_visible_scan(f, ids_out, max_rows, count_out, c->stream);
+    if (max_rows) launch_backward_visible_rows(f, grad_rgba32f, grad_depth, max_rows, grad_rows_out, c->stream);
     return check_launch(c, "gs_backward_visible_device");
 }
 
@@ -967,28 +979,17 @@ int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_
     if (int r = backward_visible_refusals(c, "gs_backward_visible", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
         return r;
     // V and its size first (the count has to reach the host anyway), then exactly min(|V|, max_rows) rows
-    launch_backward_visible_scan(c->last_fp, c->scratch, c->bwd, nullptr, 0u, nullptr, c->stream);
-    if (int r = check_launch(c, "gs_backward_visible")) return r;
-    const uint32_t blocks = (c->n + 255u) / 256u;
-    uint32_t count = 0;
-    HIP_TRY(c, hipMemcpyAsync(&count, c->bwd.vis_block_offsets + blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *count_out = count;
-    const uint32_t k = count < max_rows ? count : max_rows;
+    if (int r = visible_count_sync(c, "gs_backward_visible", count_out)) return r;
+    const uint32_t count = *count_out, k = count < max_rows ? count : max_rows;
     if (k) {
-        const size_t px = (size_t)c->width * c->height;
-        if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
         if (c->bwd_vis_rows < k) {
             free_dev(c->bwd_vis_out);
             c->bwd_vis_rows = 0;
             HIP_TRY(c, hipMalloc((void**)&c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
             c->bwd_vis_rows = k;
         }
-        float* din = c->bwd_host_in;
-        HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        launch_backward_visible_rows(c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, din,
-                                     grad_depth ? din + px * 4 : nullptr, c->bwd, k, c->bwd_vis_out, c->stream);
+        if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
+        launch_backward_visible_rows(backward_frame(c), grad_rgba32f, grad_depth, k, c->bwd_vis_out, c->stream);
         if (int r = check_launch(c, "gs_backward_visible")) return r;
         HIP_TRY(c, hipMemcpyAsync(ids_out, c->bwd.vis_ids, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(grad_rows_out, c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));

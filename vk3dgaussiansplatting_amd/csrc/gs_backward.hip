@@ -1,21 +1,25 @@
 // gs_backward.hip -- gradients of the last GS_RENDER_EXACT frame w.r.t. the uploaded gaussians (gs_backward*,
-// include/gsplat.h), as five launches after the frame's own kernels:
-//   k_bwd_block_sums + k_bwd_scan_blocks + k_bwd_offsets : offset[g] = sum of tiles_touched over the splats before g, the
-//                   splat-order position of g's first element -- the position InitSortList's truncation goes by
+// include/gsplat.h), as five launches after the frame's own kernels.  The dense form (gs_backward*: a record gradient for
+// every splat) and the visible form (gs_backward_visible*: for the splats of V = { g : tiles_touched[g] != 0 } alone, with
+// their ids) run the same kernels; where they differ the kernel is a template on VIS:
+//   k_bwd_block_sums<VIS> + k_bwd_scan_blocks<VIS> + k_bwd_offsets<VIS> : offset[g] = sum of tiles_touched over the splats
+//                   before g, the splat-order position of g's first element -- the position InitSortList's truncation goes by
 //                   (k_emit, k_gather_sorted), so an element of the list has offset[g] + (its tile's index in g's box)
-//                   below the capacity, and every such slot is an element of the list;
+//                   below the capacity, and every such slot is an element of the list.  VIS carries a second sum beside
+//                   the first, the flag tiles_touched != 0: its exclusive scan is the position of g in V (ascending g by
+//                   construction), vis_ids[position] = g, and vis_block_offsets[blocks] = |V|;
 //   k_bwd_blend   : per tile, the blend of RenderGaussians.comp:112-142 replayed front to back in the EXACT arithmetic
 //                   (same expressions, same pinned exp: the same entries contribute and each pixel stops on the same
 //                   entry K with the same T_K), then walked back to front with the colour behind every entry as a running
 //                   sum; the 256 pixels' derivatives of each list entry are reduced on chip in a fixed tree and stored as
 //                   one 10-float row in the slot of the entry, with plain stores;
-//   k_bwd_rowsum  : per splat, its rows summed in slot order (= tile raster order inside its box);
-//   k_bwd_chain   : per splat, the summed row through the per-splat part of the frame (conic <- 2-D covariance <- scale,
-//                   rotation; screen position and depth <- position; colour <- SH coefficients and position), written in
-//                   the 336-byte record layout of gs_upload_gaussians.
-// The visible form (gs_backward_visible*) runs the three slot-offset kernels with a second sum, the flag tiles_touched != 0
-// (k_bwd_vis_block_sums + k_bwd_vis_scan_blocks + k_bwd_vis_offsets: V and |V|), the same k_bwd_blend, and one fused
-// k_bwd_vis_rowsum_chain over V alone; it shares the row sum and the chain with the dense kernels as __device__ functions.
+//   k_bwd_rowsum_chain<VIS> : per splat, its rows summed in slot order (= tile raster order inside its box), then the sum
+//                   through the per-splat part of the frame (conic <- 2-D covariance <- scale, rotation; screen position
+//                   and depth <- position; colour <- SH coefficients and position), written in the 336-byte record layout
+//                   of gs_upload_gaussians.  Dense: thread g < N writes record g.  VIS: thread i < min(|V|, max_rows)
+//                   handles g = vis_ids[i] and writes record i.
+// Dense: launch_backward runs all five.  Visible: launch_backward_visible_scan runs the first three (alone it is
+// gs_visible_count), launch_backward_visible_rows the last two.
 // No float atomics anywhere: the gradients are bitwise reproducible, and the same for every sorter and launch shape of
 // the forward (they depend on the sorted list and the pixels only).
 #include "gs_device_utils.h"
@@ -28,53 +32,125 @@ constexpr int kRowFloats = 10;            // dL/d{sx, sy, ix, iy, iz, r, g, b, a
 constexpr int kRecordFloats = 84;         // GS_GAUSSIAN_RECORD_BYTES / 4
 
 // ---- per-splat slot offsets ---------------------------------------------------------------------------------------
+// VIS: the same three kernels with the flag tiles_touched[g] != 0 summed beside tiles_touched[g] (no atomics); the dense
+// instantiation carries none of it (the vis_* / *_out arguments are then unused and null).
 
+template <bool VIS>
 __global__ __launch_bounds__(256) void k_bwd_block_sums(const uint32_t* __restrict__ touched, uint32_t n,
-                                                         uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t s_w[4];
+                                                         uint32_t* __restrict__ block_sums,
+                                                         uint32_t* __restrict__ vis_block_sums) {
+    __shared__ uint32_t s_w[4], s_f[4];
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t t = wave_sum_to_lane63(g < n ? touched[g] : 0u);   // < 256 * tiles: no overflow
+    const uint32_t cnt = g < n ? touched[g] : 0u;
+    const uint32_t t = wave_sum_to_lane63(cnt);                       // < 256 * tiles: no overflow
     if (lane_id() == 63) s_w[wave_id()] = t;
+    if constexpr (VIS) {
+        const uint32_t f = (uint32_t)__popcll(__ballot(cnt != 0u));
+        if (lane_id() == 63) s_f[wave_id()] = f;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (threadIdx.x == 0) {
+        block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+        if constexpr (VIS) vis_block_sums[blockIdx.x] = s_f[0] + s_f[1] + s_f[2] + s_f[3];
+    }
 }
 
 // One workgroup: exclusive scan of the block sums with a 64-bit running total, stored saturated at 2^32 - 1 (beyond any
-// capacity: the slots of such splats are not elements of the list).
-__global__ __launch_bounds__(1024) void k_bwd_scan_blocks(const uint32_t* __restrict__ block_sums, uint32_t blocks,
-                                                           uint32_t* __restrict__ block_offsets) {
+// capacity: the slots of such splats are not elements of the list).  Every thread owns `per` consecutive blocks and
+// carries the running totals across them.  VIS: the flag total is at most N, 32 bits; vis_block_offsets[blocks] = |V|,
+// and the same into count_out (may be null), the caller's copy.
+template <bool VIS>
+__global__ __launch_bounds__(1024) void k_bwd_scan_blocks(const uint32_t* __restrict__ block_sums,
+                                                           const uint32_t* __restrict__ vis_block_sums, uint32_t blocks,
+                                                           uint32_t* __restrict__ block_offsets,
+                                                           uint32_t* __restrict__ vis_block_offsets,
+                                                           uint32_t* __restrict__ count_out) {
     __shared__ uint64_t s_w[16];
+    __shared__ uint32_t s_f[16];
     const uint32_t per = (blocks + 1023u) / 1024u;
     const uint32_t b0 = threadIdx.x * per;
     uint64_t mine = 0;
-    for (uint32_t k = 0; k < per; ++k)
-        if (b0 + k < blocks) mine += block_sums[b0 + k];
+    uint32_t fmine = 0, finc = 0, frun = 0;
+    for (uint32_t k = 0; k < per; ++k) {
+        if (b0 + k < blocks) {
+            mine += block_sums[b0 + k];
+            if constexpr (VIS) fmine += vis_block_sums[b0 + k];
+        }
+    }
     const uint64_t inc = wave_inclusive_scan64(mine);
     if (lane_id() == 63) s_w[wave_id()] = inc;
+    if constexpr (VIS) {
+        finc = wave_inclusive_scan(fmine);
+        if (lane_id() == 63) s_f[wave_id()] = finc;
+    }
     __syncthreads();
     uint64_t run = inc - mine;
     for (int w = 0; w < wave_id(); ++w) run += s_w[w];
+    if constexpr (VIS) {
+        frun = finc - fmine;
+        for (int w = 0; w < wave_id(); ++w) frun += s_f[w];
+    }
     for (uint32_t k = 0; k < per; ++k) {
         if (b0 + k < blocks) {
             block_offsets[b0 + k] = run < 0xFFFFFFFFull ? (uint32_t)run : 0xFFFFFFFFu;
             run += block_sums[b0 + k];
+            if constexpr (VIS) {
+                vis_block_offsets[b0 + k] = frun;
+                frun += vis_block_sums[b0 + k];
+            }
+        }
+    }
+    if constexpr (VIS) {
+        if (threadIdx.x == 1023u) {           // the last thread of the last wave: frun is the grand total
+            vis_block_offsets[blocks] = frun;
+            if (count_out) *count_out = frun;
         }
     }
 }
 
+// offsets[g]; VIS: vis_ids[position of g in V] = g for every g of V, and the same into ids_out (may be null) below max_rows.
+template <bool VIS>
 __global__ __launch_bounds__(256) void k_bwd_offsets(const uint32_t* __restrict__ touched, uint32_t n,
                                                       const uint32_t* __restrict__ block_offsets,
-                                                      uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t s_w[4];
+                                                      const uint32_t* __restrict__ vis_block_offsets,
+                                                      uint32_t* __restrict__ offsets, uint32_t* __restrict__ vis_ids,
+                                                      uint32_t* __restrict__ ids_out, uint32_t max_rows) {
+    __shared__ uint32_t s_w[4], s_f[4];
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     const uint32_t cnt = g < n ? touched[g] : 0u;
     const uint32_t inc = wave_inclusive_scan(cnt);
     if (lane_id() == 63) s_w[wave_id()] = inc;
+    uint64_t mask = 0;
+    if constexpr (VIS) {
+        mask = __ballot(cnt != 0u);
+        if (lane_id() == 63) s_f[wave_id()] = (uint32_t)__popcll(mask);
+    }
     __syncthreads();
     uint32_t before = inc - cnt;
     for (int w = 0; w < wave_id(); ++w) before += s_w[w];
     const uint64_t off = (uint64_t)block_offsets[blockIdx.x] + before;
     if (g < n) offsets[g] = off < 0xFFFFFFFFull ? (uint32_t)off : 0xFFFFFFFFu;
+    if constexpr (VIS) {
+        uint32_t vis = vis_block_offsets[blockIdx.x] + mbcnt(mask);
+        for (int w = 0; w < wave_id(); ++w) vis += s_f[w];
+        if (cnt != 0u) {                      // cnt != 0 implies g < n, and vis < |V| <= n
+            vis_ids[vis] = g;
+            if (ids_out && vis < max_rows) ids_out[vis] = g;
+        }
+    }
+}
+
+template <bool VIS>
+static void launch_slot_offsets(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
+                                hipStream_t stream) {
+    const uint32_t n = f.fp.num_gaussians, blocks = backward_blocks(n);
+    const uint32_t* touched = f.sc.tiles_touched;
+    const BackwardBuffers& bb = f.bb;
+    hipLaunchKernelGGL(k_bwd_block_sums<VIS>, dim3(blocks), dim3(256), 0, stream, touched, n, bb.block_sums, bb.vis_block_sums);
+    hipLaunchKernelGGL(k_bwd_scan_blocks<VIS>, dim3(1), dim3(1024), 0, stream, bb.block_sums, bb.vis_block_sums, blocks,
+                       bb.block_offsets, bb.vis_block_offsets, count_out);
+    hipLaunchKernelGGL(k_bwd_offsets<VIS>, dim3(blocks), dim3(256), 0, stream, touched, n, bb.block_offsets,
+                       bb.vis_block_offsets, bb.offsets, bb.vis_ids, ids_out, max_rows);
 }
 
 // ---- blend backward -----------------------------------------------------------------------------------------------
@@ -262,6 +338,12 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
     }
 }
 
+static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, hipStream_t stream) {
+    const BwdBlendArgs args{f.sc.raster, f.sorted_id, f.ranges, f.scene.pos, reinterpret_cast<const float4*>(grad_rgba),
+                            grad_depth, f.bb.offsets, f.sc.extents, f.bb.rows, f.fp.capacity};
+    hipLaunchKernelGGL(k_bwd_blend, dim3(f.fp.grid_w * f.fp.grid_h), dim3(256), 0, stream, f.fp, args);
+}
+
 // ---- per splat ----------------------------------------------------------------------------------------------------
 
 // Sum of the splat's rows in slot order; zero for a splat that emits nothing.
@@ -278,17 +360,6 @@ __device__ __forceinline__ void bwd_row_sum(const uint32_t* __restrict__ touched
 #pragma unroll
         for (int k = 0; k < kRowFloats; ++k) acc[k] += r[k];
     }
-}
-
-__global__ __launch_bounds__(256) void k_bwd_rowsum(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
-                                                     const float* __restrict__ rows, uint32_t n, uint32_t capacity,
-                                                     float* __restrict__ sums) {
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= n) return;
-    float acc[kRowFloats];
-    bwd_row_sum(touched, offsets, rows, g, capacity, acc);
-#pragma unroll
-    for (int k = 0; k < kRowFloats; ++k) sums[(size_t)g * kRowFloats + k] = acc[k];
 }
 
 // GLSL `M * v`, M column-major, in the reference's operand order
@@ -525,163 +596,55 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
     o[20] = zero4;                                                       // covariance
 }
 
-__global__ __launch_bounds__(256) void k_bwd_chain(const FrameParams fp, const SceneBuffers scene,
-                                                    const uint32_t* __restrict__ touched, const float* __restrict__ sums,
-                                                    float* __restrict__ out) {
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= fp.num_gaussians) return;
-    const float* rs = sums + (size_t)g * kRowFloats;
-    float row[kRowFloats];
-#pragma unroll
-    for (int k = 0; k < kRowFloats; ++k) row[k] = rs[k];
-    bwd_chain_record(fp, scene, g, touched[g] != 0u, row, reinterpret_cast<float4*>(out + (size_t)g * kRecordFloats));
-}
-
-void launch_backward(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, const uint32_t* sorted_id,
-                     const uint32_t* ranges, const float* grad_rgba, const float* grad_depth, const BackwardBuffers& bb,
-                     float* grad_records, hipStream_t stream) {
-    const uint32_t n = fp.num_gaussians;
-    const uint32_t blocks = (n + 255u) / 256u;
-    const uint32_t tiles = fp.grid_w * fp.grid_h;
-    hipLaunchKernelGGL(k_bwd_block_sums, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_sums);
-    hipLaunchKernelGGL(k_bwd_scan_blocks, dim3(1), dim3(1024), 0, stream, bb.block_sums, blocks, bb.block_offsets);
-    hipLaunchKernelGGL(k_bwd_offsets, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_offsets, bb.offsets);
-    const BwdBlendArgs args{sc.raster, sorted_id, ranges, scene.pos, reinterpret_cast<const float4*>(grad_rgba),
-                            grad_depth, bb.offsets, sc.extents, bb.rows, fp.capacity};
-    hipLaunchKernelGGL(k_bwd_blend, dim3(tiles), dim3(256), 0, stream, fp, args);
-    hipLaunchKernelGGL(k_bwd_rowsum, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, bb.offsets, bb.rows, n,
-                       fp.capacity, bb.sums);
-    hipLaunchKernelGGL(k_bwd_chain, dim3(blocks), dim3(256), 0, stream, fp, scene, sc.tiles_touched, bb.sums, grad_records);
-}
-
-// ---- the visible set V = { g : tiles_touched[g] != 0 } (gs_backward_visible*) ---------------------------------------
-// The three slot-offset kernels again with a second sum beside the first: the flag tiles_touched[g] != 0.  Its exclusive scan
-// is the position of g in V (ascending g by construction, no atomics); vis_block_offsets[blocks] holds |V|.
-
-__global__ __launch_bounds__(256) void k_bwd_vis_block_sums(const uint32_t* __restrict__ touched, uint32_t n,
-                                                             uint32_t* __restrict__ block_sums,
-                                                             uint32_t* __restrict__ vis_block_sums) {
-    __shared__ uint32_t s_w[4], s_f[4];
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t cnt = g < n ? touched[g] : 0u;
-    const uint32_t t = wave_sum_to_lane63(cnt);
-    const uint32_t f = (uint32_t)__popcll(__ballot(cnt != 0u));
-    if (lane_id() == 63) { s_w[wave_id()] = t; s_f[wave_id()] = f; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        vis_block_sums[blockIdx.x] = s_f[0] + s_f[1] + s_f[2] + s_f[3];
-    }
-}
-
-// One workgroup, as k_bwd_scan_blocks: every thread owns `per` consecutive blocks and carries both running totals across
-// them.  The flag total is at most N: 32 bits.  count_out (may be null): the caller's copy of |V|.
-__global__ __launch_bounds__(1024) void k_bwd_vis_scan_blocks(const uint32_t* __restrict__ block_sums,
-                                                               const uint32_t* __restrict__ vis_block_sums, uint32_t blocks,
-                                                               uint32_t* __restrict__ block_offsets,
-                                                               uint32_t* __restrict__ vis_block_offsets,
-                                                               uint32_t* __restrict__ count_out) {
-    __shared__ uint64_t s_w[16];
-    __shared__ uint32_t s_f[16];
-    const uint32_t per = (blocks + 1023u) / 1024u;
-    const uint32_t b0 = threadIdx.x * per;
-    uint64_t mine = 0;
-    uint32_t fmine = 0;
-    for (uint32_t k = 0; k < per; ++k)
-        if (b0 + k < blocks) { mine += block_sums[b0 + k]; fmine += vis_block_sums[b0 + k]; }
-    const uint64_t inc = wave_inclusive_scan64(mine);
-    const uint32_t finc = wave_inclusive_scan(fmine);
-    if (lane_id() == 63) { s_w[wave_id()] = inc; s_f[wave_id()] = finc; }
-    __syncthreads();
-    uint64_t run = inc - mine;
-    uint32_t frun = finc - fmine;
-    for (int w = 0; w < wave_id(); ++w) { run += s_w[w]; frun += s_f[w]; }
-    for (uint32_t k = 0; k < per; ++k) {
-        if (b0 + k < blocks) {
-            block_offsets[b0 + k] = run < 0xFFFFFFFFull ? (uint32_t)run : 0xFFFFFFFFu;
-            vis_block_offsets[b0 + k] = frun;
-            run += block_sums[b0 + k];
-            frun += vis_block_sums[b0 + k];
-        }
-    }
-    if (threadIdx.x == 1023u) {               // the last thread of the last wave: frun is the grand total
-        vis_block_offsets[blocks] = frun;
-        if (count_out) *count_out = frun;
-    }
-}
-
-// offsets[g] as k_bwd_offsets; vis_ids[position of g in V] = g for every g of V, and the same into ids_out (may be null)
-// below max_rows.
-__global__ __launch_bounds__(256) void k_bwd_vis_offsets(const uint32_t* __restrict__ touched, uint32_t n,
-                                                          const uint32_t* __restrict__ block_offsets,
-                                                          const uint32_t* __restrict__ vis_block_offsets,
-                                                          uint32_t* __restrict__ offsets, uint32_t* __restrict__ vis_ids,
-                                                          uint32_t* __restrict__ ids_out, uint32_t max_rows) {
-    __shared__ uint32_t s_w[4], s_f[4];
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t cnt = g < n ? touched[g] : 0u;
-    const uint32_t inc = wave_inclusive_scan(cnt);
-    const uint64_t mask = __ballot(cnt != 0u);
-    if (lane_id() == 63) { s_w[wave_id()] = inc; s_f[wave_id()] = (uint32_t)__popcll(mask); }
-    __syncthreads();
-    uint32_t before = inc - cnt;
-    uint32_t vis = vis_block_offsets[blockIdx.x] + mbcnt(mask);
-    for (int w = 0; w < wave_id(); ++w) { before += s_w[w]; vis += s_f[w]; }
-    const uint64_t off = (uint64_t)block_offsets[blockIdx.x] + before;
-    if (g < n) offsets[g] = off < 0xFFFFFFFFull ? (uint32_t)off : 0xFFFFFFFFu;
-    if (cnt != 0u) {                          // cnt != 0 implies g < n, and vis < |V| <= n
-        vis_ids[vis] = g;
-        if (ids_out && vis < max_rows) ids_out[vis] = g;
-    }
-}
-
-// Row sum + chain of the visible splats alone: thread i < min(|V|, max_rows) sums the rows of g = vis_ids[i] in slot order
-// and writes record gradient i.  The grid covers min(N, max_rows) (|V| lives on the device); threads beyond the count leave.
-__global__ __launch_bounds__(256) void k_bwd_vis_rowsum_chain(const FrameParams fp, const SceneBuffers scene,
-                                                               const uint32_t* __restrict__ touched,
-                                                               const uint32_t* __restrict__ offsets,
-                                                               const float* __restrict__ rows,
-                                                               const uint32_t* __restrict__ vis_ids,
-                                                               const uint32_t* __restrict__ vis_count, uint32_t max_rows,
-                                                               float* __restrict__ out) {
+// Row sum + chain.  Dense: thread g < N sums the rows of splat g and writes record gradient g (all zero for a splat outside
+// V).  VIS: thread i < min(|V|, max_rows) does so for g = vis_ids[i] and writes record gradient i; the grid covers
+// min(N, max_rows) (|V| lives on the device, in *vis_count) and the threads beyond the count leave.
+template <bool VIS>
+__global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, const SceneBuffers scene,
+                                                           const uint32_t* __restrict__ touched,
+                                                           const uint32_t* __restrict__ offsets,
+                                                           const float* __restrict__ rows,
+                                                           const uint32_t* __restrict__ vis_ids,
+                                                           const uint32_t* __restrict__ vis_count, uint32_t max_rows,
+                                                           float* __restrict__ out) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t count = *vis_count;
-    if (i >= (count < max_rows ? count : max_rows)) return;
-    const uint32_t g = vis_ids[i];
+    uint32_t g = i;
+    bool any = true;
+    if constexpr (VIS) {
+        const uint32_t count = *vis_count;
+        if (i >= (count < max_rows ? count : max_rows)) return;
+        g = vis_ids[i];
+    } else {
+        if (g >= fp.num_gaussians) return;
+        any = touched[g] != 0u;
+    }
     float row[kRowFloats];
     bwd_row_sum(touched, offsets, rows, g, fp.capacity, row);
-    bwd_chain_record(fp, scene, g, true, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats));
+    bwd_chain_record(fp, scene, g, any, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats));
 }
 
-void launch_backward_visible_scan(const FrameParams& fp, const SplatScratch& sc, const BackwardBuffers& bb, uint32_t* ids_out,
-                                  uint32_t max_rows, uint32_t* count_out, hipStream_t stream) {
-    const uint32_t n = fp.num_gaussians;
-    const uint32_t blocks = (n + 255u) / 256u;
-    hipLaunchKernelGGL(k_bwd_vis_block_sums, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_sums,
-                       bb.vis_block_sums);
-    hipLaunchKernelGGL(k_bwd_vis_scan_blocks, dim3(1), dim3(1024), 0, stream, bb.block_sums, bb.vis_block_sums, blocks,
-                       bb.block_offsets, bb.vis_block_offsets, count_out);
-    hipLaunchKernelGGL(k_bwd_vis_offsets, dim3(blocks), dim3(256), 0, stream, sc.tiles_touched, n, bb.block_offsets,
-                       bb.vis_block_offsets, bb.offsets, bb.vis_ids, ids_out, max_rows);
+void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
+                     hipStream_t stream) {
+    launch_slot_offsets<false>(f, nullptr, 0u, nullptr, stream);
+    launch_blend(f, grad_rgba, grad_depth, stream);
+    hipLaunchKernelGGL(k_bwd_rowsum_chain<false>, dim3(backward_blocks(f.fp.num_gaussians)), dim3(256), 0, stream, f.fp,
+                       f.scene, f.sc.tiles_touched, f.bb.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);
 }
 
-void launch_backward_visible_rows(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,
-                                  const uint32_t* sorted_id, const uint32_t* ranges, const float* grad_rgba,
-                                  const float* grad_depth, const BackwardBuffers& bb, uint32_t max_rows, float* grad_rows,
+void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
                                   hipStream_t stream) {
-    const uint32_t n = fp.num_gaussians;
-    const uint32_t blocks = (n + 255u) / 256u;
-    const uint32_t tiles = fp.grid_w * fp.grid_h;
-    const BwdBlendArgs args{sc.raster, sorted_id, ranges, scene.pos, reinterpret_cast<const float4*>(grad_rgba),
-                            grad_depth, bb.offsets, sc.extents, bb.rows, fp.capacity};
-    hipLaunchKernelGGL(k_bwd_blend, dim3(tiles), dim3(256), 0, stream, fp, args);
-    const uint32_t* count = bb.vis_block_offsets + blocks;
-    const uint32_t row_blocks = ((n < max_rows ? n : max_rows) + 255u) / 256u;      // |V| <= n lives on the device
-    hipLaunchKernelGGL(k_bwd_vis_rowsum_chain, dim3(row_blocks), dim3(256), 0, stream, fp, scene, sc.tiles_touched, bb.offsets,
-                       bb.rows, bb.vis_ids, count, max_rows, grad_rows);
+    launch_slot_offsets<true>(f, ids_out, max_rows, count_out, stream);
+}
+
+void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
+                                  uint32_t max_rows, float* grad_rows, hipStream_t stream) {
+    const uint32_t n = f.fp.num_gaussians;
+    launch_blend(f, grad_rgba, grad_depth, stream);
+    hipLaunchKernelGGL(k_bwd_rowsum_chain<true>, dim3(backward_blocks(n < max_rows ? n : max_rows)), dim3(256), 0, stream,
+                       f.fp, f.scene, f.sc.tiles_touched, f.bb.offsets, f.bb.rows, f.bb.vis_ids,
+                       f.bb.vis_block_offsets + backward_blocks(n), max_rows, grad_rows);
 }
 
 size_t backward_row_bytes(uint32_t capacity) { return (size_t)capacity * kRowFloats * sizeof(float); }
-size_t backward_sum_bytes(uint32_t n) { return (size_t)n * kRowFloats * sizeof(float); }
 
 } // namespace gs

@@ -61,9 +61,9 @@ struct gs_ctx {
     float* out_rgba32f = nullptr;     // [H][W][4] while GS_OUTPUT_RGBA32F is on and a resolution is set
     float* out_depth = nullptr;       // [H][W] while GS_OUTPUT_DEPTH is on and a resolution is set
     bool outputs_valid = false;       // a frame has been enqueued since the mask or the resolution last changed
-    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity, sums by the scene), freed with the
-    // resolution; bwd_frame = the last enqueued frame can be differentiated (no gs_set_resolution, gs_set_tile_rows*,
-    // upload or gs_debug_init_sort_list since)
+    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity), freed with the resolution;
+    // bwd_frame = the last enqueued frame can be differentiated (no gs_set_resolution, gs_set_tile_rows*, upload or
+    // gs_debug_init_sort_list since)
     gs::BackwardBuffers bwd{};
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
     float* bwd_host_out = nullptr;    // ... and the record gradients [N][84]

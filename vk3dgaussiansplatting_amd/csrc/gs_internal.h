@@ -247,28 +247,33 @@ struct BackwardBuffers {
     uint32_t* offsets;        // [N]  first slot of a splat: its tiles_touched summed over the splats before it (saturated)
     uint32_t* block_sums;     // [ceil(N / 256)]
     uint32_t* block_offsets;  // [ceil(N / 256)]
-    float* sums;              // [N][10]  a splat's rows summed in slot order
     // gs_backward_visible*: V = the splats with tiles_touched != 0, ascending
     uint32_t* vis_ids;            // [N]  the first |V| entries: V
     uint32_t* vis_block_sums;     // [ceil(N / 256)]  members of V per block
     uint32_t* vis_block_offsets;  // [ceil(N / 256) + 1]  exclusive scan; the last entry is |V|
 };
 size_t backward_row_bytes(uint32_t capacity);
-size_t backward_sum_bytes(uint32_t n);
-// dL/d(record) [N][84] of the last frame (fp = its FrameParams, full grid, GS_RENDER_EXACT), from dL/dRGBA32F [H][W][4] and
-// dL/dDEPTH [H][W] (may be null).
-void launch_backward(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, const uint32_t* sorted_id,
-                     const uint32_t* ranges, const float* grad_rgba, const float* grad_depth, const BackwardBuffers& bb,
-                     float* grad_records, hipStream_t stream);
+inline uint32_t backward_blocks(uint32_t n) { return (n + 255u) / 256u; }   // 256 splats per block of the per-splat kernels
+// The frame a backward pass differentiates: its FrameParams (full grid, GS_RENDER_EXACT), the scene, what its forward left
+// (scratch, sorted list, ranges) and the backward's own scratch
+struct BackwardFrame {
+    FrameParams fp;
+    SceneBuffers scene;
+    SplatScratch sc;
+    const uint32_t* sorted_id;
+    const uint32_t* ranges;
+    BackwardBuffers bb;
+};
+// dL/d(record) [N][84] of the frame, from dL/dRGBA32F [H][W][4] and dL/dDEPTH [H][W] (may be null).
+void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
+                     hipStream_t stream);
 // The visible form, in two steps on one stream.  _scan: the slot offsets of launch_backward plus V (bb.vis_ids, |V| in
 // bb.vis_block_offsets[blocks]); ids_out (device, may be null) gets the first max_rows of V, count_out (device, may be null)
 // |V|.  _rows: the blend backward, then record gradient i of splat vis_ids[i] into grad_rows[i][84], i < min(|V|, max_rows).
-void launch_backward_visible_scan(const FrameParams& fp, const SplatScratch& sc, const BackwardBuffers& bb, uint32_t* ids_out,
-                                  uint32_t max_rows, uint32_t* count_out, hipStream_t stream);
-void launch_backward_visible_rows(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,
-                                  const uint32_t* sorted_id, const uint32_t* ranges, const float* grad_rgba,
-                                  const float* grad_depth, const BackwardBuffers& bb, uint32_t max_rows, float* grad_rows,
+void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
                                   hipStream_t stream);
+void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
+                                  uint32_t max_rows, float* grad_rows, hipStream_t stream);
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,
                        const SceneBuffers& s, hipStream_t stream);
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream);

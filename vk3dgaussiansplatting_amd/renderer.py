@@ -453,29 +453,30 @@ class Renderer:
         rank's strip (owned rows packed) instead of addressing the whole frame."""
         self._ctx.check(_lib.lib().gs_set_tile_rows_interleaved(self._ctx.handle, phase, stride, int(compact_output)))
 
+    @staticmethod
+    def _camera_args(cam: Camera):
+        """view, proj, pos (contiguous float32) and sh_mode, as gs_render* and gs_debug_init_sort_list take them."""
+        return (np.ascontiguousarray(cam.getViewMatrix(), dtype=np.float32),
+                np.ascontiguousarray(cam.getProjectionMatrix(), dtype=np.float32),
+                np.ascontiguousarray(cam.getPosition(), dtype=np.float32), int(cam.getShMode()))
+
     # -- Renderer.cpp:297-515
     def draw(self, scene: Scene, out: np.ndarray | None = None) -> np.ndarray:
-        cam = scene.getCamera()
         if out is None:
             out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
-        view = np.ascontiguousarray(cam.getViewMatrix(), dtype=np.float32)
-        proj = np.ascontiguousarray(cam.getProjectionMatrix(), dtype=np.float32)
-        pos = np.ascontiguousarray(cam.getPosition(), dtype=np.float32)
+        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
         self.lastStatus = self._ctx.check(_lib.lib().gs_render(
-            self._ctx.handle, _p(view), _p(proj), _p(pos), int(cam.getShMode()), _p(out)))
+            self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode, _p(out)))
         self._accumulate()
         return out
 
     def drawDevice(self, scene: Scene, device_ptr: int | None = None, sync: bool = True, compact_rows: bool = False):
         """Same frame with the image left in HBM (device_ptr = e.g. torch tensor .data_ptr()).  compact_rows only
         documents the call site: whether rows are packed is a property of the context (setTileRowsInterleaved)."""
-        cam = scene.getCamera()
-        view = np.ascontiguousarray(cam.getViewMatrix(), dtype=np.float32)
-        proj = np.ascontiguousarray(cam.getProjectionMatrix(), dtype=np.float32)
-        pos = np.ascontiguousarray(cam.getPosition(), dtype=np.float32)
+        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
         fn = _lib.lib().gs_render_device if sync else _lib.lib().gs_render_device_async
-        self.lastStatus = self._ctx.check(fn(self._ctx.handle, _p(view), _p(proj), _p(pos),
-                                             int(cam.getShMode()), C.c_void_p(device_ptr or 0)))
+        self.lastStatus = self._ctx.check(fn(self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode,
+                                             C.c_void_p(device_ptr or 0)))
         if sync:
             self._accumulate()
 
@@ -511,12 +512,8 @@ class Renderer:
 
     # -- stage-level read-back (no reference counterpart)
     def debugInitSortList(self, scene: Scene) -> int:
-        cam = scene.getCamera()
-        view = np.ascontiguousarray(cam.getViewMatrix(), dtype=np.float32)
-        proj = np.ascontiguousarray(cam.getProjectionMatrix(), dtype=np.float32)
-        pos = np.ascontiguousarray(cam.getPosition(), dtype=np.float32)
-        return self._ctx.check(_lib.lib().gs_debug_init_sort_list(
-            self._ctx.handle, _p(view), _p(proj), _p(pos), int(cam.getShMode())))
+        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
+        return self._ctx.check(_lib.lib().gs_debug_init_sort_list(self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode))
 
     def debugRead(self, which: int) -> np.ndarray:
         info = self.sceneInfo()
@@ -562,10 +559,8 @@ class Renderer:
         return int(dev.value)
 
     # -- gradients of a frame (no reference counterpart; include/gsplat.h, gs_backward*)
-    def backward(self, grad_rgba32f: np.ndarray, grad_depth: np.ndarray | None = None) -> np.ndarray:
-        """dL/d(record), float32 (N, 84) in the record layout of setGaussians, of the last frame drawn (GS_RENDER_EXACT, whole
-        frame) from dL/dRGBA32F (float32 (H, W, 4)) and optionally dL/dDEPTH (float32 (H, W)): the quantities of
-        setOutputs(rgba32f=True, depth=True), whether or not they are enabled."""
+    def _grad_args(self, grad_rgba32f, grad_depth):
+        """dL/dRGBA32F (H, W, 4) and dL/dDEPTH (H, W) or None as contiguous float32 of the frame's shape."""
         info = self.sceneInfo()
         g = np.ascontiguousarray(grad_rgba32f, dtype=np.float32)
         if g.shape != (info.height, info.width, 4):
@@ -575,7 +570,14 @@ class Renderer:
             d = np.ascontiguousarray(grad_depth, dtype=np.float32)
             if d.shape != (info.height, info.width):
                 raise ValueError(f"grad_depth must have shape {(info.height, info.width)}, not {d.shape}")
-        out = np.zeros((info.num_gaussians, FLOATS_PER_GAUSSIAN), dtype=np.float32)
+        return g, d
+
+    def backward(self, grad_rgba32f: np.ndarray, grad_depth: np.ndarray | None = None) -> np.ndarray:
+        """dL/d(record), float32 (N, 84) in the record layout of setGaussians, of the last frame drawn (GS_RENDER_EXACT, whole
+        frame) from dL/dRGBA32F (float32 (H, W, 4)) and optionally dL/dDEPTH (float32 (H, W)): the quantities of
+        setOutputs(rgba32f=True, depth=True), whether or not they are enabled."""
+        g, d = self._grad_args(grad_rgba32f, grad_depth)
+        out = np.zeros((self.sceneInfo().num_gaussians, FLOATS_PER_GAUSSIAN), dtype=np.float32)
         self._ctx.check(_lib.lib().gs_backward(self._ctx.handle, _p(g), None if d is None else _p(d), _p(out)))
         return out
 
@@ -596,15 +598,7 @@ class Renderer:
         """backward() for the splats the frame rasterised alone: (ids uint32 (k,), rows float32 (k, 84), count) with ids
         ascending, rows[i] = backward()[ids[i]] bit for bit, count = |V| and k = min(count, max_rows).  max_rows=None sizes
         with visibleCount().  lastStatus is GS_WARN_OVERFLOW when count > max_rows."""
-        info = self.sceneInfo()
-        g = np.ascontiguousarray(grad_rgba32f, dtype=np.float32)
-        if g.shape != (info.height, info.width, 4):
-            raise ValueError(f"grad_rgba32f must have shape {(info.height, info.width, 4)}, not {g.shape}")
-        d = None
-        if grad_depth is not None:
-            d = np.ascontiguousarray(grad_depth, dtype=np.float32)
-            if d.shape != (info.height, info.width):
-                raise ValueError(f"grad_depth must have shape {(info.height, info.width)}, not {d.shape}")
+        g, d = self._grad_args(grad_rgba32f, grad_depth)
         if max_rows is None:
             max_rows = self.visibleCount()
         max_rows = int(max_rows)
