@@ -451,6 +451,38 @@ int gs_backward_visible(gs_ctx* ctx, const float* grad_rgba32f, const float* gra
 int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth,
                                uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
 
+/* Photometric loss of a frame against a photograph (no reference counterpart): the number a 3DGS optimisation minimises,
+ *   loss = (1 - lambda) * L1 + lambda * DSSIM,
+ * and its gradient with respect to the frame, in the layout gs_backward* takes.  H and W are the context's resolution.
+ * Input: rgba float[H][W][4] (the quantities of GS_OUTPUT_RGBA32F: premultiplied colour before the clamp and alpha =
+ * 1 - T_end), target float[H][W][3], bg[3] (HOST floats in both forms; NULL = black), lambda in [0, 1].
+ *   I_c    = rgba_c + (1 - rgba_a) * bg_c, not clamped; with bg == NULL, I = rgb and alpha is not read into the loss;
+ *   L1     = the mean over the H * W * 3 values of |I - G|; its derivative is sign(I - G), sign(0) = 0;
+ *   SSIM   : per channel, window 11 x 11 separable, w(k) ~ exp(-k^2 / (2 * 1.5^2)), k = -5 .. 5, normalised to sum 1 in
+ *            double and rounded once to float; pixels outside the image count as ZERO (what conv2d(padding = 5, groups = 3)
+ *            computes).  With conv = that convolution: mu1 = conv(I), mu2 = conv(G), s1 = conv(I I) - mu1 mu1,
+ *            s2 = conv(G G) - mu2 mu2, s12 = conv(I G) - mu1 mu2, C1 = 0.01^2, C2 = 0.03^2,
+ *            ssim = ((2 mu1 mu2 + C1) (2 s12 + C2)) / ((mu1^2 + mu2^2 + C1) (s1 + s2 + C2));
+ *   DSSIM  = 1 - the mean over H * W * 3 of ssim.
+ * Output: loss_out[3] = {loss, L1, DSSIM}; grad_rgba32f float[H][W][4] = dloss/d(rgba): r, g, b = dloss/dI_c,
+ * a = -sum_c bg_c * dloss/dI_c, exactly 0.0f with bg == NULL.  grad_rgba32f == NULL: the three numbers only (one launch
+ * fewer).  rgba32f == NULL: the context's own GS_OUTPUT_RGBA32F buffer of the last frame (no copy), under the conditions
+ * and with the messages of gs_output_device.  GS_RENDER_FAST contexts are allowed: the loss does not ask how the image was
+ * made.  I == G gives DSSIM = 0 and a zero gradient exactly.
+ * Bitwise reproducible: no float atomics; every 16 x 16 tile sums its pixels in a fixed tree and one workgroup sums the
+ * tiles in a fixed order (in double) -- the same bits from call to call, from both forms, and after any change of
+ * resolution and back.  Scratch: 36 bytes per pixel + 8 bytes per tile, allocated on the first call and freed with the
+ * resolution; gs_photometric_loss also stages its arguments on the device (44 bytes per pixel).
+ *   gs_photometric_loss        : HOST pointers; synchronous (loss_out and grad_rgba32f are written when it returns).
+ *   gs_photometric_loss_device : DEVICE pointers (bg: host); enqueued on the context's stream, no host sync.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued: a NULL target_rgb or loss_out, a lambda outside [0, 1]
+ * or not finite, a non-finite bg, no resolution set, a sharded context (gs_dist_shard_rows), a context that owns a subset
+ * of the tile rows, grad_rgba32f equal to rgba32f (for rgba32f == NULL: to the context's buffer). */
+int gs_photometric_loss(gs_ctx* ctx, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                        float loss_out[3], float* grad_rgba32f);
+int gs_photometric_loss_device(gs_ctx* ctx, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                               float* loss_out, float* grad_rgba32f);
+
 /* Runs ONLY the InitSortList stage of a frame (project + count scan + emit) and waits; afterwards
  * GS_BUF_UNSORTED_*, GS_BUF_COLOR, GS_BUF_COV and GS_BUF_COUNT are readable (stage-level parity). */
 int gs_debug_init_sort_list(gs_ctx* ctx, const float view[16], const float proj[16],

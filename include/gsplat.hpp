@@ -176,6 +176,23 @@ public:
         return rc;
     }
 
+    // L1 + D-SSIM of a frame against a target (gsplat.h, gs_photometric_loss): HOST rgba [H][W][4] (nullptr = the context's
+    // own GS_OUTPUT_RGBA32F buffer), target [H][W][3], bg[3] (nullptr = black) -> loss_out[3] = {loss, L1, DSSIM} and
+    // dloss/d(rgba) [H][W][4] (nullptr = the numbers only), which backward() takes as it is.
+    int photometricLoss(const float* rgba32f, const float* target_rgb, float lambda, const float* bg, float* loss_out,
+                        float* grad_rgba32f) {
+        const int rc = gs_photometric_loss(ctx_, rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    // the same with DEVICE pointers (bg stays a host pointer), enqueued on the context's stream without waiting
+    int photometricLossDevice(const float* rgba32f, const float* target_rgb, float lambda, const float* bg, float* loss_out,
+                              float* grad_rgba32f) {
+        const int rc = gs_photometric_loss_device(ctx_, rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

@@ -120,6 +120,7 @@ EXPORTS = [
     "gs_set_outputs", "gs_read_output", "gs_output_device",
     "gs_backward", "gs_backward_device", "gs_upload_gaussians_device",
     "gs_visible_count", "gs_backward_visible", "gs_backward_visible_device",
+    "gs_photometric_loss", "gs_photometric_loss_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -247,6 +248,8 @@ def lib() -> C.CDLL:
     L.gs_visible_count.argtypes = [ctxp, vp]
     L.gs_backward_visible.argtypes = [ctxp, vp, vp, vp, vp, u32, vp]
     L.gs_backward_visible_device.argtypes = [ctxp, vp, vp, vp, vp, u32, vp]
+    L.gs_photometric_loss.argtypes = [ctxp, vp, vp, f32, vp, vp, vp]
+    L.gs_photometric_loss_device.argtypes = [ctxp, vp, vp, f32, vp, vp, vp]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -14,6 +14,11 @@ rasterised (gs_backward_visible_device): no N-sized gradient is written, and tor
 It is meant for a leaf `records`.  torch's backward formulas of the ops a non-leaf `records` comes from (cat, slicing) do
 not take sparse gradients, so a non-leaf input receives the same rows scattered into a dense [N, 84] tensor.
 
+    loss = photometric_loss(rgba, target, lambda_dssim=0.2, renderer=r)         # 0-dim: (1 - l) L1 + l (1 - SSIM)
+
+photometric_loss is the library's fused L1 + D-SSIM (gs_photometric_loss_device): the three numbers and dloss/d(rgba) come
+from one call on the device, and backward hands that gradient, times the upstream scalar, to the frame.
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -115,3 +120,34 @@ def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: 
         raise ValueError("records must be on the GPU")
     mode = ("sparse" if records.grad_fn is None else "scatter") if sparse_grad else None
     return _Frame.apply(records.contiguous(), renderer, view, proj, cam_pos, int(sh_mode), bool(depth), mode)
+
+
+class _Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgba, target, renderer, lam, bg):
+        numbers = torch.empty(3, dtype=torch.float32, device=rgba.device)
+        grad = torch.empty_like(rgba) if ctx.needs_input_grad[0] else None
+        torch.cuda.current_stream(rgba.device).synchronize()        # the library works on a stream of its own
+        renderer.photometricLossDevice(rgba.data_ptr(), target.data_ptr(), lam, bg, numbers.data_ptr(),
+                                       None if grad is None else grad.data_ptr())
+        renderer.synchronize()
+        ctx.grad = grad
+        return numbers[0].clone()
+
+    @staticmethod
+    def backward(ctx, upstream):
+        return (None if ctx.grad is None else ctx.grad * upstream), None, None, None, None
+
+
+def photometric_loss(rgba: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None, *, renderer: Renderer):
+    """(1 - lambda_dssim) * L1 + lambda_dssim * (1 - SSIM) of rgba (float32 [H, W, 4] on the renderer's GPU: the RGBA32F
+    quantities, e.g. render()'s output) composited over bg (3 floats, None = black) against target (float32 [H, W, 3]), as a
+    0-dim tensor, differentiable w.r.t. rgba.  H and W are the renderer's resolution; the renderer must hold a scene (any
+    render() gives it one).  The definition is that of gs_photometric_loss in include/gsplat.h."""
+    shape = (renderer.height, renderer.width)
+    for name, t, ch in (("rgba", rgba, 4), ("target", target, 3)):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape + (ch,):
+            raise ValueError(f"{name} must be float32 {shape + (ch,)}, not {t.dtype} {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be on the GPU")
+    return _Loss.apply(rgba.contiguous(), target.detach().contiguous(), renderer, float(lambda_dssim), bg)

@@ -87,6 +87,7 @@ void free_backward(gs_ctx* c) {
 
 void free_resolution(gs_ctx* c) {
     free_backward(c);
+    free_dev(c->loss.maps); free_dev(c->loss.tile_sums); free_dev(c->loss_host);
     c->bwd_frame = false;
     drop_sort_graph(c);
     free_sort(c->sort);
@@ -942,6 +943,72 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     launch_backward(backward_frame(c), grad_rgba32f, grad_depth, c->bwd_host_out, c->stream);
     if (int r = check_launch(c, "gs_backward")) return r;
     HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+// gs_photometric_loss*: the refusals (nothing enqueued), the image the call reads (rgba32f, or the context's own
+// GS_OUTPUT_RGBA32F buffer for NULL), then the scratch of the first call
+static int loss_prepare(gs_ctx* c, const char* who, const float*& rgba32f, const float* target_rgb, float lambda,
+                        const float* bg, const float* loss_out, const float* grad_rgba32f) {
+    if (!target_rgb || !loss_out) return fail(c, GS_ERR_INVALID, std::string(who) + ": null target_rgb or loss_out");
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(c, GS_ERR_INVALID, std::string(who) + ": lambda must be a finite value in [0, 1]");
+    if (bg && !(std::isfinite(bg[0]) && std::isfinite(bg[1]) && std::isfinite(bg[2])))
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": bg must be finite");
+    if (!c->capacity) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_set_resolution not called");
+    if (c->dist_sharded)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": a sharded context (gs_dist_shard_rows) has no whole frame to compare");
+    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
+    if (!rgba32f) {
+        void* dev = nullptr;
+        size_t size = 0;
+        if (int r = output_buffer(c, GS_OUTPUT_RGBA32F, who, &dev, &size)) return r;
+        if (!c->outputs_valid)
+            return fail(c, GS_ERR_INVALID, std::string(who) + ": no frame rendered since the outputs were enabled or resized");
+        rgba32f = static_cast<const float*>(dev);
+    }
+    if (grad_rgba32f && grad_rgba32f == rgba32f)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": grad_rgba32f must not be the image it differentiates");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->loss.maps) {
+        hipError_t e = hipMalloc((void**)&c->loss.maps, loss_map_bytes(c->width, c->height));
+        if (e == hipSuccess) e = hipMalloc((void**)&c->loss.tile_sums, loss_tile_bytes(c->width, c->height));
+        if (e != hipSuccess) {
+            free_dev(c->loss.maps); free_dev(c->loss.tile_sums);
+            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        }
+    }
+    return GS_OK;
+}
+
+int gs_photometric_loss_device(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                               float* loss_out, float* grad_rgba32f) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = loss_prepare(c, "gs_photometric_loss_device", rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
+    launch_photometric_loss(c->loss, rgba32f, target_rgb, lambda, bg, c->width, c->height, loss_out, grad_rgba32f, c->stream);
+    return check_launch(c, "gs_photometric_loss_device");
+}
+
+int gs_photometric_loss(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                        float loss_out[3], float* grad_rgba32f) {
+    if (!c) return GS_ERR_INVALID;
+    const float* image = rgba32f;      // host, or (NULL form) the context's device buffer after loss_prepare
+    if (int r = loss_prepare(c, "gs_photometric_loss", image, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
+    // device copies: rgba [px][4] | gradient [px][4] | target [px][3] | the three numbers (+ 1: 16-byte multiples)
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->loss_host) HIP_TRY(c, hipMalloc((void**)&c->loss_host, (px * 11 + 4) * sizeof(float)));
+    float* d_rgba = c->loss_host, *d_grad = d_rgba + px * 4, *d_target = d_grad + px * 4, *d_loss = d_target + px * 3;
+    if (rgba32f) {
+        HIP_TRY(c, hipMemcpyAsync(d_rgba, rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        image = d_rgba;
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_target, target_rgb, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    launch_photometric_loss(c->loss, image, d_target, lambda, bg, c->width, c->height, d_loss, grad_rgba32f ? d_grad : nullptr,
+                            c->stream);
+    if (int r = check_launch(c, "gs_photometric_loss")) return r;
+    HIP_TRY(c, hipMemcpyAsync(loss_out, d_loss, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (grad_rgba32f) HIP_TRY(c, hipMemcpyAsync(grad_rgba32f, d_grad, px * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GS_OK;
 }

@@ -70,6 +70,10 @@ struct gs_ctx {
     float* bwd_vis_out = nullptr;     // gs_backward_visible (host pointers): bwd_vis_rows record gradients, grown on demand
     uint32_t bwd_vis_rows = 0;
     bool bwd_frame = false;
+    // gs_photometric_loss*: scratch allocated on the first call (9 floats per pixel + 8 bytes per tile), freed with the
+    // resolution; loss_host = the device copies of the host form's arguments (rgba, target, gradient, the three numbers)
+    gs::LossBuffers loss{};
+    float* loss_host = nullptr;
     uint32_t* ranges = nullptr;
     uint32_t* tile_order = nullptr;   // [tiles] RenderGaussians' dispatch order (GS_TILE_ORDER_LONGEST_FIRST)
     uint8_t* framebuffer = nullptr;

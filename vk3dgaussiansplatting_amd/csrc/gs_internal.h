@@ -274,6 +274,17 @@ void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uin
                                   hipStream_t stream);
 void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
                                   uint32_t max_rows, float* grad_rows, hipStream_t stream);
+// gs_photometric_loss* (gs_loss.hip): scratch of the loss, allocated on the first call and freed with the resolution
+struct LossBuffers {
+    float* maps;              // [3][H][W][3]  A, B, E of gs_loss.hip: derivatives of ssim, scaled by -lambda / (3 H W)
+    float* tile_sums;         // [tiles][2]    per 16 x 16 tile: sum of 1 - ssim, sum of |I - G|
+};
+size_t loss_map_bytes(uint32_t width, uint32_t height);
+size_t loss_tile_bytes(uint32_t width, uint32_t height);
+// loss_out[3] = {loss, L1, DSSIM} and, unless grad is null, grad[H][W][4] = dloss/dRGBA32F of rgba[H][W][4] against
+// target[H][W][3]; bg: three HOST floats or null (black).  All other pointers are device pointers.
+void launch_photometric_loss(const LossBuffers& lb, const float* rgba, const float* target, float lambda, const float* bg,
+                             uint32_t width, uint32_t height, float* loss_out, float* grad, hipStream_t stream);
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,
                        const SceneBuffers& s, hipStream_t stream);
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream);

@@ -621,6 +621,48 @@ class Renderer:
             C.c_void_p(ids_ptr) if ids_ptr else None, C.c_void_p(rows_ptr) if rows_ptr else None, int(max_rows),
             C.c_void_p(count_ptr) if count_ptr else None))
 
+    # -- photometric loss of a frame (no reference counterpart; include/gsplat.h, gs_photometric_loss*)
+    @staticmethod
+    def _bg_arg(bg):
+        """bg as three contiguous float32 (kept alive by the caller for the call) or None."""
+        if bg is None:
+            return None
+        b = np.ascontiguousarray(bg, dtype=np.float32)
+        if b.shape != (3,):
+            raise ValueError(f"bg must have 3 components, not shape {b.shape}")
+        return b
+
+    def photometricLoss(self, rgba: np.ndarray | None, target: np.ndarray, lam: float = 0.2, bg=None, want_grad: bool = True):
+        """(1 - lam) * L1 + lam * (1 - SSIM) of rgba (float32 (H, W, 4): the quantities of setOutputs(rgba32f=True); None =
+        the context's own buffer of the last frame) over the background bg (3 floats, None = black) against target (float32
+        (H, W, 3)).  Returns (numbers, grad): numbers = float32 (3,) {loss, L1, DSSIM}; grad = dloss/d(rgba) float32 (H, W, 4)
+        as backward() takes it, or None with want_grad=False."""
+        info = self.sceneInfo()
+        a = None
+        if rgba is not None:
+            a = np.ascontiguousarray(rgba, dtype=np.float32)
+            if a.shape != (info.height, info.width, 4):
+                raise ValueError(f"rgba must have shape {(info.height, info.width, 4)}, not {a.shape}")
+        t = np.ascontiguousarray(target, dtype=np.float32)
+        if t.shape != (info.height, info.width, 3):
+            raise ValueError(f"target must have shape {(info.height, info.width, 3)}, not {t.shape}")
+        b = self._bg_arg(bg)
+        numbers = np.zeros(3, dtype=np.float32)
+        grad = np.zeros((info.height, info.width, 4), dtype=np.float32) if want_grad else None
+        self._ctx.check(_lib.lib().gs_photometric_loss(self._ctx.handle, None if a is None else _p(a), _p(t), float(lam),
+                                                       None if b is None else _p(b), _p(numbers),
+                                                       None if grad is None else _p(grad)))
+        return numbers, grad
+
+    def photometricLossDevice(self, rgba_ptr: int | None, target_ptr: int, lam: float, bg, loss_ptr: int, grad_ptr: int | None):
+        """The same with device addresses (rgba: float32 (H, W, 4) or None for the context's own buffer, target: (H, W, 3),
+        loss: 3 floats, grad: (H, W, 4) or None); bg stays a host value.  Enqueued on the context's stream without waiting."""
+        b = self._bg_arg(bg)
+        self._ctx.check(_lib.lib().gs_photometric_loss_device(
+            self._ctx.handle, C.c_void_p(rgba_ptr) if rgba_ptr else None, C.c_void_p(target_ptr) if target_ptr else None,
+            float(lam), None if b is None else _p(b), C.c_void_p(loss_ptr) if loss_ptr else None,
+            C.c_void_p(grad_ptr) if grad_ptr else None))
+
     def uploadDevice(self, ptr: int, n: int):
         """Gaussian records (float32 (n, 84)) from device memory.  With the scene's n: rewritten in place on the context's
         stream, resolution kept; with another n: a new scene, and the resolution is set again here."""
