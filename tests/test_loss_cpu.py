@@ -1,7 +1,7 @@
 """The photometric loss (include/gsplat.h, gs_photometric_loss*) without a GPU: `loss_reference`, the float64 restatement of
 the header's definition that tests/test_loss_gpu.py holds the kernels to, checked here against central differences and
-against a direct 121-tap loop; the seeded inputs of both files; and the two symbols in the header, the binding and the
-library."""
+against a direct 121-tap loop; the seeded inputs of both files, those of more than 1024 tiles with their precondition and
+their float32 guard; and the two symbols in the header, the binding and the library."""
 import functools
 
 import numpy as np
@@ -20,6 +20,19 @@ LAMBDAS = (0.2, 0.0, 1.0)
 BG = (0.2, 0.5, 0.9)
 BGS = (None, (1.0, 1.0, 1.0), BG)
 SEED = 4
+
+# More than 1024 tiles: k_loss_reduce gives each of its 1024 threads per = ceil(tiles / 1024) consecutive tiles.  W x H, each
+# the smallest that reaches its edge: 1024 tiles (per = 1, every thread busy, one valid row per tile); 1025 (per = 2, 513
+# threads, the last owns a single tile); the same with grid_w = 1; 2049 (per = 3, ragged tail); 8193 (per = 9, as a 1080p
+# frame's 8160 tiles with per = 8; 911 threads busy).  MANY_TILES_2D: 33 x 32 = 1056 tiles, interior tiles with full halos.
+STRIPS = [(16384, 1), (16385, 1), (1, 16385), (32769, 2), (131073, 1)]
+MANY_TILES_2D = (528, 512)
+APART_KINDS = ("noise_apart", "near_apart")         # held to TOL["noise"], the project's own 2e-5
+# (kind, w, h, lambda, bg) of tests/test_loss_gpu.py::test_by_value_many_tiles
+MANY_TILE_CASES = [(kind, w, h, lam, bg) for w, h in STRIPS for kind in APART_KINDS for lam in (0.2, 1.0) for bg in (None, BG)]
+MANY_TILE_CASES.append(("noise_apart",) + MANY_TILES_2D + (0.2, BG))
+# (kind, w, h) of the float32 guard: lambda = 0.2, no background
+MANY_TILE_GUARD = [(kind, w, h) for w, h in STRIPS for kind in APART_KINDS] + [("noise_apart",) + MANY_TILES_2D]
 
 
 @functools.lru_cache(maxsize=None)
@@ -79,13 +92,19 @@ def loss_float32(rgba, target, lam=0.2, bg=None, separable=True):
 def make_inputs(kind, w, h, seed, alpha):
     """Seeded float32 (rgba [H][W][4], target [H][W][3]).  noise: I uniform in [-0.1, 1.1], G uniform in [0, 1]; near:
     I = G + 0.02 N(0, 1); flat: G = 0.7, I = 0.69, both + 1e-3 N(0, 1) (conv(I^2) - mu^2 cancels).  alpha: random in [0, 1] (for a background: rgb
-    is then chosen so that the composited image over `alpha` = bg is the I above), else 0."""
-    rng = np.random.default_rng([seed, w, h, {"noise": 0, "near": 1, "flat": 2}[kind]])
+    is then chosen so that the composited image over `alpha` = bg is the I above), else 0.  For any number of values, where
+    noise and near come as close as float32 rounding (|I - G| of 6e-8 and 0 among 1e5 values), two kinds apart by
+    construction, s = +-1 at random: noise_apart: I = G + s U(1e-3, 0.6); near_apart: I = G + s (1e-3 + 0.02 |N(0, 1)|)."""
+    rng = np.random.default_rng([seed, w, h, {"noise": 0, "near": 1, "flat": 2, "noise_apart": 3, "near_apart": 4}[kind]])
     g = rng.uniform(0.0, 1.0, (h, w, 3))
     if kind == "noise":
         i = rng.uniform(-0.1, 1.1, (h, w, 3))
     elif kind == "near":
         i = g + 0.02 * rng.standard_normal((h, w, 3))
+    elif kind in APART_KINDS:
+        s = rng.choice((-1.0, 1.0), (h, w, 3))
+        i = g + s * (rng.uniform(1e-3, 0.6, (h, w, 3)) if kind == "noise_apart"
+                     else 1e-3 + 0.02 * np.abs(rng.standard_normal((h, w, 3))))
     else:
         g = 0.7 + 1e-3 * rng.standard_normal((h, w, 3))
         i = 0.69 + 1e-3 * rng.standard_normal((h, w, 3))
@@ -96,6 +115,42 @@ def make_inputs(kind, w, h, seed, alpha):
         i = i - (1.0 - a)[..., None] * np.asarray(alpha, np.float64)
     rgba[..., :3] = i
     return rgba, g.astype(np.float32)
+
+
+def composited_float32(rgba, bg):
+    """I = rgb + (1 - a) * bg in float32, in the kernels' order of operations."""
+    i = rgba[..., :3].astype(np.float32)
+    if bg is not None:
+        i = i + (np.float32(1.0) - rgba[..., 3:4]) * np.asarray(bg, np.float32)
+    assert i.dtype == np.float32
+    return i
+
+
+def _frozen(*arrays):
+    for a in arrays:
+        a.setflags(write=False)
+    return arrays
+
+
+@functools.lru_cache(maxsize=None)
+def many_tile_case(kind, w, h, lam, bg):
+    """(rgba, target, reference numbers, reference gradient) of one many-tile case: computed once per process, shared by
+    the tests that need it, read-only."""
+    rgba, target = make_inputs(kind, w, h, SEED, bg)
+    return _frozen(rgba, target, *loss_reference(rgba, target, lam, bg))
+
+
+@functools.lru_cache(maxsize=None)
+def float32_torch_errors(kind, w, h):
+    """What float32 torch (both summation orders, lambda = 0.2, no background) is wrong by on make_inputs(kind, w, h, SEED):
+    (|loss - ref| / |ref|, max |gradient - ref| / max |ref|), the worse of the two orders."""
+    rgba, target, ref_n, ref_g = many_tile_case(kind, w, h, 0.2, None)
+    worst_l = worst_g = 0.0
+    for separable in (True, False):
+        n, g = loss_float32(rgba, target, 0.2, None, separable)
+        worst_l = max(worst_l, abs(float(n[0]) - ref_n[0]) / abs(ref_n[0]))
+        worst_g = max(worst_g, float(np.abs(g - ref_g).max() / np.abs(ref_g).max()))
+    return worst_l, worst_g
 
 
 def direct_numbers(rgba, target, lam, bg):
@@ -168,6 +223,36 @@ def test_float32_orders_agree_with_the_reference():
         n, g = loss_float32(rgba, target, separable=separable)
         assert np.abs(n - ref_n).max() <= 2e-6 * np.abs(ref_n).max()
         assert np.abs(g - ref_g).max() <= 2e-6 * np.abs(ref_g).max()
+
+
+@pytest.mark.parametrize("w,h", STRIPS + [MANY_TILES_2D], ids=[f"{w}x{h}" for w, h in STRIPS + [MANY_TILES_2D]])
+def test_apart_kinds_are_apart(w, h):
+    """The precondition of the by-value tests on the many-tile inputs, every kind with and without a background:
+    min |composited I - G| > 5e-7 with the composite and the difference in float32 (1.0e-3 by construction), so that no
+    sign(I - G) hangs on float32 rounding; both signs occur, and alpha is random under a background and 0 without."""
+    for kind in APART_KINDS:
+        for bg in (None, BG):
+            rgba, target = make_inputs(kind, w, h, SEED, bg)
+            assert rgba.dtype == target.dtype == np.float32 and rgba.shape == (h, w, 4) and target.shape == (h, w, 3)
+            d = composited_float32(rgba, bg) - target
+            assert d.dtype == np.float32
+            gap = float(np.abs(d).min())
+            print(f"{kind} {w}x{h} bg={bg}: min |I - G| {gap:.3e}")
+            assert gap > 5e-7 and gap > 0.99e-3, (kind, bg, gap)
+            assert (d > 0).any() and (d < 0).any()
+            assert rgba[..., 3].any() == (bg is not None)
+
+
+@pytest.mark.parametrize("kind,w,h", MANY_TILE_GUARD, ids=[f"{k}-{w}x{h}" for k, w, h in MANY_TILE_GUARD])
+def test_float32_torch_stays_within_a_fraction_of_tol_many_tiles(kind, w, h):
+    """The guard of tests/test_loss_gpu.py::test_float32_torch_stays_within_a_fraction_of_tol on the many-tile inputs, where
+    no GPU is needed for it: float32 torch stays within tol / 5 = 4e-6 of the float64 reference.  Worst when written: loss
+    1.7e-6 (near_apart, 131073 x 1), gradient 9.9e-7 of its scale (noise_apart, 528 x 512)."""
+    pytest.importorskip("torch")
+    tol = TOL["noise"]
+    worst_l, worst_g = float32_torch_errors(kind, w, h)
+    print(f"float32 torch, {kind} {w}x{h}: loss {worst_l:.3e}, gradient {worst_g:.3e} of its scale (tol {tol})")
+    assert worst_l <= tol / 5 and worst_g <= tol / 5
 
 
 def test_loss_symbols_are_exported():

@@ -1,6 +1,7 @@
 """The photometric loss on the MI355X (include/gsplat.h, gs_photometric_loss*; csrc/gs_loss.hip) against `loss_reference`
-of tests/test_loss_cpu.py (float64), by value, by bits, by known answers, through the zero-copy path, the refusals and
-torch autograd.  A one-splat scene exists only so that a resolution can be set; rgba and target are passed explicitly."""
+of tests/test_loss_cpu.py (float64), by value (also past 1024 tiles), by bits, by known answers, through the zero-copy
+path, the refusals and torch autograd.  A one-splat scene exists only so that a resolution can be set; rgba and target are
+passed explicitly."""
 import ctypes as C
 import os
 import subprocess
@@ -14,7 +15,8 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import make_renderer, make_scene
 from test_backward_cpu import small_scene
-from test_loss_cpu import BG, BGS, LAMBDAS, SEED, SHAPES, TOL, loss_float32, loss_reference, make_inputs
+from test_loss_cpu import (BG, BGS, LAMBDAS, MANY_TILE_CASES, MANY_TILE_GUARD, SEED, SHAPES, TOL,
+                           composited_float32, float32_torch_errors, loss_reference, make_inputs, many_tile_case)
 
 pytestmark = pytest.mark.gpu
 
@@ -96,22 +98,53 @@ def test_by_value(contexts, w, h, kind):
     print(f"WORST {kind} {w}x{h}: gradient {worst_g:.3e} of the plane's scale, numbers {worst_n:.3e} (tol {tol})")
 
 
-@pytest.mark.parametrize("kind", list(TOL))
-def test_float32_torch_stays_within_a_fraction_of_tol(kind):
+def case_id(kind, w, h, lam, bg):
+    return f"{kind}-{w}x{h}-lam{lam}-{'bg' if bg else 'black'}"
+
+
+@pytest.mark.parametrize("kind,w,h,lam,bg", MANY_TILE_CASES, ids=[case_id(*c) for c in MANY_TILE_CASES])
+def test_by_value_many_tiles(contexts, kind, w, h, lam, bg):
+    """More than 1024 tiles, where k_loss_reduce gives a thread `per` > 1 tiles, a ragged last slice or none at all
+    (test_loss_cpu.STRIPS, MANY_TILES_2D): the assertions of test_by_value at its tol of 2e-5, every number relative (each
+    DSSIM here exceeds 1e-3, which is asserted).  The kinds are noise_apart and near_apart, whose |I - G| is at least 1e-3 by
+    construction: the precondition, evaluated in float32, holds for every case.  Strips: both kinds x lambda in {0.2, 1} x
+    bg in {NULL, (0.2, 0.5, 0.9)}; 528 x 512: noise_apart, lambda 0.2, with the background.  A reduce that drops or doubles a
+    tile moves the numbers by about 1 / tiles (6e-5 for the single pixel of the 1025th tile) and no gradient value.
+    The kernels on an MI355X, worst over these cases: gradient 1.1e-6 of the plane's scale (near_apart, 1 x 16385, lambda 1,
+    with the background; noise_apart at most 3.0e-7), numbers 5.3e-8 relative (noise_apart, 16384 x 1)."""
+    tol = TOL["noise"]
+    rgba, target, ref_n, ref_g = many_tile_case(kind, w, h, lam, bg)
+    assert np.abs(composited_float32(rgba, bg) - target).min() > 5e-7       # no sign(I - G) hangs on float32 rounding
+    assert np.abs(composited(rgba, bg) - target).min() > 5e-7
+    assert ref_n[2] >= 1e-3
+    got_n, got_g = contexts(w, h).photometricLoss(rgba, target, lam, bg)
+    err, scale = plane_errors(got_g, ref_g)
+    nerr, nb = np.abs(got_n.astype(np.float64) - ref_n), tol * np.abs(ref_n)
+    worst_g, worst_n = float((err / np.where(scale > 0, scale, 1.0)).max()), float((nerr / np.abs(ref_n)).max())
+    print(f"WORST {case_id(kind, w, h, lam, bg)}: gradient {worst_g:.3e} of the plane's scale, numbers {worst_n:.3e} (tol {tol})")
+    assert np.all(err <= tol * scale), (err, scale)
+    assert np.all(nerr <= nb), (got_n, ref_n)
+
+
+GUARD_CASES = ([pytest.param(kind, SHAPES, id=kind) for kind in TOL] +
+               [pytest.param(kind, [(w, h)], id=f"{kind}-{w}x{h}") for kind, w, h in MANY_TILE_GUARD])
+
+
+@pytest.mark.parametrize("kind,shapes", GUARD_CASES)
+def test_float32_torch_stays_within_a_fraction_of_tol(kind, shapes):
     """The guard on the margin: the float32 evaluation by torch (both summation orders, lambda = 0.2, no background: what
     the tolerance was derived from) on every shape.  The figures the tolerance was set from, 2.2e-6 and 1.7e-6, are 0.11
     and 0.085 of 2e-5, and on these inputs torch's float32 gradient reaches 0.10 to 0.17 of it for `near` whatever the
     seed: `a tenth of tol` cannot hold for that figure, so the guard is tol / 5 -- a margin of five, twice the worst figure
-    measured (0.108 with this seed).  A torch whose float32 convolution is wrong by more than that fails here."""
-    tol = TOL[kind]
+    measured (0.108 with this seed).  A torch whose float32 convolution is wrong by more than that fails here.  The
+    many-tile inputs of test_by_value_many_tiles, one shape per case: at worst 1.7e-6 of the loss (near_apart, 131073 x 1)
+    and 9.9e-7 of the gradient's scale (noise_apart, 528 x 512) against 4e-6.  near_apart is left out at 528 x 512: the
+    near kind reaches 3.4e-6 there, 0.84 of the guard."""
+    tol = TOL.get(kind, TOL["noise"])              # the many-tile kinds are held to the same 2e-5
     worst_l = worst_g = 0.0
-    for w, h in SHAPES:
-        rgba, target = make_inputs(kind, w, h, SEED, None)
-        ref_n, ref_g = loss_reference(rgba, target, 0.2, None)
-        for separable in (True, False):
-            n, g = loss_float32(rgba, target, 0.2, None, separable)
-            worst_l = max(worst_l, abs(float(n[0]) - ref_n[0]) / abs(ref_n[0]))
-            worst_g = max(worst_g, np.abs(g - ref_g).max() / np.abs(ref_g).max())
+    for w, h in shapes:
+        err_l, err_g = float32_torch_errors(kind, w, h)
+        worst_l, worst_g = max(worst_l, err_l), max(worst_g, err_g)
     print(f"float32 torch, {kind}: loss {worst_l:.3e}, gradient {worst_g:.3e} of its scale (tol {tol})")
     assert worst_l <= tol / 5 and worst_g <= tol / 5
 
@@ -171,7 +204,57 @@ def test_bits_are_reproducible(contexts):
     assert np.array_equal(bits(n0), bits(n3)) and np.array_equal(bits(g0), bits(g3))
 
 
+def test_bits_are_reproducible_many_tiles(contexts):
+    """16385 x 1 (1025 tiles: two per thread of the reduce, the last thread's slice ragged): the host form twice and the
+    device form once give identical uint32 views of loss_out and of the gradient."""
+    pytest.importorskip("torch")
+    w, h = 16385, 1
+    r = contexts(w, h)
+    rgba, target = many_tile_case("noise_apart", w, h, 0.2, BG)[:2]
+    n0, g0 = r.photometricLoss(rgba, target, 0.2, BG)
+    n1, g1 = r.photometricLoss(rgba, target, 0.2, BG)
+    assert n0.all() and np.any(g0 != 0)
+    assert np.array_equal(bits(n0), bits(n1)) and np.array_equal(bits(g0), bits(g1))
+    n2, g2 = device_call(r, rgba, target, 0.2, BG)
+    assert np.array_equal(bits(n0), bits(n2)) and np.array_equal(bits(g0), bits(g2))
+
+
 # ---- 4. known answers -----------------------------------------------------------------------------------------------------
+
+ODD_TILES = {"first": lambda tiles, per: 0, "last": lambda tiles, per: tiles - 1, "per-1": lambda tiles, per: per - 1,
+             "per": lambda tiles, per: per, "tiles-2": lambda tiles, per: tiles - 2}
+
+
+@pytest.mark.parametrize("odd", list(ODD_TILES))
+@pytest.mark.parametrize("w,h", [(16385, 1), (32769, 2)], ids=["16385x1", "32769x2"])
+def test_l1_exact_many_tiles(contexts, w, h, odd):
+    """A known answer for the sum over the tiles, with no reference and no tolerance beyond the last rounding: lambda = 0,
+    no background, G = 0.5 everywhere, I - G = 0.25 everywhere but in one whole tile, where it is 0.5.  Every |I - G|, every
+    tile's sum (12 or 24 per 16 pixels) and every partial sum of them is exact in float and in double, so L1 is
+    float32(sum / (3 W H)) to 1 ulp (the kernel multiplies by the rounded reciprocal) and the loss is L1.  The odd tile is
+    the first, the last (one pixel wide), the last of the first thread's slice of `per` tiles, the first of the second
+    thread's, and the last but one: a dropped or doubled tile is 0.25 or 0.5 per value of it away, and which one says where."""
+    grid_w, grid_h = (w + 15) // 16, (h + 15) // 16
+    tiles = grid_w * grid_h
+    per = (tiles + 1023) // 1024
+    assert tiles > 1024 and per > 1
+    tile = ODD_TILES[odd](tiles, per)
+    tx, ty = tile % grid_w, tile // grid_w
+    diff = np.full((h, w, 3), 0.25, np.float32)
+    diff[ty * 16:(ty + 1) * 16, tx * 16:(tx + 1) * 16] = 0.5
+    in_tile = int(np.count_nonzero(diff == 0.5))
+    assert in_tile == 3 * min(16, w - tx * 16) * min(16, h - ty * 16) > 0
+    target = np.full((h, w, 3), 0.5, np.float32)
+    rgba = np.zeros((h, w, 4), np.float32)
+    rgba[..., :3] = target + diff                                   # 0.75 and 1.0: exact
+    expected_sum = 0.25 * (3 * w * h - in_tile) + 0.5 * in_tile
+    want = np.float32(expected_sum / (3 * w * h))
+    n, g = contexts(w, h).photometricLoss(rgba, target, 0.0, None)
+    print(f"{w}x{h} tile {tile} of {tiles} (per {per}): L1 {n[1]!r}, expected {want!r}")
+    assert abs(np.float64(n[1]) - np.float64(want)) <= np.spacing(want), (tile, n, want)
+    assert bits(n[:1]) == bits(n[1:2])
+    assert np.array_equal(g[..., :3], np.full((h, w, 3), np.float32(1.0 / (3 * w * h)))) and not bits(g[..., 3]).any()
+
 
 def test_identical_images(contexts):
     """I == G, lambda = 0.2: all three numbers <= 1e-6 and an rgb gradient of at most 1e-6 / (3 H W) in magnitude, with and
