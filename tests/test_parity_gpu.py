@@ -1206,15 +1206,21 @@ def test_c_abi_sharded_frame_single_rank(with_torch):
     assert p.returncode == 0 and "dist-ok" in p.stdout, (p.stdout[-500:], p.stderr[-3000:])
 
 
+# the size classes of gs_tilesort.hip that the runs of each case below fall into (by the cloud size n), all of them and no other:
+# asserted from the oracle's ranges with the routing table restated in test_designed_runs_cpu.py, which places runs on the edges
+_TILE_BUCKET_CASE_CLASSES = {3000: {"S1"}, 60_000: {"chunked"}, 200_000: {"global"}, 50_000: {"S1", "S2", "S3"}}
+
+
 @pytest.mark.parametrize("n,w,h,mu", [
-    (3000, 320, 180, -3.2),      # small runs (256-thread LDS variant)
-    (60_000, 64, 48, -2.0),      # ~5-9 k elements per tile (1024-thread / 160 KB variant)
-    (200_000, 48, 32, -2.5),     # > 10 k elements per tile (global-memory fallback)
-    (50_000, 250, 130, -1.0),    # mixture incl. partial tiles
+    (3000, 320, 180, -3.2),      # small runs, 12 ... 45 elements (256-thread LDS variant, S1)
+    (60_000, 64, 48, -2.0),      # 5.5-7.4 k elements in every tile (1024-thread / 160 KB variant, chunked)
+    (200_000, 48, 32, -2.5),     # 27-36 k elements in every tile (global-memory fallback)
+    (50_000, 250, 130, -1.0),    # 0.8-2.6 k: S1, S2 and S3 together, partial tiles, and a list that overflows its capacity
 ])
 def test_tile_bucket_sorter_is_bit_identical(oracle_mod, n, w, h, mu):
     """GS_SORT_TILE_BUCKET (the GpuSort seam's alternative back-end) must give exactly the contractual
     result: same keys, payload order, ranges and pixels as the oracle."""
+    from test_designed_runs_cpu import size_class
     aos = synth.generate(n, w, h, mu, seed=1234 + n)
     sc = make_scene(aos, w, h)
     r = make_renderer(sc, w, h, sort=gs.GS_SORT_TILE_BUCKET)
@@ -1222,6 +1228,8 @@ def test_tile_bucket_sorter_is_bit_identical(oracle_mod, n, w, h, mu):
     _, ref = oracle_run(oracle_mod, sc, w, h)
     lens = ref["ranges"][:, 1].astype(np.int64) - ref["ranges"][:, 0]
     print("max run", lens.max(), "mean", lens.mean())
+    assert {size_class(v) for v in lens} == _TILE_BUCKET_CASE_CLASSES[n], "the case does not reach the size class it is here for"
+    assert (ref["stage1"]["counter"] > ref["stage1"]["capacity"]) == (n == 50_000)
     assert_frame_equals_oracle(r, img, ref)
     # twice: the in-place per-tile sort must not depend on stale buffer contents
     img2 = r.draw(sc)
