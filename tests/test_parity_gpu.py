@@ -524,8 +524,10 @@ def _radix4_fed():
 @pytest.mark.parametrize("bits", [44, 48])
 @pytest.mark.parametrize("sorter", [_radix4_per_pass, _radix4_fed, gs.RadixSort8], ids=["radix4", "radix4_fed", "radix8"])
 def test_radix_sort_matches_stable_sort(n, bits, sorter):
-    """GpuSort seam on caller arrays: ragged sizes around the 64-lane and 2048- / 4096-key group edges,
-    heavy ties (payload order must be preserved).  Tile words carry bits above the sorted ones when bits < 48 is
+    """GpuSort seam on caller arrays: ragged sizes around the 64-lane and 2048-key group edges (a list of fewer than
+    GS_SORT8_SMALL_BELOW keys sorts in 2048-key groups under the 8-bit sorter too, so 4095, 4096 and 4097 are two groups here;
+    its 4096-key groups are in test_radix_sort_8bit_4096_key_groups_match_stable_sort), heavy ties (payload order must be
+    preserved).  Tile words carry bits above the sorted ones when bits < 48 is
     paired with a wider draw (the 8-bit variant's last pass must mask them).  radix4_fed: one Count launch per sort, every
     Scatter feeds the next pass's counts (GS_COUNT_FED) -- also beyond the list length GS_COUNT_AUTO would choose it for."""
     rng = np.random.default_rng(n * 131 + bits)
@@ -538,6 +540,30 @@ def test_radix_sort_matches_stable_sort(n, bits, sorter):
     rs = sorter()
     rs.initForScene(n, 1 << (bits - 32))
     assert rs.radixSortNumSortBits == bits
+    t, d, i = rs.computeSort(tile, depth, ident)
+    key = (tile.astype(np.uint64) << np.uint64(32)) | depth.astype(np.uint64)
+    order = np.argsort(key, kind="stable")
+    assert np.array_equal(i, ident[order])
+    assert np.array_equal(t, tile[order]) and np.array_equal(d, depth[order])
+    rs.cleanup()
+
+
+@pytest.mark.parametrize("n", [2930 * 4096 - 1, 2930 * 4096, 2930 * 4096 + 1])
+def test_radix_sort_8bit_4096_key_groups_match_stable_sort(n):
+    """The 8-bit sorter's 4096-key groups by value: launch_radix_sort8 uses them from a capacity of GS_SORT8_SMALL_BELOW
+    (12,000,000; the stand-alone sorter's capacity is n).  2930 whole groups, one key less (a last group short of one key) and
+    one key more (a last group of one key), 48 bits, the heavy ties of test_radix_sort_matches_stable_sort: keys, payload
+    and its order against a stable sort."""
+    assert n >= 12_000_000 and -(-n // 4096) in (2930, 2931)
+    rng = np.random.default_rng(n)
+    tile = rng.integers(0, 1 << 16, n, dtype=np.uint32)
+    depth = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+    depth[rng.integers(0, n, n // 3)] = 12345              # many equal keys
+    tile[: n // 2] = tile[0]
+    ident = np.arange(n, dtype=np.uint32)
+    rs = gs.RadixSort8()
+    rs.initForScene(n, 1 << 16)
+    assert rs.radixSortNumSortBits == 48 and rs.maxNumSortElements == n
     t, d, i = rs.computeSort(tile, depth, ident)
     key = (tile.astype(np.uint64) << np.uint64(32)) | depth.astype(np.uint64)
     order = np.argsort(key, kind="stable")
