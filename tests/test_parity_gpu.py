@@ -2025,3 +2025,66 @@ def test_frames_without_timers(oracle_mod, small_cloud, sort):
                 assert np.array_equal(img[48:144], band["image"][48:144])
             r.setTileRows(0, r.sceneInfo().tiles_y)
     r.cleanup()
+
+
+# sorter -> (scatter_launches, scatter_bytes_per_elem, scatter_tile_launches, scatter_tile_bytes_per_elem) at 144 tiles
+# (40 key bits, 16-bit tile words).  A pass moves the depth bytes it reads and writes + 2 x 2 bytes of tile word + 8 bytes of
+# id: the 4-bit depth passes 8, 8, 8, 6, 4, 4, 4, 2 bytes of depth word (140 / 8 = 17.5), the 8-bit ones 8, 6, 4, 2
+# (68 / 4 = 17.0), a tile-word pass none (12); the bucket sorter carries the depth word through its passes (8 + 4 + 8 = 20).
+_PASS_LAYOUT_144_TILES = {
+    gs.GS_SORT_RADIX4: (8, 17.5, 2, 12.0),
+    gs.GS_SORT_RADIX8: (4, 17.0, 1, 12.0),
+    gs.GS_SORT_TILE_BUCKET: (2, 20.0, 0, 0.0),
+    gs.GS_SORT_RADIX4_SPLAT_FIRST: (8, 17.5, 2, 12.0),
+    gs.GS_SORT_RADIX8_SPLAT_FIRST: (4, 17.0, 1, 12.0),
+}
+# ... and the launches at 16 tiles (36 key bits): one tile-word pass of either width
+_PASS_LAUNCHES_16_TILES = {
+    gs.GS_SORT_RADIX4: (8, 1),
+    gs.GS_SORT_RADIX8: (4, 1),
+    gs.GS_SORT_TILE_BUCKET: (1, 0),
+    gs.GS_SORT_RADIX4_SPLAT_FIRST: (8, 1),
+    gs.GS_SORT_RADIX8_SPLAT_FIRST: (4, 1),
+}
+
+
+@pytest.mark.parametrize("sort", ALL_SORTS)
+def test_frames_with_per_pass_timers(oracle_mod, small_cloud, sort):
+    """record_timings = 2 is what bench.py --full runs: nothing is captured, every radix pass is launched directly with a
+    pair of events around its Scatter.  Three frames: the oracle's list, ranges and pixels, five buckets > 0 that fit
+    inside the total (the intervals telescope inside the outer pair of events; the margin is the rounding of the float
+    sums), and the exact pass layout.  Then a band of one tile row (16 tiles, 36 key bits, a share below one half: the
+    launchers' reduced grid): the oracle's band, one tile-word pass fewer, the same bytes per pass."""
+    w, h = 256, 144
+    sc = make_scene(small_cloud, w, h, pos=(0.2, 0.1, -1.0), yaw=0.1, pitch=-0.05)
+    _, ref = oracle_run(oracle_mod, sc, w, h)
+    r = gs.Renderer(w, h, warmup_frames=0, sort_algorithm=sort, record_timings=2)
+    r.init(sc.getResourceManager())
+    r.initForScene(sc)
+    launches, bytes_per_elem, tile_launches, tile_bytes = _PASS_LAYOUT_144_TILES[sort]
+
+    def check_timings(t, launches, tile_launches, tile_bytes):
+        buckets = (t.init_sort_list_ms, t.radix_sort_ms, t.find_ranges_ms, t.render_ms)
+        assert all(b > 0.0 for b in buckets) and t.total_ms > 0.0, (buckets, t.total_ms)
+        assert sum(buckets) <= t.total_ms * (1 + 1e-3), (buckets, t.total_ms)
+        assert (t.scatter_launches, t.scatter_tile_launches) == (launches, tile_launches)
+        assert (t.scatter_bytes_per_elem, t.scatter_tile_bytes_per_elem) == (bytes_per_elem, tile_bytes)
+
+    for _ in range(3):
+        img = r.draw(sc)
+        assert_frame_equals_oracle(r, img, ref)
+        check_timings(r.timings(), launches, tile_launches, tile_bytes)
+    r.setTileRows(0, 1)
+    _, band = oracle_run(oracle_mod, sc, w, h, row_begin=0, row_end=1)
+    e = band["e"]
+    assert e > 0
+    for _ in range(2):
+        img = r.draw(sc)
+        assert r.timings().num_sort_elements == e
+        assert np.array_equal(r.debugRead(gs.BUF_SORTED_TILE), band["tile"][:e])
+        assert np.array_equal(r.debugRead(gs.BUF_SORTED_DEPTH), band["depth"][:e])
+        assert np.array_equal(r.debugRead(gs.BUF_SORTED_ID), band["id"][:e])
+        assert np.array_equal(r.debugRead(gs.BUF_RANGES), band["ranges"])
+        assert np.array_equal(img[0:16], band["image"][0:16])
+        check_timings(r.timings(), *_PASS_LAUNCHES_16_TILES[sort], tile_bytes)
+    r.cleanup()

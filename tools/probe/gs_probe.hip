@@ -152,19 +152,6 @@ __global__ __launch_bounds__(256) void k_lds_poison(uint32_t pattern, uint32_t* 
 
 using namespace gs;
 
-namespace {
-int fail(gs_ctx* ctx, int code, const std::string& msg) {
-    if (ctx) ctx->last_error = msg;
-    return code;
-}
-#define HIP_TRY(ctx, expr)                                                                       \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail((ctx), GS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-}
-
 extern "C" {
 
 // Re-runs RenderGaussians of the last frame with per-tile

@@ -14,85 +14,42 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <new>
 #include <string>
 #include <vector>
 
 using namespace gs;
 
-static thread_local std::string g_create_error;
-void gsi_set_create_error(const std::string& msg) { g_create_error = msg; }
-
 namespace {
-
-int fail(gs_ctx* ctx, int code, const std::string& msg) {
-    if (ctx) ctx->last_error = msg; else g_create_error = msg;
-    return code;
-}
-
-#define HIP_TRY(ctx, expr)                                                                       \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess)                                                                    \
-            return fail((ctx), GS_ERR_HIP,                                                       \
-                        std::string(#expr) + ": " + hipGetErrorString(_e));                      \
-    } while (0)
-
-template <typename T>
-void free_dev(T*& p) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-}
 
 void free_scene(gs_ctx* c) {
     if (c->shared) {                  // drop this context's reference; the last one frees the arrays
         if (c->shared->refs.fetch_sub(1) == 1) {
-            SceneBuffers& b = c->shared->b;
-            free_dev(b.pos); free_dev(b.scale); free_dev(b.rot);
-            free_dev(b.sh); free_dev(b.opacity); free_dev(b.sig2); free_dev(b.block_bounds);
+            c->shared->mem.release();
             delete c->shared;
         }
         c->shared = nullptr;
     }
     c->scene = SceneBuffers{};
-    free_dev(c->scratch.raster); free_dev(c->scratch.depth_key); free_dev(c->scratch.tiles_touched);
-    free_dev(c->scratch.extents); free_dev(c->scratch.block_sums); free_dev(c->scratch.block_offsets);
-    free_dev(c->scratch.help_list); free_dev(c->scratch.help_count); free_dev(c->scratch.help_slot);
-    free_dev(c->scratch.wave_wrote);
-    free_dev(c->scratch.band_list);
-    free_dev(c->scratch.block_flags); free_dev(c->scratch.flag_offsets);
-    free_dev(c->scratch.sorted_sums); free_dev(c->scratch.aux_params);
-    free_dev(c->scratch.view_z);
+    c->scene_mem.release();
     c->n = 0;
 }
 
-void free_sort(SortBuffers& s) {
-    for (int k = 0; k < 2; ++k) { free_dev(s.lo[k]); free_dev(s.hi[k]); free_dev(s.id[k]); }
-    free_dev(s.table); free_dev(s.seg_sum); free_dev(s.params); free_dev(s.coarse);
-    free_dev(s.fed[0]); s.fed[1] = s.fed[2] = nullptr;      // one allocation, three sets
-}
-
 void drop_sort_graph(gs_ctx* c) {
-    if (c->sort_graph) { (void)hipGraphExecDestroy(c->sort_graph); c->sort_graph = nullptr; }
-    if (c->presort_graph) { (void)hipGraphExecDestroy(c->presort_graph); c->presort_graph = nullptr; }
-    if (c->chain_graph) { (void)hipGraphExecDestroy(c->chain_graph); c->chain_graph = nullptr; }
+    for (FrameGraph* g : {&c->run_graph[0], &c->run_graph[1], &c->chain_graph})
+        if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
     c->sort_graph_failed = false;
 }
 
-void free_backward(gs_ctx* c) {
-    free_dev(c->bwd.rows); free_dev(c->bwd.offsets); free_dev(c->bwd.block_sums); free_dev(c->bwd.block_offsets);
-    free_dev(c->bwd.vis_ids); free_dev(c->bwd.vis_block_sums); free_dev(c->bwd.vis_block_offsets);
-    free_dev(c->bwd_host_in); free_dev(c->bwd_host_out); free_dev(c->bwd_vis_out);
-    c->bwd_vis_rows = 0;
-}
-
 void free_resolution(gs_ctx* c) {
-    free_backward(c);
-    free_dev(c->loss.maps); free_dev(c->loss.tile_sums); free_dev(c->loss_host);
+    c->bwd_mem.release();
+    c->bwd_vis_rows = 0;
+    c->loss_mem.release();
     c->bwd_frame = false;
     drop_sort_graph(c);
-    free_sort(c->sort);
-    free_dev(c->ranges); free_dev(c->tile_order); free_dev(c->framebuffer);
-    free_dev(c->out_rgba32f); free_dev(c->out_depth);
+    c->res_mem.release();
+    c->sort = SortBuffers{};          // fed[1], fed[2] point into the allocation of fed[0]
     c->outputs_valid = false;
     // the strips of a sharded frame are sized by the resolution: gs_dist_shard_rows must be called again
     gsi_dist_free_buffers(c);
@@ -114,40 +71,43 @@ uint32_t num_sort_bits_for(uint32_t num_tiles) {
 inline bool sorts_splat_first(uint32_t algo) { return algo == GS_SORT_RADIX4_SPLAT_FIRST || algo == GS_SORT_RADIX8_SPLAT_FIRST; }
 inline uint32_t digit_bits_of(uint32_t algo) { return algo == GS_SORT_RADIX8 || algo == GS_SORT_RADIX8_SPLAT_FIRST ? 8u : (uint32_t)kRadixBits; }
 
-int alloc_sort(gs_ctx* ctx, SortBuffers& s, uint32_t capacity, uint32_t digit_bits) {
+// the sort buffers of a list of `capacity` elements, owned by `mem` (which the caller releases, after a failure too)
+int alloc_sort(gs_ctx* ctx, DeviceOwner& mem, SortBuffers& s, uint32_t capacity) {
     const size_t bytes = (size_t)capacity * sizeof(uint32_t);
     for (int k = 0; k < 2; ++k) {
-        HIP_TRY(ctx, hipMalloc((void**)&s.lo[k], bytes));
-        HIP_TRY(ctx, hipMalloc((void**)&s.hi[k], bytes));
-        HIP_TRY(ctx, hipMalloc((void**)&s.id[k], bytes));
+        HIP_TRY(ctx, mem.alloc(s.lo[k], bytes));
+        HIP_TRY(ctx, mem.alloc(s.hi[k], bytes));
+        HIP_TRY(ctx, mem.alloc(s.id[k], bytes));
     }
-    if (digit_bits == 8u) {   // gs_sort8.hip: [groups][256] counts; segment counts + their scan
+    s.digit_bits = digit_bits_of(ctx->cfg.sort_algorithm);
+    if (s.digit_bits == 8u) {   // gs_sort8.hip: [groups][256] counts; segment counts + their scan
         const uint32_t max_groups = (capacity + kSort8TileSmall - 1) / kSort8TileSmall;   // the smaller of the two group sizes
-        HIP_TRY(ctx, hipMalloc((void**)&s.table, (size_t)kBins8 * max_groups * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&s.seg_sum, (size_t)2 * kBins8 * kSegments * sizeof(uint32_t)));
+        HIP_TRY(ctx, mem.alloc(s.table, (size_t)kBins8 * max_groups * sizeof(uint32_t)));
+        HIP_TRY(ctx, mem.alloc(s.seg_sum, (size_t)2 * kBins8 * kSegments * sizeof(uint32_t)));
     } else {
         const uint32_t max_groups = (capacity + kSortTile - 1) / kSortTile;
-        HIP_TRY(ctx, hipMalloc((void**)&s.table, (size_t)kBins * max_groups * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void**)&s.seg_sum, (size_t)kBins * kSegments * sizeof(uint32_t)));
+        HIP_TRY(ctx, mem.alloc(s.table, (size_t)kBins * max_groups * sizeof(uint32_t)));
+        HIP_TRY(ctx, mem.alloc(s.seg_sum, (size_t)kBins * kSegments * sizeof(uint32_t)));
         // fed counts: three rotating sets of [groups][16] rows (k_scatter<.., FED>); every row a pass reads was written or
         // cleared earlier in the same sort, so no initial clear
         const size_t set_words = (size_t)kBins * max_groups;
-        HIP_TRY(ctx, hipMalloc((void**)&s.fed[0], 3 * set_words * sizeof(uint32_t)));
+        HIP_TRY(ctx, mem.alloc(s.fed[0], 3 * set_words * sizeof(uint32_t)));
         s.fed[1] = s.fed[0] + set_words;
         s.fed[2] = s.fed[1] + set_words;
     }
-    s.digit_bits = digit_bits;
-    HIP_TRY(ctx, hipMalloc((void**)&s.params, sizeof(SortParams)));
+    HIP_TRY(ctx, mem.alloc(s.params, sizeof(SortParams)));
     HIP_TRY(ctx, hipMemset(s.params, 0, sizeof(SortParams)));
-    HIP_TRY(ctx, hipMalloc((void**)&s.coarse, (size_t)kMaxSortPasses * kBins * kCoarse * sizeof(uint32_t)));
+    HIP_TRY(ctx, mem.alloc(s.coarse, (size_t)kMaxSortPasses * kBins * kCoarse * sizeof(uint32_t)));
     return GS_OK;
 }
 
-// the stand-alone 4-bit sorter knows its element count: fed counts (gs_sort.hip) for short lists
-bool fed_for(const gs_ctx* c, uint32_t n) {
-    if (digit_bits_of(c->cfg.sort_algorithm) != (uint32_t)kRadixBits) return false;
-    return c->cfg.count_launches == GS_COUNT_FED ||
-           (c->cfg.count_launches == GS_COUNT_AUTO && n <= kFedMaxGroups * (uint32_t)kSortTile);
+// The run of the stand-alone sorters: the whole key over a list of n elements, nothing dropped.  They know their element
+// count: fed counts (gs_sort.hip) for short lists of the 4-bit sorter.
+SortRun whole_list_run(const gs_ctx* c, uint32_t n, uint32_t num_sort_bits) {
+    const bool fed = digit_bits_of(c->cfg.sort_algorithm) == (uint32_t)kRadixBits &&
+                     (c->cfg.count_launches == GS_COUNT_FED ||
+                      (c->cfg.count_launches == GS_COUNT_AUTO && n <= kFedMaxGroups * (uint32_t)kSortTile));
+    return {.capacity = n, .num_sort_bits = num_sort_bits, .fed = fed};
 }
 
 int check_launch(gs_ctx* ctx, const char* what) {
@@ -156,20 +116,124 @@ int check_launch(gs_ctx* ctx, const char* what) {
     return GS_OK;
 }
 
-// Renderer::recordCommandBuffer (Renderer.cpp:540-629): stage order + the 7 timestamp points.
+// ---- the stages of a frame behind project + scan (Renderer::recordCommandBuffer, Renderer.cpp:540-629), once per sorter:
+//      what a stage launches, the bucket of gs_timings its interval is booked under, the name check_launch reports it by,
+//      and whether its arguments are free of the camera (such stages can be captured once and replayed)
+enum StageKind : uint8_t { kStageSplatList, kStageGatherEmit, kStageEmit, kStagePasses, kStageRanges, kStageTileSort };
+struct Stage {
+    StageKind kind;
+    uint32_t run;            // kStagePasses: which of gs_ctx::runs
+    FrameBucket bucket;
+    const char* name;
+    bool camera_free;
+};
+// GS_SORT_RADIX*_SPLAT_FIRST: the depth passes run over the list of emitting splats, the emit walks that list in depth order,
+// the tile-word passes finish.  InitSortList = project + lists + emit, RadixSort = all passes.
+const Stage kSplatFirstFrame[] = {
+    {kStageSplatList, 0, kBucketInit, "InitSortList", true},
+    {kStagePasses, 0, kBucketSort, "RadixSort", true},
+    {kStageGatherEmit, 0, kBucketInit, "InitSortList", true},
+    {kStagePasses, 1, kBucketSort, "RadixSort", true},
+    {kStageRanges, 0, kBucketRanges, "FindRanges", true},    // computeRanges (Subrenderer.cpp:172-216)
+};
+// GS_SORT_RADIX4 / _RADIX8: computeInitSortList (Subrenderer.cpp:37-170), gpuSort->computeSort (RadixSort.cpp:207-653), ranges
+const Stage kPlainFrame[] = {
+    {kStageEmit, 0, kBucketInit, "InitSortList", false},
+    {kStagePasses, 0, kBucketSort, "RadixSort", true},
+    {kStageRanges, 0, kBucketRanges, "FindRanges", true},
+};
+// GS_SORT_TILE_BUCKET: the tile-word passes alone, then -- it needs the ranges -- the per-tile depth sort, booked under
+// RadixSort.  That sort forks onto helper_stream, so nothing of this frame is captured as a chain.
+const Stage kBucketFrame[] = {
+    {kStageEmit, 0, kBucketInit, "InitSortList", false},
+    {kStagePasses, 0, kBucketSort, "RadixSort", false},
+    {kStageRanges, 0, kBucketRanges, "FindRanges", false},
+    {kStageTileSort, 0, kBucketSort, "TileSort", false},
+};
+
+// What the stages of one enqueue_frame share
+struct Frame {
+    gs_ctx* c;
+    FrameParams fp;          // the frame's own
+    FrameParams fixed;       // what the camera-free stages take
+    bool ordered;
+    bool direct;             // record_timings >= 2: nothing is captured
+    int sorted;              // ping-pong half of the list the last run of passes left
+};
+
+// `launch` enqueues launches whose arguments never change and returns the ping-pong half of the list they leave (< 0:
+// not enqueued).  Captured once into `g` (nothing executes during capture) and replayed; direct launches where the frame
+// asks for them or a capture has failed.
+template <typename F>
+int capture_or_replay(Frame& f, FrameGraph& g, F&& launch) {
+    gs_ctx* c = f.c;
+    hipStream_t st = c->stream;
+    if (!f.direct && !g.exec && !c->sort_graph_failed) {
+        hipGraph_t graph = nullptr;
+        bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) == hipSuccess;
+        if (ok) {
+            g.result = launch();
+            ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr;
+        }
+        if (ok) ok = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess;
+        if (graph) (void)hipGraphDestroy(graph);
+        if (!ok) { g.exec = nullptr; c->sort_graph_failed = true; (void)hipGetLastError(); }
+    }
+    if (!f.direct && g.exec) return hipGraphLaunch(g.exec, st) == hipSuccess ? g.result : -1;
+    return launch();
+}
+
+// One stage onto the stream -> the half that holds the list behind it, < 0 when launch_radix_sort refused its run.
+// graphs: a run of passes replays as its own graph (else it is being captured as part of a longer one).
+int launch_stage(Frame& f, const Stage& s, bool graphs) {
+    gs_ctx* c = f.c;
+    hipStream_t st = c->stream;
+    switch (s.kind) {
+        case kStageSplatList: launch_splat_list(f.fixed, c->scratch, c->sort, st); break;
+        case kStageGatherEmit:
+            launch_gather_sorted(f.fixed, c->scratch, c->sort, f.sorted, st);
+            launch_emit_sorted(f.fixed, c->scratch, c->sort, f.sorted, st);
+            break;
+        case kStageEmit: launch_emit(f.fp, c->scratch, c->sort, st); break;
+        case kStagePasses: {
+            auto passes = [&] { return launch_radix_sort(c->sort, c->runs[s.run], st); };
+            f.sorted = graphs ? capture_or_replay(f, c->run_graph[s.run], passes) : passes();
+            break;
+        }
+        case kStageRanges:
+            launch_find_ranges(f.fixed, c->sort.hi[f.sorted], c->sort.params, c->ranges, st);
+            if (f.ordered) launch_tile_order(f.fixed, c->ranges, c->tile_order, st);
+            break;
+        case kStageTileSort:
+            launch_tile_sort(f.fp, c->ranges, c->sort.lo[f.sorted], c->sort.id[f.sorted], c->sort.lo[f.sorted ^ 1],
+                             c->sort.id[f.sorted ^ 1], st, c->helper_stream, c->fork_ev, c->join_ev);
+            break;
+    }
+    return f.sorted;
+}
+
+// record_timings: the interval that ends here belongs to bucket b
+int mark(gs_ctx* c, FrameBucket b) {
+    HIP_TRY(c, hipEventRecord(c->marks[c->num_marks], c->stream));
+    c->mark_bucket[c->num_marks++] = b;
+    return GS_OK;
+}
+
 int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* cam_pos,
                   uint32_t sh_mode, uint8_t* out_dev) {
     if (!c->n) return fail(c, GS_ERR_NO_SCENE, "gs_render: no gaussians uploaded");
     if (!c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_render: gs_set_resolution not called");
     if (!view || !proj || !cam_pos) return fail(c, GS_ERR_INVALID, "gs_render: null camera argument");
     if (sh_mode > 2u) return fail(c, GS_ERR_INVALID, "gs_render: sh_mode must be 0, 1 or 2");
-    FrameParams fp = make_frame_params(c, view, proj, cam_pos, sh_mode);
+    Frame f{c, make_frame_params(c, view, proj, cam_pos, sh_mode)};
+    FrameParams& fp = f.fp;
     if (!out_dev) fp.compact_out = 0u;   // the internal framebuffer is always a whole frame in real rows
     const bool tm = c->cfg.record_timings != 0;
     hipStream_t st = c->stream;
 
     c->unsorted_valid = false;
-    if (tm) { HIP_TRY(c, hipEventRecord(c->ev[0], st)); HIP_TRY(c, hipEventRecord(c->ev[1], st)); }
+    c->num_marks = 0;
+    if (tm) if (int r = mark(c, kBucketNone)) return r;
     // computeInitSortList (Subrenderer.cpp:37-170): per-frame resets, then the dispatch.  Only the
     // ranges need clearing here: the 0xFF sentinel fill of both lists (Subrenderer.cpp:42-46,
     // RadixSort.cpp:676-692) is unobservable once every later stage runs over E instead of C.
@@ -177,90 +241,35 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     fp.parity = (c->emit_parity ^= 1u);
     c->last_fp = fp;
     const bool splat_first = sorts_splat_first(c->cfg.sort_algorithm);
-    const uint32_t digit = digit_bits_of(c->cfg.sort_algorithm);
     fp.splat_first = splat_first ? 1u : 0u;
     const bool bucket = c->cfg.sort_algorithm == GS_SORT_TILE_BUCKET;
-    const bool per_pass_events = c->cfg.record_timings >= 2;
     const float tile_share = c->grid_h ? (float)c->rows_owned / (float)c->grid_h : 1.0f;
-    const bool ordered = c->cfg.tile_order == GS_TILE_ORDER_LONGEST_FIRST;
-    // one capture-or-replay of a run of radix passes (nothing executes during capture)
-    auto radix_passes = [&](hipGraphExec_t& exec, int& result, auto&& launch) -> int {
-        if (!per_pass_events && !exec && !c->sort_graph_failed) {
-            hipGraph_t graph = nullptr;
-            bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed) == hipSuccess;
-            if (ok) {
-                result = launch(nullptr);
-                ok = hipStreamEndCapture(st, &graph) == hipSuccess && graph != nullptr;
-            }
-            if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
-            if (graph) (void)hipGraphDestroy(graph);
-            if (!ok) { exec = nullptr; c->sort_graph_failed = true; (void)hipGetLastError(); }
-        }
-        if (!per_pass_events && exec) {
-            if (hipGraphLaunch(exec, st) != hipSuccess) return -1;
-            return result;
-        }
-        return launch(per_pass_events ? c->scatter_ev : nullptr);
-    };
+    f.ordered = c->cfg.tile_order == GS_TILE_ORDER_LONGEST_FIRST;
+    f.direct = c->cfg.record_timings >= 2;
+    hipEvent_t* const pass_events = f.direct ? c->scatter_ev : nullptr;
     launch_project(fp, c->scene, c->scratch, st);
     launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, st);
-    bool ranges_done = false;
+    f.fixed = fp;
     if (splat_first) {
-        // GS_SORT_RADIX4_SPLAT_FIRST: the eight passes over the depth word run on the list of emitting splats, the emit
-        // walks that list, the tile-word passes finish.  InitSortList = project + lists + emit, RadixSort = all passes.
         // Nothing between the first scan and RenderGaussians depends on the camera: those kernels take a FrameParams
         // without it (and with a fixed helper counter, cleared by the first kernel of the chain), so their arguments
         // never change and the whole chain -- FindRanges included -- replays as ONE graph when no timers are asked for.
-        FrameParams fps = fp;
+        FrameParams& fps = f.fixed;
         std::memset(fps.view, 0, sizeof(fps.view)); std::memset(fps.proj, 0, sizeof(fps.proj));
         std::memset(fps.cam_pos, 0, sizeof(fps.cam_pos));
         fps.sh_mode = 0u; fps.w_norm2 = 0.0f; fps.compact_out = 0u;
         fps.parity = 0u;
-        auto depth_passes = [&](hipEvent_t* evs) {
-            // the frame's own depth passes (shrinking depth words, payload as wide as the tile ids) over the splat list
-            return launch_radix_sort(c->sort, c->n, 32u, st, evs, 0u, true, c->hi16, 1.0f, /*start*/ 1, /*coarse_pass*/ 0,
-                                     c->scratch.aux_params, digit);
-        };
-        auto tile_passes = [&](hipEvent_t* evs) {
-            return launch_radix_sort(c->sort, c->capacity, c->band_sort_bits, st, evs ? evs + 16 : nullptr, 32u, true, c->hi16,
-                                     tile_share, /*start*/ 0, /*coarse_pass*/ 8, nullptr, digit);
-        };
-        if (!tm) {
-            const int sorted = radix_passes(c->chain_graph, c->chain_result, [&](hipEvent_t*) {
-                launch_splat_list(fps, c->scratch, c->sort, st);
-                const int presorted = depth_passes(nullptr);
-                launch_gather_sorted(fps, c->scratch, c->sort, presorted, st);
-                launch_emit_sorted(fps, c->scratch, c->sort, presorted, st);
-                const int si = tile_passes(nullptr);
-                launch_find_ranges(fps, c->sort.hi[si], c->sort.params, c->ranges, st);
-                if (ordered) launch_tile_order(fps, c->ranges, c->tile_order, st);
-                return si;
-            });
-            if (sorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or sort buffers of another digit width)");
-            c->sorted_index = sorted;
-            ranges_done = true;
-        } else {
-            launch_splat_list(fps, c->scratch, c->sort, st);
-            if (int r = check_launch(c, "InitSortList")) return r;
-            HIP_TRY(c, hipEventRecord(c->pre_ev[0], st));
-            const int presorted = radix_passes(c->presort_graph, c->presort_result, depth_passes);
-            if (presorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or sort buffers of another digit width)");
-            if (int r = check_launch(c, "RadixSort")) return r;
-            HIP_TRY(c, hipEventRecord(c->pre_ev[1], st));
-            launch_gather_sorted(fps, c->scratch, c->sort, presorted, st);
-            launch_emit_sorted(fps, c->scratch, c->sort, presorted, st);
-            if (int r = check_launch(c, "InitSortList")) return r;
-            HIP_TRY(c, hipEventRecord(c->pre_ev[2], st));
-            const int sorted = radix_passes(c->sort_graph, c->sort_graph_result, tile_passes);
-            if (sorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or sort buffers of another digit width)");
-            c->sorted_index = sorted;
-        }
+        // the frame's own depth passes (shrinking depth words, payload as wide as the tile ids) over the splat list in
+        // half 1, then the tile-word passes over the emitted list in half 0
+        c->runs[0] = {.capacity = c->n, .num_sort_bits = 32u, .start = 1, .params = c->scratch.aux_params,
+                      .drop_depth_payload = true, .hi16 = c->hi16, .scatter_events = pass_events};
+        c->runs[1] = {.capacity = c->capacity, .first_bit = 32u, .num_sort_bits = c->band_sort_bits, .coarse_pass = 8,
+                      .drop_depth_payload = true, .hi16 = c->hi16, .share = tile_share,
+                      .scatter_events = pass_events ? pass_events + 2 * sort_pass_count(c->runs[0], c->sort.digit_bits) : nullptr};
+        c->num_runs = 2;
     } else {
-        launch_emit(fp, c->scratch, c->sort, st);
-        if (int r = check_launch(c, "InitSortList")) return r;
-        if (tm) HIP_TRY(c, hipEventRecord(c->ev[2], st));
-        // gpuSort->computeSort (RadixSort.cpp:207-653).  The passes' arguments are fixed once resolution and tile rows are:
-        // captured once, replayed as a hipGraph.  Without timers FindRanges (same property) rides in the same graph.
+        // The passes' arguments are fixed once resolution and tile rows are: captured once, replayed as a hipGraph.
+        // Without timers FindRanges (same property) rides in the same graph.
         // fed counts (gs_sort.hip): for the contractual sorter, when the list is short.  The host enqueues a frame without
         // knowing its element count, so GS_COUNT_AUTO goes by the count of a recent frame, which k_scan_blocks leaves in
         // a pinned host word (nothing waits for it; none yet: a Count launch per pass); a change of mind re-captures
@@ -274,56 +283,43 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
                    note - 1u <= (c->sort_fed ? limit : limit - limit / 16u));
         }
         if (fed != c->sort_fed) {
-            if (c->sort_graph || c->chain_graph) HIP_TRY(c, hipStreamSynchronize(st));   // the graph may still be executing (rare: the mode flips)
+            if (c->run_graph[0].exec || c->chain_graph.exec) HIP_TRY(c, hipStreamSynchronize(st));   // the graph may still be executing (rare: the mode flips)
             drop_sort_graph(c);
             c->sort_fed = fed;
         }
-        auto all_passes = [&](hipEvent_t* evs) {
-            return launch_radix_sort(c->sort, c->capacity, c->band_sort_bits, st, evs, bucket ? 32u : 0u, !bucket, c->hi16, tile_share,
-                                     0, 0, nullptr, digit, fed);
-        };
-        if (!tm && !bucket) {
-            const int sorted = radix_passes(c->chain_graph, c->chain_result, [&](hipEvent_t*) {
-                const int si = all_passes(nullptr);
-                launch_find_ranges(fp, c->sort.hi[si], c->sort.params, c->ranges, st);
-                if (ordered) launch_tile_order(fp, c->ranges, c->tile_order, st);
-                return si;
-            });
-            if (sorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or sort buffers of another digit width)");
-            c->sorted_index = sorted;
-            ranges_done = true;
-        } else {
-            const int sorted = radix_passes(c->sort_graph, c->sort_graph_result, all_passes);
-            if (sorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or sort buffers of another digit width)");
-            c->sorted_index = sorted;
-        }
+        // the bucket sorter runs the tile-word passes alone and carries the depth words through them
+        c->runs[0] = {.capacity = c->capacity, .first_bit = bucket ? 32u : 0u, .num_sort_bits = c->band_sort_bits,
+                      .drop_depth_payload = !bucket, .hi16 = c->hi16, .share = tile_share, .fed = fed,
+                      .scatter_events = pass_events};
+        c->num_runs = 1;
     }
+    const Stage* stages = splat_first ? kSplatFirstFrame : bucket ? kBucketFrame : kPlainFrame;
+    const size_t num_stages = splat_first ? std::size(kSplatFirstFrame) : bucket ? std::size(kBucketFrame) : std::size(kPlainFrame);
+    // With timers (and for the bucket sorter) the stages go to the stream one by one, with a mark behind each.  Without:
+    // everything from the first camera-free stage through FindRanges is ONE graph.
+    for (size_t i = 0; i < num_stages; ++i) {
+        const Stage& s = stages[i];
+        const bool chain = !tm && s.camera_free;
+        f.sorted = chain ? capture_or_replay(f, c->chain_graph, [&] {
+                               for (size_t j = i; j < num_stages; ++j)
+                                   if (launch_stage(f, stages[j], false) < 0) return -1;
+                               return f.sorted;
+                           })
+                         : launch_stage(f, s, true);
+        if (f.sorted < 0) return fail(c, GS_ERR_HIP, "gs_render: the radix passes could not be enqueued (hipGraphLaunch failed or the sort buffers cannot serve them)");
+        if (int r = check_launch(c, chain ? "RadixSort" : s.name)) return r;
+        if (chain) break;
+        if (tm) if (int r = mark(c, s.bucket)) return r;
+    }
+    c->sorted_index = f.sorted;
     c->depth_dropped = !bucket;
-    if (int r = check_launch(c, "RadixSort")) return r;
-    if (tm) HIP_TRY(c, hipEventRecord(c->ev[3], st));
-    // computeRanges (Subrenderer.cpp:172-216)
-    if (!ranges_done) {
-        launch_find_ranges(fp, c->sort.hi[c->sorted_index], c->sort.params, c->ranges, st);
-        if (ordered) launch_tile_order(fp, c->ranges, c->tile_order, st);
-    }
-    if (int r = check_launch(c, "FindRanges")) return r;
-    if (bucket) {
-        // second half of the alternative sorter: per-tile depth sort (needs the ranges)
-        const int si = c->sorted_index;
-        if (tm) HIP_TRY(c, hipEventRecord(c->alt_ev[0], st));
-        launch_tile_sort(fp, c->ranges, c->sort.lo[si], c->sort.id[si], c->sort.lo[si ^ 1], c->sort.id[si ^ 1], st,
-                         c->helper_stream, c->fork_ev, c->join_ev);
-        if (int r = check_launch(c, "TileSort")) return r;
-        if (tm) HIP_TRY(c, hipEventRecord(c->alt_ev[1], st));
-    }
-    if (tm) HIP_TRY(c, hipEventRecord(c->ev[4], st));
     // computeRenderGaussians (Subrenderer.cpp:218-346), with the outputs of gs_set_outputs beside the image
     const RenderOutputs outs{reinterpret_cast<float4*>(c->out_rgba32f), c->out_depth, c->scratch.view_z};
-    launch_render(fp, c->scratch.raster, c->sort.id[c->sorted_index], c->ranges, ordered ? c->tile_order : nullptr,
+    launch_render(fp, c->scratch.raster, c->sort.id[c->sorted_index], c->ranges, f.ordered ? c->tile_order : nullptr,
                   out_dev ? out_dev : c->framebuffer, c->cfg.render_mode, c->cfg.render_kernel, st, outs);
     if (int r = check_launch(c, "RenderGaussians")) return r;
     if (c->outputs) c->outputs_valid = true;
-    if (tm) { HIP_TRY(c, hipEventRecord(c->ev[5], st)); HIP_TRY(c, hipEventRecord(c->ev[6], st)); }
+    if (tm) if (int r = mark(c, kBucketRender)) return r;
     c->have_frame = true;
     c->bwd_frame = true;
     return GS_OK;
@@ -352,81 +348,40 @@ int finish_frame(gs_ctx* c) {
     SortParams sp{};
     HIP_TRY(c, hipMemcpy(&sp, c->sort.params, sizeof(sp), hipMemcpyDeviceToHost));
     gs_timings t{};
-    if (c->cfg.record_timings) {
-        if (sorts_splat_first(c->cfg.sort_algorithm)) {
-            // project + lists | depth passes | gather + emit | tile-word passes
-            float a = 0.0f, b = 0.0f, d = 0.0f, e = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&a, c->ev[1], c->pre_ev[0]));
-            HIP_TRY(c, hipEventElapsedTime(&b, c->pre_ev[0], c->pre_ev[1]));
-            HIP_TRY(c, hipEventElapsedTime(&d, c->pre_ev[1], c->pre_ev[2]));
-            HIP_TRY(c, hipEventElapsedTime(&e, c->pre_ev[2], c->ev[3]));
-            t.init_sort_list_ms = a + d;
-            t.radix_sort_ms = b + e;
-        } else {
-            HIP_TRY(c, hipEventElapsedTime(&t.init_sort_list_ms, c->ev[1], c->ev[2]));
-            HIP_TRY(c, hipEventElapsedTime(&t.radix_sort_ms, c->ev[2], c->ev[3]));
+    if (c->cfg.record_timings && c->num_marks >= 2) {
+        // every interval of the frame's timeline into the bucket its closing mark names; the total spans them all
+        float* const bucket_ms[] = {nullptr, &t.init_sort_list_ms, &t.radix_sort_ms, &t.find_ranges_ms, &t.render_ms};
+        for (uint32_t i = 1; i < c->num_marks; ++i) {
+            float ms = 0.0f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c->marks[i - 1], c->marks[i]));
+            *bucket_ms[c->mark_bucket[i]] += ms;
         }
-        HIP_TRY(c, hipEventElapsedTime(&t.find_ranges_ms, c->ev[3], c->ev[4]));
-        HIP_TRY(c, hipEventElapsedTime(&t.render_ms, c->ev[4], c->ev[5]));
-        HIP_TRY(c, hipEventElapsedTime(&t.total_ms, c->ev[0], c->ev[6]));
-        if (c->cfg.sort_algorithm == GS_SORT_TILE_BUCKET) {
-            // the per-tile sort runs behind FindRanges: book it under RadixSort, not FindRanges
-            float ranges_ms = 0.0f, tile_ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ranges_ms, c->ev[3], c->alt_ev[0]));
-            HIP_TRY(c, hipEventElapsedTime(&tile_ms, c->alt_ev[0], c->alt_ev[1]));
-            t.find_ranges_ms = ranges_ms;
-            t.radix_sort_ms += tile_ms;
-        }
+        HIP_TRY(c, hipEventElapsedTime(&t.total_ms, c->marks[0], c->marks[c->num_marks - 1]));
     }
-    if (c->cfg.record_timings >= 2 && sorts_splat_first(c->cfg.sort_algorithm)) {
-        // "full" = the eight depth passes over the SPLAT list, "tile" = the tile-word passes over the elements
-        float sum_pre = 0.0f, sum_tile = 0.0f, bytes_pre = 0.0f;
-        const uint32_t digit = digit_bits_of(c->cfg.sort_algorithm), n_pre = 32u / digit;
-        const uint32_t n_tile = (c->band_sort_bits - 32u + digit - 1u) / digit;
-        for (uint32_t k = 0; k < n_pre; ++k) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->scatter_ev[2 * k], c->scatter_ev[2 * k + 1]));
-            sum_pre += ms;
-            int lo_in, lo_out;
-            scatter_depth_bytes(k * digit, 0u, true, &lo_in, &lo_out, digit);
-            bytes_pre += (float)(lo_in + lo_out) + 2.0f * (c->hi16 ? 2.0f : 4.0f) + 8.0f;   // depth + count + splat, r + w
+    if (c->cfg.record_timings >= 2) {
+        // [0]: the passes that move depth bytes (splat-first: over the SPLAT list, so per splat of that list); [1]: the
+        // tile-word passes of a frame that leave the depth words behind.  Averaged apart.
+        float sum_ms[2] = {}, sum_bytes[2] = {};
+        uint32_t n[2] = {};
+        for (uint32_t r = 0; r < c->num_runs; ++r) {
+            const SortRun& run = c->runs[r];
+            const uint32_t passes = sort_pass_count(run, c->sort.digit_bits);
+            for (uint32_t k = 0; k < passes; ++k) {
+                float ms = 0.0f;
+                HIP_TRY(c, hipEventElapsedTime(&ms, run.scatter_events[2 * k], run.scatter_events[2 * k + 1]));
+                const SortPass p = sort_pass(run, c->sort.digit_bits, k);
+                const int which = p.lo_in == 0 && p.lo_out == 0 ? 1 : 0;
+                sum_ms[which] += ms;
+                sum_bytes[which] += (float)(p.lo_in + p.lo_out) + 2.0f * (run.hi16 ? 2.0f : 4.0f) + 8.0f;   // depth + tile + id, r + w
+                ++n[which];
+            }
         }
-        for (uint32_t k = 0; k < n_tile; ++k) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->scatter_ev[16 + 2 * k], c->scatter_ev[16 + 2 * k + 1]));
-            sum_tile += ms;
-        }
-        t.scatter_ms_avg = sum_pre / (float)n_pre;
-        t.scatter_launches = n_pre;
-        t.scatter_bytes_per_elem = bytes_pre / (float)n_pre;   // per SPLAT of the list
-        t.scatter_tile_ms_avg = n_tile ? sum_tile / (float)n_tile : 0.0f;
-        t.scatter_tile_launches = n_tile;
-        t.scatter_tile_bytes_per_elem = 2.0f * (c->hi16 ? 2.0f : 4.0f) + 8.0f;
-    } else if (c->cfg.record_timings >= 2) {
-        const uint32_t first_bit = c->cfg.sort_algorithm == GS_SORT_TILE_BUCKET ? 32u : 0u;
-        const uint32_t digit = digit_bits_of(c->cfg.sort_algorithm);
-        const uint32_t passes = (c->band_sort_bits - first_bit + digit - 1u) / digit;
-        // launches that move all 24 bytes per element (k_scatter<true>) and the tile-word passes of the frame
-        // path that leave the depth words behind (k_scatter<false>, 16 bytes per element) are averaged apart
-        const bool bucket = c->cfg.sort_algorithm == GS_SORT_TILE_BUCKET;
-        float sum_full = 0.0f, sum_tile = 0.0f, bytes_full = 0.0f, bytes_tile = 0.0f;
-        uint32_t n_full = 0, n_tile = 0;
-        for (uint32_t k = 0; k < passes; ++k) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->scatter_ev[2 * k], c->scatter_ev[2 * k + 1]));
-            const uint32_t shift = first_bit + k * digit;
-            int lo_in, lo_out;
-            scatter_depth_bytes(shift, first_bit, !bucket, &lo_in, &lo_out, digit);
-            const float moved = (float)(lo_in + lo_out) + 2.0f * (c->hi16 ? 2.0f : 4.0f) + 8.0f;   // depth + tile + id, r + w
-            if (shift < 32u || bucket) { sum_full += ms; ++n_full; bytes_full += moved; }
-            else { sum_tile += ms; ++n_tile; bytes_tile += moved; }
-        }
-        t.scatter_bytes_per_elem = n_full ? bytes_full / (float)n_full : 0.0f;
-        t.scatter_tile_bytes_per_elem = n_tile ? bytes_tile / (float)n_tile : 0.0f;
-        t.scatter_ms_avg = n_full ? sum_full / (float)n_full : 0.0f;
-        t.scatter_launches = n_full;
-        t.scatter_tile_ms_avg = n_tile ? sum_tile / (float)n_tile : 0.0f;
-        t.scatter_tile_launches = n_tile;
+        t.scatter_launches = n[0];
+        t.scatter_ms_avg = n[0] ? sum_ms[0] / (float)n[0] : 0.0f;
+        t.scatter_bytes_per_elem = n[0] ? sum_bytes[0] / (float)n[0] : 0.0f;
+        t.scatter_tile_launches = n[1];
+        t.scatter_tile_ms_avg = n[1] ? sum_ms[1] / (float)n[1] : 0.0f;
+        t.scatter_tile_bytes_per_elem = n[1] ? sum_bytes[1] / (float)n[1] : 0.0f;
     }
     t.num_sort_elements = sp.num_elems;
     t.overflowed = sp.overflow;
@@ -469,6 +424,16 @@ void gs_default_config(gs_config* cfg) {
     cfg->render_kernel = GS_RENDER_KERNEL_AUTO;
     cfg->tile_order = GS_TILE_ORDER_LONGEST_FIRST;
     cfg->count_launches = GS_COUNT_AUTO;
+}
+
+// n events of gs_create (those created before a failure stay for gs_destroy) and their end in gs_destroy
+static hipError_t create_events(hipEvent_t* ev, int n, unsigned flags) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < n && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&ev[i], flags);
+    return e;
+}
+static void destroy_events(hipEvent_t* ev, int n) {
+    for (int i = 0; i < n; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
 }
 
 int gs_create(const gs_config* cfg_in, gs_ctx** out) {
@@ -523,45 +488,24 @@ int gs_create(const gs_config* cfg_in, gs_ctx** out) {
             (void)hipGetLastError();
         }
     }
-    for (auto& ev : c->ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) {
-            std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
-            gs_destroy(c);
-            return fail(nullptr, GS_ERR_HIP, msg);
-        }
-    for (auto& ev : c->alt_ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) {
-            std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
-            gs_destroy(c);
-            return fail(nullptr, GS_ERR_HIP, msg);
-        }
-    for (auto& ev : c->pre_ev)
-        if ((e = hipEventCreate(&ev)) != hipSuccess) {
-            std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
-            gs_destroy(c);
-            return fail(nullptr, GS_ERR_HIP, msg);
-        }
-    if (cfg.sort_algorithm == GS_SORT_TILE_BUCKET) {
-        if (init_tile_sort() != 0) {
-            gs_destroy(c);
-            return fail(nullptr, GS_ERR_HIP, "gs_create: cannot reserve 160 KB of LDS for the per-tile sort");
-        }
-        e = hipStreamCreateWithFlags(&c->helper_stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
-            gs_destroy(c);
-            return fail(nullptr, GS_ERR_HIP, msg);
-        }
+    if (cfg.sort_algorithm == GS_SORT_TILE_BUCKET && init_tile_sort() != 0) {
+        gs_destroy(c);
+        return fail(nullptr, GS_ERR_HIP, "gs_create: cannot reserve 160 KB of LDS for the per-tile sort");
     }
-    if (cfg.record_timings >= 2)
-        for (auto& ev : c->scatter_ev)
-            if ((e = hipEventCreate(&ev)) != hipSuccess) {
-                std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
-                gs_destroy(c);
-                return fail(nullptr, GS_ERR_HIP, msg);
-            }
+    // the marks of a frame's timeline; a pair of events per radix pass only where they are recorded; the bucket sorter's
+    // helper stream with its fork / join events
+    e = create_events(c->marks, kMaxFrameMarks, hipEventDefault);
+    if (e == hipSuccess && cfg.record_timings >= 2) e = create_events(c->scatter_ev, 32, hipEventDefault);
+    if (e == hipSuccess && cfg.sort_algorithm == GS_SORT_TILE_BUCKET) {
+        e = hipStreamCreateWithFlags(&c->helper_stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = create_events(&c->fork_ev, 1, hipEventDisableTiming);
+        if (e == hipSuccess) e = create_events(&c->join_ev, 1, hipEventDisableTiming);
+    }
+    if (e != hipSuccess) {
+        std::string msg = std::string("gs_create: ") + hipGetErrorString(e);
+        gs_destroy(c);
+        return fail(nullptr, GS_ERR_HIP, msg);
+    }
     *out = c;
     return GS_OK;
 }
@@ -573,12 +517,10 @@ int gs_destroy(gs_ctx* c) {
     if (c->dist_comm) (void)gs_dist_destroy(c);
     free_resolution(c);
     free_scene(c);
-    for (auto& ev : c->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : c->scatter_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : c->alt_ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : c->pre_ev) if (ev) (void)hipEventDestroy(ev);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    if (c->join_ev) (void)hipEventDestroy(c->join_ev);
+    destroy_events(c->marks, kMaxFrameMarks);
+    destroy_events(c->scatter_ev, 32);
+    destroy_events(&c->fork_ev, 1);
+    destroy_events(&c->join_ev, 1);
     if (c->helper_stream) { (void)hipStreamSynchronize(c->helper_stream); (void)hipStreamDestroy(c->helper_stream); }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->elems_note) (void)hipHostFree(c->elems_note);
@@ -586,7 +528,7 @@ int gs_destroy(gs_ctx* c) {
     return GS_OK;
 }
 
-const char* gs_last_error(const gs_ctx* c) { return c ? c->last_error.c_str() : g_create_error.c_str(); }
+const char* gs_last_error(const gs_ctx* c) { return c ? c->last_error.c_str() : gsi_create_error.c_str(); }
 
 int gs_set_stream(gs_ctx* c, void* hip_stream) {
     if (!c) return GS_ERR_INVALID;
@@ -598,47 +540,38 @@ int gs_set_stream(gs_ctx* c, void* hip_stream) {
 // per-context, per-frame outputs of InitSortList's first kernel
 static int alloc_scratch(gs_ctx* c, uint32_t n) {
     const size_t N = n;
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.raster, N * sizeof(SplatRaster)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.depth_key, N * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.tiles_touched, N * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.extents, N * sizeof(uint2)));
+    DeviceOwner& mem = c->scene_mem;
+    SplatScratch& sc = c->scratch;
+    hipStream_t st = c->stream;
+    HIP_TRY(c, mem.alloc_zeroed(sc.raster, N * sizeof(SplatRaster), st));
+    HIP_TRY(c, mem.alloc(sc.depth_key, N * sizeof(uint32_t)));
+    HIP_TRY(c, mem.alloc(sc.tiles_touched, N * sizeof(uint32_t)));
+    HIP_TRY(c, mem.alloc(sc.extents, N * sizeof(uint2)));
     c->num_blocks = (n + kProjThreads - 1) / kProjThreads;
     // k_scan_blocks reads/writes whole 16-byte groups up to 1024 * per entries: zero-padded
     const size_t padded = (size_t)c->num_blocks + 8192;
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.block_sums, padded * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.block_offsets, padded * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.block_sums, 0, padded * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.block_offsets, 0, padded * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.raster, 0, N * sizeof(SplatRaster), c->stream));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.wave_wrote, (size_t)c->num_blocks * 4));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.wave_wrote, 0, (size_t)c->num_blocks * 4, c->stream));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.help_list, (size_t)kEmitHelpCap * sizeof(uint2)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.help_count, 4 * sizeof(uint32_t)));
-    c->scratch.elems_note = nullptr;
+    HIP_TRY(c, mem.alloc_zeroed(sc.block_sums, padded * sizeof(uint32_t), st));
+    HIP_TRY(c, mem.alloc_zeroed(sc.block_offsets, padded * sizeof(uint32_t), st));
+    HIP_TRY(c, mem.alloc_zeroed(sc.wave_wrote, (size_t)c->num_blocks * 4, st));
+    HIP_TRY(c, mem.alloc_zeroed(sc.help_list, (size_t)kEmitHelpCap * sizeof(uint2), st));
+    HIP_TRY(c, mem.alloc_zeroed(sc.help_count, 4 * sizeof(uint32_t), st));
+    sc.elems_note = nullptr;
     if (c->elems_note) {
         void* dev = nullptr;
-        if (hipHostGetDevicePointer(&dev, c->elems_note, 0) == hipSuccess) c->scratch.elems_note = (uint32_t*)dev;
+        if (hipHostGetDevicePointer(&dev, c->elems_note, 0) == hipSuccess) sc.elems_note = (uint32_t*)dev;
         else (void)hipGetLastError();
     }
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.band_list, (size_t)c->num_blocks * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc((void**)&c->scratch.help_slot, (size_t)c->num_blocks * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.help_count, 0, 4 * sizeof(uint32_t), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.help_list, 0, (size_t)kEmitHelpCap * sizeof(uint2), c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->scratch.help_slot, 0xFF, (size_t)c->num_blocks * sizeof(uint32_t), c->stream));
-    if (c->outputs & GS_OUTPUT_DEPTH) {   // k_project stores the view depths only while the depth output is on
-        HIP_TRY(c, hipMalloc((void**)&c->scratch.view_z, N * sizeof(float)));
-        HIP_TRY(c, hipMemsetAsync(c->scratch.view_z, 0, N * sizeof(float), c->stream));
-    }
+    HIP_TRY(c, mem.alloc(sc.band_list, (size_t)c->num_blocks * sizeof(uint32_t)));
+    HIP_TRY(c, mem.alloc(sc.help_slot, (size_t)c->num_blocks * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(sc.help_slot, 0xFF, (size_t)c->num_blocks * sizeof(uint32_t), st));
+    // k_project stores the view depths only while the depth output is on
+    if (c->outputs & GS_OUTPUT_DEPTH) HIP_TRY(c, mem.alloc_zeroed(sc.view_z, N * sizeof(float), st));
     c->emit_parity = 0;
     if (sorts_splat_first(c->cfg.sort_algorithm)) {
-        HIP_TRY(c, hipMalloc((void**)&c->scratch.block_flags, padded * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc((void**)&c->scratch.flag_offsets, padded * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc((void**)&c->scratch.sorted_sums, padded * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc((void**)&c->scratch.aux_params, 2 * sizeof(SortParams)));
-        HIP_TRY(c, hipMemsetAsync(c->scratch.block_flags, 0, padded * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->scratch.flag_offsets, 0, padded * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->scratch.sorted_sums, 0, padded * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->scratch.aux_params, 0, 2 * sizeof(SortParams), c->stream));
+        HIP_TRY(c, mem.alloc_zeroed(sc.block_flags, padded * sizeof(uint32_t), st));
+        HIP_TRY(c, mem.alloc_zeroed(sc.flag_offsets, padded * sizeof(uint32_t), st));
+        HIP_TRY(c, mem.alloc_zeroed(sc.sorted_sums, padded * sizeof(uint32_t), st));
+        HIP_TRY(c, mem.alloc_zeroed(sc.aux_params, 2 * sizeof(SortParams), st));
     }
     return GS_OK;
 }
@@ -673,21 +606,20 @@ static int new_scene(gs_ctx* c, uint32_t n, const char* who) {
     if (!c->shared) return fail(c, GS_ERR_INVALID, std::string(who) + ": out of host memory");
     c->shared->n = n;
     const size_t N = n;
-    {
-        SceneBuffers& b = c->shared->b;
-        hipError_t e = hipMalloc((void**)&b.pos, 3 * N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.scale, 3 * N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.rot, 4 * N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.sh, 48 * N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.opacity, N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.sig2, N * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&b.block_bounds, ((size_t)(n + 63u) / 64u + 4u) * 8 * sizeof(float));
-        if (e != hipSuccess) {
-            free_scene(c);
-            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-        }
-        c->scene = b;
+    SceneBuffers& b = c->shared->b;
+    DeviceOwner& mem = c->shared->mem;
+    hipError_t e = mem.alloc(b.pos, 3 * N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.scale, 3 * N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.rot, 4 * N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.sh, 48 * N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.opacity, N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.sig2, N * sizeof(float));
+    if (e == hipSuccess) e = mem.alloc(b.block_bounds, ((size_t)(n + 63u) / 64u + 4u) * 8 * sizeof(float));
+    if (e != hipSuccess) {
+        free_scene(c);
+        return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
     }
+    c->scene = b;
     if (int r = alloc_scratch(c, n)) { free_scene(c); return r; }
     return GS_OK;
 }
@@ -776,12 +708,13 @@ int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     c->num_sort_bits = num_sort_bits_for(gw * gh);
     c->band_sort_bits = c->num_sort_bits;
     c->hi16 = (uint64_t)gw * gh <= 65535u;
-    int rc = alloc_sort(c, c->sort, c->capacity, digit_bits_of(c->cfg.sort_algorithm));
+    int rc = alloc_sort(c, c->res_mem, c->sort, c->capacity);
     if (rc != GS_OK) { free_resolution(c); return rc; }
     // any failure from here on leaves the context without a resolution (capacity 0), never half set up
-    hipError_t e = hipMalloc((void**)&c->ranges, ((size_t)gw * gh * 2 * sizeof(uint32_t) + 15) & ~(size_t)15);   // cleared 16 bytes at a time
-    if (e == hipSuccess) e = hipMalloc((void**)&c->tile_order, tile_order_words(gw, gh) * sizeof(uint32_t));   // table + scratch of the two kernels
-    if (e == hipSuccess) e = hipMalloc((void**)&c->framebuffer, (size_t)width * height * 4);
+    DeviceOwner& mem = c->res_mem;
+    hipError_t e = mem.alloc(c->ranges, ((size_t)gw * gh * 2 * sizeof(uint32_t) + 15) & ~(size_t)15);   // cleared 16 bytes at a time
+    if (e == hipSuccess) e = mem.alloc(c->tile_order, tile_order_words(gw, gh) * sizeof(uint32_t));   // table + scratch of the two kernels
+    if (e == hipSuccess) e = mem.alloc(c->framebuffer, (size_t)width * height * 4);
     if (e == hipSuccess) e = hipMemset(c->ranges, 0, (size_t)gw * gh * 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->framebuffer, 0, (size_t)width * height * 4);
     if (e == hipSuccess) e = alloc_outputs(c);
@@ -797,14 +730,21 @@ static hipError_t alloc_outputs(gs_ctx* c) {
     const size_t px = (size_t)c->width * c->height;
     hipError_t e = hipSuccess;
     if (px && (c->outputs & GS_OUTPUT_RGBA32F)) {
-        e = hipMalloc((void**)&c->out_rgba32f, px * 4 * sizeof(float));
+        e = c->res_mem.alloc(c->out_rgba32f, px * 4 * sizeof(float));
         if (e == hipSuccess) e = hipMemset(c->out_rgba32f, 0, px * 4 * sizeof(float));
     }
     if (e == hipSuccess && px && (c->outputs & GS_OUTPUT_DEPTH)) {
-        e = hipMalloc((void**)&c->out_depth, px * sizeof(float));
+        e = c->res_mem.alloc(c->out_depth, px * sizeof(float));
         if (e == hipSuccess) e = hipMemset(c->out_depth, 0, px * sizeof(float));
     }
     return e;
+}
+
+// the three buffers of the mask, inside the lifetimes that hold them
+static void free_outputs(gs_ctx* c) {
+    c->res_mem.free(c->out_rgba32f);
+    c->res_mem.free(c->out_depth);
+    c->scene_mem.free(c->scratch.view_z);
 }
 
 int gs_set_outputs(gs_ctx* c, uint32_t mask) {
@@ -813,17 +753,17 @@ int gs_set_outputs(gs_ctx* c, uint32_t mask) {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the buffers
     // k_project and RenderGaussians are launched outside the captured graphs (enqueue_frame): no graph depends on the mask
-    free_dev(c->out_rgba32f); free_dev(c->out_depth); free_dev(c->scratch.view_z);
+    free_outputs(c);
     c->outputs = mask;
     c->outputs_valid = false;
     hipError_t e = hipSuccess;
     if (c->n && (mask & GS_OUTPUT_DEPTH)) {
-        e = hipMalloc((void**)&c->scratch.view_z, (size_t)c->n * sizeof(float));
+        e = c->scene_mem.alloc(c->scratch.view_z, (size_t)c->n * sizeof(float));
         if (e == hipSuccess) e = hipMemset(c->scratch.view_z, 0, (size_t)c->n * sizeof(float));
     }
     if (e == hipSuccess) e = alloc_outputs(c);
     if (e != hipSuccess) {   // back to RGBA8-only frames rather than half set up
-        free_dev(c->out_rgba32f); free_dev(c->out_depth); free_dev(c->scratch.view_z);
+        free_outputs(c);
         c->outputs = 0;
         return fail(c, GS_ERR_HIP, std::string("gs_set_outputs: ") + hipGetErrorString(e));
     }
@@ -884,15 +824,17 @@ static int backward_prepare(gs_ctx* c, const char* who) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->bwd.rows) {
         const size_t blocks = backward_blocks(c->n);
-        hipError_t e = hipMalloc((void**)&c->bwd.rows, backward_row_bytes(c->capacity));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.offsets, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_sums, blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.block_offsets, blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_sums, blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->bwd.vis_block_offsets, (blocks + 1) * sizeof(uint32_t));
+        DeviceOwner& mem = c->bwd_mem;
+        hipError_t e = mem.alloc(c->bwd.rows, backward_row_bytes(c->capacity));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.offsets, (size_t)c->n * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.block_sums, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.block_offsets, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_block_sums, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_block_offsets, (blocks + 1) * sizeof(uint32_t));
         if (e != hipSuccess) {
-            free_backward(c);
+            mem.release();
+            c->bwd_vis_rows = 0;
             return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
         }
     }
@@ -908,7 +850,7 @@ static BackwardFrame backward_frame(const gs_ctx* c) {
 // pointers are replaced by their device copies (a null grad_depth stays null)
 static int stage_host_grads(gs_ctx* c, const float*& grad_rgba32f, const float*& grad_depth) {
     const size_t px = (size_t)c->width * c->height;
-    if (!c->bwd_host_in) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_in, px * 5 * sizeof(float)));
+    if (!c->bwd_host_in) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_in, px * 5 * sizeof(float)));
     float* din = c->bwd_host_in;
     HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -938,7 +880,7 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward: null gradient pointer");
     if (int r = backward_prepare(c, "gs_backward")) return r;
-    if (!c->bwd_host_out) HIP_TRY(c, hipMalloc((void**)&c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
+    if (!c->bwd_host_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
     if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
     launch_backward(backward_frame(c), grad_rgba32f, grad_depth, c->bwd_host_out, c->stream);
     if (int r = check_launch(c, "gs_backward")) return r;
@@ -972,10 +914,10 @@ static int loss_prepare(gs_ctx* c, const char* who, const float*& rgba32f, const
         return fail(c, GS_ERR_INVALID, std::string(who) + ": grad_rgba32f must not be the image it differentiates");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->loss.maps) {
-        hipError_t e = hipMalloc((void**)&c->loss.maps, loss_map_bytes(c->width, c->height));
-        if (e == hipSuccess) e = hipMalloc((void**)&c->loss.tile_sums, loss_tile_bytes(c->width, c->height));
+        hipError_t e = c->loss_mem.alloc(c->loss.maps, loss_map_bytes(c->width, c->height));
+        if (e == hipSuccess) e = c->loss_mem.alloc(c->loss.tile_sums, loss_tile_bytes(c->width, c->height));
         if (e != hipSuccess) {
-            free_dev(c->loss.maps); free_dev(c->loss.tile_sums);
+            c->loss_mem.release();
             return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
         }
     }
@@ -997,7 +939,7 @@ int gs_photometric_loss(gs_ctx* c, const float* rgba32f, const float* target_rgb
     if (int r = loss_prepare(c, "gs_photometric_loss", image, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
     // device copies: rgba [px][4] | gradient [px][4] | target [px][3] | the three numbers (+ 1: 16-byte multiples)
     const size_t px = (size_t)c->width * c->height;
-    if (!c->loss_host) HIP_TRY(c, hipMalloc((void**)&c->loss_host, (px * 11 + 4) * sizeof(float)));
+    if (!c->loss_host) HIP_TRY(c, c->loss_mem.alloc(c->loss_host, (px * 11 + 4) * sizeof(float)));
     float* d_rgba = c->loss_host, *d_grad = d_rgba + px * 4, *d_target = d_grad + px * 4, *d_loss = d_target + px * 3;
     if (rgba32f) {
         HIP_TRY(c, hipMemcpyAsync(d_rgba, rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1050,9 +992,9 @@ int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_
     const uint32_t count = *count_out, k = count < max_rows ? count : max_rows;
     if (k) {
         if (c->bwd_vis_rows < k) {
-            free_dev(c->bwd_vis_out);
+            c->bwd_mem.free(c->bwd_vis_out);
             c->bwd_vis_rows = 0;
-            HIP_TRY(c, hipMalloc((void**)&c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
+            HIP_TRY(c, c->bwd_mem.alloc(c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
             c->bwd_vis_rows = k;
         }
         if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
@@ -1080,7 +1022,7 @@ static int apply_tile_rows(gs_ctx* c, uint32_t row_begin, uint32_t row_end, uint
     const uint32_t owned_tiles = c->rows_owned * c->grid_w;
     c->band_sort_bits = num_sort_bits_for(owned_tiles ? owned_tiles : 1u);
     c->hi16 = owned_tiles <= 65535u;
-    if (c->sort_graph || c->presort_graph || c->chain_graph) {
+    if (c->run_graph[0].exec || c->run_graph[1].exec || c->chain_graph.exec) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // the graph may still be executing
         drop_sort_graph(c);
     }
@@ -1362,8 +1304,9 @@ int gs_sort_host(gs_ctx* c, uint32_t* tile, uint32_t* depth, uint32_t* id, uint3
     if (n == 0) return GS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     SortBuffers sb{};
-    int rc = alloc_sort(c, sb, n, digit_bits_of(c->cfg.sort_algorithm));
-    if (rc != GS_OK) { free_sort(sb); return rc; }
+    DeviceOwner mem;
+    int rc = alloc_sort(c, mem, sb, n);
+    if (rc != GS_OK) { mem.release(); return rc; }
     const size_t bytes = (size_t)n * sizeof(uint32_t);
     hipError_t e = hipMemcpyAsync(sb.hi[0], tile, bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(sb.lo[0], depth, bytes, hipMemcpyHostToDevice, c->stream);
@@ -1371,16 +1314,14 @@ int gs_sort_host(gs_ctx* c, uint32_t* tile, uint32_t* depth, uint32_t* id, uint3
     int si = 0;
     if (e == hipSuccess) {
         launch_set_sort_params(sb.params, sb.coarse, n, c->stream);
-        si = launch_radix_sort(sb, n, num_sort_bits, c->stream, nullptr, 0u, false, false, 1.0f, 0, 0, nullptr,
-                               digit_bits_of(c->cfg.sort_algorithm), fed_for(c, n));
-        e = hipGetLastError();
-        if (si < 0) { free_sort(sb); return fail(c, GS_ERR_INVALID, "gs_sort_host: sort buffers of another digit width"); }
+        si = launch_radix_sort(sb, whole_list_run(c, n, num_sort_bits), c->stream);
+        e = si < 0 ? hipErrorInvalidValue : hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(tile, sb.hi[si], bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(depth, sb.lo[si], bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(id, sb.id[si], bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    free_sort(sb);
+    mem.release();
     if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_sort_host: ") + hipGetErrorString(e));
     return GS_OK;
 }
@@ -1390,12 +1331,13 @@ int gs_sort_bench(gs_ctx* c, uint32_t n, uint32_t num_tiles, uint32_t iters, uin
     if (!c || !ms_per_sort || n == 0 || num_tiles == 0 || iters == 0) return GS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     SortBuffers sb{};
-    int rc = alloc_sort(c, sb, n, digit_bits_of(c->cfg.sort_algorithm));
-    if (rc != GS_OK) { free_sort(sb); return rc; }
-    const uint32_t bits = num_sort_bits_for(num_tiles);
+    DeviceOwner mem;
+    int rc = alloc_sort(c, mem, sb, n);
+    if (rc != GS_OK) { mem.release(); return rc; }
+    const SortRun run = whole_list_run(c, n, num_sort_bits_for(num_tiles));
     uint32_t* bad = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc((void**)&bad, sizeof(uint32_t));
+    hipError_t e = mem.alloc(bad, sizeof(uint32_t));
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     float total_ms = 0.0f;
@@ -1405,8 +1347,7 @@ int gs_sort_bench(gs_ctx* c, uint32_t n, uint32_t num_tiles, uint32_t iters, uin
         launch_set_sort_params(sb.params, sb.coarse, n, c->stream);
         e = hipEventRecord(e0, c->stream);
         if (e != hipSuccess) break;
-        si = launch_radix_sort(sb, n, bits, c->stream, nullptr, 0u, false, false, 1.0f, 0, 0, nullptr,
-                               digit_bits_of(c->cfg.sort_algorithm), fed_for(c, n));
+        si = launch_radix_sort(sb, run, c->stream);
         if (si < 0) { si = 0; e = hipErrorInvalidValue; break; }
         e = hipEventRecord(e1, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -1423,8 +1364,7 @@ int gs_sort_bench(gs_ctx* c, uint32_t n, uint32_t num_tiles, uint32_t iters, uin
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (bad) (void)hipFree(bad);
-    free_sort(sb);
+    mem.release();
     if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_sort_bench: ") + hipGetErrorString(e));
     *ms_per_sort = total_ms / (float)iters;
     if (sorted_ok) *sorted_ok = bad_host == 0 ? 1u : 0u;
@@ -1436,10 +1376,11 @@ int gs_membench(gs_ctx* c, int kind, size_t bytes, uint32_t blocks, uint32_t ite
     HIP_TRY(c, hipSetDevice(c->device));
     bytes &= ~(size_t)15;
     if (blocks == 0) blocks = 2048;
-    void *src = nullptr, *dst = nullptr;
+    char *src = nullptr, *dst = nullptr;
+    DeviceOwner mem;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipMalloc(&src, bytes + 65536);     // slack: the skewed scatter probes write a little past `bytes`
-    if (e == hipSuccess) e = hipMalloc(&dst, bytes + 65536);
+    hipError_t e = mem.alloc(src, bytes + 65536);     // slack: the skewed scatter probes write a little past `bytes`
+    if (e == hipSuccess) e = mem.alloc(dst, bytes + 65536);
     if (e == hipSuccess) e = hipMemsetAsync(src, 0x5A, bytes, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(dst, 0, bytes, c->stream);
     if (e == hipSuccess) e = hipEventCreate(&e0);
@@ -1455,8 +1396,7 @@ int gs_membench(gs_ctx* c, int kind, size_t bytes, uint32_t blocks, uint32_t ite
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (src) (void)hipFree(src);
-    if (dst) (void)hipFree(dst);
+    mem.release();
     if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_membench: ") + hipGetErrorString(e));
     const double moved = (double)bytes * ((kind & 1) || kind >= 4 ? 2.0 : 1.0) * iters;
     *gbps = (float)(moved / (ms * 1e-3) / 1e9);

@@ -1,4 +1,5 @@
-// gs_ctx.h -- the context behind the opaque gs_ctx handle of include/gsplat.h.  Internal: shared by gs_api.cpp and by
+// gs_ctx.h -- the context behind the opaque gs_ctx handle of include/gsplat.h, the owner of its device memory
+// (DeviceOwner) and the one error exit of the host code (fail / HIP_TRY).  Internal: shared by gs_api.cpp, gs_dist.cpp and
 // the tuning probes of tools/probe (libgsplat_probe.so), which are built from this tree against the same layout.
 #pragma once
 
@@ -14,24 +15,66 @@
 #include <utility>
 #include <vector>
 
+// The device allocations of one lifetime.  The structs the kernels take by value (SceneBuffers, SortBuffers, ...) stay
+// plain pointers; the owner beside them remembers which of their slots it filled and frees them together, so that a
+// pointer added to such a struct cannot be forgotten by the code that ends its lifetime.  The slots must not move.
+struct DeviceOwner {
+    std::vector<void**> slots;
+    template <typename T> hipError_t alloc(T*& slot, size_t bytes) {
+        const hipError_t e = hipMalloc((void**)&slot, bytes);
+        if (e == hipSuccess) slots.push_back((void**)&slot); else slot = nullptr;
+        return e;
+    }
+    template <typename T> hipError_t alloc_zeroed(T*& slot, size_t bytes, hipStream_t stream) {
+        const hipError_t e = alloc(slot, bytes);
+        return e == hipSuccess ? hipMemsetAsync(slot, 0, bytes, stream) : e;
+    }
+    template <typename T> void free(T*& slot) {      // one slot inside the lifetime (no-op for a slot that is not held)
+        const auto it = std::find(slots.begin(), slots.end(), (void**)&slot);
+        if (it == slots.end()) return;
+        (void)hipFree(slot);
+        slot = nullptr;
+        slots.erase(it);
+    }
+    void release() {
+        for (void** s : slots) { (void)hipFree(*s); *s = nullptr; }
+        slots.clear();
+    }
+};
+
 // The uploaded gaussian arrays (read-only on the path), reference-counted so that the contexts that render them
-// (gs_share_scene: frame slots, tile-row bands) can be destroyed in any order.
+// (gs_share_scene: frame slots, tile-row bands) can be destroyed in any order; the last reference releases `mem`.
 struct SharedScene {
     gs::SceneBuffers b{};
+    DeviceOwner mem;
     uint32_t n = 0;
     std::atomic<uint32_t> refs{1};
 };
 
 using HostClock = std::chrono::steady_clock;
 
+// A captured run of launches and what its capture returned (the ping-pong half that holds the sorted list)
+struct FrameGraph {
+    hipGraphExec_t exec = nullptr;
+    int result = 0;
+};
+
+// The five buckets of gs_timings a frame's intervals are booked under (Renderer.cpp:458-475)
+enum FrameBucket : uint8_t { kBucketNone, kBucketInit, kBucketSort, kBucketRanges, kBucketRender };
+// marks of the longest frame (splat-first): begin, splat list, depth passes, gather + emit, tile passes, ranges, render
+constexpr int kMaxFrameMarks = 7;
+
 struct gs_ctx {
     gs_config cfg{};
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    hipEvent_t ev[7] = {};
-    hipEvent_t scatter_ev[32] = {};   // record_timings == 2: a pair per pass (<= 16 passes)
-    hipEvent_t alt_ev[2] = {};        // GS_SORT_TILE_BUCKET: after FindRanges / after the per-tile sort
+    // record_timings: one timeline per frame -- an event at every bucket boundary, and the bucket the interval that ends
+    // there is booked under (the reference's 7 timestamp points, Renderer.cpp:540-629, per sorter)
+    hipEvent_t marks[kMaxFrameMarks] = {};
+    uint8_t mark_bucket[kMaxFrameMarks] = {};
+    uint32_t num_marks = 0;
+    hipEvent_t scatter_ev[32] = {};   // record_timings == 2: a pair per pass (<= 16 passes), the frame's runs one after the other
     hipStream_t helper_stream = nullptr;   // GS_SORT_TILE_BUCKET: big size classes run beside the small ones
     hipEvent_t fork_ev = nullptr, join_ev = nullptr;
     std::string last_error;
@@ -40,6 +83,7 @@ struct gs_ctx {
     uint32_t n = 0;
     gs::SceneBuffers scene{};
     gs::SplatScratch scratch{};
+    DeviceOwner scene_mem;            // of `scratch` (the gaussian arrays belong to `shared`)
     uint32_t num_blocks = 0;
     uint32_t emit_parity = 0;     // FrameParams::parity of the last InitSortList launch
     SharedScene* shared = nullptr;    // owner of `scene`'s arrays (this context holds one reference)
@@ -55,6 +99,7 @@ struct gs_ctx {
     uint32_t band_sort_bits = 0;
     bool hi16 = false;   // the frame's sort list stores the compact tile ids as uint16 (at most 65535 owned tiles)
     gs::SortBuffers sort{};
+    DeviceOwner res_mem;              // of everything sized by the resolution: sort, ranges, tile_order, framebuffer, outputs
     // gs_set_outputs: the optional per-pixel outputs, addressed like the RGBA8 image (the view depths of the splats live in
     // scratch.view_z, which follows the mask and the scene)
     uint32_t outputs = 0;             // GS_OUTPUT_* mask
@@ -65,6 +110,7 @@ struct gs_ctx {
     // bwd_frame = the last enqueued frame can be differentiated (no gs_set_resolution, gs_set_tile_rows*, upload or
     // gs_debug_init_sort_list since)
     gs::BackwardBuffers bwd{};
+    DeviceOwner bwd_mem;              // of bwd and bwd_host_in / _out / bwd_vis_out
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
     float* bwd_host_out = nullptr;    // ... and the record gradients [N][84]
     float* bwd_vis_out = nullptr;     // gs_backward_visible (host pointers): bwd_vis_rows record gradients, grown on demand
@@ -73,6 +119,7 @@ struct gs_ctx {
     // gs_photometric_loss*: scratch allocated on the first call (9 floats per pixel + 8 bytes per tile), freed with the
     // resolution; loss_host = the device copies of the host form's arguments (rgba, target, gradient, the three numbers)
     gs::LossBuffers loss{};
+    DeviceOwner loss_mem;             // of loss and loss_host
     float* loss_host = nullptr;
     uint32_t* ranges = nullptr;
     uint32_t* tile_order = nullptr;   // [tiles] RenderGaussians' dispatch order (GS_TILE_ORDER_LONGEST_FIRST)
@@ -81,12 +128,10 @@ struct gs_ctx {
     // The radix passes of a frame (3 launches per pass, parameters fixed once resolution and band are) replayed
     // as one hipGraph launch: 36 launches -> 1 on the host side.  Built lazily, dropped when anything it baked in
     // changes.  Not used while per-Scatter events are recorded (record_timings == 2).
-    hipGraphExec_t sort_graph = nullptr;
-    hipGraphExec_t presort_graph = nullptr;   // GS_SORT_RADIX4_SPLAT_FIRST: the eight depth passes over the splat list
-    hipGraphExec_t chain_graph = nullptr;     // ... without timers: everything from the splat list to FindRanges as one graph
-    int chain_result = 0;
-    hipEvent_t pre_ev[3] = {};        // ... after the splat list / after its passes / after the emit
-    int sort_graph_result = 0, presort_result = 1;
+    gs::SortRun runs[2] = {};         // the runs of passes the last frame launched (splat-first: depth passes, tile passes)
+    uint32_t num_runs = 0;
+    FrameGraph run_graph[2];          // with timers: each run replays alone
+    FrameGraph chain_graph;           // without timers: every camera-free stage up to FindRanges as one graph
     bool sort_graph_failed = false;
     uint32_t* elems_note = nullptr;   // pinned host word k_scan_blocks writes (element count + 1 of the latest list; 0: none
                                       // since the rows were set) -- what GS_COUNT_AUTO goes by
@@ -124,8 +169,23 @@ struct gs_ctx {
 };
 
 
-// Text for gs_last_error(NULL) from translation units that have no context at hand (gs_dist.cpp); hidden: not an export.
-__attribute__((visibility("hidden"))) void gsi_set_create_error(const std::string& msg);
+// Text of gs_last_error(NULL): what failed without a context at hand; hidden: not an export.
+__attribute__((visibility("hidden"))) inline thread_local std::string gsi_create_error;
+
+// The error exit of every entry point: the text for gs_last_error, the code for the caller.
+inline int fail(gs_ctx* ctx, int code, const std::string& msg) {
+    if (ctx) ctx->last_error = msg; else gsi_create_error = msg;
+    return code;
+}
+
+#define HIP_TRY(ctx, expr)                                                                       \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return fail((ctx), GS_ERR_HIP,                                                       \
+                        std::string(#expr) + ": " + hipGetErrorString(_e));                      \
+    } while (0)
+
 // gs_dist.cpp: frees the buffers of a sharded frame (they are sized by the resolution); hidden: not an export.
 __attribute__((visibility("hidden"))) void gsi_dist_free_buffers(gs_ctx* c);
 // Renderer.cpp:458-475 for a frame enqueued with gs_render_device_async: wait, read the timestamps, fill gs_get_timings.

@@ -87,17 +87,6 @@ Rccl& rccl() {                       // bound once per process, whichever contex
     return r;
 }
 
-int fail(gs_ctx* c, int code, const std::string& msg) {
-    if (c) c->last_error = msg;
-    return code;
-}
-
-#define DIST_TRY(c, call)                                                                              \
-    do {                                                                                               \
-        const hipError_t e_ = (call);                                                                  \
-        if (e_ != hipSuccess) return fail((c), GS_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
 size_t band_bytes(const gs_ctx* c, uint32_t rb, uint32_t re) {            // the pixel rows of tile rows [rb, re) that exist
     const uint32_t y0 = std::min(rb * 16u, c->height), y1 = std::min(re * 16u, c->height);
     return (size_t)(y1 - y0) * c->width * 4u;
@@ -143,7 +132,7 @@ int enqueue_gather(gs_ctx* c, int slot, hipStream_t st) {
                 const uint32_t owned = c->grid_h > p ? (c->grid_h - p + R - 1u) / R : 0u;
                 if (!owned) continue;
                 const uint8_t* src = p == 0u ? static_cast<uint8_t*>(c->dist_strip[slot]) : gathered + (size_t)p * c->dist_strip_bytes;
-                DIST_TRY(c, hipMemcpy2DAsync(static_cast<uint8_t*>(c->dist_image[slot]) + (size_t)p * block, block * R, src, block, block,
+                HIP_TRY(c, hipMemcpy2DAsync(static_cast<uint8_t*>(c->dist_image[slot]) + (size_t)p * block, block * R, src, block, block,
                                              owned, hipMemcpyDeviceToDevice, st));
             }
         } else {
@@ -209,10 +198,10 @@ extern "C" {
 int gs_dist_unique_id(void* id_out) {
     if (!id_out) return GS_ERR_INVALID;
     Rccl& r = rccl();
-    if (!r.handle) { gsi_set_create_error("gs_dist_unique_id: " + r.error); return GS_ERR_HIP; }   // gs_last_error(NULL)
+    if (!r.handle) { gsi_create_error = "gs_dist_unique_id: " + r.error; return GS_ERR_HIP; }   // gs_last_error(NULL)
     RcclUniqueId id;
     const RcclResult rc = r.GetUniqueId(&id);
-    if (rc != 0) { gsi_set_create_error(std::string("gs_dist_unique_id: ") + r.GetErrorString(rc)); return GS_ERR_HIP; }
+    if (rc != 0) { gsi_create_error = std::string("gs_dist_unique_id: ") + r.GetErrorString(rc); return GS_ERR_HIP; }
     std::memcpy(id_out, &id, sizeof(id));
     return GS_OK;
 }
@@ -223,7 +212,7 @@ int gs_dist_init(gs_ctx* c, const void* unique_id, int rank, int world) {
     if (c->dist_comm) return fail(c, GS_ERR_INVALID, "gs_dist_init: already initialised (gs_dist_destroy first)");
     Rccl& r = rccl();
     if (!r.handle) return fail(c, GS_ERR_HIP, "gs_dist_init: " + r.error);
-    DIST_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipSetDevice(c->device));
     RcclUniqueId id;
     std::memcpy(&id, unique_id, sizeof(id));
     RcclComm comm = nullptr;
@@ -242,12 +231,12 @@ int gs_gather_strips(gs_ctx* c, const void* strip_dev, void* gathered_dev, size_
     if (c->dist_rank == root && !gathered_dev) return fail(c, GS_ERR_INVALID, "gs_gather_strips: the root needs a destination");
     Rccl& r = rccl();
     RcclComm comm = c->dist_comm;
-    DIST_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipSetDevice(c->device));
     RcclResult rc = 0;
     if (c->dist_rank == root) {
         uint8_t* dst = static_cast<uint8_t*>(gathered_dev);
         // the root's own strip never leaves the GPU; the peers' strips arrive over their own links, all in one group
-        DIST_TRY(c, hipMemcpyAsync(dst + (size_t)root * bytes, strip_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(dst + (size_t)root * bytes, strip_dev, bytes, hipMemcpyDeviceToDevice, c->stream));
         if (c->dist_world > 1) {
             rc = r.GroupStart();
             for (int p = 0; p < c->dist_world && rc == 0; ++p)
@@ -268,8 +257,8 @@ int gs_dist_shard_rows(gs_ctx* c, uint32_t dealing) {
     if (!c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_dist_shard_rows: gs_set_resolution not called");
     if (dealing > GS_ROWS_BALANCED) return fail(c, GS_ERR_INVALID, "gs_dist_shard_rows: dealing must be GS_ROWS_CONTIGUOUS, _INTERLEAVED or _BALANCED");
     const uint32_t R = (uint32_t)c->dist_world, r = (uint32_t)c->dist_rank;
-    DIST_TRY(c, hipSetDevice(c->device));
-    if (c->stream) DIST_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->stream) HIP_TRY(c, hipStreamSynchronize(c->stream));
     gsi_dist_free_buffers(c);
     c->dist_dealing = dealing;
     int rc;
@@ -283,11 +272,11 @@ int gs_dist_shard_rows(gs_ctx* c, uint32_t dealing) {
         rc = apply_band(c);
     }
     if (rc != GS_OK) return rc;
-    if (!c->dist_stream) DIST_TRY(c, hipStreamCreateWithFlags(&c->dist_stream, hipStreamNonBlocking));
+    if (!c->dist_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->dist_stream, hipStreamNonBlocking));
     for (int k = 0; k < 2; ++k) {
-        if (!c->dist_begin[k]) DIST_TRY(c, hipEventCreate(&c->dist_begin[k]));
-        if (!c->dist_rendered[k]) DIST_TRY(c, hipEventCreate(&c->dist_rendered[k]));
-        if (!c->dist_done[k]) DIST_TRY(c, hipEventCreateWithFlags(&c->dist_done[k], hipEventDisableTiming));
+        if (!c->dist_begin[k]) HIP_TRY(c, hipEventCreate(&c->dist_begin[k]));
+        if (!c->dist_rendered[k]) HIP_TRY(c, hipEventCreate(&c->dist_rendered[k]));
+        if (!c->dist_done[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->dist_done[k], hipEventDisableTiming));
     }
     // every buffer holds whole frames' worth of tile rows (padded to 16-pixel rows): bands may grow under GS_ROWS_BALANCED
     // without a re-allocation, and 2 x 33 MB at 4K is nothing against 288 GB
@@ -319,7 +308,7 @@ int gs_render_sharded_async(gs_ctx* c, const float view[16], const float proj[16
     if (!c) return GS_ERR_INVALID;
     if (c->outputs) return fail(c, GS_ERR_INVALID, "gs_render_sharded_async: sharded frames do not gather the outputs of gs_set_outputs: set the mask to 0 first");
     if (int rc = check_sharded(c, "gs_render_sharded_async")) return rc;
-    DIST_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipSetDevice(c->device));
     const int slot = c->dist_next;
     const bool root = c->dist_rank == 0;
     // the slot's buffers were last touched by the gather of the frame before the previous one
@@ -357,8 +346,8 @@ int gs_sharded_frame(gs_ctx* c, uint32_t which, void** frame_dev) {
     if (int rc = check_sharded(c, "gs_sharded_frame")) return rc;
     const int slot = slot_of(c, which, "gs_sharded_frame");
     if (slot < 0) return which > 1u ? GS_ERR_INVALID : GS_ERR_NO_SCENE;
-    DIST_TRY(c, hipSetDevice(c->device));
-    DIST_TRY(c, hipEventSynchronize(c->dist_done[slot]));
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(c->dist_done[slot]));
     if (c->dist_rank == 0) *frame_dev = c->dist_image[slot];
     return GS_OK;
 }
@@ -370,7 +359,7 @@ int gs_sharded_read(gs_ctx* c, uint32_t which, uint8_t* rgba_out) {
     if (rc != GS_OK) return rc;
     if (c->dist_rank != 0) return GS_OK;
     if (!rgba_out) return fail(c, GS_ERR_INVALID, "gs_sharded_read: rank 0 needs rgba_out");
-    DIST_TRY(c, hipMemcpy(rgba_out, dev, (size_t)c->width * c->height * 4u, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(rgba_out, dev, (size_t)c->width * c->height * 4u, hipMemcpyDeviceToHost));
     return GS_OK;
 }
 
@@ -440,8 +429,8 @@ int gs_dist_rebalance(gs_ctx* c, uint32_t* moved_out) {
         if (rc != 0) return fail(c, GS_ERR_HIP, std::string("gs_dist_rebalance: ") + r.GetErrorString(rc));
     }
     if (first_hip != hipSuccess) { (void)hipGetLastError(); return fail(c, GS_ERR_HIP, std::string("gs_dist_rebalance: ") + hipGetErrorString(first_hip)); }
-    DIST_TRY(c, hipStreamSynchronize(c->stream));
-    DIST_TRY(c, hipMemcpy(all.data(), xchg, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(all.data(), xchg, all.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     // dist.py: RowBalancer.update, statement for statement.  T_r = F + sum of weight(row): F = the intercept of the
     // least-squares line through the (elements, ms) pairs of the last epochs, inside [0, 0.8 min(T)]; weight(row) =
     // elements(row) x (T_r - F) / E_r (elements(row) when a rank has no time to report).  Identical inputs on every rank ->

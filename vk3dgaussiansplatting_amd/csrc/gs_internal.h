@@ -169,21 +169,70 @@ struct SortBuffers {
     uint32_t* fed[3];                // 4-bit digits: [G_max][16] digit counts per group, three rotating sets of the fed
                                      // sort (k_scatter<.., FED>); null for 8-bit digits
     SortParams* params;
-    uint32_t digit_bits;             // what alloc_sort sized table / seg_sum for (4 or 8): the launchers refuse the other width
+    uint32_t digit_bits;             // what alloc_sort sized table / seg_sum for (4 or 8): the digit width of every run over these buffers
 };
 
-// Bytes of the depth word a radix pass reads / writes per element (k_scatter<LO_IN, LO_OUT, HI16>); shared by the
-// launcher and by the timing code that reports the bytes a pass moves.
-inline void scatter_depth_bytes(uint32_t shift, uint32_t first_bit, bool drop_depth_payload, int* lo_in, int* lo_out,
-                                uint32_t digit_bits = kRadixBits) {
-    *lo_in = 4; *lo_out = 4;
-    if (!drop_depth_payload) return;
-    if (shift >= 32u) { *lo_in = 0; *lo_out = 0; return; }
-    if (first_bit == 0u) {   // what the passes still to come read: nothing below bit shift + digit_bits
-        *lo_in = shift >= 16u ? 2 : 4;
-        *lo_out = shift + digit_bits >= 32u ? 0 : (shift + digit_bits >= 16u ? 2 : 4);
-    }
+// One run of radix passes: key bits [first_bit, num_sort_bits) of tile << 32 | depth over the list in ping-pong half
+// `start` of a SortBuffers (in a frame the tile word is the compact tile id of FrameParams: a context that owns a subset of
+// the tile rows sorts over fewer significant bits).  The digit width is SortBuffers::digit_bits.
+struct SortRun {
+    uint32_t capacity = 0;             // elements the list can hold: sizes the grids
+    uint32_t first_bit = 0;
+    uint32_t num_sort_bits = 0;
+    int start = 0;
+    uint32_t coarse_pass = 0;          // first slab of SortBuffers::coarse (one per pass; two runs of a frame must not share slabs)
+    const SortParams* params = nullptr;   // dispatch record of this list (null: SortBuffers::params)
+    bool drop_depth_payload = false;   // frame path: a pass carries only the depth bytes that later passes still read
+    bool hi16 = false;                 // frame path: the hi arrays hold 16-bit tile ids (at most 65535 owned tiles)
+    float share = 1.0f;                // the context's share of the tiles: below one half the grids shrink with it
+    bool fed = false;                  // 4-bit digits only -- one Count launch for the whole run, every Scatter feeds the next
+                                       // pass's counts (k_scatter<.., FED>); same output, meant for at most kFedMaxGroups groups
+    hipEvent_t* scatter_events = nullptr;   // optional 2 * passes events recorded right before / after every Scatter launch
+};
+
+// Pass k of a run, as the launchers dispatch it and as the timing code reports the bytes it moves.
+struct SortPass {
+    uint32_t shift;          // of the 64-bit key
+    uint32_t bits, mask;     // of this pass's digit (the last 8-bit pass may be narrower)
+    bool tile_word;          // the digit lies in the tile word (shift >= 32), else in the depth word
+    bool word16;             // that word is stored as 16 bits: the tile ids of a band (hi16) and, in a frame, the upper
+                             // half of the depth word once the lower half is consumed (see k_scatter)
+    uint32_t word_shift;     // of the digit within the word as stored
+    int lo_in, lo_out;       // bytes of the depth word read / written per element (k_scatter<LO_IN, LO_OUT, HI16>)
+    bool last;
+};
+inline uint32_t sort_pass_count(const SortRun& r, uint32_t digit_bits) {
+    return r.num_sort_bits > r.first_bit ? (r.num_sort_bits - r.first_bit + digit_bits - 1u) / digit_bits : 0u;
 }
+inline SortPass sort_pass(const SortRun& r, uint32_t digit_bits, uint32_t k) {
+    SortPass p{};
+    p.shift = r.first_bit + k * digit_bits;                                                // RadixSort.cpp:309
+    p.bits = r.num_sort_bits - p.shift < digit_bits ? r.num_sort_bits - p.shift : digit_bits;
+    p.mask = (1u << p.bits) - 1u;
+    p.tile_word = p.shift >= 32u;
+    p.last = p.shift + digit_bits >= r.num_sort_bits;
+    p.lo_in = 4; p.lo_out = 4;
+    if (r.drop_depth_payload) {
+        if (p.tile_word) { p.lo_in = 0; p.lo_out = 0; }
+        else if (r.first_bit == 0u) {   // what the passes still to come read: nothing below bit shift + digit_bits
+            p.lo_in = p.shift >= 16u ? 2 : 4;
+            p.lo_out = p.shift + digit_bits >= 32u ? 0 : (p.shift + digit_bits >= 16u ? 2 : 4);
+        }
+    }
+    const bool lo16 = !p.tile_word && p.lo_in == 2;
+    p.word16 = (p.tile_word && r.hi16) || lo16;
+    p.word_shift = lo16 ? p.shift - 16u : p.shift & 31u;
+    return p;
+}
+// The instantiations of the Scatter kernels by depth bytes: X(LO_IN, LO_OUT) for the pair of pass p
+#define GS_SCATTER_BY_DEPTH_BYTES(p, X)                          \
+    do {                                                         \
+        if ((p).lo_in == 4 && (p).lo_out == 4) X(4, 4);          \
+        else if ((p).lo_in == 4 && (p).lo_out == 2) X(4, 2);     \
+        else if ((p).lo_in == 2 && (p).lo_out == 2) X(2, 2);     \
+        else if ((p).lo_in == 2 && (p).lo_out == 0) X(2, 0);     \
+        else X(0, 0);                                            \
+    } while (0)
 
 // ---- launchers (each enqueues on `stream`, no host sync) ------------------------------------
 void launch_project(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,
@@ -200,26 +249,11 @@ void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffer
 void launch_splat_list(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, hipStream_t stream);
 void launch_gather_sorted(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, int sorted, hipStream_t stream);
 void launch_emit_sorted(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, int sorted, hipStream_t stream);
-// Sorts buffers [0] -> result index returned (0 or 1) after num_sort_bits/4 passes.
-// scatter_events: optional 2*passes events recorded right before / after every Scatter launch.
-// Passes run over key bits [first_bit, num_sort_bits) of tile << 32 | depth (in a frame the tile word is the compact
-// tile id of FrameParams: a context that owns a subset of the tile rows sorts over fewer significant bits).
-// drop_depth_payload: the tile-word passes (bits >= 32) do not carry the depth words (frame path only).
-// hi16: the hi arrays hold 16-bit tile ids (frame path, at most 65535 owned tiles).
-// start: the ping-pong buffer the list lies in; coarse_pass: first slab of sb.coarse to use (one per pass; two sorts
-// in one frame must not share slabs); params: dispatch record of this list (default sb.params).
-// fed: 4-bit digits only -- one Count launch for the whole sort, every Scatter feeds the next pass's counts (k_scatter<.., FED>);
-// same output, meant for lists of at most kFedMaxGroups groups (correct, but slow, beyond).
-// Returns -1 without launching anything when digit_bits is not the width sb was allocated for.
-int launch_radix_sort(const SortBuffers& sb, uint32_t capacity, uint32_t num_sort_bits,
-                      hipStream_t stream, hipEvent_t* scatter_events = nullptr, uint32_t first_bit = 0,
-                      bool drop_depth_payload = false, bool hi16 = false, float share = 1.0f,
-                      int start = 0, uint32_t coarse_pass = 0, const SortParams* params = nullptr,
-                      uint32_t digit_bits = kRadixBits, bool fed = false);
-// the same with 8-bit digits (gs_sort8.hip); launch_radix_sort forwards here when digit_bits == 8
-int launch_radix_sort8(const SortBuffers& sb, uint32_t capacity, uint32_t num_sort_bits, hipStream_t stream,
-                       hipEvent_t* scatter_events, uint32_t first_bit, bool drop_depth_payload, bool hi16, float share,
-                       int start, uint32_t coarse_pass, const SortParams* params);
+// Sorts the list of `run` -> the ping-pong half (0 or 1) that holds the result; -1 without launching anything when the
+// buffers cannot serve the run (another digit width, fed counts without their rows).  sb.coarse must be zero on entry.
+int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t stream);
+// the same with 8-bit digits (gs_sort8.hip); launch_radix_sort forwards here when sb.digit_bits == 8
+int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t stream);
 // GS_SORT_TILE_BUCKET: per-tile depth sort of the owned tiles (gs_tilesort.hip)
 int init_tile_sort();
 void launch_tile_sort(const FrameParams& fp, const uint32_t* ranges, uint32_t* lo, uint32_t* id,

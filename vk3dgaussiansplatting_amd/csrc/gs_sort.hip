@@ -570,80 +570,60 @@ void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict
     }
 }
 
-int launch_radix_sort(const SortBuffers& sb, uint32_t capacity, uint32_t num_sort_bits,
-                      hipStream_t stream, hipEvent_t* scatter_events, uint32_t first_bit,
-                      bool drop_depth_payload, bool hi16, float share, int start, uint32_t coarse_pass,
-                      const SortParams* params, uint32_t digit_bits, bool fed) {
-    if (sb.digit_bits != digit_bits) return -1;   // table / seg_sum are sized per digit width (alloc_sort)
-    if (digit_bits == 8u)
-        return launch_radix_sort8(sb, capacity, num_sort_bits, stream, scatter_events, first_bit, drop_depth_payload, hi16,
-                                  share, start, coarse_pass, params);
-    if (fed && !sb.fed[0]) return -1;
-    if (!params) params = sb.params;
-    uint32_t max_groups = (capacity + kSortTile - 1) / kSortTile;
+int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t stream) {
+    if (sb.digit_bits == 8u) return launch_radix_sort8(sb, run, stream);
+    if (sb.digit_bits != (uint32_t)kRadixBits || (run.fed && !sb.fed[0])) return -1;   // table / seg_sum are sized per digit width
+    const bool fed = run.fed, hi16 = run.hi16;
+    const SortParams* params = run.params ? run.params : sb.params;
+    uint32_t max_groups = (run.capacity + kSortTile - 1) / kSortTile;
     // a context that owns a share of the tiles (tile-row band of a multi-GPU frame) launches Scatter over twice
     // that share of the capacity's groups; k_scatter walks on if a frame should hold more
-    if (share < 0.5f) {
-        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * share) + 64u;
+    if (run.share < 0.5f) {
+        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * run.share) + 64u;
         max_groups = g < max_groups ? g : max_groups;
     }
-    // a fed sort is chosen for short lists (gs_api.cpp: from the element count of the frame before): its grid need not
+    // a fed sort is chosen for short lists (the frame goes by the element count of the frame before): its grid need not
     // cover more groups than such a list has; k_scatter walks on if this frame holds more
     if (fed && max_groups > 2u * kFedMaxGroups) max_groups = 2u * kFedMaxGroups;
     // sb.coarse (the coarse digit totals of every pass; Count adds into them with atomics) must be zero on entry:
     // k_scan_blocks clears it in a frame, k_set_sort_params for the stand-alone sorter
-    int src = start;
-    uint32_t pass = 0;
-    for (uint32_t shift = first_bit; shift < num_sort_bits; shift += kRadixBits, ++pass) { // RadixSort.cpp:309
+    int src = run.start;
+    const uint32_t passes = sort_pass_count(run, kRadixBits);
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const SortPass p = sort_pass(run, kRadixBits, pass);
         const int dst = src ^ 1;
-        const bool tile_pass = shift >= 32u;
-        const bool last = shift + kRadixBits >= num_sort_bits;
-        const uint32_t* word = tile_pass ? sb.hi[src] : sb.lo[src];
-        // 16-bit words: the tile ids of a band (hi16) and, in a frame, the upper half of the depth word once the
-        // lower half is consumed (passes 4-7, see k_scatter)
-        int cin, cout;
-        scatter_depth_bytes(shift, first_bit, drop_depth_payload, &cin, &cout);
-        const bool lo16 = !tile_pass && cin == 2;
-        const bool word16 = (tile_pass && hi16) || lo16;
-        uint32_t* coarse = sb.coarse + (size_t)(coarse_pass + pass) * kBins * kCoarse;   // zeroed above; this pass's Count adds into it
+        const uint32_t* word = p.tile_word ? sb.hi[src] : sb.lo[src];
+        uint32_t* coarse = sb.coarse + (size_t)(run.coarse_pass + pass) * kBins * kCoarse;   // zeroed above; this pass's Count adds into it
         // fed counts: one Count launch per SORT (the rows of pass 0); pass p reads set p % 3, adds into (p + 1) % 3
         // (nothing in the last pass) and clears (p + 2) % 3
         uint32_t* const rows_in = fed ? sb.fed[pass % 3u] : nullptr;
-        uint32_t* const rows_next = fed && !last ? sb.fed[(pass + 1u) % 3u] : nullptr;
+        uint32_t* const rows_next = fed && !p.last ? sb.fed[(pass + 1u) % 3u] : nullptr;
         uint32_t* const rows_zero = fed ? sb.fed[(pass + 2u) % 3u] : nullptr;
         if (!fed || pass == 0u) {
             uint32_t* const fr = fed ? rows_in : nullptr;
             uint32_t* const fz = fed ? sb.fed[1] : nullptr;
-            if (word16)
+            if (p.word16)
                 hipLaunchKernelGGL((k_count<true>), dim3(kSegments), dim3(kCountThreads), 0, stream, params,
-                                   word, sb.table, sb.seg_sum, coarse, lo16 ? shift - 16u : shift & 31u, fr, fz);
+                                   word, sb.table, sb.seg_sum, coarse, p.word_shift, fr, fz);
             else
                 hipLaunchKernelGGL((k_count<false>), dim3(kSegments), dim3(kCountThreads), 0, stream, params,
-                                   word, sb.table, sb.seg_sum, coarse, shift & 31u, fr, fz);
+                                   word, sb.table, sb.seg_sum, coarse, p.word_shift, fr, fz);
         }
-        if (scatter_events) (void)hipEventRecord(scatter_events[2 * pass], stream);
-        // bytes of the depth word read / written by this pass (see k_scatter)
-        int lo_in, lo_out;
-        scatter_depth_bytes(shift, first_bit, drop_depth_payload, &lo_in, &lo_out);
-        const uint32_t pgrid = max_groups;
+        if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
 #define GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, FED, T0, T1, T2)                                                        \
-        hipLaunchKernelGGL((k_scatter<LO_IN, LO_OUT, HI16, FED>), dim3(pgrid), dim3(kSortThreads), 0, stream, params, \
+        hipLaunchKernelGGL((k_scatter<LO_IN, LO_OUT, HI16, FED>), dim3(max_groups), dim3(kSortThreads), 0, stream, params, \
                            sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst], sb.hi[dst], sb.id[dst],                  \
-                           T0, T1, T2, shift)
+                           T0, T1, T2, p.shift)
 #define GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, HI16) \
         do { if (fed) GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, true, rows_in, rows_next, rows_zero); \
              else GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, false, sb.table, sb.seg_sum, coarse); } while (0)
 #define GS_LAUNCH_SCATTER_H(LO_IN, LO_OUT) \
         do { if (hi16) GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, true); else GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, false); } while (0)
-        if (lo_in == 4 && lo_out == 4) GS_LAUNCH_SCATTER_H(4, 4);
-        else if (lo_in == 4 && lo_out == 2) GS_LAUNCH_SCATTER_H(4, 2);
-        else if (lo_in == 2 && lo_out == 2) GS_LAUNCH_SCATTER_H(2, 2);
-        else if (lo_in == 2 && lo_out == 0) GS_LAUNCH_SCATTER_H(2, 0);
-        else GS_LAUNCH_SCATTER_H(0, 0);
+        GS_SCATTER_BY_DEPTH_BYTES(p, GS_LAUNCH_SCATTER_H);
 #undef GS_LAUNCH_SCATTER_H
 #undef GS_LAUNCH_SCATTER_F
 #undef GS_LAUNCH_SCATTER
-        if (scatter_events) (void)hipEventRecord(scatter_events[2 * pass + 1], stream);
+        if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass + 1], stream);
         src = dst;                                                            // RadixSort.cpp:638-641
     }
     return src;

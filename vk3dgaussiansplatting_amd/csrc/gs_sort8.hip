@@ -363,70 +363,58 @@ void k_scatter8(const SortParams* __restrict__ params, const uint32_t* __restric
     }
 }
 
-int launch_radix_sort8(const SortBuffers& sb, uint32_t capacity, uint32_t num_sort_bits, hipStream_t stream,
-                       hipEvent_t* scatter_events, uint32_t first_bit, bool drop_depth_payload, bool hi16, float share,
-                       int start, uint32_t coarse_pass, const SortParams* params) {
+int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t stream) {
     if (sb.digit_bits != 8u) return -1;           // 4-bit buffers hold 16 x 512 segment words, not 2 x 256 x 512
-    if (!params) params = sb.params;
+    const bool hi16 = run.hi16;
+    const SortParams* params = run.params ? run.params : sb.params;
     // Group size by what the list can be expected to hold (the host never reads the element count back): 2048-key groups for
     // short lists -- more workgroups, shorter latency chains -- 4096 for long ones (digit runs twice as long).
-    const float bound = (float)capacity * (share < 0.5f ? share : 1.0f);   // a band holds about its share of the capacity
+    const float bound = (float)run.capacity * (run.share < 0.5f ? run.share : 1.0f);   // a band holds about its share of the capacity
     const bool small = bound < (float)kSort8SmallBelow;
     const uint32_t tile = small ? (uint32_t)kSort8TileSmall : (uint32_t)kSort8Tile;
-    uint32_t max_groups = (capacity + tile - 1) / tile;
-    if (share < 0.5f) {   // a tile-row band: see launch_radix_sort
-        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * share) + 64u;
+    uint32_t max_groups = (run.capacity + tile - 1) / tile;
+    if (run.share < 0.5f) {   // a tile-row band: see launch_radix_sort
+        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * run.share) + 64u;
         max_groups = g < max_groups ? g : max_groups;
     }
     uint32_t* seg_base = sb.seg_sum + (size_t)kBins8 * kSegments;
-    int src = start;
-    uint32_t pass = 0;
-    for (uint32_t shift = first_bit; shift < num_sort_bits; shift += 8u, ++pass) {
+    int src = run.start;
+    const uint32_t passes = sort_pass_count(run, 8u);
+    for (uint32_t pass = 0; pass < passes; ++pass) {
+        const SortPass p = sort_pass(run, 8u, pass);
         const int dst = src ^ 1;
-        const uint32_t bits = num_sort_bits - shift < 8u ? num_sort_bits - shift : 8u;
-        const uint32_t mask = (1u << bits) - 1u;
-        const bool tile_pass = shift >= 32u;
-        const uint32_t* word = tile_pass ? sb.hi[src] : sb.lo[src];
-        int lo_in, lo_out;
-        scatter_depth_bytes(shift, first_bit, drop_depth_payload, &lo_in, &lo_out, 8u);
-        const bool lo16 = !tile_pass && lo_in == 2;
-        const bool word16 = (tile_pass && hi16) || lo16;
+        const uint32_t* word = p.tile_word ? sb.hi[src] : sb.lo[src];
         // the pass's digit totals (k_scan8 -> k_scatter8): a slab of sb.coarse
-        uint32_t* totals = sb.coarse + (size_t)(coarse_pass + pass) * kBins * kCoarse;
-        const uint32_t sh = lo16 ? shift - 16u : shift & 31u;
+        uint32_t* totals = sb.coarse + (size_t)(run.coarse_pass + pass) * kBins * kCoarse;
 #define GS_LAUNCH_COUNT8(W16, RUNS)                                                                                  \
         do { if (small) hipLaunchKernelGGL((k_count8<W16, RUNS, kSort8TileSmall>), dim3(kSegments), dim3(kC8Threads), 0, stream, \
-                                           params, word, sb.table, sb.seg_sum, sh, mask);                            \
+                                           params, word, sb.table, sb.seg_sum, p.word_shift, p.mask);                \
              else hipLaunchKernelGGL((k_count8<W16, RUNS, kSort8Tile>), dim3(kSegments), dim3(kC8Threads), 0, stream,  \
-                                     params, word, sb.table, sb.seg_sum, sh, mask); } while (0)
+                                     params, word, sb.table, sb.seg_sum, p.word_shift, p.mask); } while (0)
         // Runs of equal digits in neighbouring keys: the depth digits wherever splats are replicated into tiles (not in the
         // splat list of the splat-first order, whose passes stop at bit 32), and the top tile digit -- the keys arrive
         // sorted by everything below it, so the long lists of a capture's heavy tiles lie in runs (C-hard: that Count
         // 37 -> 17 us with the runs added once; uniform fog pays 2.5 us for it).
-        const bool runs = tile_pass ? shift + 8u >= num_sort_bits : num_sort_bits > 32u;
-        if (runs) { if (word16) GS_LAUNCH_COUNT8(true, true); else GS_LAUNCH_COUNT8(false, true); }
-        else { if (word16) GS_LAUNCH_COUNT8(true, false); else GS_LAUNCH_COUNT8(false, false); }
+        const bool runs = p.tile_word ? p.last : run.num_sort_bits > 32u;
+        if (runs) { if (p.word16) GS_LAUNCH_COUNT8(true, true); else GS_LAUNCH_COUNT8(false, true); }
+        else { if (p.word16) GS_LAUNCH_COUNT8(true, false); else GS_LAUNCH_COUNT8(false, false); }
 #undef GS_LAUNCH_COUNT8
         hipLaunchKernelGGL(k_scan8, dim3(kBins8), dim3(kSegments), 0, stream, sb.seg_sum, seg_base, totals);
-        if (scatter_events) (void)hipEventRecord(scatter_events[2 * pass], stream);
+        if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
 #define GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, R)                                                                   \
         hipLaunchKernelGGL((k_scatter8<LO_IN, LO_OUT, HI16, R>), dim3(max_groups), dim3(kSort8Threads), 0, stream, params, \
                            sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst], sb.hi[dst], sb.id[dst], sb.table, seg_base,    \
-                           totals, shift, mask)
+                           totals, p.shift, p.mask)
 #define GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, HI16)                                                                        \
         do { if (small) GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, kSort8KeysSmall);                                   \
              else GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, kSort8KeysPerThread); } while (0)
 #define GS_LAUNCH_SCATTER8_H(LO_IN, LO_OUT) \
         do { if (hi16) GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, true); else GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, false); } while (0)
-        if (lo_in == 4 && lo_out == 4) GS_LAUNCH_SCATTER8_H(4, 4);
-        else if (lo_in == 4 && lo_out == 2) GS_LAUNCH_SCATTER8_H(4, 2);
-        else if (lo_in == 2 && lo_out == 2) GS_LAUNCH_SCATTER8_H(2, 2);
-        else if (lo_in == 2 && lo_out == 0) GS_LAUNCH_SCATTER8_H(2, 0);
-        else GS_LAUNCH_SCATTER8_H(0, 0);
+        GS_SCATTER_BY_DEPTH_BYTES(p, GS_LAUNCH_SCATTER8_H);
 #undef GS_LAUNCH_SCATTER8_H
 #undef GS_LAUNCH_SCATTER8
 #undef GS_LAUNCH_SCATTER8_R
-        if (scatter_events) (void)hipEventRecord(scatter_events[2 * pass + 1], stream);
+        if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass + 1], stream);
         src = dst;
     }
     return src;
