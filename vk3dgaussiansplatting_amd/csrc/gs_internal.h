@@ -196,9 +196,9 @@ struct SortPass {
     uint32_t bits, mask;     // of this pass's digit (the last 8-bit pass may be narrower)
     bool tile_word;          // the digit lies in the tile word (shift >= 32), else in the depth word
     bool word16;             // that word is stored as 16 bits: the tile ids of a band (hi16) and, in a frame, the upper
-                             // half of the depth word once the lower half is consumed (see k_scatter)
-    uint32_t word_shift;     // of the digit within the word as stored
-    int lo_in, lo_out;       // bytes of the depth word read / written per element (k_scatter<LO_IN, LO_OUT, HI16>)
+                             // half of the depth word once the lower half is consumed (gs_sort_words.h)
+    uint32_t word_shift;     // of the digit within the word as stored (= word_shift_of, gs_sort_words.h)
+    int lo_in, lo_out;       // bytes of the depth word read / written per element (LO_IN / LO_OUT of gs_sort_words.h)
     bool last;
 };
 inline uint32_t sort_pass_count(const SortRun& r, uint32_t digit_bits) {
@@ -224,15 +224,6 @@ inline SortPass sort_pass(const SortRun& r, uint32_t digit_bits, uint32_t k) {
     p.word_shift = lo16 ? p.shift - 16u : p.shift & 31u;
     return p;
 }
-// The instantiations of the Scatter kernels by depth bytes: X(LO_IN, LO_OUT) for the pair of pass p
-#define GS_SCATTER_BY_DEPTH_BYTES(p, X)                          \
-    do {                                                         \
-        if ((p).lo_in == 4 && (p).lo_out == 4) X(4, 4);          \
-        else if ((p).lo_in == 4 && (p).lo_out == 2) X(4, 2);     \
-        else if ((p).lo_in == 2 && (p).lo_out == 2) X(2, 2);     \
-        else if ((p).lo_in == 2 && (p).lo_out == 0) X(2, 0);     \
-        else X(0, 0);                                            \
-    } while (0)
 
 // ---- launchers (each enqueues on `stream`, no host sync) ------------------------------------
 void launch_project(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_find_ranges(const uint32_t* __restrict_
                                                       const SortParams* __restrict__ params,
                                                       uint32_t* __restrict__ ranges, uint32_t hi16, TileMap map) {
     const uint32_t e = params->num_elems;
-    // hi16: 16-bit tile ids (see k_scatter) -- eight elements per 16-byte load, else four
+    // hi16: 16-bit tile ids (gs_sort_words.h) -- eight elements per 16-byte load, else four
     const uint16_t* tile16 = reinterpret_cast<const uint16_t*>(tile);
     const uint32_t per = hi16 ? 8u : 4u;
     const uint32_t chunks = (e + per - 1u) / per;

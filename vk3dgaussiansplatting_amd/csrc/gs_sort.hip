@@ -20,21 +20,14 @@
 // Short lists (at most kFedMaxGroups groups; gs_config.count_launches) sort with ONE k_count launch: every Scatter counts the next
 // pass's digit of the keys it stores and feeds the next pass's per-group count rows (k_scatter<.., FED>, "fed counts").
 // Inside a frame the words are narrower than the reference's: 16-bit compact tile ids when they fit, and depth words
-// that shrink as their digits are consumed (see k_scatter); the stand-alone sorter (gs_sort_host) always moves three
+// that shrink as their digits are consumed (gs_sort_words.h); the stand-alone sorter (gs_sort_host) always moves three
 // 32-bit words.  Output is bit-identical to a stable sort by the low num_sort_bits of the key.
 // Launch grids are fixed; the device-side element count (SortParams, the IndirectSetup record)
 // bounds every loop -- no host read-back inside a frame.
 #include "gs_device_utils.h"
-#include "gs_internal.h"
-
-#include <type_traits>
+#include "gs_sort_words.h"
 
 namespace gs {
-
-// The keys of a pass are read once: non-temporal loads keep them from displacing the partly written destination lines
-// in L2, which neighbouring groups are about to complete (config C's RadixSort 0.590 -> 0.552 ms, config D's 1.59 ->
-// 1.33 with the 4-bit passes; DESIGN.md section 4.1.  Non-temporal STORES, or such loads in Count, cost 10-80 %).
-#define GS_KEY_LOAD(p) __builtin_nontemporal_load(p)
 
 __device__ __forceinline__ uint32_t digit_of(uint32_t word, uint32_t sh) { return (word >> sh) & 15u; }
 
@@ -58,7 +51,7 @@ __device__ __forceinline__ uint32_t row16_inclusive_scan(uint32_t v) {
     return v;
 }
 
-constexpr int kCountKeysPerLane = kSortTile / 64;   // 32
+static_assert(kCountChunk == kSortTile, "a Count wave takes a whole group per step");
 constexpr int kCountMaxK = 128;                     // groups per segment whose counts are kept in LDS (8 KB)
 #ifndef GS_COUNT_WAVES
 #define GS_COUNT_WAVES 8
@@ -67,40 +60,6 @@ constexpr int kCountWaves = GS_COUNT_WAVES;         // waves of a Count workgrou
                                                     // (8 measured 1.6 % better than 4 on config C's sort, 16 no better)
 constexpr int kCountThreads = kCountWaves * 64;
 static_assert(kCountKeysPerLane % 8 == 0, "k_count consumes the group in chunks of 8 keys per lane");
-
-template <bool W16>
-struct CountRegs { uint4 v[kCountKeysPerLane / (W16 ? 8 : 4)]; };
-
-template <bool W16>
-__device__ __forceinline__ void count_load(const uint32_t* __restrict__ word, uint32_t grp, uint32_t e, int lane,
-                                           CountRegs<W16>& k) {
-    constexpr int V = kCountKeysPerLane / (W16 ? 8 : 4);
-    constexpr uint32_t PER = W16 ? 8u : 4u;          // keys per 16-byte load
-    const uint32_t tile_base = grp * kSortTile;
-    if (tile_base + kSortTile <= e) {
-        const uint4* w4 = W16 ? reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(word) + tile_base)
-                              : reinterpret_cast<const uint4*>(word + tile_base);
-#pragma unroll
-        for (int r = 0; r < V; ++r) k.v[r] = w4[r * 64 + lane];
-    } else {   // ragged last group: element-wise; keys past the end are skipped by the bounds test of the count
-#pragma unroll
-        for (int r = 0; r < V; ++r) {
-            const uint32_t i0 = tile_base + (uint32_t)(r * 64 + lane) * PER;
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if constexpr (W16) {
-                    const uint16_t* h = reinterpret_cast<const uint16_t*>(word);
-                    const uint32_t i = i0 + 2u * (uint32_t)q;
-                    w[q] = (i < e ? (uint32_t)h[i] : 0u) | ((i + 1u < e ? (uint32_t)h[i + 1u] : 0u) << 16);
-                } else {
-                    w[q] = i0 + (uint32_t)q < e ? word[i0 + q] : 0u;
-                }
-            }
-            k.v[r] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-}
 
 // Digit histogram of the wave's group into four 64-bit registers of 16-bit fields: a[j] holds digits j, j+4, j+8, j+12.
 template <bool W16, bool FULL>
@@ -149,11 +108,11 @@ __global__ __launch_bounds__(kCountThreads) void k_count(const SortParams* __res
     const uint32_t grp0 = blockIdx.x * K;
     uint32_t grp = grp0 + (uint32_t)wave;
     CountRegs<W16> cur;
-    if (grp < grp_end) count_load<W16>(word, grp, e, lane, cur);
+    if (grp < grp_end) count_load<W16>(word, grp * kSortTile, e, lane, cur);
     while (grp < grp_end) {
         const uint32_t nxt_grp = grp + kCountWaves;
         CountRegs<W16> nxt;
-        if (nxt_grp < grp_end) count_load<W16>(word, nxt_grp, e, lane, nxt);   // in flight while this group is counted
+        if (nxt_grp < grp_end) count_load<W16>(word, nxt_grp * kSortTile, e, lane, nxt);   // in flight while this group is counted
         uint64_t a[4] = {0, 0, 0, 0};
         if (grp * kSortTile + kSortTile <= e) count_keys<W16, true>(cur, grp, e, lane, sh, a);
         else count_keys<W16, false>(cur, grp, e, lane, sh, a);
@@ -259,18 +218,8 @@ __global__ __launch_bounds__(kCountThreads) void k_count(const SortParams* __res
 
 constexpr uint32_t kSortTileLog2 = 11;
 static_assert((1u << kSortTileLog2) == (uint32_t)kSortTile, "destination group of an element = index >> kSortTileLog2");
-__device__ __forceinline__ void fed_zero_row(uint32_t* rows, uint32_t grp, int d) { rows[grp * kBins + d] = 0u; }
 
-
-// LO_IN / LO_OUT = bytes of the depth word read / written per element (4, 2 or 0).  The stand-alone sorter
-// (gs_sort_host) and GS_SORT_TILE_BUCKET use <4, 4>: everything moves.  In a frame the depth word is needed only as a
-// sort key -- FindRanges reads the tile words, RenderGaussians the ids, gs_debug_read rebuilds the sorted depth
-// words from the ids -- so bits a pass has consumed are dead weight: passes 0-2 run <4, 4>, pass 3 writes only the
-// upper half <4, 2>, passes 4-6 sort on that half <2, 2>, pass 7 (last depth digit) does not write it <2, 0>, and the
-// tile-word passes run <0, 0>.
-// HI16: the tile words are 16-bit compact tile ids (at most 65535 owned tiles): 2 bytes less read and 2 less written
-// per element in every pass.
-// FULL: the group holds kSortTile valid keys (every group but the last): no per-element bounds logic.
+// LO_IN, LO_OUT, HI16, FULL: the word layout of the pass and whether the group is whole, see gs_sort_words.h.
 // FED: "fed counts" -- the pass has no Count launch of its own.  Every Scatter workgroup of pass p counts, per digit run it
 // stores and per destination group the run reaches (at most two: a run is at most one group long), the NEXT digit of the
 // keys it stores (LDS atomics while they pass through the store loop) and adds those <= 32 rows of 16 counts to the rows
@@ -289,14 +238,12 @@ __device__ __forceinline__ void scatter_group(
     const uint32_t* __restrict__ in_hi, const uint32_t* __restrict__ in_id,
     uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi, uint32_t* __restrict__ out_id,
     const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_sum, const uint32_t* __restrict__ coarse,
-    uint32_t shift, uint2* s_slot, typename std::conditional<HI16, uint16_t, uint32_t>::type* s_third,
+    uint32_t shift, uint2* s_slot, third_word<HI16>* s_third,
     uint32_t* s_wcnt, uint32_t* s_pre, uint32_t* s_next, uint32_t* s_first) {
     constexpr int R = kSortKeysPerThread;
-    // what travels beside the 8-byte slot {id, word}: nothing when the element is id + one 32-bit word (tile-word
-    // passes; depth passes whose depth and tile words are both 16 bits wide), else the tile word (s_third)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool use_hi = shift >= 32u;
-    const uint32_t sh = use_hi ? shift - 32u : (LO_IN == 2 ? shift - 16u : shift);   // bit offset inside the stored word
+    const uint32_t sh = word_shift_of<LO_IN>(shift);
     const uint32_t tile_base = grp * kSortTile;
     const uint32_t base = tile_base + (uint32_t)wave * (R * 64) + lane;
     const uint32_t valid = FULL ? (uint32_t)kSortTile : e - tile_base;
@@ -319,7 +266,7 @@ __device__ __forceinline__ void scatter_group(
         // rows of all groups, first batch: thread t takes digits 4 (t & 3) .. + 3 of rows t >> 2, + 64, ... (a wave
         // instruction = 16 whole rows); issued ahead of the keys (L2 hits: they are back long before the keys are)
         s_next[tid] = 0u; s_next[tid + kSortThreads] = 0u;
-        if (tid < kBins) fed_zero_row(const_cast<uint32_t*>(coarse), grp, tid);
+        if (tid < kBins) const_cast<uint32_t*>(coarse)[grp * kBins + tid] = 0u;
         const uint4* __restrict__ rows4 = reinterpret_cast<const uint4*>(table);
 #pragma unroll
         for (int k = 0; k < kFedBatch; ++k) {
@@ -468,11 +415,7 @@ __device__ __forceinline__ void scatter_group(
     for (int r = 0; r < R; ++r) {
         const uint32_t dg = digit_of(use_hi ? hi[r] : lo[r], sh);
         const uint32_t p = (uint32_t)__shfl((int)wbase, (int)dg, 64) + rank[r];
-        if (FULL || base + r * 64 < e) {
-            if constexpr (LO_IN == 0) s_slot[p] = make_uint2(id[r], hi[r]);
-            else if constexpr (LO_IN == 2 && HI16) s_slot[p] = make_uint2(id[r], lo[r] | (hi[r] << 16));
-            else { s_slot[p] = make_uint2(id[r], lo[r]); s_third[p] = (typename std::conditional<HI16, uint16_t, uint32_t>::type)hi[r]; }
-        }
+        if (FULL || base + r * 64 < e) stage_elem<LO_IN, HI16>(s_slot, s_third, p, id[r], lo[r], hi[r]);
     }
     __syncthreads();
 
@@ -481,20 +424,11 @@ __device__ __forceinline__ void scatter_group(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const uint32_t p = (uint32_t)r * kSortThreads + tid;
-        const uint2 sl = s_slot[p];
         uint32_t l, h;
-        if constexpr (LO_IN == 0) { l = 0u; h = sl.y; }
-        else if constexpr (LO_IN == 2 && HI16) { l = sl.y & 0xFFFFu; h = sl.y >> 16; }
-        else { l = sl.y; h = s_third[p]; }
+        const uint32_t id_p = unstage_elem<LO_IN, HI16>(s_slot, s_third, p, l, h);
         const uint32_t d = digit_of(use_hi ? h : l, sh);
         const uint32_t o = (uint32_t)__shfl((int)gofs, (int)d, 64) + p;
-        if (FULL || p < valid) {
-            if constexpr (LO_OUT == 4) out_lo[o] = l;
-            else if constexpr (LO_OUT == 2) reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)(LO_IN == 4 ? l >> 16 : l);
-            if constexpr (HI16) reinterpret_cast<uint16_t*>(out_hi)[o] = (uint16_t)h;
-            else out_hi[o] = h;
-            out_id[o] = sl.x;
-        }
+        if (FULL || p < valid) store_elem<LO_IN, LO_OUT, HI16>(out_lo, out_hi, out_id, o, id_p, l, h);
         if constexpr (FED) {
             if (seg_sum) {   // not the last pass: the key's NEXT digit, counted under (run, destination group)
                 // Lanes hold consecutive sorted positions, and in the depth passes the elements of one splat lie side by side
@@ -542,22 +476,17 @@ void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict
                uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi, uint32_t* __restrict__ out_id,
                const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_sum,
                const uint32_t* __restrict__ coarse, uint32_t shift) {
-    constexpr bool kThird = LO_IN == 4 || (LO_IN == 2 && !HI16);
     __shared__ uint2 s_slot[kSortTile];
-    __shared__ typename std::conditional<HI16, uint16_t, uint32_t>::type s_third[kThird ? kSortTile : 1];
+    __shared__ third_word<HI16> s_third[has_third(LO_IN, HI16) ? kSortTile : 1];
     __shared__ __attribute__((aligned(16))) uint32_t s_wcnt[kBins * kSortWaves];
     __shared__ __attribute__((aligned(16))) uint32_t s_pre[FED ? 2 * kBins * kSortWaves : 2 * kBins];
     __shared__ uint32_t s_next[FED ? 2 * kBins * kBins : 1];      // [run][destination group 0 / 1][next digit]
     __shared__ uint32_t s_first[FED ? kBins : 1];
     const uint32_t e = params->num_elems, G = params->num_groups, K = params->groups_per_seg;
-    // one group per workgroup as a rule: the grid is sized from an upper estimate of the element count (the list
-    // capacity scaled to the context's share of the tiles) and walks on only if a frame exceeds it
-    // Workgroups b, b + 8, ... share an XCD (observed placement, speed only): each of the eight takes a contiguous run of
-    // the groups, so that the digit runs of neighbouring groups -- neighbours in the destination too -- meet in one L2.
-    const uint32_t per_xcd = (G + 7u) / 8u;
+    const uint32_t per_xcd = (G + 7u) / 8u;      // the workgroup's walk over the groups: xcd_group, gs_sort_words.h
     bool again = false;
     for (uint32_t vb = blockIdx.x; vb < 8u * per_xcd; vb += gridDim.x) {
-        const uint32_t grp = (vb & 7u) * per_xcd + (vb >> 3);
+        const uint32_t grp = xcd_group(vb, per_xcd);
         if (grp >= G) continue;
         if (again) __syncthreads();   // LDS is reused
         again = true;
@@ -575,13 +504,7 @@ int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t str
     if (sb.digit_bits != (uint32_t)kRadixBits || (run.fed && !sb.fed[0])) return -1;   // table / seg_sum are sized per digit width
     const bool fed = run.fed, hi16 = run.hi16;
     const SortParams* params = run.params ? run.params : sb.params;
-    uint32_t max_groups = (run.capacity + kSortTile - 1) / kSortTile;
-    // a context that owns a share of the tiles (tile-row band of a multi-GPU frame) launches Scatter over twice
-    // that share of the capacity's groups; k_scatter walks on if a frame should hold more
-    if (run.share < 0.5f) {
-        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * run.share) + 64u;
-        max_groups = g < max_groups ? g : max_groups;
-    }
+    uint32_t max_groups = scatter_grid(run, kSortTile);
     // a fed sort is chosen for short lists (the frame goes by the element count of the frame before): its grid need not
     // cover more groups than such a list has; k_scatter walks on if this frame holds more
     if (fed && max_groups > 2u * kFedMaxGroups) max_groups = 2u * kFedMaxGroups;
@@ -602,27 +525,20 @@ int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t str
         if (!fed || pass == 0u) {
             uint32_t* const fr = fed ? rows_in : nullptr;
             uint32_t* const fz = fed ? sb.fed[1] : nullptr;
-            if (p.word16)
-                hipLaunchKernelGGL((k_count<true>), dim3(kSegments), dim3(kCountThreads), 0, stream, params,
+            with_bool(p.word16, [&](auto w16) {
+                hipLaunchKernelGGL((k_count<w16.value>), dim3(kSegments), dim3(kCountThreads), 0, stream, params,
                                    word, sb.table, sb.seg_sum, coarse, p.word_shift, fr, fz);
-            else
-                hipLaunchKernelGGL((k_count<false>), dim3(kSegments), dim3(kCountThreads), 0, stream, params,
-                                   word, sb.table, sb.seg_sum, coarse, p.word_shift, fr, fz);
+            });
         }
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
-#define GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, FED, T0, T1, T2)                                                        \
-        hipLaunchKernelGGL((k_scatter<LO_IN, LO_OUT, HI16, FED>), dim3(max_groups), dim3(kSortThreads), 0, stream, params, \
-                           sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst], sb.hi[dst], sb.id[dst],                  \
-                           T0, T1, T2, p.shift)
-#define GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, HI16) \
-        do { if (fed) GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, true, rows_in, rows_next, rows_zero); \
-             else GS_LAUNCH_SCATTER(LO_IN, LO_OUT, HI16, false, sb.table, sb.seg_sum, coarse); } while (0)
-#define GS_LAUNCH_SCATTER_H(LO_IN, LO_OUT) \
-        do { if (hi16) GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, true); else GS_LAUNCH_SCATTER_F(LO_IN, LO_OUT, false); } while (0)
-        GS_SCATTER_BY_DEPTH_BYTES(p, GS_LAUNCH_SCATTER_H);
-#undef GS_LAUNCH_SCATTER_H
-#undef GS_LAUNCH_SCATTER_F
-#undef GS_LAUNCH_SCATTER
+        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16) {
+            with_bool(fed, [&](auto f) {
+                hipLaunchKernelGGL((k_scatter<lo_in.value, lo_out.value, h16.value, f.value>), dim3(max_groups),
+                                   dim3(kSortThreads), 0, stream, params, sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst],
+                                   sb.hi[dst], sb.id[dst], fed ? rows_in : sb.table, fed ? rows_next : sb.seg_sum,
+                                   fed ? rows_zero : coarse, p.shift);
+            });
+        });
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass + 1], stream);
         src = dst;                                                            // RadixSort.cpp:638-641
     }

@@ -21,66 +21,25 @@
 //                        (RadixSortScatter.comp:58-171).  Groups are dealt to workgroups so that neighbouring groups
 //                        share an XCD: a digit run is only 16 keys long on average, and the runs of neighbouring
 //                        groups complete each other's cache lines inside one L2.
-// Word widths inside a frame as in gs_sort.hip: 16-bit compact tile ids, depth words that shrink once their lower
-// half is consumed (pass 0 moves all of it, pass 1 keeps the upper half, pass 2 sorts on that half, pass 3 drops it).
+// Word widths inside a frame: 16-bit compact tile ids, depth words that shrink once their lower half is consumed; the
+// layouts and the code that moves them are gs_sort_words.h, shared with gs_sort.hip.
 #include "gs_device_utils.h"
-#include "gs_internal.h"
-
-#include <type_traits>
+#include "gs_sort_words.h"
 
 namespace gs {
 
-// The keys of a pass are read once: non-temporal loads keep them from displacing the partly written destination lines
-// in L2, which neighbouring groups are about to complete (config C's RadixSort 0.590 -> 0.552 ms, config D's 1.59 ->
-// 1.33 with the 4-bit passes; DESIGN.md section 4.1.  Non-temporal STORES, or such loads in Count, cost 10-80 %).
-#define GS_KEY_LOAD(p) __builtin_nontemporal_load(p)
-
-constexpr int kC8Chunk = 2048;                          // keys a Count wave takes per step
+constexpr int kC8Chunk = kCountChunk;                   // keys a Count wave takes per step
 constexpr int kC8Waves = 8;
 constexpr int kC8Threads = kC8Waves * 64;
 constexpr int kC8MaxK = 32;                             // groups of a segment whose counters sit in LDS at once (32 KB)
 static_assert(kSort8TileSmall % kC8Chunk == 0 && kSort8Tile % kC8Chunk == 0, "a group is a whole number of Count steps");
-
-template <bool W16>
-struct Count8Regs { uint4 v[W16 ? 4 : 8]; };            // 32 keys per lane
-
-template <bool W16>
-__device__ __forceinline__ void count8_load(const uint32_t* __restrict__ word, uint32_t chunk, uint32_t e, int lane,
-                                            Count8Regs<W16>& k) {
-    constexpr int V = W16 ? 4 : 8;
-    constexpr uint32_t PER = W16 ? 8u : 4u;              // keys per 16-byte load
-    const uint32_t first = chunk * kC8Chunk;
-    if (first + kC8Chunk <= e) {
-        const uint4* w4 = W16 ? reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(word) + first)
-                              : reinterpret_cast<const uint4*>(word + first);
-#pragma unroll
-        for (int r = 0; r < V; ++r) k.v[r] = w4[r * 64 + lane];
-    } else {   // ragged end of the list: element-wise, keys past the end are skipped by the bounds test of the count
-#pragma unroll
-        for (int r = 0; r < V; ++r) {
-            const uint32_t i0 = first + (uint32_t)(r * 64 + lane) * PER;
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if constexpr (W16) {
-                    const uint16_t* h = reinterpret_cast<const uint16_t*>(word);
-                    const uint32_t i = i0 + 2u * (uint32_t)q;
-                    w[q] = (i < e ? (uint32_t)h[i] : 0u) | ((i + 1u < e ? (uint32_t)h[i + 1u] : 0u) << 16);
-                } else {
-                    w[q] = i0 + (uint32_t)q < e ? word[i0 + q] : 0u;
-                }
-            }
-            k.v[r] = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-    }
-}
 
 // RUNS (the passes over the depth word): the keys of one splat carry one depth and lie side by side in the list -- in
 // InitSortList's order and, the sort being stable, after every depth pass -- so neighbouring lanes of a wave
 // instruction (keys 4 or 8 apart) often hold the same digit, and same-address LDS atomics serialise.  The first lane of
 // every run of equal digits (runs end at the 16-lane rows of the DPP shift) adds the run's length for all of them.
 template <bool W16, bool FULL, bool RUNS>
-__device__ __forceinline__ void count8_keys(const Count8Regs<W16>& k, uint32_t chunk, uint32_t e, int lane, uint32_t sh,
+__device__ __forceinline__ void count8_keys(const CountRegs<W16>& k, uint32_t chunk, uint32_t e, int lane, uint32_t sh,
                                             uint32_t mask, uint32_t* hist) {
     constexpr int V = W16 ? 4 : 8;
     constexpr uint32_t PER = W16 ? 8u : 4u;
@@ -131,12 +90,12 @@ __global__ __launch_bounds__(kC8Threads) void k_count8(const SortParams* __restr
         const uint32_t b1 = b0 + kC8MaxK < grp_end ? b0 + kC8MaxK : grp_end;
         const uint32_t ch_end = b1 * kC8ChunksPerGroup < chunks ? b1 * kC8ChunksPerGroup : chunks;
         uint32_t ch = b0 * kC8ChunksPerGroup + (uint32_t)wave;
-        Count8Regs<W16> cur;
-        if (ch < ch_end) count8_load<W16>(word, ch, e, lane, cur);
+        CountRegs<W16> cur;
+        if (ch < ch_end) count_load<W16>(word, ch * kC8Chunk, e, lane, cur);
         while (ch < ch_end) {
             const uint32_t nxt_ch = ch + kC8Waves;
-            Count8Regs<W16> nxt;
-            if (nxt_ch < ch_end) count8_load<W16>(word, nxt_ch, e, lane, nxt);   // in flight while this step is counted
+            CountRegs<W16> nxt;
+            if (nxt_ch < ch_end) count_load<W16>(word, nxt_ch * kC8Chunk, e, lane, nxt);   // in flight while this step is counted
             uint32_t* hist = s_hist[ch / kC8ChunksPerGroup - b0];
             if (ch * kC8Chunk + kC8Chunk <= e) count8_keys<W16, true, RUNS>(cur, ch, e, lane, sh, mask, hist);
             else count8_keys<W16, false, RUNS>(cur, ch, e, lane, sh, mask, hist);
@@ -193,13 +152,12 @@ __device__ __forceinline__ void scatter8_group(
     uint32_t e, uint32_t seg, uint32_t grp, const uint32_t* __restrict__ in_lo, const uint32_t* __restrict__ in_hi,
     const uint32_t* __restrict__ in_id, uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi,
     uint32_t* __restrict__ out_id, const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_base,
-    const uint32_t* __restrict__ totals, uint32_t shift, uint32_t mask, uint2* s_slot, typename std::conditional<HI16, uint16_t, uint32_t>::type* s_third,
+    const uint32_t* __restrict__ totals, uint32_t shift, uint32_t mask, uint2* s_slot, third_word<HI16>* s_third,
     uint32_t* s_cnt, uint32_t* s_wbase, uint32_t* s_gpre, uint32_t* s_gofs, uint32_t* s_tot) {
     constexpr int NT = kSort8Threads, W = NT / 64, TILE = NT * R;
-    using third_t = typename std::conditional<HI16, uint16_t, uint32_t>::type;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool use_hi = shift >= 32u;
-    const uint32_t sh = use_hi ? shift - 32u : (LO_IN == 2 ? shift - 16u : shift);   // bit offset inside the stored word
+    const uint32_t sh = word_shift_of<LO_IN>(shift);
     const uint32_t tile_base = grp * TILE;
     const uint32_t base = tile_base + (uint32_t)wave * (R * 64) + lane;
     const uint32_t valid = FULL ? (uint32_t)TILE : e - tile_base;
@@ -296,11 +254,7 @@ __device__ __forceinline__ void scatter8_group(
     for (int r = 0; r < R; ++r) {
         const uint32_t dg = ((use_hi ? hi[r] : lo[r]) >> sh) & mask;
         const uint32_t p = wbase[dg] + rank[r];
-        if (FULL || base + r * 64 < e) {
-            if constexpr (LO_IN == 0) s_slot[p] = make_uint2(id[r], hi[r]);
-            else if constexpr (LO_IN == 2 && HI16) s_slot[p] = make_uint2(id[r], lo[r] | (hi[r] << 16));
-            else { s_slot[p] = make_uint2(id[r], lo[r]); s_third[p] = (third_t)hi[r]; }
-        }
+        if (FULL || base + r * 64 < e) stage_elem<LO_IN, HI16>(s_slot, s_third, p, id[r], lo[r], hi[r]);
     }
     __syncthreads();
 
@@ -309,18 +263,10 @@ __device__ __forceinline__ void scatter8_group(
     for (int r = 0; r < R; ++r) {
         const uint32_t p = (uint32_t)r * NT + tid;
         if (FULL || p < valid) {
-            const uint2 sl = s_slot[p];
             uint32_t l, h;
-            if constexpr (LO_IN == 0) { l = 0u; h = sl.y; }
-            else if constexpr (LO_IN == 2 && HI16) { l = sl.y & 0xFFFFu; h = sl.y >> 16; }
-            else { l = sl.y; h = s_third[p]; }
+            const uint32_t id_p = unstage_elem<LO_IN, HI16>(s_slot, s_third, p, l, h);
             const uint32_t d = ((use_hi ? h : l) >> sh) & mask;
-            const uint32_t o = s_gofs[d] + p;
-            if constexpr (LO_OUT == 4) out_lo[o] = l;
-            else if constexpr (LO_OUT == 2) reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)(LO_IN == 4 ? l >> 16 : l);
-            if constexpr (HI16) reinterpret_cast<uint16_t*>(out_hi)[o] = (uint16_t)h;
-            else out_hi[o] = h;
-            out_id[o] = sl.x;
+            store_elem<LO_IN, LO_OUT, HI16>(out_lo, out_hi, out_id, s_gofs[d] + p, id_p, l, h);
         }
     }
 }
@@ -332,10 +278,9 @@ void k_scatter8(const SortParams* __restrict__ params, const uint32_t* __restric
                 uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi, uint32_t* __restrict__ out_id,
                 const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_base,
                 const uint32_t* __restrict__ totals, uint32_t shift, uint32_t mask) {
-    constexpr bool kThird = LO_IN == 4 || (LO_IN == 2 && !HI16);
     constexpr int W = kSort8Threads / 64, TILE = kSort8Threads * R;
     __shared__ uint2 s_slot[TILE];
-    __shared__ typename std::conditional<HI16, uint16_t, uint32_t>::type s_third[kThird ? TILE : 1];
+    __shared__ third_word<HI16> s_third[has_third(LO_IN, HI16) ? TILE : 1];
     __shared__ __attribute__((aligned(16))) uint32_t s_cnt[W * kBins8];
     __shared__ __attribute__((aligned(16))) uint32_t s_wbase[W * kBins8];
     __shared__ __attribute__((aligned(16))) uint32_t s_gpre[kBins8];
@@ -343,13 +288,10 @@ void k_scatter8(const SortParams* __restrict__ params, const uint32_t* __restric
     __shared__ __attribute__((aligned(16))) uint32_t s_tot[kBins8];
     const uint32_t e = params->num_elems;
     const uint32_t G = (e + TILE - 1) / TILE, K = (G + kSegments - 1) / kSegments;
-    // Workgroups b, b + 8, ... share an XCD (observed placement, speed only): each of the eight takes a contiguous run of
-    // the groups, so that the short digit runs of neighbouring groups -- neighbours in the destination too -- meet in
-    // one L2 and leave it as whole lines.
-    const uint32_t per_xcd = (G + 7u) / 8u;
+    const uint32_t per_xcd = (G + 7u) / 8u;      // the workgroup's walk over the groups: xcd_group, gs_sort_words.h
     bool again = false;
     for (uint32_t vb = blockIdx.x; vb < 8u * per_xcd; vb += gridDim.x) {
-        const uint32_t grp = (vb & 7u) * per_xcd + (vb >> 3);
+        const uint32_t grp = xcd_group(vb, per_xcd);
         if (grp >= G) continue;
         if (again) __syncthreads();   // LDS is reused
         again = true;
@@ -372,11 +314,7 @@ int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t st
     const float bound = (float)run.capacity * (run.share < 0.5f ? run.share : 1.0f);   // a band holds about its share of the capacity
     const bool small = bound < (float)kSort8SmallBelow;
     const uint32_t tile = small ? (uint32_t)kSort8TileSmall : (uint32_t)kSort8Tile;
-    uint32_t max_groups = (run.capacity + tile - 1) / tile;
-    if (run.share < 0.5f) {   // a tile-row band: see launch_radix_sort
-        const uint32_t g = (uint32_t)((float)max_groups * 2.0f * run.share) + 64u;
-        max_groups = g < max_groups ? g : max_groups;
-    }
+    const uint32_t max_groups = scatter_grid(run, tile);
     uint32_t* seg_base = sb.seg_sum + (size_t)kBins8 * kSegments;
     int src = run.start;
     const uint32_t passes = sort_pass_count(run, 8u);
@@ -386,34 +324,24 @@ int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t st
         const uint32_t* word = p.tile_word ? sb.hi[src] : sb.lo[src];
         // the pass's digit totals (k_scan8 -> k_scatter8): a slab of sb.coarse
         uint32_t* totals = sb.coarse + (size_t)(run.coarse_pass + pass) * kBins * kCoarse;
-#define GS_LAUNCH_COUNT8(W16, RUNS)                                                                                  \
-        do { if (small) hipLaunchKernelGGL((k_count8<W16, RUNS, kSort8TileSmall>), dim3(kSegments), dim3(kC8Threads), 0, stream, \
-                                           params, word, sb.table, sb.seg_sum, p.word_shift, p.mask);                \
-             else hipLaunchKernelGGL((k_count8<W16, RUNS, kSort8Tile>), dim3(kSegments), dim3(kC8Threads), 0, stream,  \
-                                     params, word, sb.table, sb.seg_sum, p.word_shift, p.mask); } while (0)
         // Runs of equal digits in neighbouring keys: the depth digits wherever splats are replicated into tiles (not in the
         // splat list of the splat-first order, whose passes stop at bit 32), and the top tile digit -- the keys arrive
         // sorted by everything below it, so the long lists of a capture's heavy tiles lie in runs (C-hard: that Count
         // 37 -> 17 us with the runs added once; uniform fog pays 2.5 us for it).
         const bool runs = p.tile_word ? p.last : run.num_sort_bits > 32u;
-        if (runs) { if (p.word16) GS_LAUNCH_COUNT8(true, true); else GS_LAUNCH_COUNT8(false, true); }
-        else { if (p.word16) GS_LAUNCH_COUNT8(true, false); else GS_LAUNCH_COUNT8(false, false); }
-#undef GS_LAUNCH_COUNT8
+        with_bool(runs, [&](auto rn) { with_bool(p.word16, [&](auto w16) { with_bool(small, [&](auto sm) {
+            hipLaunchKernelGGL((k_count8<w16.value, rn.value, sm.value ? kSort8TileSmall : kSort8Tile>), dim3(kSegments),
+                               dim3(kC8Threads), 0, stream, params, word, sb.table, sb.seg_sum, p.word_shift, p.mask);
+        }); }); });
         hipLaunchKernelGGL(k_scan8, dim3(kBins8), dim3(kSegments), 0, stream, sb.seg_sum, seg_base, totals);
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
-#define GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, R)                                                                   \
-        hipLaunchKernelGGL((k_scatter8<LO_IN, LO_OUT, HI16, R>), dim3(max_groups), dim3(kSort8Threads), 0, stream, params, \
-                           sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst], sb.hi[dst], sb.id[dst], sb.table, seg_base,    \
-                           totals, p.shift, p.mask)
-#define GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, HI16)                                                                        \
-        do { if (small) GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, kSort8KeysSmall);                                   \
-             else GS_LAUNCH_SCATTER8_R(LO_IN, LO_OUT, HI16, kSort8KeysPerThread); } while (0)
-#define GS_LAUNCH_SCATTER8_H(LO_IN, LO_OUT) \
-        do { if (hi16) GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, true); else GS_LAUNCH_SCATTER8(LO_IN, LO_OUT, false); } while (0)
-        GS_SCATTER_BY_DEPTH_BYTES(p, GS_LAUNCH_SCATTER8_H);
-#undef GS_LAUNCH_SCATTER8_H
-#undef GS_LAUNCH_SCATTER8
-#undef GS_LAUNCH_SCATTER8_R
+        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16) {
+            with_bool(small, [&](auto sm) {
+                hipLaunchKernelGGL((k_scatter8<lo_in.value, lo_out.value, h16.value, sm.value ? kSort8KeysSmall : kSort8KeysPerThread>),
+                                   dim3(max_groups), dim3(kSort8Threads), 0, stream, params, sb.lo[src], sb.hi[src], sb.id[src],
+                                   sb.lo[dst], sb.hi[dst], sb.id[dst], sb.table, seg_base, totals, p.shift, p.mask);
+            });
+        });
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass + 1], stream);
         src = dst;
     }
