@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 7   /* 7: gs_backward / gs_backward_device / gs_upload_gaussians_device.  7 (later): gs_visible_count / gs_backward_visible / gs_backward_visible_device (same version: detect them by the presence of the symbols).  6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
+#define GS_API_VERSION 7   /* 7: gs_backward / gs_backward_device / gs_upload_gaussians_device.  7 (later): gs_visible_count / gs_backward_visible / gs_backward_visible_device (same version: detect them by the presence of the symbols).  7 (later still): gs_default_adam_params / gs_adam_rows_device / gs_upload_rows_device (GS_ADAM_*, gs_adam_params; same version again: detect them by the presence of the symbols).  6: gs_set_outputs / gs_read_output / gs_output_device (GS_OUTPUT_*).  5: gs_config grew count_launches (GS_COUNT_*).  2: gs_config grew tile_order; 3: gs_config starts with struct_size, gs_api_version(),
                               gs_runtime_versions(), gs_dist_* / gs_gather_strips; 4: GS_ROWS_BALANCED + gs_dist_rebalance /
                               gs_dist_bands, gs_render_sharded_async / gs_sharded_frame / gs_sharded_read (two sharded
                               frames in flight, the assembled frame left in HBM), GS_BUF_COLOR for every non-culled splat */
@@ -450,6 +450,67 @@ int gs_backward_visible(gs_ctx* ctx, const float* grad_rgba32f, const float* gra
                         uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
 int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth,
                                uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
+
+/* One optimiser step on the rows gs_backward_visible* lists (no reference counterpart), in two calls that keep no state
+ * inside the library: an Adam step on the CALLER's records and moments, and the upload of the changed rows alone.
+ *
+ * Field groups: the 59 floats of the 84-float record that gs_backward gives gradients to.  The other 25 (3, 7, 19 + 4k for
+ * k = 0..14, and 76..83) are never read or written by either call, in records, m or v. */
+#define GS_ADAM_POSITION 0   /* floats 0, 1, 2 */
+#define GS_ADAM_SCALE 1      /* floats 4, 5, 6 */
+#define GS_ADAM_ROTATION 2   /* floats 8..11 */
+#define GS_ADAM_SH_DC 3      /* floats 12, 13, 14 */
+#define GS_ADAM_OPACITY 4    /* float 15 */
+#define GS_ADAM_SH_REST 5    /* floats 16 + 4k + {0, 1, 2}, k = 0..14 */
+#define GS_ADAM_GROUPS 6
+
+typedef struct gs_adam_params {
+    uint32_t struct_size;          /* sizeof(gs_adam_params) of the caller's header: filled by gs_default_adam_params, checked */
+    uint32_t step;                 /* t >= 1 of THIS step (the caller counts) */
+    float beta1, beta2, eps;
+    float lr[GS_ADAM_GROUPS];      /* per group: learning rate ... */
+    float lo[GS_ADAM_GROUPS];      /* ... and the clamp [lo, hi] of the updated value (infinite = none) */
+    float hi[GS_ADAM_GROUPS];
+} gs_adam_params;
+/* step 1, beta1 0.9, beta2 0.999, eps 1e-15; lr: position 1.6e-4, scale 5e-3, rotation 1e-3, SH DC 2.5e-3, opacity 5e-2,
+ * SH rest 1.25e-4 -- the rates of the INRIA 3DGS trainer.  NOTE: there they act on log-scales and logit-opacities; here
+ * they act on the record's own values (scale and opacity as the frame reads them), so the clamps below stand in for what
+ * exp and sigmoid guarantee, and a caller may want other rates.  lo / hi: scale [1e-7, +inf], opacity [0, 1], every other
+ * group [-inf, +inf]. */
+void gs_default_adam_params(gs_adam_params* p);
+/* torch.optim.SparseAdam's rule on rows ids[i], i < min(*count_dev, max_rows), of records / m / v (each float[n][84],
+ * DEVICE, the caller's; m and v start as zeros) with the gradient rows grad_rows[i][84] -- ids, grad_rows and count_dev
+ * as gs_backward_visible_device leaves them.  Every field of a listed row moves, also one with a zero gradient, and eps
+ * is added before the bias correction.  All arithmetic is float32, never contracted, in exactly this order, so the
+ * result is bitwise reproducible (and restated exactly by NumPy float32: tests/test_adam_cpu.py):
+ *   host, per group: step_g = (float)(((double)lr_g * sqrt(1 - pow((double)beta2, t))) / (1 - pow((double)beta1, t)));
+ *   host: c1 = 1.0f - beta1, c2 = 1.0f - beta2;
+ *   m' = beta1 * m + c1 * g
+ *   v' = beta2 * v + (c2 * g) * g
+ *   p' = p - step_g * (m' / (sqrtf(v') + eps))
+ *   p' = p' < lo_g ? lo_g : (p' > hi_g ? hi_g : p')        (a NaN stays a NaN)
+ * An ids[i] >= n is skipped (compared, never dereferenced).  Ids are distinct, as gs_backward_visible* writes them;
+ * duplicates are the caller's error.  ids, grad_rows and count_dev are only read; count_dev is never read by the host.
+ * Enqueued on the context's stream, no host sync; the grid is sized from max_rows and the blocks past the count exit at
+ * once.  max_rows == 0: GS_OK, nothing launched.  The call needs no scene and no resolution: it uses the context's device
+ * and stream only.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued (a NULL ctx: the code alone): a NULL pointer with
+ * max_rows > 0, n == 0, a struct_size other than sizeof(gs_adam_params), step == 0, a beta outside [0, 1), an lr or eps
+ * that is negative or not finite (or an lr whose step_g is not finite), lo_g > hi_g or a NaN bound. */
+int gs_adam_rows_device(gs_ctx* ctx, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                        const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev,
+                        uint32_t max_rows, const gs_adam_params* p);
+/* The sparse form of the in-place gs_upload_gaussians_device: for every listed g = ids[i], i < min(*count_dev, max_rows),
+ * the planes of splat g (position, scale, rotation, the 48 SH values, opacity and the cull bound derived from scale and
+ * rotation) are rewritten from record g of aos336_dev (float[n][84], DEVICE), then the per-64-splat boxes are rebuilt:
+ * afterwards the scene is bit for bit what gs_upload_gaussians_device makes of records that differ from the uploaded
+ * ones in the listed rows only.  An ids[i] >= n is skipped; ids are distinct.  Enqueued on the context's stream, no host
+ * sync; every context sharing the scene (gs_share_scene) renders the new values; resolution, scratch and captured graphs
+ * stay; gs_backward* needs a new frame, as after the full upload.  max_rows == 0: GS_OK, nothing launched.
+ * GS_ERR_INVALID (message, nothing enqueued; a NULL ctx: the code alone): a NULL pointer with max_rows > 0, n == 0, an n
+ * that differs from the scene's (this call never makes a new scene).  GS_ERR_NO_SCENE: no gaussians uploaded yet. */
+int gs_upload_rows_device(gs_ctx* ctx, const void* aos336_dev, uint32_t n,
+                          const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows);
 
 /* Photometric loss of a frame against a photograph (no reference counterpart): the number a 3DGS optimisation minimises,
  *   loss = (1 - lambda) * L1 + lambda * DSSIM,

@@ -193,6 +193,27 @@ public:
         return rc;
     }
 
+    // One optimiser step on the rows backwardVisible(device = true) lists (gsplat.h, gs_adam_rows_device and
+    // gs_upload_rows_device): Adam on the caller's DEVICE records [N][84] and moments m, v, then the planes of the listed
+    // splats rewritten from those records.  Both are enqueued on the context's stream without waiting; ids, grad_rows and
+    // count are device pointers as backwardVisible left them.
+    static gs_adam_params defaultAdamParams() {
+        gs_adam_params p;
+        gs_default_adam_params(&p);
+        return p;
+    }
+    int adamRows(float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
+                 const uint32_t* count, uint32_t max_rows, const gs_adam_params& params) {
+        const int rc = gs_adam_rows_device(ctx_, records, m, v, n, ids, grad_rows, count, max_rows, &params);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int uploadRows(const void* records, uint32_t n, const uint32_t* ids, const uint32_t* count, uint32_t max_rows) {
+        const int rc = gs_upload_rows_device(ctx_, records, n, ids, count, max_rows);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

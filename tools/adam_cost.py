@@ -1,0 +1,123 @@
+"""What the optimiser step on the visible rows costs on the GPU (include/gsplat.h): gs_adam_rows_device +
+gs_upload_rows_device against the route INTEGRATION.md documented before them, torch.optim.SparseAdam.step() on the same
+sparse gradient + the full in-place gs_upload_gaussians_device.  Config C under its own camera: one frame, then
+gs_backward_visible_device with a random image gradient lists the rows.  Everything runs on one torch stream handed to
+gs_set_stream; every repetition is bracketed by HIP events (one pair per call, so the two halves of a route are also known
+alone), the two routes alternate repetition by repetition so that both see the same neighbours, and the means are over
+--iters repetitions after --warmup.  Bytes per row are what the Adam kernel has to move: the gradient's 59 fields read, and
+the 59 fields of records, m and v read and written (7 x 236); the upload reads a record (336) and writes 60 plane values
+(240), and both uploads then read 16 bytes per splat of the scene for the block bounds.
+
+    python tools/adam_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/adam_cost.txt]"""
+import argparse, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--config", default="C")
+ap.add_argument("--iters", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adam_cost.txt"))
+a = ap.parse_args()
+
+import numpy as np
+import torch
+import vk3dgaussiansplatting_amd as gs
+from vk3dgaussiansplatting_amd import synth
+
+ADAM_BYTES_PER_ROW = 7 * 59 * 4
+UPLOAD_BYTES_PER_ROW = 336 + 60 * 4
+
+aos, cfg = synth.generate_config(a.config)
+aos = np.ascontiguousarray(aos, dtype=np.float32)
+n, w, h = len(aos), cfg["width"], cfg["height"]
+rm = gs.ResourceManager(); rm.setGaussians(aos)
+sc = gs.Scene(rm, aspect_ratio=w / h)
+cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
+r = gs.Renderer(w, h, record_timings=False, warmup_frames=0)
+r.init(rm); r.initForScene(sc)
+
+dev = torch.device("cuda:0")
+rng = np.random.default_rng(0)
+grad_image = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device=dev)
+r.drawDevice(sc, None, sync=True)
+rows_listed = r.visibleCount()
+ids = torch.zeros(rows_listed, dtype=torch.int32, device=dev)
+rows = torch.zeros(rows_listed, 84, device=dev)
+count = torch.zeros(1, dtype=torch.int32, device=dev)
+torch.cuda.synchronize()
+r.backwardVisibleDevice(grad_image.data_ptr(), None, ids.data_ptr(), rows.data_ptr(), rows_listed, count.data_ptr())
+r.synchronize()
+assert int(count.item()) == rows_listed and bool(torch.isfinite(rows).all())
+
+records = torch.tensor(aos, device=dev)
+m, v = torch.zeros_like(records), torch.zeros_like(records)
+# the documented route: one [N, 84] leaf, a sparse COO gradient over the listed rows, SparseAdam, then every record uploaded
+leaf = torch.nn.Parameter(torch.tensor(aos, device=dev))
+opt = torch.optim.SparseAdam([leaf], lr=1e-3)
+leaf.grad = torch.sparse_coo_tensor(ids.long()[None], rows, size=(n, 84)).coalesce()
+stream = torch.cuda.Stream(device=dev)
+torch.cuda.synchronize()
+r.setStream(stream.cuda_stream)
+
+
+def timed(calls):
+    """The calls back to back on the stream, an event before each and one behind the last: milliseconds per call."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(calls) + 1)]
+    for e, call in zip(ev, calls):
+        e.record(stream)
+        call()
+    ev[-1].record(stream)
+    ev[-1].synchronize()
+    return [ev[k].elapsed_time(ev[k + 1]) for k in range(len(calls))]
+
+
+step = [0]
+
+
+def adam():
+    step[0] += 1
+    r.adamRowsDevice(records.data_ptr(), m.data_ptr(), v.data_ptr(), n, ids.data_ptr(), rows.data_ptr(), count.data_ptr(),
+                     rows_listed, gs.default_adam_params(step=step[0]))
+
+
+new_route = [adam, lambda: r.uploadRowsDevice(records.data_ptr(), n, ids.data_ptr(), count.data_ptr(), rows_listed)]
+old_route = [opt.step, lambda: r.uploadDevice(leaf.data_ptr(), n)]
+new_ms, old_ms = [], []
+with torch.cuda.stream(stream):
+    for k in range(a.warmup + a.iters):
+        t_new, t_old = timed(new_route), timed(old_route)
+        if k >= a.warmup:
+            new_ms.append(t_new)
+            old_ms.append(t_old)
+torch.cuda.synchronize()
+r.setStream(None)
+r.cleanup()
+
+new_ms, old_ms = np.array(new_ms), np.array(old_ms)
+mean = lambda x: round(float(np.mean(x)), 4)
+spread = lambda x: [round(float(np.min(x)), 4), round(float(np.max(x)), 4)]
+adam_ms, upload_rows_ms = mean(new_ms[:, 0]), mean(new_ms[:, 1])
+new_total, old_total = mean(new_ms.sum(1)), mean(old_ms.sum(1))
+line = {"config": a.config, "width": w, "height": h, "gaussians": n, "rows": rows_listed, "iters": a.iters, "warmup": a.warmup,
+        "adam_rows_ms_mean": adam_ms, "adam_rows_ms_min_max": spread(new_ms[:, 0]),
+        "adam_bytes_per_row": ADAM_BYTES_PER_ROW,
+        "adam_achieved_tbytes_per_s": round(rows_listed * ADAM_BYTES_PER_ROW / (adam_ms * 1e-3) / 1e12, 3),
+        "upload_rows_ms_mean": upload_rows_ms, "upload_rows_ms_min_max": spread(new_ms[:, 1]),
+        "upload_rows_bytes_per_row": UPLOAD_BYTES_PER_ROW, "block_bounds_bytes_per_gaussian": 16,
+        "upload_rows_achieved_tbytes_per_s": round((rows_listed * UPLOAD_BYTES_PER_ROW + 16 * n) / (upload_rows_ms * 1e-3) / 1e12, 3),
+        "adam_rows_plus_upload_rows_ms_mean": new_total, "adam_rows_plus_upload_rows_ms_min_max": spread(new_ms.sum(1)),
+        "sparse_adam_step_ms_mean": mean(old_ms[:, 0]), "sparse_adam_step_ms_min_max": spread(old_ms[:, 0]),
+        "full_upload_ms_mean": mean(old_ms[:, 1]), "full_upload_ms_min_max": spread(old_ms[:, 1]),
+        "sparse_adam_plus_full_upload_ms_mean": old_total, "sparse_adam_plus_full_upload_ms_min_max": spread(old_ms.sum(1)),
+        "documented_route_over_new_route": round(old_total / new_total, 2),
+        "new_route_is_faster": bool(new_total < old_total)}
+print(json.dumps(line), flush=True)
+os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+with open(a.out, "w") as f:
+    f.write("# tools/adam_cost.py on one MI355X: gs_adam_rows_device + gs_upload_rows_device against torch.optim.SparseAdam.step() on the\n"
+            "# same sparse gradient + the full in-place gs_upload_gaussians_device; config C under its own camera, the rows of one\n"
+            "# gs_backward_visible_device; HIP events around every call on one stream, the routes alternating, means (and min, max) over\n"
+            "# `iters` repetitions after `warmup`.  GPU times; the host-side wait for the count that the documented route also needs\n"
+            "# (gs_visible_count, to size the COO tensor) is not in them.  Recorded numbers, not a bound.\n")
+    f.write(json.dumps(line) + "\n")

@@ -40,6 +40,14 @@ GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read
 
 RECORD_BYTES = 336
 
+# field groups of gs_adam_params (GS_ADAM_*): the 59 floats of the 84-float record gs_backward gives gradients to
+GS_ADAM_POSITION, GS_ADAM_SCALE, GS_ADAM_ROTATION, GS_ADAM_SH_DC, GS_ADAM_OPACITY, GS_ADAM_SH_REST = range(6)
+GS_ADAM_GROUPS = 6
+# group of every float of a record; -1: one of the 25 floats gs_adam_rows_device and gs_upload_rows_device never touch
+ADAM_GROUP_OF_FLOAT = tuple(
+    [GS_ADAM_POSITION] * 3 + [-1] + [GS_ADAM_SCALE] * 3 + [-1] + [GS_ADAM_ROTATION] * 4 + [GS_ADAM_SH_DC] * 3 + [GS_ADAM_OPACITY]
+    + ([GS_ADAM_SH_REST] * 3 + [-1]) * 15 + [-1] * 8)
+
 
 class GsConfig(C.Structure):
     _fields_ = [
@@ -97,6 +105,20 @@ class GsSceneInfo(C.Structure):
     ]
 
 
+class GsAdamParams(C.Structure):
+    """gs_adam_params: one Adam step of gs_adam_rows_device (filled by gs_default_adam_params)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("step", C.c_uint32),
+        ("beta1", C.c_float),
+        ("beta2", C.c_float),
+        ("eps", C.c_float),
+        ("lr", C.c_float * GS_ADAM_GROUPS),
+        ("lo", C.c_float * GS_ADAM_GROUPS),
+        ("hi", C.c_float * GS_ADAM_GROUPS),
+    ]
+
+
 class GsHostTimings(C.Structure):
     """gs_host_timings: the RECORD_CPU_TIMES figures (Renderer.cpp:399-456)."""
     _fields_ = [
@@ -121,6 +143,7 @@ EXPORTS = [
     "gs_backward", "gs_backward_device", "gs_upload_gaussians_device",
     "gs_visible_count", "gs_backward_visible", "gs_backward_visible_device",
     "gs_photometric_loss", "gs_photometric_loss_device",
+    "gs_default_adam_params", "gs_adam_rows_device", "gs_upload_rows_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -250,6 +273,10 @@ def lib() -> C.CDLL:
     L.gs_backward_visible_device.argtypes = [ctxp, vp, vp, vp, vp, u32, vp]
     L.gs_photometric_loss.argtypes = [ctxp, vp, vp, f32, vp, vp, vp]
     L.gs_photometric_loss_device.argtypes = [ctxp, vp, vp, f32, vp, vp, vp]
+    L.gs_default_adam_params.argtypes = [C.POINTER(GsAdamParams)]
+    L.gs_default_adam_params.restype = None
+    L.gs_adam_rows_device.argtypes = [ctxp, vp, vp, vp, u32, vp, vp, vp, u32, C.POINTER(GsAdamParams)]
+    L.gs_upload_rows_device.argtypes = [ctxp, vp, u32, vp, vp, u32]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -19,6 +19,12 @@ not take sparse gradients, so a non-leaf input receives the same rows scattered 
 photometric_loss is the library's fused L1 + D-SSIM (gs_photometric_loss_device): the three numbers and dloss/d(rgba) come
 from one call on the device, and backward hands that gradient, times the upstream scalar, to the frame.
 
+    opt = VisibleAdam(records, renderer=r)                                      # records: a plain tensor, updated in place
+    numbers = opt.step(view, proj, cam_pos, sh_mode, target)                    # {loss, L1, DSSIM}, nothing waited for
+
+VisibleAdam is the whole training step on the device: upload of the rows the last step moved, frame, loss, visible-row
+gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one stream without a host wait.
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -29,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager
+from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager, default_adam_params
 
 
 def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
@@ -151,3 +157,79 @@ def photometric_loss(rgba: torch.Tensor, target: torch.Tensor, lambda_dssim: flo
         if not t.is_cuda:
             raise ValueError(f"{name} must be on the GPU")
     return _Loss.apply(rgba.contiguous(), target.detach().contiguous(), renderer, float(lambda_dssim), bg)
+
+
+class VisibleAdam:
+    """Adam on the splats each frame rasterises, with the whole step on the device.
+
+    records: float32 [N, 84] on the renderer's GPU, a plain tensor (no autograd); it is updated in place and stays the
+    caller's.  The optimiser holds the moments m and v (zeros, like records), the ids / gradient rows / count a step lists
+    (max_rows of them, N by default), the image-gradient buffer and the step counter; the library keeps no optimiser state.
+    params: default_adam_params()'s overrides (lr, lo, hi per GS_ADAM_* group, beta1, beta2, eps).
+
+    step() enqueues, on self.stream (a torch stream handed to the renderer with gs_set_stream): the upload of the records
+    -- in full the first time, afterwards of the rows the previous step moved (gs_upload_rows_device reads the ids and
+    count that step left) --, the frame, gs_photometric_loss_device on the context's own RGBA32F buffer,
+    gs_backward_visible_device and gs_adam_rows_device.  It waits for nothing: self.stream is made to follow the caller's
+    current stream (so a target or records written there are seen), and the returned tensor {loss, L1, DSSIM} belongs to
+    self.stream -- synchronise it, or make another stream wait for it, before the numbers are read.  Rows past max_rows
+    are not updated (self.count holds |V| of the last step: compare after a synchronise).
+
+    Between steps the caller may change records only in rows the last step listed, or must call reset_upload() so that
+    the next step uploads everything."""
+
+    def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, **params):
+        if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
+            raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
+        if not records.is_cuda or not records.is_contiguous() or records.requires_grad:
+            raise ValueError("records must be a contiguous tensor on the GPU that does not require grad")
+        self.records, self.renderer = records, renderer
+        self.params = default_adam_params(**params)
+        dev, n = records.device, records.shape[0]
+        self.max_rows = n if max_rows is None else int(max_rows)
+        self.m, self.v = torch.zeros_like(records), torch.zeros_like(records)
+        self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)        # int32 storage for the library's uint32
+        self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.grad = torch.zeros(renderer.height, renderer.width, 4, dtype=torch.float32, device=dev)
+        self.t = 0
+        self._full_upload = True
+        self.stream = torch.cuda.Stream(device=dev)
+        torch.cuda.synchronize(dev)                       # the zeros above; gs_set_stream waits for the context's stream itself
+        renderer.setStream(self.stream.cuda_stream)
+
+    def reset_upload(self):
+        """The next step uploads every record (after the caller changed rows the last step did not list)."""
+        self._full_upload = True
+
+    def step(self, view, proj, cam_pos, sh_mode: int, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None) -> torch.Tensor:
+        r, n = self.renderer, self.records.shape[0]
+        if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
+            raise ValueError(f"target must be float32 {(r.height, r.width, 3)} on the GPU")
+        target = target.contiguous()
+        v = np.ascontiguousarray(view, dtype=np.float32).reshape(16)
+        p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
+        c = np.ascontiguousarray(cam_pos, dtype=np.float32).reshape(3)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
+        with torch.cuda.stream(self.stream):
+            numbers = torch.empty(3, dtype=torch.float32, device=self.records.device)
+            target.record_stream(self.stream)
+            if self._full_upload:
+                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
+                if getattr(r, "_autograd_mask", None) != _lib.GS_OUTPUT_RGBA32F:
+                    r.setOutputs(rgba32f=True)
+                    r._autograd_mask = _lib.GS_OUTPUT_RGBA32F
+                self._full_upload = False
+            else:
+                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+            r._ctx.check(_lib.lib().gs_render_device_async(r._ctx.handle, ptr(v), ptr(p), ptr(c), int(sh_mode), None))
+            r._autograd_frame = getattr(r, "_autograd_frame", 0) + 1
+            r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers.data_ptr(), self.grad.data_ptr())
+            r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
+                                    self.count.data_ptr())
+            self.t += 1
+            self.params.step = self.t
+            r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
+                             self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+        return numbers

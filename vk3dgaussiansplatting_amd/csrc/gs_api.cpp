@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <iterator>
+#include <limits>
 #include <new>
 #include <string>
 #include <vector>
@@ -686,6 +687,73 @@ int gs_upload_gaussians_device(gs_ctx* c, const void* aos336_dev, uint32_t n) {
     }
     c->n = n;
     return GS_OK;
+}
+
+int gs_upload_rows_device(gs_ctx* c, const void* aos336_dev, uint32_t n, const uint32_t* ids_dev, const uint32_t* count_dev,
+                          uint32_t max_rows) {
+    if (!c) return GS_ERR_INVALID;
+    if (max_rows && (!aos336_dev || !ids_dev || !count_dev))
+        return fail(c, GS_ERR_INVALID, "gs_upload_rows_device: null aos336_dev, ids_dev or count_dev with max_rows > 0");
+    if (n == 0) return fail(c, GS_ERR_INVALID, "gs_upload_rows_device: n is 0");
+    if (!c->shared || !c->n) return fail(c, GS_ERR_NO_SCENE, "gs_upload_rows_device: no gaussians uploaded yet");
+    if (c->n != n)
+        return fail(c, GS_ERR_INVALID, "gs_upload_rows_device: n differs from the scene's (gs_upload_gaussians_device makes a new scene)");
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the listed planes in place, then the boxes of all blocks (16 bytes per splat read): what the full in-place upload leaves
+    launch_upload_rows(static_cast<const float*>(aos336_dev), n, ids_dev, count_dev, max_rows, c->scene, c->stream);
+    launch_block_bounds(n, c->scene, c->stream);
+    c->bwd_frame = false;
+    return check_launch(c, "gs_upload_rows_device");
+}
+
+void gs_default_adam_params(gs_adam_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->step = 1;
+    p->beta1 = 0.9f; p->beta2 = 0.999f; p->eps = 1e-15f;
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
+    p->lr[GS_ADAM_POSITION] = 1.6e-4f;
+    p->lr[GS_ADAM_SCALE] = 5e-3f;     p->lo[GS_ADAM_SCALE] = 1e-7f;
+    p->lr[GS_ADAM_ROTATION] = 1e-3f;
+    p->lr[GS_ADAM_SH_DC] = 2.5e-3f;
+    p->lr[GS_ADAM_OPACITY] = 5e-2f;   p->lo[GS_ADAM_OPACITY] = 0.0f; p->hi[GS_ADAM_OPACITY] = 1.0f;
+    p->lr[GS_ADAM_SH_REST] = 1.25e-4f;
+}
+
+int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_dev, uint32_t n, const uint32_t* ids_dev,
+                        const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, const gs_adam_params* p) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_adam_rows_device: ";
+    if (max_rows && (!records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
+        return fail(c, GS_ERR_INVALID, who + "null records, m, v, ids, grad_rows or count with max_rows > 0");
+    if (!p) return fail(c, GS_ERR_INVALID, who + "null gs_adam_params");
+    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
+    if (p->struct_size != sizeof(gs_adam_params))
+        return fail(c, GS_ERR_INVALID, who + "gs_adam_params.struct_size does not match this library (call gs_default_adam_params first)");
+    if (p->step == 0) return fail(c, GS_ERR_INVALID, who + "step counts from 1");
+    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f) || !(p->beta2 >= 0.0f && p->beta2 < 1.0f))
+        return fail(c, GS_ERR_INVALID, who + "beta1 and beta2 must be in [0, 1)");
+    if (!(p->eps >= 0.0f) || !std::isfinite(p->eps)) return fail(c, GS_ERR_INVALID, who + "eps must be finite and not negative");
+    AdamStep a;
+    a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps;
+    a.c1 = 1.0f - p->beta1; a.c2 = 1.0f - p->beta2;
+    // the bias correction of step t in double, rounded once per group
+    const double t = (double)p->step;
+    const double root2 = std::sqrt(1.0 - std::pow((double)p->beta2, t)), bias1 = 1.0 - std::pow((double)p->beta1, t);
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) {
+        if (!(p->lr[g] >= 0.0f) || !std::isfinite(p->lr[g])) return fail(c, GS_ERR_INVALID, who + "lr must be finite and not negative");
+        if (!(p->lo[g] <= p->hi[g])) return fail(c, GS_ERR_INVALID, who + "lo must not exceed hi, and neither may be a NaN");
+        a.step[g] = (float)((double)p->lr[g] * root2 / bias1);
+        if (!std::isfinite(a.step[g])) return fail(c, GS_ERR_INVALID, who + "lr times the bias correction is not a finite float");
+        a.lo[g] = p->lo[g]; a.hi[g] = p->hi[g];
+    }
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_adam_rows(records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
+    return check_launch(c, "gs_adam_rows_device");
 }
 
 static hipError_t alloc_outputs(gs_ctx* c);

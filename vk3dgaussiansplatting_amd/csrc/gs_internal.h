@@ -313,6 +313,17 @@ void launch_photometric_loss(const LossBuffers& lb, const float* rgba, const flo
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,
                        const SceneBuffers& s, hipStream_t stream);
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream);
+// gs_upload_rows_device: the planes of splats ids[i], i < min(*count, max_rows), rewritten from records[ids[i]] (records: the
+// whole [n][84] array); an id >= n is skipped.  The caller rebuilds the block bounds.  max_rows > 0.
+void launch_upload_rows(const float* records, uint32_t n, const uint32_t* ids, const uint32_t* count, uint32_t max_rows,
+                        const SceneBuffers& s, hipStream_t stream);
+// gs_adam_rows_device (gs_adam.hip): what the kernel needs of gs_adam_params, the bias correction folded into step[] on the host
+struct AdamStep {
+    float beta1, beta2, c1, c2, eps;
+    float step[6], lo[6], hi[6];      // per GS_ADAM_* group
+};
+void launch_adam_rows(float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
+                      const uint32_t* count, uint32_t max_rows, const AdamStep& a, hipStream_t stream);
 void launch_stream_probe(int kind, const void* src, void* dst, size_t bytes, uint32_t blocks, hipStream_t stream);
 // helpers for the stand-alone sorter entry points
 void launch_set_sort_params(SortParams* params, uint32_t* coarse, uint32_t n, hipStream_t stream);

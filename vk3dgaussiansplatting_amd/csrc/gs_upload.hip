@@ -7,6 +7,45 @@
 
 namespace gs {
 
+// One record (rec: its 84 floats) into the planes of splat g; n = total splats (plane stride).  Called by the four waves of
+// a workgroup with part = 0..3 and lane = record: they split the 59 fields, and part 3 adds the cull bound sig2.  The one
+// place a record becomes planes: the full upload and the upload of listed rows write the same bits.
+__device__ __forceinline__ void store_record_planes(const float* rec, uint32_t part, size_t g, uint32_t n, const SceneBuffers& s) {
+    for (uint32_t fld = part; fld < 59u; fld += 4u) {
+        if (fld < 3u) s.pos[(size_t)fld * n + g] = rec[0 + fld];
+        else if (fld < 6u) s.scale[(size_t)(fld - 3u) * n + g] = rec[4 + (fld - 3u)];
+        else if (fld < 10u) s.rot[(size_t)(fld - 6u) * n + g] = rec[8 + (fld - 6u)];
+        else if (fld < 58u) {
+            const uint32_t k = fld - 10u, coeff = k / 3u, ch = k % 3u;
+            s.sh[(size_t)k * n + g] = rec[12 + coeff * 4u + ch];
+        } else s.opacity[g] = rec[12 + 3];
+    }
+    if (part == 3u) {
+        // |R|_2^2 * max(scale)^2 >= largest eigenvalue of Sigma = (R S)(R S)^T, with R as Common.glsl:17-30
+        // builds it from the (not necessarily unit) quaternion
+        const float q0 = rec[8], x = rec[9], y = rec[10], z = rec[11];
+        const float e[9] = {1.0f - 2.0f * y * y - 2.0f * z * z, 2.0f * x * y - 2.0f * q0 * z, 2.0f * x * z + 2.0f * q0 * y,
+                            2.0f * x * y + 2.0f * q0 * z, 1.0f - 2.0f * x * x - 2.0f * z * z, 2.0f * y * z - 2.0f * q0 * x,
+                            2.0f * x * z - 2.0f * q0 * y, 2.0f * y * z + 2.0f * q0 * x, 1.0f - 2.0f * x * x - 2.0f * y * y};
+        // |R|_2^2 <= min(trace, largest absolute row sum) of R R^T (Gershgorin): 1 for a unit quaternion, where the
+        // Frobenius norm alone says 3
+        float f2 = 0.0f, gersh = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) f2 += e[k] * e[k];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            float row = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) row += fabsf(e[3 * i] * e[3 * j] + e[3 * i + 1] * e[3 * j + 1] + e[3 * i + 2] * e[3 * j + 2]);
+            gersh = fmaxf(gersh, row);
+        }
+        const float r2 = (gersh < f2 ? gersh : f2) * 1.0001f;      // a NaN takes f2, NaN again: the splat is kept
+        const float s0 = fabsf(rec[4]), s1 = fabsf(rec[5]), s2 = fabsf(rec[6]);
+        const float sm = fmaxf(s0, fmaxf(s1, s2));
+        s.sig2[g] = r2 * sm * sm;
+    }
+}
+
 // chunk: [count][84] floats starting at splat `first`; n = total splats (plane stride)
 __global__ __launch_bounds__(256) void k_aos_to_soa(const float* __restrict__ chunk, uint32_t first,
                                                      uint32_t count, uint32_t n, SceneBuffers s) {
@@ -19,42 +58,32 @@ __global__ __launch_bounds__(256) void k_aos_to_soa(const float* __restrict__ ch
     __syncthreads();
     // coalesced plane writes: lane = record
     const uint32_t r = threadIdx.x & 63u, part = threadIdx.x >> 6;   // 4 waves split the 59 fields
-    if (r < nrec) {
-        const size_t g = (size_t)first + rec0 + r;
-        for (uint32_t fld = part; fld < 59u; fld += 4u) {
-            if (fld < 3u) s.pos[(size_t)fld * n + g] = tile[r][0 + fld];
-            else if (fld < 6u) s.scale[(size_t)(fld - 3u) * n + g] = tile[r][4 + (fld - 3u)];
-            else if (fld < 10u) s.rot[(size_t)(fld - 6u) * n + g] = tile[r][8 + (fld - 6u)];
-            else if (fld < 58u) {
-                const uint32_t k = fld - 10u, coeff = k / 3u, ch = k % 3u;
-                s.sh[(size_t)k * n + g] = tile[r][12 + coeff * 4u + ch];
-            } else s.opacity[g] = tile[r][12 + 3];
-        }
-        if (part == 3u) {
-            // |R|_2^2 * max(scale)^2 >= largest eigenvalue of Sigma = (R S)(R S)^T, with R as Common.glsl:17-30
-            // builds it from the (not necessarily unit) quaternion
-            const float q0 = tile[r][8], x = tile[r][9], y = tile[r][10], z = tile[r][11];
-            const float e[9] = {1.0f - 2.0f * y * y - 2.0f * z * z, 2.0f * x * y - 2.0f * q0 * z, 2.0f * x * z + 2.0f * q0 * y,
-                                2.0f * x * y + 2.0f * q0 * z, 1.0f - 2.0f * x * x - 2.0f * z * z, 2.0f * y * z - 2.0f * q0 * x,
-                                2.0f * x * z - 2.0f * q0 * y, 2.0f * y * z + 2.0f * q0 * x, 1.0f - 2.0f * x * x - 2.0f * y * y};
-            // |R|_2^2 <= min(trace, largest absolute row sum) of R R^T (Gershgorin): 1 for a unit quaternion, where the
-            // Frobenius norm alone says 3
-            float f2 = 0.0f, gersh = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) f2 += e[k] * e[k];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                float row = 0.0f;
-#pragma unroll
-                for (int j = 0; j < 3; ++j) row += fabsf(e[3 * i] * e[3 * j] + e[3 * i + 1] * e[3 * j + 1] + e[3 * i + 2] * e[3 * j + 2]);
-                gersh = fmaxf(gersh, row);
-            }
-            const float r2 = (gersh < f2 ? gersh : f2) * 1.0001f;      // a NaN takes f2, NaN again: the splat is kept
-            const float s0 = fabsf(tile[r][4]), s1 = fabsf(tile[r][5]), s2 = fabsf(tile[r][6]);
-            const float sm = fmaxf(s0, fmaxf(s1, s2));
-            s.sig2[g] = r2 * sm * sm;
-        }
+    if (r < nrec) store_record_planes(tile[r], part, (size_t)first + rec0 + r, n, s);
+}
+
+// gs_upload_rows_device: a workgroup per 64 listed rows; records = the whole [n][84] array, the fields of row ids[i] staged
+// for i below min(*count, max_rows) and ids[i] < n.  The ids ascend (gs_backward_visible* writes them so), which keeps the plane writes
+// of neighbouring lanes close.
+__global__ __launch_bounds__(256) void k_upload_rows(const float* __restrict__ records, uint32_t n,
+                                                      const uint32_t* __restrict__ ids, const uint32_t* __restrict__ count,
+                                                      uint32_t max_rows, SceneBuffers s) {
+    __shared__ float tile[64][85];
+    __shared__ uint32_t id_of[64];
+    const uint32_t listed = *count, rows = listed < max_rows ? listed : max_rows;
+    const uint32_t row0 = blockIdx.x * 64u;
+    if (row0 >= rows) return;                                    // the whole block is past the count
+    const uint32_t nrow = (rows - row0) < 64u ? (rows - row0) : 64u;
+    if (threadIdx.x < nrow) id_of[threadIdx.x] = ids[row0 + threadIdx.x];
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < nrow * 84u; k += 256u) {
+        const uint32_t g = id_of[k / 84u], col = k % 84u;
+        // the 59 fields only: the other 25 floats of a record (w of every group but 2 and 3, 76..83) are never read
+        const bool field = col < 76u && ((col & 3u) != 3u || col == 11u || col == 15u);
+        if (g < n && field) tile[k / 84u][col] = records[(size_t)g * 84u + col];
     }
+    __syncthreads();
+    const uint32_t r = threadIdx.x & 63u, part = threadIdx.x >> 6;
+    if (r < nrow && id_of[r] < n) store_record_planes(tile[r], part, (size_t)id_of[r], n, s);
 }
 
 // Per wave of the project kernel (64 consecutive splats -- neighbours in space, the arrays are in Morton order): the box
@@ -95,6 +124,12 @@ __global__ __launch_bounds__(256) void k_block_bounds(uint32_t n, SceneBuffers s
 void launch_block_bounds(uint32_t n, const SceneBuffers& s, hipStream_t stream) {
     if (n == 0) return;
     hipLaunchKernelGGL(k_block_bounds, dim3((n + 255u) / 256u), dim3(256), 0, stream, n, s);
+}
+
+void launch_upload_rows(const float* records, uint32_t n, const uint32_t* ids, const uint32_t* count, uint32_t max_rows,
+                        const SceneBuffers& s, hipStream_t stream) {
+    if (max_rows == 0) return;
+    hipLaunchKernelGGL(k_upload_rows, dim3(max_rows / 64u + (max_rows % 64u ? 1u : 0u)), dim3(256), 0, stream, records, n, ids, count, max_rows, s);
 }
 
 void launch_aos_to_soa(const float* chunk, uint32_t first, uint32_t count, uint32_t n,

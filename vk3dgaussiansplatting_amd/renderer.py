@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import GsConfig, GsHostTimings, GsSceneInfo, GsTimings
+from ._lib import GsAdamParams, GsConfig, GsHostTimings, GsSceneInfo, GsTimings
 
 FLOATS_PER_GAUSSIAN = 84
 GAUSSIAN_DTYPE = np.dtype([
@@ -262,6 +262,29 @@ def saveImage(path: str, rgba: np.ndarray):
     rc = _lib.lib().gs_write_image(os.fsencode(path), _p(img), img.shape[1], img.shape[0])
     if rc != 0:
         raise GsplatError(rc, f"gs_write_image({path!r}) failed")
+
+
+def default_adam_params(**overrides) -> GsAdamParams:
+    """gs_default_adam_params: step 1, beta1 0.9, beta2 0.999, eps 1e-15, the INRIA learning rates per GS_ADAM_* group
+    (acting on record-space values here) and the clamps scale >= 1e-7, opacity in [0, 1].  overrides: beta1, beta2, eps,
+    step as numbers; lr, lo, hi as a sequence of six or as {GS_ADAM_* group: value} for some of them."""
+    p = GsAdamParams()
+    _lib.lib().gs_default_adam_params(C.byref(p))
+    for name, value in overrides.items():
+        if name in ("lr", "lo", "hi"):
+            arr = getattr(p, name)
+            items = value.items() if isinstance(value, dict) else enumerate(value)
+            if not isinstance(value, dict) and len(value) != _lib.GS_ADAM_GROUPS:
+                raise ValueError(f"{name} needs {_lib.GS_ADAM_GROUPS} values or a dict of groups")
+            for g, x in items:
+                arr[int(g)] = float(x)
+        elif name in ("beta1", "beta2", "eps"):
+            setattr(p, name, float(value))
+        elif name == "step":
+            p.step = int(value)
+        else:
+            raise TypeError(f"default_adam_params: unknown parameter {name!r}")
+    return p
 
 
 class _Context:
@@ -672,6 +695,23 @@ class Renderer:
             self._ctx.check(_lib.lib().gs_set_resolution(self._ctx.handle, self.width, self.height))
             info = self.sceneInfo()
             self.numGaussians, self.numSortElements = info.num_gaussians, info.capacity
+
+    # -- one optimiser step on the listed rows (no reference counterpart; include/gsplat.h, gs_adam_rows_device)
+    def adamRowsDevice(self, records_ptr: int, m_ptr: int, v_ptr: int, n: int, ids_ptr: int, rows_ptr: int, count_ptr: int,
+                       max_rows: int, params: GsAdamParams):
+        """Adam on rows ids[i], i < min(count, max_rows), of the caller's records, m and v (device addresses, float32 (n, 84))
+        with the gradient rows (max_rows, 84); ids, rows and count as backwardVisibleDevice left them.  params:
+        default_adam_params(), with `step` = the number of this step, counted from 1.  Enqueued on the context's stream
+        without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_adam_rows_device(self._ctx.handle, vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(ids_ptr),
+                                                       vp(rows_ptr), vp(count_ptr), int(max_rows), C.byref(params)))
+
+    def uploadRowsDevice(self, ptr: int, n: int, ids_ptr: int, count_ptr: int, max_rows: int):
+        """uploadDevice for the listed rows alone: the planes of splats ids[i], i < min(count, max_rows), rewritten in place from
+        the records at ptr (float32 (n, 84), n = the scene's).  Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_upload_rows_device(self._ctx.handle, vp(ptr), int(n), vp(ids_ptr), vp(count_ptr), int(max_rows)))
 
     # -- Renderer.cpp:230-270
     def cleanup(self):
