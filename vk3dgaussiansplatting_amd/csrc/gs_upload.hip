@@ -29,6 +29,10 @@ __device__ __forceinline__ void store_record_planes(const float* rec, uint32_t p
                             2.0f * x * z - 2.0f * q0 * y, 2.0f * y * z + 2.0f * q0 * x, 1.0f - 2.0f * x * x - 2.0f * y * y};
         // |R|_2^2 <= min(trace, largest absolute row sum) of R R^T (Gershgorin): 1 for a unit quaternion, where the
         // Frobenius norm alone says 3
+        // the maxima keep a NaN (fmaxf would drop it): a NaN scale, or a row of R R^T that is inf - inf (an infinite
+        // quaternion component, or a finite one whose square overflows), must end in a NaN or infinite bound -- the
+        // splat's own covariance is NaN then, and the reference puts such a splat into tile 0
+        auto nan_max = [](float a, float b) { return (a > b || a != a) ? a : b; };
         float f2 = 0.0f, gersh = 0.0f;
 #pragma unroll
         for (int k = 0; k < 9; ++k) f2 += e[k] * e[k];
@@ -37,11 +41,11 @@ __device__ __forceinline__ void store_record_planes(const float* rec, uint32_t p
             float row = 0.0f;
 #pragma unroll
             for (int j = 0; j < 3; ++j) row += fabsf(e[3 * i] * e[3 * j] + e[3 * i + 1] * e[3 * j + 1] + e[3 * i + 2] * e[3 * j + 2]);
-            gersh = fmaxf(gersh, row);
+            gersh = nan_max(row, gersh);
         }
-        const float r2 = (gersh < f2 ? gersh : f2) * 1.0001f;      // a NaN takes f2, NaN again: the splat is kept
+        const float r2 = (gersh < f2 ? gersh : f2) * 1.0001f;      // a NaN takes f2, NaN or infinite: the splat is kept
         const float s0 = fabsf(rec[4]), s1 = fabsf(rec[5]), s2 = fabsf(rec[6]);
-        const float sm = fmaxf(s0, fmaxf(s1, s2));
+        const float sm = nan_max(s0, nan_max(s1, s2));
         s.sig2[g] = r2 * sm * sm;
     }
 }
