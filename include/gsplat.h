@@ -512,6 +512,75 @@ int gs_adam_rows_device(gs_ctx* ctx, float* records_dev, float* m_dev, float* v_
 int gs_upload_rows_device(gs_ctx* ctx, const void* aos336_dev, uint32_t n,
                           const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows);
 
+/* Adaptive density control (no reference counterpart): the statistics of a training step, and the new cloud -- clone where
+ * the screen gradient is large and the splat small, split where it is large, prune what is transparent or huge.  All arrays
+ * are the CALLER's, on the DEVICE; the library keeps no training state.  Callers detect both calls by their symbols
+ * (GS_API_VERSION is unchanged).
+ *
+ * gs_densify_stats_device: ids_dev / count_dev as gs_backward_visible_device left them for the CURRENT frame; for every
+ * i < min(*count_dev, max_rows), g = ids_dev[i] (an id >= n is skipped: compared, never dereferenced):
+ *   (dsx, dsy) = the splat's dL/d(screen position): its rows of the backward's scratch summed in slot order, clamped at the
+ *                list capacity -- the very bits the record gradient was chained from;
+ *   gx = dsx * 0.5f * W, gy = dsy * 0.5f * H        (NDC units: the INRIA threshold 2e-4 applies)
+ *   grad_accum[g] = grad_accum[g] + sqrtf(gx * gx + gy * gy)      (float32, not contracted)
+ *   seen[g]      += 1
+ *   radius        = ceilf(3 * sqrtf(max(lambda0, lambda1))) of the frame's 2-D covariance, the expressions of the tile extents
+ *   max_radius[g] = radius > max_radius[g] ? radius : max_radius[g]
+ * grad_accum, seen, max_radius: float / uint32 / float [n].  Ids are distinct, so there are no atomics and the result is
+ * bitwise reproducible, the same for every sorter.  Enqueued on the context's stream, no host sync; count_dev is never read
+ * by the host, the grid is sized from max_rows.  max_rows == 0: GS_OK, nothing launched.
+ * GS_ERR_INVALID (message in gs_last_error, nothing enqueued): everything gs_backward refuses, with its messages; no
+ * gs_backward* form that computed gradient rows has run on this frame ("no gs_backward* on this frame": gs_visible_count
+ * alone, a new frame, an upload, a new resolution or tile rows all leave none); a NULL pointer with max_rows > 0; an n other
+ * than the scene's. */
+int gs_densify_stats_device(gs_ctx* ctx, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows,
+                            uint32_t n, float* grad_accum, uint32_t* seen, float* max_radius);
+
+typedef struct gs_densify_params {
+    uint32_t struct_size;   /* sizeof(gs_densify_params) of the caller's header: filled by gs_default_densify_params, checked */
+    float grad_threshold;   /* 2e-4 */
+    float split_scale;      /* max scale above which a growing splat is split, not cloned (the caller's percent_dense * extent); 0.01 */
+    float prune_opacity;    /* 0.005 */
+    float prune_scale;      /* +inf = none (INRIA: 0.1 * extent) */
+    float prune_radius;     /* pixels; +inf = none */
+    float split_shrink;     /* 1.6 = 0.8 * 2 */
+    uint64_t seed;          /* 0 */
+} gs_densify_params;
+void gs_default_densify_params(gs_densify_params* p);
+/* The new cloud from records / m / v (float[n][84]) and the statistics (float / uint32 / float [n]).  Per input splat g, in
+ * float32, every comparison exactly as written (a NaN compares false), max(a, b) = a > b ? a : b:
+ *   smax   = max(max(s0, s1), s2) over floats 4..6; op = float 15
+ *   pruned = op < prune_opacity || smax > prune_scale || max_radius[g] > prune_radius
+ *   mean   = seen[g] ? grad_accum[g] / (float)seen[g] : 0
+ *   grow   = !pruned && mean >= grad_threshold;  split = grow && smax > split_scale;  clone = grow && !split
+ * g has k(g) outputs -- 0 pruned, 2 growing, else 1 -- at rows [o(g), o(g) + k(g)) of records_out / m_out / v_out, o = the
+ * exclusive scan of k: the output is stable, and children sit next to their parent (the storage order keeps its locality).
+ *   kept  : record, m and v rows copied bit for bit.
+ *   clone : output 0 as kept; output 1 the same record with zero m and v rows.
+ *   split : two children with zero m and v rows; all 84 floats of the parent except
+ *           scale_child[k] = s[k] / split_shrink                                           (floats 4..6)
+ *           pos_child[i]   = pos[i] + off[i]                                               (floats 0..2)
+ *           off[i] = ((R[i][0] * s[0]) * z[0] + (R[i][1] * s[1]) * z[1]) + (R[i][2] * s[2]) * z[2]
+ *           with R = the rotation matrix of the record's own (unnormalised) rot as the frame builds it, R[row][col], i.e. a
+ *           draw from the gaussian the frame rasterises, Sigma = M M^T, M = R diag(s).
+ * The normals z[axis] of child c are counter-based -- a function of (seed, g, c, axis) alone, uint32 arithmetic:
+ *   mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   h = mix(mix(g ^ (uint32)seed) + (uint32)(seed >> 32));   w(c, a, j) = mix(h + (c * 6 + a * 2 + j + 1) * 0x9E3779B9)
+ *   u1 = ((w(c, a, 0) >> 8) + 1) * 2^-24  in (0, 1];   u2 = (w(c, a, 1) >> 8) * 2^-24
+ *   z = sqrtf(-2 * logf(u1)) * cosf(6.2831855f * u2)        (the device's logf and cosf: |z| <= 5.77)
+ * counts_out[4] (DEVICE): [0] the number of outputs, not truncated; [1], [2], [3] the cloned, split and pruned input splats.
+ * Rows with index >= max_out are not written and nothing past the written rows is touched; max_out >= 2 n always fits.
+ * m, v, m_out and v_out may be NULL all together, and only all together (records alone).  Bitwise reproducible; enqueued on
+ * the context's stream, no host sync; needs no scene and no resolution.  Scratch: 4 bytes per splat + 20 bytes per 256
+ * splats, the context's, grown on demand and freed by gs_destroy.
+ * GS_ERR_INVALID (message, nothing enqueued): a NULL required pointer (records_out only with max_out > 0), n == 0 or
+ * n >= 2^31, a wrong struct_size, a NaN grad_threshold, split_shrink that fails split_shrink > 0, an output array that shares
+ * bytes with an input or another output, a partly NULL moment quadruple. */
+int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const float* v, uint32_t n,
+                      const float* grad_accum, const uint32_t* seen, const float* max_radius,
+                      const gs_densify_params* p,
+                      float* records_out, float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out);
+
 /* Photometric loss of a frame against a photograph (no reference counterpart): the number a 3DGS optimisation minimises,
  *   loss = (1 - lambda) * L1 + lambda * DSSIM,
  * and its gradient with respect to the frame, in the layout gs_backward* takes.  H and W are the context's resolution.

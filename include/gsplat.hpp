@@ -214,6 +214,30 @@ public:
         return rc;
     }
 
+    // Adaptive density control (gsplat.h, gs_densify_stats_device and gs_densify_device): the statistics of the step just
+    // differentiated into the caller's DEVICE arrays [n], and the new cloud -- clones and split children beside their
+    // parents -- into records_out / m_out / v_out [max_out][84]; counts_out[4] (device) = outputs, cloned, split, pruned.
+    // Both are enqueued on the context's stream without waiting.
+    static gs_densify_params defaultDensifyParams() {
+        gs_densify_params p;
+        gs_default_densify_params(&p);
+        return p;
+    }
+    int densifyStats(const uint32_t* ids, const uint32_t* count, uint32_t max_rows, uint32_t n, float* grad_accum,
+                     uint32_t* seen, float* max_radius) {
+        const int rc = gs_densify_stats_device(ctx_, ids, count, max_rows, n, grad_accum, seen, max_radius);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int densify(const float* records, const float* m, const float* v, uint32_t n, const float* grad_accum, const uint32_t* seen,
+                const float* max_radius, const gs_densify_params& params, float* records_out, float* m_out, float* v_out,
+                uint32_t max_out, uint32_t* counts_out) {
+        const int rc = gs_densify_device(ctx_, records, m, v, n, grad_accum, seen, max_radius, &params, records_out, m_out, v_out,
+                                         max_out, counts_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

@@ -119,6 +119,20 @@ class GsAdamParams(C.Structure):
     ]
 
 
+class GsDensifyParams(C.Structure):
+    """gs_densify_params: the thresholds of gs_densify_device (filled by gs_default_densify_params)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("grad_threshold", C.c_float),
+        ("split_scale", C.c_float),
+        ("prune_opacity", C.c_float),
+        ("prune_scale", C.c_float),
+        ("prune_radius", C.c_float),
+        ("split_shrink", C.c_float),
+        ("seed", C.c_uint64),
+    ]
+
+
 class GsHostTimings(C.Structure):
     """gs_host_timings: the RECORD_CPU_TIMES figures (Renderer.cpp:399-456)."""
     _fields_ = [
@@ -144,6 +158,7 @@ EXPORTS = [
     "gs_visible_count", "gs_backward_visible", "gs_backward_visible_device",
     "gs_photometric_loss", "gs_photometric_loss_device",
     "gs_default_adam_params", "gs_adam_rows_device", "gs_upload_rows_device",
+    "gs_densify_stats_device", "gs_default_densify_params", "gs_densify_device",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -277,9 +292,28 @@ def lib() -> C.CDLL:
     L.gs_default_adam_params.restype = None
     L.gs_adam_rows_device.argtypes = [ctxp, vp, vp, vp, u32, vp, vp, vp, u32, C.POINTER(GsAdamParams)]
     L.gs_upload_rows_device.argtypes = [ctxp, vp, u32, vp, vp, u32]
+    L.gs_densify_stats_device.argtypes = [ctxp, vp, vp, u32, u32, vp, vp, vp]
+    L.gs_default_densify_params.argtypes = [C.POINTER(GsDensifyParams)]
+    L.gs_default_densify_params.restype = None
+    L.gs_densify_device.argtypes = [ctxp, vp, vp, vp, u32, vp, vp, vp, C.POINTER(GsDensifyParams), vp, vp, vp, u32, vp]
     _lib = L
     _check_hip_runtime(L)
     return L
+
+
+def default_densify_params(**overrides) -> GsDensifyParams:
+    """gs_default_densify_params: grad_threshold 2e-4, split_scale 0.01, prune_opacity 0.005, prune_scale and prune_radius
+    +inf (none), split_shrink 1.6, seed 0.  overrides: any of those fields by name."""
+    p = GsDensifyParams()
+    lib().gs_default_densify_params(C.byref(p))
+    for name, value in overrides.items():
+        if name == "seed":
+            p.seed = int(value)
+        elif name != "struct_size" and any(name == f[0] for f in GsDensifyParams._fields_):
+            setattr(p, name, float(value))
+        else:
+            raise TypeError(f"default_densify_params: unknown parameter {name!r}")
+    return p
 
 
 def hip_runtime_path() -> str | None:

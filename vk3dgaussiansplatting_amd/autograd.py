@@ -25,6 +25,9 @@ from one call on the device, and backward hands that gradient, times the upstrea
 VisibleAdam is the whole training step on the device: upload of the rows the last step moved, frame, loss, visible-row
 gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one stream without a host wait.
 
+    opt = VisibleAdam(records, renderer=r, track_density=True)                  # + gs_densify_stats_device in every step
+    n_out, cloned, split, pruned = opt.densify(grad_threshold=2e-4)             # opt.records / m / v are the new cloud
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -176,9 +179,13 @@ class VisibleAdam:
     are not updated (self.count holds |V| of the last step: compare after a synchronise).
 
     Between steps the caller may change records only in rows the last step listed, or must call reset_upload() so that
-    the next step uploads everything."""
+    the next step uploads everything.
 
-    def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, **params):
+    track_density=True: the optimiser also owns grad_accum, seen and max_radius (zeros of N), step() enqueues
+    gs_densify_stats_device right behind the backward, and densify() replaces the cloud."""
+
+    def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, track_density: bool = False,
+                 **params):
         if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
             raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
         if not records.is_cuda or not records.is_contiguous() or records.requires_grad:
@@ -187,6 +194,10 @@ class VisibleAdam:
         self.params = default_adam_params(**params)
         dev, n = records.device, records.shape[0]
         self.max_rows = n if max_rows is None else int(max_rows)
+        self._rows_follow_n = max_rows is None
+        self.track_density = bool(track_density)
+        if self.track_density:
+            self._zero_stats(n, dev)
         self.m, self.v = torch.zeros_like(records), torch.zeros_like(records)
         self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)        # int32 storage for the library's uint32
         self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
@@ -197,6 +208,44 @@ class VisibleAdam:
         self.stream = torch.cuda.Stream(device=dev)
         torch.cuda.synchronize(dev)                       # the zeros above; gs_set_stream waits for the context's stream itself
         renderer.setStream(self.stream.cuda_stream)
+
+    def _zero_stats(self, n: int, dev):
+        self.grad_accum = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.seen = torch.zeros(n, dtype=torch.int32, device=dev)                   # int32 storage for the library's uint32
+        self.max_radius = torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def densify(self, **params):
+        """Clone, split and prune by the statistics gathered since the last call (gs_densify_device, params:
+        default_densify_params()'s overrides) -> (n_out, cloned, split, pruned).  self.records, self.m and self.v become new
+        tensors of n_out rows, the children beside their parents; the statistics start again from zero; ids, rows and max_rows
+        follow the new size (a max_rows given to the constructor stays); the next step uploads the whole cloud as a new scene.
+        t and the hyper-parameters stay.  Reading the four counts is the one host wait of this rare event."""
+        if not self.track_density:
+            raise RuntimeError("VisibleAdam(track_density=True) gathers the statistics densify() goes by")
+        p = _lib.default_densify_params(**params)
+        r, dev, n = self.renderer, self.records.device, self.records.shape[0]
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            out = [torch.empty(2 * n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(3)]
+            counts = torch.zeros(4, dtype=torch.int32, device=dev)
+            r.densifyDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.grad_accum.data_ptr(),
+                            self.seen.data_ptr(), self.max_radius.data_ptr(), p, out[0].data_ptr(), out[1].data_ptr(),
+                            out[2].data_ptr(), 2 * n, counts.data_ptr())
+            n_out, cloned, split, pruned = (int(x) for x in counts.cpu().numpy().view(np.uint32))      # waits for the stream
+            if n_out == 0:
+                raise RuntimeError("densify() would prune every gaussian")
+            self.records, self.m, self.v = (t[:n_out].clone() for t in out)
+            self._zero_stats(n_out, dev)
+            if self._rows_follow_n:
+                self.max_rows = n_out
+            self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
+            self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+            self.count.zero_()
+        self.stream.synchronize()
+        # another n is another scene: the next step uploads everything and sets the resolution and the RGBA32F output again
+        self._full_upload = True
+        r._autograd_mask = None
+        return n_out, cloned, split, pruned
 
     def reset_upload(self):
         """The next step uploads every record (after the caller changed rows the last step did not list)."""
@@ -228,6 +277,9 @@ class VisibleAdam:
             r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers.data_ptr(), self.grad.data_ptr())
             r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
                                     self.count.data_ptr())
+            if self.track_density:
+                r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
+                                     self.seen.data_ptr(), self.max_radius.data_ptr())
             self.t += 1
             self.params.step = self.t
             r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),

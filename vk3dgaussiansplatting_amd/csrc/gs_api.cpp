@@ -47,7 +47,7 @@ void free_resolution(gs_ctx* c) {
     c->bwd_mem.release();
     c->bwd_vis_rows = 0;
     c->loss_mem.release();
-    c->bwd_frame = false;
+    c->bwd_frame = false; c->bwd_rows = false;
     drop_sort_graph(c);
     c->res_mem.release();
     c->sort = SortBuffers{};          // fed[1], fed[2] point into the allocation of fed[0]
@@ -233,6 +233,7 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     hipStream_t st = c->stream;
 
     c->unsorted_valid = false;
+    c->bwd_rows = false;          // from here on the rows scratch belongs to a frame that is no longer the current one
     c->num_marks = 0;
     if (tm) if (int r = mark(c, kBucketNone)) return r;
     // computeInitSortList (Subrenderer.cpp:37-170): per-frame resets, then the dispatch.  Only the
@@ -518,6 +519,7 @@ int gs_destroy(gs_ctx* c) {
     if (c->dist_comm) (void)gs_dist_destroy(c);
     free_resolution(c);
     free_scene(c);
+    c->densify_mem.release();
     destroy_events(c->marks, kMaxFrameMarks);
     destroy_events(c->scatter_ev, 32);
     destroy_events(&c->fork_ev, 1);
@@ -672,7 +674,7 @@ int gs_upload_gaussians_device(gs_ctx* c, const void* aos336_dev, uint32_t n) {
         // context that shares them renders the new values; resolution, scratch and captured graphs stay
         launch_aos_to_soa(src, 0, n, n, c->scene, c->stream);
         launch_block_bounds(n, c->scene, c->stream);
-        c->bwd_frame = false;
+        c->bwd_frame = false; c->bwd_rows = false;
         HIP_TRY(c, hipGetLastError());
         return GS_OK;
     }
@@ -703,7 +705,7 @@ int gs_upload_rows_device(gs_ctx* c, const void* aos336_dev, uint32_t n, const u
     // the listed planes in place, then the boxes of all blocks (16 bytes per splat read): what the full in-place upload leaves
     launch_upload_rows(static_cast<const float*>(aos336_dev), n, ids_dev, count_dev, max_rows, c->scene, c->stream);
     launch_block_bounds(n, c->scene, c->stream);
-    c->bwd_frame = false;
+    c->bwd_frame = false; c->bwd_rows = false;
     return check_launch(c, "gs_upload_rows_device");
 }
 
@@ -903,6 +905,7 @@ static int backward_prepare(gs_ctx* c, const char* who) {
         if (e != hipSuccess) {
             mem.release();
             c->bwd_vis_rows = 0;
+            c->bwd_rows = false;
             return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
         }
     }
@@ -941,6 +944,7 @@ int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_d
     if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward_device: null gradient pointer");
     if (int r = backward_prepare(c, "gs_backward_device")) return r;
     launch_backward(backward_frame(c), grad_rgba32f, grad_depth, grad_records, c->stream);
+    c->bwd_rows = true;
     return check_launch(c, "gs_backward_device");
 }
 
@@ -951,6 +955,7 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     if (!c->bwd_host_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
     if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
     launch_backward(backward_frame(c), grad_rgba32f, grad_depth, c->bwd_host_out, c->stream);
+    c->bwd_rows = true;
     if (int r = check_launch(c, "gs_backward")) return r;
     HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1046,7 +1051,10 @@ int gs_backward_visible_device(gs_ctx* c, const float* grad_rgba32f, const float
         return r;
     const BackwardFrame f = backward_frame(c);
     launch_backward_visible_scan(f, ids_out, max_rows, count_out, c->stream);
-    if (max_rows) launch_backward_visible_rows(f, grad_rgba32f, grad_depth, max_rows, grad_rows_out, c->stream);
+    if (max_rows) {
+        launch_backward_visible_rows(f, grad_rgba32f, grad_depth, max_rows, grad_rows_out, c->stream);
+        c->bwd_rows = true;
+    }
     return check_launch(c, "gs_backward_visible_device");
 }
 
@@ -1067,6 +1075,7 @@ int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_
         }
         if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
         launch_backward_visible_rows(backward_frame(c), grad_rgba32f, grad_depth, k, c->bwd_vis_out, c->stream);
+        c->bwd_rows = true;
         if (int r = check_launch(c, "gs_backward_visible")) return r;
         HIP_TRY(c, hipMemcpyAsync(ids_out, c->bwd.vis_ids, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(grad_rows_out, c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
@@ -1076,13 +1085,109 @@ int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_
     return count > max_rows && !count_only ? GS_WARN_OVERFLOW : GS_OK;
 }
 
+int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,
+                            float* grad_accum, uint32_t* seen, float* max_radius) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_densify_stats_device";
+    if (max_rows && (!ids_dev || !count_dev || !grad_accum || !seen || !max_radius))
+        return fail(c, GS_ERR_INVALID, who + ": null ids, count, grad_accum, seen or max_radius with max_rows > 0");
+    if (int r = backward_prepare(c, who.c_str())) return r;
+    if (!c->bwd_rows) return fail(c, GS_ERR_INVALID, who + ": no gs_backward* on this frame");
+    if (n != c->n) return fail(c, GS_ERR_INVALID, who + ": n differs from the scene's");
+    if (!max_rows) return GS_OK;
+    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.offsets, c->bwd.rows,
+                             c->scratch.raster, c->last_fp.capacity, c->last_fp.width, c->last_fp.height,
+                             grad_accum, seen, max_radius};
+    launch_densify_stats(a, c->stream);
+    return check_launch(c, who.c_str());
+}
+
+void gs_default_densify_params(gs_densify_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->grad_threshold = 2e-4f;
+    p->split_scale = 0.01f;
+    p->prune_opacity = 0.005f;
+    p->prune_scale = std::numeric_limits<float>::infinity();
+    p->prune_radius = std::numeric_limits<float>::infinity();
+    p->split_shrink = 1.6f;
+    p->seed = 0;
+}
+
+// the scratch of gs_densify_device for n splats, kept from call to call and grown when a larger cloud comes
+static int densify_scratch(gs_ctx* c, uint32_t n, const std::string& who) {
+    if (c->densify_cap >= n) return GS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
+    DeviceOwner& mem = c->densify_mem;
+    mem.release();
+    c->densify_cap = 0;
+    const size_t blocks = backward_blocks(n);
+    hipError_t e = mem.alloc(c->densify_offsets, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(c->densify_block_sums, 4 * blocks * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(c->densify_block_offsets, blocks * sizeof(uint32_t));
+    if (e != hipSuccess) {
+        mem.release();
+        return fail(c, GS_ERR_HIP, who + hipGetErrorString(e));
+    }
+    c->densify_cap = n;
+    return GS_OK;
+}
+
+int gs_densify_device(gs_ctx* c, const float* records, const float* m, const float* v, uint32_t n, const float* grad_accum,
+                      const uint32_t* seen, const float* max_radius, const gs_densify_params* p, float* records_out,
+                      float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_densify_device: ";
+    if (!records || !grad_accum || !seen || !max_radius || !counts_out)
+        return fail(c, GS_ERR_INVALID, who + "null records, grad_accum, seen, max_radius or counts_out");
+    if (max_out && !records_out) return fail(c, GS_ERR_INVALID, who + "null records_out with max_out > 0");
+    if (!p) return fail(c, GS_ERR_INVALID, who + "null gs_densify_params");
+    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
+    if (n >= 0x80000000u) return fail(c, GS_ERR_INVALID, who + "n must be below 2^31 (the outputs are counted in 32 bits)");
+    if (p->struct_size != sizeof(gs_densify_params))
+        return fail(c, GS_ERR_INVALID, who + "gs_densify_params.struct_size does not match this library (call gs_default_densify_params first)");
+    if (p->grad_threshold != p->grad_threshold) return fail(c, GS_ERR_INVALID, who + "grad_threshold is a NaN");
+    if (!(p->split_shrink > 0.0f)) return fail(c, GS_ERR_INVALID, who + "split_shrink must be greater than 0");
+    const bool moments = m || v || m_out || v_out;
+    if (moments && !(m && v && (!max_out || (m_out && v_out))))
+        return fail(c, GS_ERR_INVALID, who + "m, v, m_out and v_out must be given all together or not at all");
+    // no output may share bytes with an input, or with another output
+    struct Span { const void* at; size_t bytes; };
+    const size_t in_bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES, out_bytes = (size_t)max_out * GS_GAUSSIAN_RECORD_BYTES;
+    const Span ins[] = {{records, in_bytes}, {m, in_bytes}, {v, in_bytes}, {grad_accum, (size_t)n * 4}, {seen, (size_t)n * 4},
+                        {max_radius, (size_t)n * 4}};
+    const Span outs[] = {{records_out, out_bytes}, {m_out, out_bytes}, {v_out, out_bytes}, {counts_out, 16}};
+    auto overlap = [](const Span& a, const Span& b) {
+        const uintptr_t a0 = (uintptr_t)a.at, b0 = (uintptr_t)b.at;
+        return a.at && b.at && a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+    };
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlap(o, i)) return fail(c, GS_ERR_INVALID, who + "an output array aliases an input");
+    for (size_t o = 0; o < std::size(outs); ++o)
+        for (size_t k = o + 1; k < std::size(outs); ++k)
+            if (overlap(outs[o], outs[k])) return fail(c, GS_ERR_INVALID, who + "two output arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, who)) return r;
+    DensifyArgs a{};
+    a.records = records; a.m = m; a.v = v; a.n = n;
+    a.grad_accum = grad_accum; a.seen = seen; a.max_radius = max_radius;
+    a.rule = DensifyRule{p->grad_threshold, p->split_scale, p->prune_opacity, p->prune_scale, p->prune_radius};
+    a.split_shrink = p->split_shrink; a.seed = p->seed;
+    a.records_out = records_out; a.m_out = m_out; a.v_out = v_out; a.max_out = max_out;
+    a.offsets = c->densify_offsets; a.block_sums = c->densify_block_sums; a.block_offsets = c->densify_block_offsets;
+    launch_densify(a, counts_out, c->stream);
+    return check_launch(c, "gs_densify_device");
+}
+
 static int apply_tile_rows(gs_ctx* c, uint32_t row_begin, uint32_t row_end, uint32_t stride, uint32_t phase,
                            bool compact_out) {
     c->row_begin = row_begin; c->row_end = row_end; c->row_stride = stride;
     c->first_row = row_begin + phase;
     c->rows_owned = c->first_row < row_end ? (row_end - c->first_row + stride - 1u) / stride : 0u;
     c->compact_out = compact_out;
-    c->bwd_frame = false;
+    c->bwd_frame = false; c->bwd_rows = false;
     if (c->elems_note) {           // another band: another list length (GS_COUNT_AUTO learns it from the next frame)
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the old one
         *(volatile uint32_t*)c->elems_note = 0u;
@@ -1167,7 +1272,7 @@ int gs_debug_init_sort_list(gs_ctx* c, const float view[16], const float proj[16
     FrameParams fp = make_frame_params(c, view, proj, cam_pos, sh_mode);
     fp.parity = (c->emit_parity ^= 1u);
     c->last_fp = fp;
-    c->bwd_frame = false;
+    c->bwd_frame = false; c->bwd_rows = false;
     launch_project(fp, c->scene, c->scratch, c->stream);
     launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, c->stream);
     launch_emit(fp, c->scratch, c->sort, c->stream);

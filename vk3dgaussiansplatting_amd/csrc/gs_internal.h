@@ -324,6 +324,41 @@ struct AdamStep {
 };
 void launch_adam_rows(float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
                       const uint32_t* count, uint32_t max_rows, const AdamStep& a, hipStream_t stream);
+// gs_densify_stats_device (gs_densify.hip): the listed ids of the frame, what its backward left, and the caller's arrays
+struct DensifyStatsArgs {
+    const uint32_t* ids;
+    const uint32_t* count;
+    uint32_t max_rows, n;
+    const uint32_t* touched;          // SplatScratch::tiles_touched
+    const uint32_t* offsets;          // BackwardBuffers::offsets
+    const float* rows;                // BackwardBuffers::rows
+    const SplatRaster* raster;
+    uint32_t capacity, width, height;
+    float* grad_accum;
+    uint32_t* seen;
+    float* max_radius;
+};
+void launch_densify_stats(const DensifyStatsArgs& a, hipStream_t stream);
+// gs_densify_device: the thresholds of gs_densify_params, the caller's arrays and the context's scratch
+struct DensifyRule {
+    float grad_threshold, split_scale, prune_opacity, prune_scale, prune_radius;
+};
+struct DensifyArgs {
+    const float *records, *m, *v;     // m, v, m_out, v_out: all null or none
+    uint32_t n;
+    const float* grad_accum;
+    const uint32_t* seen;
+    const float* max_radius;
+    DensifyRule rule;
+    float split_shrink;
+    uint64_t seed;
+    float *records_out, *m_out, *v_out;
+    uint32_t max_out;
+    uint32_t* offsets;                // [n]  o(g): index of the first output of g
+    uint32_t* block_sums;             // [4][ceil(n / 256)]  outputs, cloned, split, pruned per block
+    uint32_t* block_offsets;          // [ceil(n / 256)]
+};
+void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stream);
 void launch_stream_probe(int kind, const void* src, void* dst, size_t bytes, uint32_t blocks, hipStream_t stream);
 // helpers for the stand-alone sorter entry points
 void launch_set_sort_params(SortParams* params, uint32_t* coarse, uint32_t n, hipStream_t stream);

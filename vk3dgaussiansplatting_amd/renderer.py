@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import GsAdamParams, GsConfig, GsHostTimings, GsSceneInfo, GsTimings
+from ._lib import GsAdamParams, GsConfig, GsDensifyParams, GsHostTimings, GsSceneInfo, GsTimings
 
 FLOATS_PER_GAUSSIAN = 84
 GAUSSIAN_DTYPE = np.dtype([
@@ -712,6 +712,29 @@ class Renderer:
         the records at ptr (float32 (n, 84), n = the scene's).  Enqueued on the context's stream without waiting."""
         vp = lambda a: C.c_void_p(a) if a else None
         self._ctx.check(_lib.lib().gs_upload_rows_device(self._ctx.handle, vp(ptr), int(n), vp(ids_ptr), vp(count_ptr), int(max_rows)))
+
+    # -- adaptive density control (no reference counterpart; include/gsplat.h, gs_densify_stats_device / gs_densify_device)
+    def densifyStatsDevice(self, ids_ptr: int, count_ptr: int, max_rows: int, n: int, grad_accum_ptr: int, seen_ptr: int,
+                           max_radius_ptr: int):
+        """The statistics of the step just differentiated, into the caller's device arrays (float32, uint32, float32 of n):
+        for ids[i], i < min(count, max_rows), as backwardVisibleDevice left them for this frame, grad_accum += the norm of
+        the screen-position gradient in NDC units, seen += 1, max_radius = max(itself, the screen radius in pixels).
+        Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_densify_stats_device(self._ctx.handle, vp(ids_ptr), vp(count_ptr), int(max_rows), int(n),
+                                                           vp(grad_accum_ptr), vp(seen_ptr), vp(max_radius_ptr)))
+
+    def densifyDevice(self, records_ptr: int, m_ptr: int | None, v_ptr: int | None, n: int, grad_accum_ptr: int, seen_ptr: int,
+                      max_radius_ptr: int, params: GsDensifyParams, records_out_ptr: int, m_out_ptr: int | None,
+                      v_out_ptr: int | None, max_out: int, counts_ptr: int):
+        """The new cloud (clone, split, prune: gs_densify_device) from records / m / v (n, 84) and the statistics into
+        records_out / m_out / v_out (max_out, 84), the children beside their parents; counts (4 uint32 on the device) =
+        outputs (not truncated), cloned, split, pruned.  m, v, m_out and v_out: all given or all None.  params:
+        default_densify_params().  Enqueued on the context's stream without waiting; needs no scene."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_densify_device(
+            self._ctx.handle, vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(grad_accum_ptr), vp(seen_ptr), vp(max_radius_ptr),
+            C.byref(params), vp(records_out_ptr), vp(m_out_ptr), vp(v_out_ptr), int(max_out), vp(counts_ptr)))
 
     # -- Renderer.cpp:230-270
     def cleanup(self):
