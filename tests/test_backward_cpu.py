@@ -452,7 +452,7 @@ def sampled_reference_gradient(tmp_dir, p, aos, stage1, ids, ranges, tiles, w_rg
 def padded_cloud(aos, n, seed, filler):
     """The records `aos` scattered, order preserved, over a cloud of n records whose other records emit nothing (filler
     'behind': behind the origin camera; 'outside': in front of it, far outside the +-1.3 NDC cull).  Returns (cloud, the
-    ascending positions of the live records).  k_bwd_scan_blocks gives each of its 1024 threads per = ceil(ceil(n / 256)
+    ascending positions of the live records).  k_splat_scan_blocks gives each of its 1024 threads per = ceil(ceil(n / 256)
     / 1024) consecutive 256-splat blocks: live records sit at 0 and n - 1 and on both sides of the 256 * per boundaries
     of threads 1, 63, 64 (the first of the second wave), 65, 512 and the last thread with data, the others at seeded
     positions."""

@@ -6,7 +6,7 @@ the last column, the longest / median / a short / the shortest list, an empty ti
 depends on the lists of those tiles only and the reference is evaluated on the frame's own full-size sorted list
 restricted to them (sampled_reference_gradient; test_sampled_reference_equals_the_full_one shows it equals the full
 reference).  Every splat outside the union of those lists must get exactly zero.  What this reaches that the small
-scenes of test_backward_gpu.py do not: k_bwd_scan_blocks with several blocks per thread, offsets saturated at 2^32 - 1,
+scenes of test_backward_gpu.py do not: k_splat_scan_blocks with several blocks per thread, offsets saturated at 2^32 - 1,
 slots up to 2^24 / 2^26, tile lists of up to 24 063 entries (376 batches of k_bwd_blend), boxes of thousands of rows in
 k_bwd_rowsum_chain, the half tile row of 1080 lines, the 4K grid, a grid of more than 65 535 tiles and the tiles_touched /
 extents the splat-first sorters leave.  The tolerance is compare_with_reference's, unchanged.
@@ -135,7 +135,7 @@ def test_by_value_at_full_size(oracle_mod, tmp_path, name, sh_mode):
 @pytest.mark.parametrize("filler", ["behind", "outside"])
 @pytest.mark.parametrize("n", [262_144, 262_145, 524_545, 1_048_577])
 def test_compaction_invariance(filler, n):
-    """Slot offsets across the thread boundaries of k_bwd_scan_blocks: the 6000 splats of the ragged scene (compared
+    """Slot offsets across the thread boundaries of k_splat_scan_blocks: the 6000 splats of the ragged scene (compared
     with the float64 reference in test_backward_gpu.py) scattered, order preserved, over n records whose others emit
     nothing (padded_cloud; n = 262 144: 1024 blocks, one per thread; 262 145: two; 524 545: three, the last block
     partial; 1 048 577: five) with live splats at 0, n - 1 and on both sides of thread and wave boundaries.  The sort is

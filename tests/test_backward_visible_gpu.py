@@ -161,7 +161,7 @@ def test_truncated_list(oracle_mod):
 @pytest.mark.parametrize("n", [511, 512, 513, 262_145])
 def test_padded_cloud(oracle_mod, filler, n):
     """small_scene scattered, order preserved, over n records whose others emit nothing, with live records at 0, n - 1 and
-    on both sides of the 256-splat block boundaries (n = 262 145: of the two-block spans of k_bwd_scan_blocks<true>'
+    on both sides of the 256-splat block boundaries (n = 262 145: of the two-block spans of k_splat_scan_blocks<BwdSource<true>>'
     threads): ids = the positions of the base cloud's visible splats, rows bit-equal to the unpadded scene's."""
     aos, w, h = small_scene()
     ids0, rows0, _ = small_answer()

@@ -385,10 +385,13 @@ def assert_equals_ref(got, ref, n, max_out, moments=True):
     return err
 
 
-@pytest.mark.parametrize("n", [1, 255, 256, 257, 70_000])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 70_000, 262_144, 262_145])
 @pytest.mark.parametrize("name", list(VARIANTS))
 def test_densify_against_the_restatement(bare, name, n):
-    """The designed statistics array tiled over n records (70 000: 274 blocks, two per thread of the one-workgroup scan),
+    """The designed statistics array tiled over n records -- 1, 255, 256: one block of 256 splats, part and full; 257: two blocks;
+    70 000: 274 blocks, one for each of the first 274 of the 1024 threads of the one-workgroup scan, the other threads idle;
+    262 144: 1024 blocks, one per thread, none idle; 262 145: 1025 blocks, so two per thread, and the upper half of the threads
+    own nothing --
     as designed and with parameters that keep, prune or split every splat: the four counts, every kept and cloned record,
     the m and v rows (copies and zeros), the children's scales and every float of theirs but the position bit for bit, the
     order stable, the sentinel rows behind the outputs intact, the inputs unchanged.  Child positions within

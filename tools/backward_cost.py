@@ -1,11 +1,12 @@
 """What a backward pass (gs_backward_device, include/gsplat.h) costs against the forward frame: the forward's total_ms
 (gs_get_timings, hipEvents) and the backward's host-measured time (enqueue + gs_synchronize), medians of --iters runs after
 3 warm-up runs; then the same backward again under `rocprofv3 --kernel-trace --stats` (a child process) for its split into
-the blend backward (k_bwd_blend, with the three small slot-offset kernels before it) and the row sum + chain
+the blend backward (k_bwd_blend, with the three small kernels of the per-splat scan before it) and the row sum + chain
 (k_bwd_rowsum_chain).  The visible form (gs_backward_visible_device with max_rows = |V|) is timed in the same window, dense
 and visible iterations alternating in one process so that both see the same neighbours; it runs the <true> instantiations
 of the same kernels, which the trace tells from the dense <false> ones by the template argument in the kernel name
-(k_bwd_blend is one kernel for both).  One JSON line per config.
+(k_splat_offsets<gs::BwdSource<true>>; k_bwd_blend is one kernel for both).  A trace in which a part of the split matches
+no kernel is an error, not a zero.  One JSON line per config.
 
     python tools/backward_cost.py [C Chard ...] [--iters 20]"""
 import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile, time
@@ -103,11 +104,16 @@ for name in a.configs:
             us = {}
             for row in csv.DictReader(open(files[0])):
                 us[row["Name"]] = float(row["AverageNs"]) / 1e3
-            # "void gs::k_bwd_offsets<true>(unsigned int const*, ...)" -> "k_bwd_offsets<true>": the template argument tells the
-            # dense instantiation from the visible one
+            # "void gs::k_splat_offsets<gs::BwdSource<true> >(gs::BwdSource<true>, ...)" -> "k_splat_offsets<gs::BwdSource<true>>":
+            # the template argument tells the dense instantiation from the visible one
             kname = lambda k: re.sub(r"^(void )?(gs::)?", "", k).split("(")[0].replace(" ", "")
-            ms = lambda key: sum(v for k, v in us.items() if kname(k) == key) / 1e3
-            scan = lambda vis: sum(ms(f"{k}<{vis}>") for k in ("k_bwd_block_sums", "k_bwd_scan_blocks", "k_bwd_offsets"))
+
+            def ms(key):
+                hits = [v for k, v in us.items() if kname(k) == key]
+                if not hits:
+                    raise SystemExit(f"backward_cost: no kernel named {key} in the trace; it has {sorted(map(kname, us))}")
+                return sum(hits) / 1e3
+            scan = lambda vis: sum(ms(f"{k}<gs::BwdSource<{vis}>>") for k in ("k_splat_block_sums", "k_splat_scan_blocks", "k_splat_offsets"))
             split = {"blend_backward_ms": round(ms("k_bwd_blend") + scan("false"), 4),
                      "rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<false>"), 4),
                      "slot_offsets_ms": round(scan("false"), 4), "visible_scan_ms": round(scan("true"), 4),

@@ -10,8 +10,6 @@ namespace gs {
 
 namespace {
 
-constexpr uint32_t kAdamQuads = 19;   // a record is 21 groups of four floats; groups 0..18 hold the 59 fields
-
 __device__ __forceinline__ float pick(const float (&t)[6], uint32_t g) {
     return g == 0u ? t[0] : g == 1u ? t[1] : g == 2u ? t[2] : g == 3u ? t[3] : g == 4u ? t[4] : t[5];
 }
@@ -37,16 +35,16 @@ __global__ __launch_bounds__(256) void k_adam_rows(float* __restrict__ records, 
                                                    uint32_t max_rows, AdamStep a) {
     const uint32_t listed = *count, rows = listed < max_rows ? listed : max_rows;
     const uint64_t first = (uint64_t)blockIdx.x * 256u;
-    if (first / kAdamQuads >= rows) return;                       // the whole block is past the count
+    if (first / kRecFieldQuads >= rows) return;                   // the whole block is past the count
     const uint64_t item = first + threadIdx.x;
-    const uint32_t row = (uint32_t)(item / kAdamQuads), quad = (uint32_t)(item % kAdamQuads);
+    const uint32_t row = (uint32_t)(item / kRecFieldQuads), quad = (uint32_t)(item % kRecFieldQuads);
     if (row >= rows) return;
     const uint32_t id = ids[row];
     if (id >= n) return;
-    const size_t at = (size_t)id * 84u + quad * 4u, gat = (size_t)row * 84u + quad * 4u;
+    const size_t at = (size_t)id * kRecordFloats + quad * 4u, gat = (size_t)row * kRecordFloats + quad * 4u;
     const uint32_t g3 = quad < 4u ? quad : (uint32_t)GS_ADAM_SH_REST;    // groups 0..3 are POSITION, SCALE, ROTATION, SH_DC
-    const bool has_w = quad == 2u || quad == 3u;
-    const uint32_t gw = quad == 2u ? (uint32_t)GS_ADAM_ROTATION : (uint32_t)GS_ADAM_OPACITY;
+    const bool has_w = rec_is_field(quad * 4u + 3u);
+    const uint32_t gw = quad == kRecRot / 4u ? (uint32_t)GS_ADAM_ROTATION : (uint32_t)GS_ADAM_OPACITY;
 
     const float3 g = *reinterpret_cast<const float3*>(grad_rows + gat);
     float3 p = *reinterpret_cast<const float3*>(records + at);
@@ -71,7 +69,7 @@ __global__ __launch_bounds__(256) void k_adam_rows(float* __restrict__ records, 
 void launch_adam_rows(float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
                       const uint32_t* count, uint32_t max_rows, const AdamStep& a, hipStream_t stream) {
     if (max_rows == 0) return;
-    const uint64_t blocks = ((uint64_t)max_rows * kAdamQuads + 255u) / 256u;      // < 2^29 for every uint32 max_rows
+    const uint64_t blocks = ((uint64_t)max_rows * kRecFieldQuads + 255u) / 256u;  // < 2^29 for every uint32 max_rows
     hipLaunchKernelGGL(k_adam_rows, dim3((uint32_t)blocks), dim3(256), 0, stream, records, m, v, n, ids, grad_rows, count,
                        max_rows, a);
 }

@@ -881,6 +881,16 @@ int gs_output_device(gs_ctx* c, uint32_t which, void** dev_out, size_t* bytes) {
     return GS_OK;
 }
 
+// The buffers of a per-splat scan (gs_splat_scan.h) of K sums over n splats, into the lifetime `mem`
+static hipError_t alloc_splat_scan(DeviceOwner& mem, SplatScan& s, uint32_t n, uint32_t K) {
+    const size_t rows = (size_t)K * backward_blocks(n) * sizeof(uint32_t);
+    hipError_t e = mem.alloc(s.offsets, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(s.block_sums, rows);
+    if (e == hipSuccess) e = mem.alloc(s.block_offsets, rows);
+    if (e == hipSuccess) e = mem.alloc(s.totals, K * sizeof(uint32_t));
+    return e;
+}
+
 // gs_backward*: the refusals (nothing enqueued), then the scratch of the first call
 static int backward_prepare(gs_ctx* c, const char* who) {
     if (c->cfg.render_mode != GS_RENDER_EXACT)
@@ -893,15 +903,10 @@ static int backward_prepare(gs_ctx* c, const char* who) {
         return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->bwd.rows) {
-        const size_t blocks = backward_blocks(c->n);
         DeviceOwner& mem = c->bwd_mem;
         hipError_t e = mem.alloc(c->bwd.rows, backward_row_bytes(c->capacity));
-        if (e == hipSuccess) e = mem.alloc(c->bwd.offsets, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = mem.alloc(c->bwd.block_sums, blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = mem.alloc(c->bwd.block_offsets, blocks * sizeof(uint32_t));
+        if (e == hipSuccess) e = alloc_splat_scan(mem, c->bwd.scan, c->n, 2);
         if (e == hipSuccess) e = mem.alloc(c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
-        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_block_sums, blocks * sizeof(uint32_t));
-        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_block_offsets, (blocks + 1) * sizeof(uint32_t));
         if (e != hipSuccess) {
             mem.release();
             c->bwd_vis_rows = 0;
@@ -934,7 +939,7 @@ static int stage_host_grads(gs_ctx* c, const float*& grad_rgba32f, const float*&
 static int visible_count_sync(gs_ctx* c, const char* who, uint32_t* count) {
     launch_backward_visible_scan(backward_frame(c), nullptr, 0u, nullptr, c->stream);
     if (int r = check_launch(c, who)) return r;
-    HIP_TRY(c, hipMemcpyAsync(count, c->bwd.vis_block_offsets + backward_blocks(c->n), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count, visible_count_of(c->bwd), 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GS_OK;
 }
@@ -1095,7 +1100,7 @@ int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* 
     if (!c->bwd_rows) return fail(c, GS_ERR_INVALID, who + ": no gs_backward* on this frame");
     if (n != c->n) return fail(c, GS_ERR_INVALID, who + ": n differs from the scene's");
     if (!max_rows) return GS_OK;
-    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.offsets, c->bwd.rows,
+    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.scan.offsets, c->bwd.rows,
                              c->scratch.raster, c->last_fp.capacity, c->last_fp.width, c->last_fp.height,
                              grad_accum, seen, max_radius};
     launch_densify_stats(a, c->stream);
@@ -1122,10 +1127,7 @@ static int densify_scratch(gs_ctx* c, uint32_t n, const std::string& who) {
     DeviceOwner& mem = c->densify_mem;
     mem.release();
     c->densify_cap = 0;
-    const size_t blocks = backward_blocks(n);
-    hipError_t e = mem.alloc(c->densify_offsets, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.alloc(c->densify_block_sums, 4 * blocks * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.alloc(c->densify_block_offsets, blocks * sizeof(uint32_t));
+    const hipError_t e = alloc_splat_scan(mem, c->densify_scan, n, 4);
     if (e != hipSuccess) {
         mem.release();
         return fail(c, GS_ERR_HIP, who + hipGetErrorString(e));
@@ -1176,7 +1178,7 @@ int gs_densify_device(gs_ctx* c, const float* records, const float* m, const flo
     a.rule = DensifyRule{p->grad_threshold, p->split_scale, p->prune_opacity, p->prune_scale, p->prune_radius};
     a.split_shrink = p->split_shrink; a.seed = p->seed;
     a.records_out = records_out; a.m_out = m_out; a.v_out = v_out; a.max_out = max_out;
-    a.offsets = c->densify_offsets; a.block_sums = c->densify_block_sums; a.block_offsets = c->densify_block_offsets;
+    a.scan = c->densify_scan;
     launch_densify(a, counts_out, c->stream);
     return check_launch(c, "gs_densify_device");
 }

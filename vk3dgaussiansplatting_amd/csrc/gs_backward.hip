@@ -2,12 +2,12 @@
 // include/gsplat.h), as five launches after the frame's own kernels.  The dense form (gs_backward*: a record gradient for
 // every splat) and the visible form (gs_backward_visible*: for the splats of V = { g : tiles_touched[g] != 0 } alone, with
 // their ids) run the same kernels; where they differ the kernel is a template on VIS:
-//   k_bwd_block_sums<VIS> + k_bwd_scan_blocks<VIS> + k_bwd_offsets<VIS> : offset[g] = sum of tiles_touched over the splats
-//                   before g, the splat-order position of g's first element -- the position InitSortList's truncation goes by
-//                   (k_emit, k_gather_sorted), so an element of the list has offset[g] + (its tile's index in g's box)
-//                   below the capacity, and every such slot is an element of the list.  VIS carries a second sum beside
+//   the per-splat scan of gs_splat_scan.h over BwdSource<VIS> (three launches): offset[g] = sum of tiles_touched over the
+//                   splats before g, the splat-order position of g's first element -- the position InitSortList's truncation
+//                   goes by (k_emit, k_gather_sorted), so an element of the list has offset[g] + (its tile's index in g's box)
+//                   below the capacity, and every such slot is an element of the list.  VIS carries a second row beside
 //                   the first, the flag tiles_touched != 0: its exclusive scan is the position of g in V (ascending g by
-//                   construction), vis_ids[position] = g, and vis_block_offsets[blocks] = |V|;
+//                   construction), vis_ids[position] = g, and its total is |V| (visible_count_of);
 //   k_bwd_blend   : per tile, the blend of RenderGaussians.comp:112-142 replayed front to back in the EXACT arithmetic
 //                   (same expressions, same pinned exp: the same entries contribute and each pixel stops on the same
 //                   entry K with the same T_K), then walked back to front with the colour behind every entry as a running
@@ -18,140 +18,40 @@
 //                   and depth <- position; colour <- SH coefficients and position), written in the 336-byte record layout
 //                   of gs_upload_gaussians.  Dense: thread g < N writes record g.  VIS: thread i < min(|V|, max_rows)
 //                   handles g = vis_ids[i] and writes record i.
-// Dense: launch_backward runs all five.  Visible: launch_backward_visible_scan runs the first three (alone it is
+// Dense: launch_backward runs all five.  Visible: launch_backward_visible_scan runs the scan (alone it is
 // gs_visible_count), launch_backward_visible_rows the last two.
 // No float atomics anywhere: the gradients are bitwise reproducible, and the same for every sorter and launch shape of
 // the forward (they depend on the sorted list and the pixels only).
-#include "gs_device_utils.h"
-#include "gs_internal.h"
+#include "gs_splat_math.h"
+#include "gs_splat_scan.h"
 
 namespace gs {
 
 constexpr int kBwdBatch = 64;             // list entries staged per step of k_bwd_blend
-constexpr int kRowFloats = 10;            // dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} of one list element
-constexpr int kRecordFloats = 84;         // GS_GAUSSIAN_RECORD_BYTES / 4
 
 // ---- per-splat slot offsets ---------------------------------------------------------------------------------------
-// VIS: the same three kernels with the flag tiles_touched[g] != 0 summed beside tiles_touched[g] (no atomics); the dense
-// instantiation carries none of it (the vis_* / *_out arguments are then unused and null).
-
+// The rows of the scan.  VIS: the flag tiles_touched[g] != 0 beside tiles_touched[g], and V from its positions: vis_ids[position
+// of g in V] = g for every g of V, and the same into ids_out (may be null) below max_rows.  The dense source carries none of it
+// (its pointers are null and unused).
 template <bool VIS>
-__global__ __launch_bounds__(256) void k_bwd_block_sums(const uint32_t* __restrict__ touched, uint32_t n,
-                                                         uint32_t* __restrict__ block_sums,
-                                                         uint32_t* __restrict__ vis_block_sums) {
-    __shared__ uint32_t s_w[4], s_f[4];
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t cnt = g < n ? touched[g] : 0u;
-    const uint32_t t = wave_sum_to_lane63(cnt);                       // < 256 * tiles: no overflow
-    if (lane_id() == 63) s_w[wave_id()] = t;
-    if constexpr (VIS) {
-        const uint32_t f = (uint32_t)__popcll(__ballot(cnt != 0u));
-        if (lane_id() == 63) s_f[wave_id()] = f;
+struct BwdSource {
+    static constexpr uint32_t K = VIS ? 2u : 1u, kPlaced = K, kTotalsFrom = 1u;
+    const uint32_t* touched;
+    uint32_t *vis_ids, *ids_out;
+    uint32_t max_rows;
+    __device__ void counts(uint32_t g, uint32_t (&c)[K]) const {
+        c[0] = touched[g];
+        if constexpr (VIS) c[1] = c[0] != 0u ? 1u : 0u;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        block_sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if constexpr (VIS) vis_block_sums[blockIdx.x] = s_f[0] + s_f[1] + s_f[2] + s_f[3];
-    }
-}
-
-// One workgroup: exclusive scan of the block sums with a 64-bit running total, stored saturated at 2^32 - 1 (beyond any
-// capacity: the slots of such splats are not elements of the list).  Every thread owns `per` consecutive blocks and
-// carries the running totals across them.  VIS: the flag total is at most N, 32 bits; vis_block_offsets[blocks] = |V|,
-// and the same into count_out (may be null), the caller's copy.
-template <bool VIS>
-__global__ __launch_bounds__(1024) void k_bwd_scan_blocks(const uint32_t* __restrict__ block_sums,
-                                                           const uint32_t* __restrict__ vis_block_sums, uint32_t blocks,
-                                                           uint32_t* __restrict__ block_offsets,
-                                                           uint32_t* __restrict__ vis_block_offsets,
-                                                           uint32_t* __restrict__ count_out) {
-    __shared__ uint64_t s_w[16];
-    __shared__ uint32_t s_f[16];
-    const uint32_t per = (blocks + 1023u) / 1024u;
-    const uint32_t b0 = threadIdx.x * per;
-    uint64_t mine = 0;
-    uint32_t fmine = 0, finc = 0, frun = 0;
-    for (uint32_t k = 0; k < per; ++k) {
-        if (b0 + k < blocks) {
-            mine += block_sums[b0 + k];
-            if constexpr (VIS) fmine += vis_block_sums[b0 + k];
-        }
-    }
-    const uint64_t inc = wave_inclusive_scan64(mine);
-    if (lane_id() == 63) s_w[wave_id()] = inc;
-    if constexpr (VIS) {
-        finc = wave_inclusive_scan(fmine);
-        if (lane_id() == 63) s_f[wave_id()] = finc;
-    }
-    __syncthreads();
-    uint64_t run = inc - mine;
-    for (int w = 0; w < wave_id(); ++w) run += s_w[w];
-    if constexpr (VIS) {
-        frun = finc - fmine;
-        for (int w = 0; w < wave_id(); ++w) frun += s_f[w];
-    }
-    for (uint32_t k = 0; k < per; ++k) {
-        if (b0 + k < blocks) {
-            block_offsets[b0 + k] = run < 0xFFFFFFFFull ? (uint32_t)run : 0xFFFFFFFFu;
-            run += block_sums[b0 + k];
-            if constexpr (VIS) {
-                vis_block_offsets[b0 + k] = frun;
-                frun += vis_block_sums[b0 + k];
+    __device__ void place(uint32_t g, const uint32_t (&c)[K], const uint32_t (&pos)[K]) const {
+        if constexpr (VIS) {
+            if (c[0] != 0u) {                     // pos[1] < |V| <= n
+                vis_ids[pos[1]] = g;
+                if (ids_out && pos[1] < max_rows) ids_out[pos[1]] = g;
             }
         }
     }
-    if constexpr (VIS) {
-        if (threadIdx.x == 1023u) {           // the last thread of the last wave: frun is the grand total
-            vis_block_offsets[blocks] = frun;
-            if (count_out) *count_out = frun;
-        }
-    }
-}
-
-// offsets[g]; VIS: vis_ids[position of g in V] = g for every g of V, and the same into ids_out (may be null) below max_rows.
-template <bool VIS>
-__global__ __launch_bounds__(256) void k_bwd_offsets(const uint32_t* __restrict__ touched, uint32_t n,
-                                                      const uint32_t* __restrict__ block_offsets,
-                                                      const uint32_t* __restrict__ vis_block_offsets,
-                                                      uint32_t* __restrict__ offsets, uint32_t* __restrict__ vis_ids,
-                                                      uint32_t* __restrict__ ids_out, uint32_t max_rows) {
-    __shared__ uint32_t s_w[4], s_f[4];
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t cnt = g < n ? touched[g] : 0u;
-    const uint32_t inc = wave_inclusive_scan(cnt);
-    if (lane_id() == 63) s_w[wave_id()] = inc;
-    uint64_t mask = 0;
-    if constexpr (VIS) {
-        mask = __ballot(cnt != 0u);
-        if (lane_id() == 63) s_f[wave_id()] = (uint32_t)__popcll(mask);
-    }
-    __syncthreads();
-    uint32_t before = inc - cnt;
-    for (int w = 0; w < wave_id(); ++w) before += s_w[w];
-    const uint64_t off = (uint64_t)block_offsets[blockIdx.x] + before;
-    if (g < n) offsets[g] = off < 0xFFFFFFFFull ? (uint32_t)off : 0xFFFFFFFFu;
-    if constexpr (VIS) {
-        uint32_t vis = vis_block_offsets[blockIdx.x] + mbcnt(mask);
-        for (int w = 0; w < wave_id(); ++w) vis += s_f[w];
-        if (cnt != 0u) {                      // cnt != 0 implies g < n, and vis < |V| <= n
-            vis_ids[vis] = g;
-            if (ids_out && vis < max_rows) ids_out[vis] = g;
-        }
-    }
-}
-
-template <bool VIS>
-static void launch_slot_offsets(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
-                                hipStream_t stream) {
-    const uint32_t n = f.fp.num_gaussians, blocks = backward_blocks(n);
-    const uint32_t* touched = f.sc.tiles_touched;
-    const BackwardBuffers& bb = f.bb;
-    hipLaunchKernelGGL(k_bwd_block_sums<VIS>, dim3(blocks), dim3(256), 0, stream, touched, n, bb.block_sums, bb.vis_block_sums);
-    hipLaunchKernelGGL(k_bwd_scan_blocks<VIS>, dim3(1), dim3(1024), 0, stream, bb.block_sums, bb.vis_block_sums, blocks,
-                       bb.block_offsets, bb.vis_block_offsets, count_out);
-    hipLaunchKernelGGL(k_bwd_offsets<VIS>, dim3(blocks), dim3(256), 0, stream, touched, n, bb.block_offsets,
-                       bb.vis_block_offsets, bb.offsets, bb.vis_ids, ids_out, max_rows);
-}
+};
 
 // ---- blend backward -----------------------------------------------------------------------------------------------
 
@@ -162,7 +62,7 @@ struct BwdBlendArgs {
     const float* pos;               // SceneBuffers::pos (the view depth of an entry, with grad_depth)
     const float4* grad_rgba;        // [H][W] dL/dRGBA32F
     const float* grad_depth;        // [H][W] dL/dDEPTH or null
-    const uint32_t* offsets;        // [N] k_bwd_offsets
+    const uint32_t* offsets;        // [N] BackwardBuffers::scan.offsets
     const uint2* extents;           // SplatScratch::extents
     float* rows;                    // [capacity][kRowFloats]
     uint32_t capacity;
@@ -340,39 +240,11 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
 
 static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, hipStream_t stream) {
     const BwdBlendArgs args{f.sc.raster, f.sorted_id, f.ranges, f.scene.pos, reinterpret_cast<const float4*>(grad_rgba),
-                            grad_depth, f.bb.offsets, f.sc.extents, f.bb.rows, f.fp.capacity};
+                            grad_depth, f.bb.scan.offsets, f.sc.extents, f.bb.rows, f.fp.capacity};
     hipLaunchKernelGGL(k_bwd_blend, dim3(f.fp.grid_w * f.fp.grid_h), dim3(256), 0, stream, f.fp, args);
 }
 
 // ---- per splat ----------------------------------------------------------------------------------------------------
-
-// Sum of the splat's rows in slot order; zero for a splat that emits nothing.
-__device__ __forceinline__ void bwd_row_sum(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
-                                            const float* __restrict__ rows, uint32_t g, uint32_t capacity,
-                                            float (&acc)[kRowFloats]) {
-#pragma unroll
-    for (int k = 0; k < kRowFloats; ++k) acc[k] = 0.0f;
-    const uint64_t o = offsets[g];
-    const uint64_t e = o + touched[g];
-    const uint64_t stop = e < capacity ? e : capacity;
-    for (uint64_t s = o; s < stop; ++s) {
-        const float* r = rows + s * kRowFloats;
-#pragma unroll
-        for (int k = 0; k < kRowFloats; ++k) acc[k] += r[k];
-    }
-}
-
-// GLSL `M * v`, M column-major, in the reference's operand order
-__device__ __forceinline__ void bwd_mat4_vec4(const float* m, float vx, float vy, float vz, float vw, float out[4]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float acc = m[0 * 4 + r] * vx;
-        acc = acc + m[1 * 4 + r] * vy;
-        acc = acc + m[2 * 4 + r] * vz;
-        acc = acc + m[3 * 4 + r] * vw;
-        out[r] = acc;
-    }
-}
 
 // Common.glsl:94-138 as a function of (X, Y, Z) = (-dx, -dy, dz), with its partial derivatives
 __device__ __forceinline__ void sh_basis_grad(float X, float Y, float Z, float b[16], float bx[16], float by[16], float bz[16]) {
@@ -408,7 +280,7 @@ __device__ __forceinline__ void sh_basis_grad(float X, float Y, float Z, float b
 // From the summed row of a splat to dL/d(record).  The branch the forward took is held fixed: the clamp of x/z, y/z in
 // getCovarianceMatrix (a clamped component passes no derivative to the ratio), max(colour, 0) (no derivative below 0),
 // det == 0 (opacity 0: the splat never contributes, all zero).
-// `row` = the summed row of splat g, `any` = g emitted into the list; o = the 84 floats of its record gradient.  One body for
+// `row` = the summed row of splat g, `any` = g emitted into the list; o = the quads of its record gradient.  One body for
 // the dense and the visible kernel: the same expressions in the same order, so the same bits.
 __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const SceneBuffers& scene, uint32_t g, bool any,
                                                  const float (&row)[kRowFloats], float4* o) {
@@ -422,7 +294,7 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
     }
     if (!any) {
 #pragma unroll
-        for (int k = 0; k < kRecordFloats / 4; ++k) o[k] = zero4;
+        for (uint32_t k = 0; k < kRecordQuads; ++k) o[k] = zero4;
         return;
     }
     const float dsx = row[0], dsy = row[1], dix = row[2], diy = row[3], diz = row[4];
@@ -437,8 +309,8 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
     const float qr = q[0], qx = q[1], qy = q[2], qz = q[3];
 
     float vp[4], cp[4];
-    bwd_mat4_vec4(fp.view, p[0], p[1], p[2], 1.0f, vp);
-    bwd_mat4_vec4(fp.proj, vp[0], vp[1], vp[2], vp[3], cp);
+    mat4_mul_vec4(fp.view, p[0], p[1], p[2], 1.0f, vp);
+    mat4_mul_vec4(fp.proj, vp[0], vp[1], vp[2], vp[3], cp);
     float dvp[4] = {0.f, 0.f, 0.f, 0.f};
 
     // screen position (Common.glsl:80-89): s = ((+-ndc + 1) / 2) * extent, ndc = clip.xy / clip.w
@@ -453,15 +325,12 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
     dvp[2] += -dz;                                          // depth = -viewSpacePos.z
 
     // 2-D covariance (Common.glsl:32-78) and its inverse (RenderGaussians.comp:94-107)
-    float R[3][3];                                          // R[row][col] of getRotMat
-    R[0][0] = 1.0f - 2.0f * qy * qy - 2.0f * qz * qz; R[1][0] = 2.0f * qx * qy - 2.0f * qr * qz; R[2][0] = 2.0f * qx * qz + 2.0f * qr * qy;
-    R[0][1] = 2.0f * qx * qy + 2.0f * qr * qz; R[1][1] = 1.0f - 2.0f * qx * qx - 2.0f * qz * qz; R[2][1] = 2.0f * qy * qz - 2.0f * qr * qx;
-    R[0][2] = 2.0f * qx * qz - 2.0f * qr * qy; R[1][2] = 2.0f * qy * qz + 2.0f * qr * qx; R[2][2] = 1.0f - 2.0f * qx * qx - 2.0f * qy * qy;
+    const Mat3 rm = get_rot_mat(qr, qx, qy, qz);            // R[row][col] of getRotMat = rm.m[col][row]
     float M[3][3], Sg[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int k = 0; k < 3; ++k) M[i][k] = R[i][k] * s[k];
+        for (int k = 0; k < 3; ++k) M[i][k] = rm.m[k][i] * s[k];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -522,7 +391,7 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
             for (int k = 0; k < 3; ++k) {
                 const float dM = dSs[i][0] * M[0][k] + dSs[i][1] * M[1][k] + dSs[i][2] * M[2][k];
                 dR[i][k] = dM * s[k];
-                dscale[k] += dM * R[i][k];
+                dscale[k] += dM * rm.m[k][i];
             }
         // getRotMat's entries as functions of (r, x, y, z)
         drot[0] = 2.0f * (-qz * dR[1][0] + qy * dR[2][0] + qz * dR[0][1] - qx * dR[2][1] - qy * dR[0][2] + qx * dR[1][2]);
@@ -583,17 +452,17 @@ __device__ __forceinline__ void bwd_chain_record(const FrameParams& fp, const Sc
     for (int k = 0; k < 3; ++k)
         dpos[k] += fp.view[k * 4 + 0] * dvp[0] + fp.view[k * 4 + 1] * dvp[1] + fp.view[k * 4 + 2] * dvp[2] + fp.view[k * 4 + 3] * dvp[3];
 
-    o[0] = make_float4(dpos[0], dpos[1], dpos[2], 0.0f);
-    o[1] = make_float4(dscale[0], dscale[1], dscale[2], 0.0f);
-    o[2] = make_float4(drot[0], drot[1], drot[2], drot[3]);
+    o[kRecPos / 4] = make_float4(dpos[0], dpos[1], dpos[2], 0.0f);
+    o[kRecScale / 4] = make_float4(dscale[0], dscale[1], dscale[2], 0.0f);
+    o[kRecRot / 4] = make_float4(drot[0], drot[1], drot[2], drot[3]);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
         const bool used = k >= k_lo && k < k_hi;
-        o[3 + k] = make_float4(used ? dres[0] * b[k] : 0.0f, used ? dres[1] * b[k] : 0.0f, used ? dres[2] * b[k] : 0.0f,
-                               k == 0 ? dop : 0.0f);
+        o[kRecSh / 4 + k] = make_float4(used ? dres[0] * b[k] : 0.0f, used ? dres[1] * b[k] : 0.0f,
+                                        used ? dres[2] * b[k] : 0.0f, k == 0 ? dop : 0.0f);     // .w of k = 0: the opacity
     }
-    o[19] = zero4;                                                       // color
-    o[20] = zero4;                                                       // covariance
+    o[kRecColor / 4] = zero4;
+    o[kRecCov / 4] = zero4;
 }
 
 // Row sum + chain.  Dense: thread g < N sums the rows of splat g and writes record gradient g (all zero for a splat outside
@@ -619,21 +488,22 @@ __global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, 
         any = touched[g] != 0u;
     }
     float row[kRowFloats];
-    bwd_row_sum(touched, offsets, rows, g, fp.capacity, row);
+    splat_row_sum(touched, offsets, rows, g, fp.capacity, row);
     bwd_chain_record(fp, scene, g, any, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats));
 }
 
 void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
                      hipStream_t stream) {
-    launch_slot_offsets<false>(f, nullptr, 0u, nullptr, stream);
+    launch_splat_scan(BwdSource<false>{f.sc.tiles_touched, nullptr, nullptr, 0u}, f.fp.num_gaussians, f.bb.scan, nullptr, stream);
     launch_blend(f, grad_rgba, grad_depth, stream);
     hipLaunchKernelGGL(k_bwd_rowsum_chain<false>, dim3(backward_blocks(f.fp.num_gaussians)), dim3(256), 0, stream, f.fp,
-                       f.scene, f.sc.tiles_touched, f.bb.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);
+                       f.scene, f.sc.tiles_touched, f.bb.scan.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);
 }
 
 void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
                                   hipStream_t stream) {
-    launch_slot_offsets<true>(f, ids_out, max_rows, count_out, stream);
+    launch_splat_scan(BwdSource<true>{f.sc.tiles_touched, f.bb.vis_ids, ids_out, max_rows}, f.fp.num_gaussians, f.bb.scan, count_out,
+                      stream);
 }
 
 void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
@@ -641,10 +511,8 @@ void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba
     const uint32_t n = f.fp.num_gaussians;
     launch_blend(f, grad_rgba, grad_depth, stream);
     hipLaunchKernelGGL(k_bwd_rowsum_chain<true>, dim3(backward_blocks(n < max_rows ? n : max_rows)), dim3(256), 0, stream,
-                       f.fp, f.scene, f.sc.tiles_touched, f.bb.offsets, f.bb.rows, f.bb.vis_ids,
-                       f.bb.vis_block_offsets + backward_blocks(n), max_rows, grad_rows);
+                       f.fp, f.scene, f.sc.tiles_touched, f.bb.scan.offsets, f.bb.rows, f.bb.vis_ids, visible_count_of(f.bb),
+                       max_rows, grad_rows);
 }
-
-size_t backward_row_bytes(uint32_t capacity) { return (size_t)capacity * kRowFloats * sizeof(float); }
 
 } // namespace gs

@@ -118,10 +118,8 @@ struct gs_ctx {
     bool bwd_frame = false;
     bool bwd_rows = false;            // bwd.rows holds a backward of the current frame (a gs_backward* form ran the blend): what
                                       // gs_densify_stats_device sums; cleared with bwd_frame, by a new frame and with bwd_mem
-    // gs_densify_device: 4 bytes per splat + the block arrays, for densify_cap splats; grown on demand, freed at gs_destroy
-    uint32_t* densify_offsets = nullptr;
-    uint32_t* densify_block_sums = nullptr;
-    uint32_t* densify_block_offsets = nullptr;
+    // gs_densify_device: its scan (K = 4) for densify_cap splats; grown on demand, freed at gs_destroy
+    gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
     DeviceOwner densify_mem;
     // gs_photometric_loss*: scratch allocated on the first call (9 floats per pixel + 8 bytes per tile), freed with the

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gs_record.h"
 
 namespace gs {
 
@@ -266,18 +267,26 @@ struct RenderOutputs {
 void launch_render(const FrameParams& fp, const SplatRaster* raster, const uint32_t* sorted_id,
                    const uint32_t* ranges, const uint32_t* order, uint8_t* rgba, uint32_t render_mode,
                    uint32_t render_kernel, hipStream_t stream, const RenderOutputs& outs = RenderOutputs{});
-// gs_backward* (gs_backward.hip): scratch of a backward pass, allocated on the first call
-struct BackwardBuffers {
-    float* rows;              // [capacity][10]  dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} per element, in its slot
-    uint32_t* offsets;        // [N]  first slot of a splat: its tiles_touched summed over the splats before it (saturated)
-    uint32_t* block_sums;     // [ceil(N / 256)]
-    uint32_t* block_offsets;  // [ceil(N / 256)]
-    // gs_backward_visible*: V = the splats with tiles_touched != 0, ascending
-    uint32_t* vis_ids;            // [N]  the first |V| entries: V
-    uint32_t* vis_block_sums;     // [ceil(N / 256)]  members of V per block
-    uint32_t* vis_block_offsets;  // [ceil(N / 256) + 1]  exclusive scan; the last entry is |V|
+// The buffers of one per-splat scan (gs_splat_scan.h) of K sums over n splats, in blocks of 256 splats
+struct SplatScan {
+    uint32_t* offsets;        // [n]  row 0 summed over the splats before g, saturated at 2^32 - 1
+    uint32_t* block_sums;     // [K][ceil(n / 256)]
+    uint32_t* block_offsets;  // [K][ceil(n / 256)]  exclusive scan of block_sums, row 0 saturated
+    uint32_t* totals;         // [K]  the grand totals of the rows whose total the caller asks for
 };
-size_t backward_row_bytes(uint32_t capacity);
+// gs_backward* (gs_backward.hip): scratch of a backward pass, allocated on the first call
+constexpr int kRowFloats = 10;    // a row of BackwardBuffers::rows: dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} of one list element, in
+                                  // that order (screen position, inverse 2-D covariance, colour, opacity, view depth)
+struct BackwardBuffers {
+    float* rows;              // [capacity][kRowFloats]  per element, in its slot
+    // row 0: tiles_touched, so offsets[g] = the first slot of splat g; row 1 (gs_backward_visible* only): the flag
+    // tiles_touched != 0, whose scan is the position of g in V = the splats with tiles_touched != 0, ascending
+    SplatScan scan;           // K = 2
+    uint32_t* vis_ids;        // [N]  the first |V| entries: V
+};
+// |V| on the device after launch_backward_visible_scan: what its kernels and the host read
+inline const uint32_t* visible_count_of(const BackwardBuffers& bb) { return bb.scan.totals + 1; }
+inline size_t backward_row_bytes(uint32_t capacity) { return (size_t)capacity * kRowFloats * sizeof(float); }
 inline uint32_t backward_blocks(uint32_t n) { return (n + 255u) / 256u; }   // 256 splats per block of the per-splat kernels
 // The frame a backward pass differentiates: its FrameParams (full grid, GS_RENDER_EXACT), the scene, what its forward left
 // (scratch, sorted list, ranges) and the backward's own scratch
@@ -292,8 +301,8 @@ struct BackwardFrame {
 // dL/d(record) [N][84] of the frame, from dL/dRGBA32F [H][W][4] and dL/dDEPTH [H][W] (may be null).
 void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
                      hipStream_t stream);
-// The visible form, in two steps on one stream.  _scan: the slot offsets of launch_backward plus V (bb.vis_ids, |V| in
-// bb.vis_block_offsets[blocks]); ids_out (device, may be null) gets the first max_rows of V, count_out (device, may be null)
+// The visible form, in two steps on one stream.  _scan: the slot offsets of launch_backward plus V (bb.vis_ids, |V| at
+// visible_count_of(bb)); ids_out (device, may be null) gets the first max_rows of V, count_out (device, may be null)
 // |V|.  _rows: the blend backward, then record gradient i of splat vis_ids[i] into grad_rows[i][84], i < min(|V|, max_rows).
 void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
                                   hipStream_t stream);
@@ -330,7 +339,7 @@ struct DensifyStatsArgs {
     const uint32_t* count;
     uint32_t max_rows, n;
     const uint32_t* touched;          // SplatScratch::tiles_touched
-    const uint32_t* offsets;          // BackwardBuffers::offsets
+    const uint32_t* offsets;          // BackwardBuffers::scan.offsets
     const float* rows;                // BackwardBuffers::rows
     const SplatRaster* raster;
     uint32_t capacity, width, height;
@@ -354,9 +363,7 @@ struct DensifyArgs {
     uint64_t seed;
     float *records_out, *m_out, *v_out;
     uint32_t max_out;
-    uint32_t* offsets;                // [n]  o(g): index of the first output of g
-    uint32_t* block_sums;             // [4][ceil(n / 256)]  outputs, cloned, split, pruned per block
-    uint32_t* block_offsets;          // [ceil(n / 256)]
+    SplatScan scan;                   // K = 4: outputs, cloned, split, pruned; offsets[g] = o(g), the index of g's first output
 };
 void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stream);
 void launch_stream_probe(int kind, const void* src, void* dst, size_t bytes, uint32_t blocks, hipStream_t stream);

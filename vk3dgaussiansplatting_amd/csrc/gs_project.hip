@@ -11,12 +11,9 @@
 // (build flag -ffp-contract=off), IEEE division and sqrt: sort keys and tile extents are bit-exact
 // against oracle/gs_oracle.c.  Paths are relative to /root/reference/vkGaussianSplatting/Resources/Shaders/.
 #include <cstdlib>
-#include "gs_device_utils.h"
-#include "gs_internal.h"
+#include "gs_splat_math.h"
 
 namespace gs {
-
-struct Mat3 { float m[3][3]; }; // column-major m[col][row], like GLSL mat3x3
 
 // C = A*B, C[j][i] = (A[0][i]*B[j][0] + A[1][i]*B[j][1]) + A[2][i]*B[j][2]
 __device__ __forceinline__ Mat3 mat3_mul(const Mat3& a, const Mat3& b) {
@@ -39,34 +36,6 @@ __device__ __forceinline__ Mat3 mat3_transpose(const Mat3& a) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) t.m[j][i] = a.m[i][j];
     return t;
-}
-
-// GLSL `M * v`, M column-major: ((M[0]*v.x + M[1]*v.y) + M[2]*v.z) + M[3]*v.w
-__device__ __forceinline__ void mat4_mul_vec4(const float* m, float vx, float vy, float vz,
-                                              float vw, float out[4]) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        float acc = m[0 * 4 + r] * vx;
-        acc = acc + m[1 * 4 + r] * vy;
-        acc = acc + m[2 * 4 + r] * vz;
-        acc = acc + m[3 * 4 + r] * vw;
-        out[r] = acc;
-    }
-}
-
-// Common/Common.glsl:17-30 (column-major constructor: col0, col1, col2)
-__device__ __forceinline__ Mat3 get_rot_mat(float r, float x, float y, float z) {
-    Mat3 m;
-    m.m[0][0] = 1.0f - 2.0f * y * y - 2.0f * z * z;
-    m.m[0][1] = 2.0f * x * y - 2.0f * r * z;
-    m.m[0][2] = 2.0f * x * z + 2.0f * r * y;
-    m.m[1][0] = 2.0f * x * y + 2.0f * r * z;
-    m.m[1][1] = 1.0f - 2.0f * x * x - 2.0f * z * z;
-    m.m[1][2] = 2.0f * y * z - 2.0f * r * x;
-    m.m[2][0] = 2.0f * x * z - 2.0f * r * y;
-    m.m[2][1] = 2.0f * y * z + 2.0f * r * x;
-    m.m[2][2] = 1.0f - 2.0f * x * x - 2.0f * y * y;
-    return m;
 }
 
 // Common/Common.glsl:32-78
@@ -428,10 +397,7 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
 
                     // getGaussianTileExtents, InitSortList.comp:47-68
                     const float det = cov[0] * cov[2] - cov[1] * cov[1];
-                    const float m = (cov[0] + cov[2]) * 0.5f;
-                    const float lambda0 = m + sqrtf(maxf(m * m - det, 0.0f));
-                    const float lambda1 = m - sqrtf(maxf(m * m - det, 0.0f));
-                    const float radius = ceilf(3.0f * sqrtf(maxf(lambda0, lambda1)));
+                    const float radius = tile_extent_radius(cov[0], cov[1], cov[2]);
                     const int gw = (int)fp.grid_w, gh = (int)fp.grid_h;
                     const int min_x = clampi(f2i_sat((sx - radius) / 16.0f), 0, gw);
                     const int min_y = clampi(f2i_sat((sy - radius) / 16.0f), 0, gh);

@@ -1,0 +1,70 @@
+// gs_splat_math.h -- the per-splat expressions more than one kernel file evaluates, each written once (device).  Every
+// .hip file is built with -ffp-contract=off and correctly rounded division and square root, so an expression of this header
+// gives the same floats wherever it is compiled: the frame (gs_project.hip), its backward (gs_backward.hip), the upload
+// (gs_upload.hip) and density control (gs_densify.hip) agree bit for bit because they call the same function.
+#pragma once
+
+#include "gs_device_utils.h"
+#include "gs_internal.h"
+
+namespace gs {
+
+struct Mat3 { float m[3][3]; }; // column-major m[col][row], like GLSL mat3x3
+
+// GLSL `M * v`, M column-major: ((M[0]*v.x + M[1]*v.y) + M[2]*v.z) + M[3]*v.w
+__device__ __forceinline__ void mat4_mul_vec4(const float* m, float vx, float vy, float vz,
+                                              float vw, float out[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float acc = m[0 * 4 + r] * vx;
+        acc = acc + m[1 * 4 + r] * vy;
+        acc = acc + m[2 * 4 + r] * vz;
+        acc = acc + m[3 * 4 + r] * vw;
+        out[r] = acc;
+    }
+}
+
+// Common/Common.glsl:17-30 (column-major constructor: col0, col1, col2); R[row][col] = m[col][row]
+__device__ __forceinline__ Mat3 get_rot_mat(float r, float x, float y, float z) {
+    Mat3 m;
+    m.m[0][0] = 1.0f - 2.0f * y * y - 2.0f * z * z;
+    m.m[0][1] = 2.0f * x * y - 2.0f * r * z;
+    m.m[0][2] = 2.0f * x * z + 2.0f * r * y;
+    m.m[1][0] = 2.0f * x * y + 2.0f * r * z;
+    m.m[1][1] = 1.0f - 2.0f * x * x - 2.0f * z * z;
+    m.m[1][2] = 2.0f * y * z - 2.0f * r * x;
+    m.m[2][0] = 2.0f * x * z - 2.0f * r * y;
+    m.m[2][1] = 2.0f * y * z + 2.0f * r * x;
+    m.m[2][2] = 1.0f - 2.0f * x * x - 2.0f * y * y;
+    return m;
+}
+
+// The radius of getGaussianTileExtents (InitSortList.comp:47-68) from the 2-D covariance (cx, cy; cy, cz):
+// ceil(3 sqrt(largest eigenvalue))
+__device__ __forceinline__ float tile_extent_radius(float cx, float cy, float cz) {
+    const float det = cx * cz - cy * cy;
+    const float m = (cx + cz) * 0.5f;
+    const float lambda0 = m + sqrtf(maxf(m * m - det, 0.0f));
+    const float lambda1 = m - sqrtf(maxf(m * m - det, 0.0f));
+    return ceilf(3.0f * sqrtf(maxf(lambda0, lambda1)));
+}
+
+// The first COLS columns of splat g's rows (BackwardBuffers::rows) summed in slot order, from 0.0f, over the slots below the
+// capacity; zero for a splat that emits nothing.  Only the summed columns are read.
+template <int COLS>
+__device__ __forceinline__ void splat_row_sum(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
+                                              const float* __restrict__ rows, uint32_t g, uint32_t capacity,
+                                              float (&acc)[COLS]) {
+#pragma unroll
+    for (int k = 0; k < COLS; ++k) acc[k] = 0.0f;
+    const uint64_t o = offsets[g];
+    const uint64_t e = o + touched[g];
+    const uint64_t stop = e < capacity ? e : capacity;
+    for (uint64_t s = o; s < stop; ++s) {
+        const float* r = rows + s * kRowFloats;
+#pragma unroll
+        for (int k = 0; k < COLS; ++k) acc[k] += r[k];
+    }
+}
+
+} // namespace gs

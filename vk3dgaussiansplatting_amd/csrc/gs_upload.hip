@@ -2,8 +2,7 @@
 // (Engine/Graphics/ShaderStructs.h:59-70) to the SoA planes the per-frame kernels read with fully
 // coalesced loads.  Runs once per scene (Renderer::initForScene, Renderer.cpp:712-724), chunk by
 // chunk through a staging buffer so a 50 M-splat scene never needs a second full-size AoS copy in HBM.
-#include "gs_device_utils.h"
-#include "gs_internal.h"
+#include "gs_splat_math.h"
 
 namespace gs {
 
@@ -11,22 +10,20 @@ namespace gs {
 // a workgroup with part = 0..3 and lane = record: they split the 59 fields, and part 3 adds the cull bound sig2.  The one
 // place a record becomes planes: the full upload and the upload of listed rows write the same bits.
 __device__ __forceinline__ void store_record_planes(const float* rec, uint32_t part, size_t g, uint32_t n, const SceneBuffers& s) {
-    for (uint32_t fld = part; fld < 59u; fld += 4u) {
-        if (fld < 3u) s.pos[(size_t)fld * n + g] = rec[0 + fld];
-        else if (fld < 6u) s.scale[(size_t)(fld - 3u) * n + g] = rec[4 + (fld - 3u)];
-        else if (fld < 10u) s.rot[(size_t)(fld - 6u) * n + g] = rec[8 + (fld - 6u)];
+    for (uint32_t fld = part; fld < kRecFields; fld += 4u) {
+        if (fld < 3u) s.pos[(size_t)fld * n + g] = rec[kRecPos + fld];
+        else if (fld < 6u) s.scale[(size_t)(fld - 3u) * n + g] = rec[kRecScale + (fld - 3u)];
+        else if (fld < 10u) s.rot[(size_t)(fld - 6u) * n + g] = rec[kRecRot + (fld - 6u)];
         else if (fld < 58u) {
             const uint32_t k = fld - 10u, coeff = k / 3u, ch = k % 3u;
-            s.sh[(size_t)k * n + g] = rec[12 + coeff * 4u + ch];
-        } else s.opacity[g] = rec[12 + 3];
+            s.sh[(size_t)k * n + g] = rec[rec_sh(coeff, ch)];
+        } else s.opacity[g] = rec[kRecOpacity];
     }
     if (part == 3u) {
         // |R|_2^2 * max(scale)^2 >= largest eigenvalue of Sigma = (R S)(R S)^T, with R as Common.glsl:17-30
         // builds it from the (not necessarily unit) quaternion
-        const float q0 = rec[8], x = rec[9], y = rec[10], z = rec[11];
-        const float e[9] = {1.0f - 2.0f * y * y - 2.0f * z * z, 2.0f * x * y - 2.0f * q0 * z, 2.0f * x * z + 2.0f * q0 * y,
-                            2.0f * x * y + 2.0f * q0 * z, 1.0f - 2.0f * x * x - 2.0f * z * z, 2.0f * y * z - 2.0f * q0 * x,
-                            2.0f * x * z - 2.0f * q0 * y, 2.0f * y * z + 2.0f * q0 * x, 1.0f - 2.0f * x * x - 2.0f * y * y};
+        const Mat3 rm = get_rot_mat(rec[kRecRot], rec[kRecRot + 1], rec[kRecRot + 2], rec[kRecRot + 3]);
+        const float (&e)[3][3] = rm.m;                   // e[i]: column i of R; R^T R has the norm of R R^T
         // |R|_2^2 <= min(trace, largest absolute row sum) of R R^T (Gershgorin): 1 for a unit quaternion, where the
         // Frobenius norm alone says 3
         // the maxima keep a NaN (fmaxf would drop it): a NaN scale, or a row of R R^T that is inf - inf (an infinite
@@ -35,16 +32,16 @@ __device__ __forceinline__ void store_record_planes(const float* rec, uint32_t p
         auto nan_max = [](float a, float b) { return (a > b || a != a) ? a : b; };
         float f2 = 0.0f, gersh = 0.0f;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) f2 += e[k] * e[k];
+        for (int k = 0; k < 9; ++k) f2 += e[k / 3][k % 3] * e[k / 3][k % 3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             float row = 0.0f;
 #pragma unroll
-            for (int j = 0; j < 3; ++j) row += fabsf(e[3 * i] * e[3 * j] + e[3 * i + 1] * e[3 * j + 1] + e[3 * i + 2] * e[3 * j + 2]);
+            for (int j = 0; j < 3; ++j) row += fabsf(e[i][0] * e[j][0] + e[i][1] * e[j][1] + e[i][2] * e[j][2]);
             gersh = nan_max(row, gersh);
         }
         const float r2 = (gersh < f2 ? gersh : f2) * 1.0001f;      // a NaN takes f2, NaN or infinite: the splat is kept
-        const float s0 = fabsf(rec[4]), s1 = fabsf(rec[5]), s2 = fabsf(rec[6]);
+        const float s0 = fabsf(rec[kRecScale]), s1 = fabsf(rec[kRecScale + 1]), s2 = fabsf(rec[kRecScale + 2]);
         const float sm = nan_max(s0, nan_max(s1, s2));
         s.sig2[g] = r2 * sm * sm;
     }
@@ -53,12 +50,12 @@ __device__ __forceinline__ void store_record_planes(const float* rec, uint32_t p
 // chunk: [count][84] floats starting at splat `first`; n = total splats (plane stride)
 __global__ __launch_bounds__(256) void k_aos_to_soa(const float* __restrict__ chunk, uint32_t first,
                                                      uint32_t count, uint32_t n, SceneBuffers s) {
-    __shared__ float tile[64][85];   // 64 records, padded row to dodge bank conflicts
+    __shared__ float tile[64][kRecordFloats + 1];   // 64 records, padded row to dodge bank conflicts
     const uint32_t rec0 = blockIdx.x * 64u;
     const uint32_t nrec = (count - rec0) < 64u ? (count - rec0) : 64u;
     // coalesced read of nrec*84 consecutive floats
-    for (uint32_t k = threadIdx.x; k < nrec * 84u; k += 256u)
-        tile[k / 84u][k % 84u] = chunk[(size_t)rec0 * 84u + k];
+    for (uint32_t k = threadIdx.x; k < nrec * kRecordFloats; k += 256u)
+        tile[k / kRecordFloats][k % kRecordFloats] = chunk[(size_t)rec0 * kRecordFloats + k];
     __syncthreads();
     // coalesced plane writes: lane = record
     const uint32_t r = threadIdx.x & 63u, part = threadIdx.x >> 6;   // 4 waves split the 59 fields
@@ -71,7 +68,7 @@ __global__ __launch_bounds__(256) void k_aos_to_soa(const float* __restrict__ ch
 __global__ __launch_bounds__(256) void k_upload_rows(const float* __restrict__ records, uint32_t n,
                                                       const uint32_t* __restrict__ ids, const uint32_t* __restrict__ count,
                                                       uint32_t max_rows, SceneBuffers s) {
-    __shared__ float tile[64][85];
+    __shared__ float tile[64][kRecordFloats + 1];
     __shared__ uint32_t id_of[64];
     const uint32_t listed = *count, rows = listed < max_rows ? listed : max_rows;
     const uint32_t row0 = blockIdx.x * 64u;
@@ -79,11 +76,10 @@ __global__ __launch_bounds__(256) void k_upload_rows(const float* __restrict__ r
     const uint32_t nrow = (rows - row0) < 64u ? (rows - row0) : 64u;
     if (threadIdx.x < nrow) id_of[threadIdx.x] = ids[row0 + threadIdx.x];
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < nrow * 84u; k += 256u) {
-        const uint32_t g = id_of[k / 84u], col = k % 84u;
-        // the 59 fields only: the other 25 floats of a record (w of every group but 2 and 3, 76..83) are never read
-        const bool field = col < 76u && ((col & 3u) != 3u || col == 11u || col == 15u);
-        if (g < n && field) tile[k / 84u][col] = records[(size_t)g * 84u + col];
+    for (uint32_t k = threadIdx.x; k < nrow * kRecordFloats; k += 256u) {
+        const uint32_t g = id_of[k / kRecordFloats], col = k % kRecordFloats;
+        // the 59 fields only: the other 25 floats of a record are never read
+        if (g < n && rec_is_field(col)) tile[k / kRecordFloats][col] = records[(size_t)g * kRecordFloats + col];
     }
     __syncthreads();
     const uint32_t r = threadIdx.x & 63u, part = threadIdx.x >> 6;
