@@ -237,6 +237,22 @@ int gs_convert_ply(const char* path, void* aos336_out, uint32_t max_records, uin
 /* Text of the last gs_load_ply / gs_convert_ply failure on this thread (happly throws instead,
  * happly.h:1089-1094). */
 const char* gs_ply_last_error(void);
+/* The way back (no reference counterpart): rows float[n][84] (HOST) -> a .ply gs_load_ply reads: binary_little_endian, one
+ * `vertex` element of 62 float properties in the INRIA order -- x y z nx ny nz f_dc_0..2 f_rest_0..44 opacity scale_0..2
+ * rot_0..3 -- the normals 0.  Per row r, the inverse of the loader's conversion:
+ *   x, y, z = -r[0], -r[1], r[2];   rot_0..3 = r[10], -r[11], -r[8], -r[9];   f_dc_c = r[12 + c];
+ *   f_rest_(c + 15 ch) = r[16 + 4 c + ch]                                       (c = 0..14, ch = 0..2)
+ *   GS_PLY_FROM_RAW     (rows in the raw space below): scale_k = r[4 + k] and opacity = r[15] as they are -- the file then
+ *                       holds the trainer's parameters exactly, a lossless checkpoint;
+ *   GS_PLY_FROM_RECORDS (rows as the frame reads them): scale_k = std::log(s < FLT_MIN ? FLT_MIN : s), opacity =
+ *                       std::log(c / (1 - c)) with c = the opacity clamped to [2^-24, 1 - 2^-24], in float32 (the host's libm).
+ * Rows are written in the order given; the loader's Morton sort is stable, so a cloud that came from the loader (or from
+ * gs_densify_device on one) loads again in the same order.  Written in chunks of a few MB: no second copy of the cloud.
+ * GS_ERR_IO with a message in gs_ply_last_error when the file cannot be created or a write comes up short; GS_ERR_INVALID
+ * for a NULL path or rows, n == 0 or an unknown space. */
+#define GS_PLY_FROM_RECORDS 0u
+#define GS_PLY_FROM_RAW 1u
+int gs_write_ply(const char* path, const float* rows, uint32_t n, uint32_t space);
 
 /* Frame output sink: where the reference's frame goes to the swapchain image
  * (RenderGaussians.comp:150 imageStore, presented by Renderer.cpp:341-397) a windowless host writes the
@@ -473,9 +489,10 @@ typedef struct gs_adam_params {
     float hi[GS_ADAM_GROUPS];
 } gs_adam_params;
 /* step 1, beta1 0.9, beta2 0.999, eps 1e-15; lr: position 1.6e-4, scale 5e-3, rotation 1e-3, SH DC 2.5e-3, opacity 5e-2,
- * SH rest 1.25e-4 -- the rates of the INRIA 3DGS trainer.  NOTE: there they act on log-scales and logit-opacities; here
- * they act on the record's own values (scale and opacity as the frame reads them), so the clamps below stand in for what
- * exp and sigmoid guarantee, and a caller may want other rates.  lo / hi: scale [1e-7, +inf], opacity [0, 1], every other
+ * SH rest 1.25e-4 -- the rates of the INRIA 3DGS trainer.  NOTE: there they act on log-scales and logit-opacities; with
+ * gs_adam_rows_device they act on the record's own values (scale and opacity as the frame reads them), so the clamps below
+ * stand in for what exp and sigmoid guarantee, and a caller may want other rates.  The rates fit the raw space:
+ * gs_default_adam_params_raw and gs_adam_rows_raw_device, below.  lo / hi: scale [1e-7, +inf], opacity [0, 1], every other
  * group [-inf, +inf]. */
 void gs_default_adam_params(gs_adam_params* p);
 /* torch.optim.SparseAdam's rule on rows ids[i], i < min(*count_dev, max_rows), of records / m / v (each float[n][84],
@@ -511,6 +528,69 @@ int gs_adam_rows_device(gs_ctx* ctx, float* records_dev, float* m_dev, float* v_
  * that differs from the scene's (this call never makes a new scene).  GS_ERR_NO_SCENE: no gaussians uploaded yet. */
 int gs_upload_rows_device(gs_ctx* ctx, const void* aos336_dev, uint32_t n,
                           const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows);
+
+/* The raw parameter space (no reference counterpart): what a .ply stores and the INRIA trainer optimises, next to the
+ * record space the frame reads.  A raw array is float[n][84] in the record's own layout: the same 59 floats are fields, the
+ * same 25 are never read or written by any call below.  It differs from a record in three places: floats 4..6 are
+ * log-scales, float 15 is the logit of the opacity, floats 8..11 are the rotation before normalisation (the record's
+ * component order).  act(raw) is the record it stands for -- float32, never contracted, in exactly this order:
+ *   s_k = E(raw[4 + k])                                                                    k = 0, 1, 2
+ *   o   = 1.0f / (1.0f + E(-raw[15]))
+ *   t_i = raw[8 + i] * raw[8 + i];  inv = 1.0f / sqrtf((t0 + t1) + (t2 + t3));  q_i = raw[8 + i] * inv
+ *   every other field: the same bits
+ * E is the pinned exp of the frame's blend (exp2(x log2 e) with both clamps, t in [-126, 126], and a degree-6 polynomial;
+ * within 1e-6 relative of exp on [-20, 6], and the sigmoid built from it within 1e-6 relative on [-20, 20]).  E(-inf) =
+ * 2^-126 and E(+inf) = 2^126, the clamps; a NaN goes to the lower clamp, 2^-126, and is NOT propagated.  The rotation is
+ * the loader's expression (glm::normalize), association included: a raw rotation written to a .ply by gs_write_ply and
+ * loaded again gives the record's rotation bit for bit.  A zero rotation gives NaN, as it does in the loader.  act is
+ * restated exactly by NumPy float32 with that exp (tests/test_raw_cpu.py).
+ *
+ * All four device calls work on the CALLER's device arrays, are enqueued on the context's stream without a host sync, need
+ * no scene and no resolution, keep no state in the library and are bitwise reproducible (gs_raw_from_records_device: up to
+ * the device's logf).  Callers detect them, and gs_write_ply, by their symbols (GS_API_VERSION is unchanged).
+ *
+ * gs_default_adam_params_raw: gs_default_adam_params with every lo = -inf and every hi = +inf -- in raw space the INRIA
+ * rates are the right ones and nothing needs a clamp.
+ *
+ * gs_adam_rows_raw_device: gs_adam_rows_device in raw space, in one kernel.  The listing rules are the same: rows
+ * i < min(*count_dev, max_rows), an ids[i] >= n compared and never dereferenced, distinct ids, the grid sized from
+ * max_rows, count_dev never read by the host, max_rows == 0: GS_OK and nothing launched.  grad_rows[i] is dL/d(record
+ * ids[i]) as gs_backward_visible_device leaves it: with respect to the record's own floats, the rotation as getRotMat
+ * reads it.  Per listed row, with g = the gradient row and the record's CURRENT values (what the frame rasterised):
+ *   position, SH:  gt = g
+ *   scale k:       gt = g[4 + k] * records[4 + k]
+ *   opacity:       gt = (g[15] * o) * (1.0f - o)                                           o = records[15]
+ *   rotation:      inv = 1.0f / sqrtf((t0 + t1) + (t2 + t3)) of the OLD raw[8..11];        q = records[8..11]
+ *                  d = (g8 * q0 + g9 * q1) + (g10 * q2 + g11 * q3);   gt_i = (g[8 + i] - q_i * d) * inv
+ * then the rule of gs_adam_rows_device, exactly as it stands, on (raw, m, v, gt) -- the group's step, lo and hi apply to
+ * the RAW value --, then records[fields] = act(raw'), the identity fields receiving the bits of raw'.  The chain stands on
+ * records == act(raw) in the listed rows, which every call of this block keeps.  Only the 59 fields of listed rows are
+ * touched, in raw, m, v and records; ids, grad_rows and count_dev are only read.
+ * GS_ERR_INVALID: everything gs_adam_rows_device refuses, with its words behind this call's name, a NULL raw, and a records
+ * that shares bytes with raw, m or v.
+ *
+ * gs_records_from_raw_device: records[fields] = act(raw) for every row g < n.
+ * gs_raw_from_records_device: the inverse, with the device's logf (1 ulp), otherwise float32 in this order:
+ *   raw_s = logf(s < FLT_MIN ? FLT_MIN : s)
+ *   c = o < 0x1p-24f ? 0x1p-24f : (o > 0x1.fffffep-1f ? 0x1.fffffep-1f : o);   raw_o = logf(c / (1.0f - c))
+ *   rotation and every other field: the same bits
+ * The two clamps keep a record opacity of exactly 0 or 1 trainable: |logit| <= 16.7.  act of the result is the record
+ * again up to the rounding of one log and one exp.  Both refuse (GS_ERR_INVALID) a NULL array, n == 0 and arrays that
+ * share bytes.
+ *
+ * gs_reset_opacity_raw_device: the INRIA opacity reset.  For every g < n with records[g][15] > max_opacity:
+ * raw[g][15] = L, L = (float)log((double)max_opacity / (1.0 - (double)max_opacity)) computed on the host, and
+ * records[g][15] = 1.0f / (1.0f + E(-L)); for every g, reset or not, m[g][15] = v[g][15] = 0.  m and v may be NULL together.
+ * No other float is touched.  The caller follows it with a full upload (gs_upload_gaussians_device).  GS_ERR_INVALID: a
+ * NULL raw or records, one of m and v without the other, n == 0, a max_opacity that fails 0 < max_opacity < 1. */
+void gs_default_adam_params_raw(gs_adam_params* p);
+int gs_adam_rows_raw_device(gs_ctx* ctx, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                            const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev,
+                            uint32_t max_rows, const gs_adam_params* p);
+int gs_records_from_raw_device(gs_ctx* ctx, const float* raw_dev, float* records_dev, uint32_t n);
+int gs_raw_from_records_device(gs_ctx* ctx, const float* records_dev, float* raw_dev, uint32_t n);
+int gs_reset_opacity_raw_device(gs_ctx* ctx, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                                float max_opacity);
 
 /* Adaptive density control (no reference counterpart): the statistics of a training step, and the new cloud -- clone where
  * the screen gradient is large and the splat small, split where it is large, prune what is transparent or huge.  All arrays

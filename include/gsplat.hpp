@@ -214,6 +214,38 @@ public:
         return rc;
     }
 
+    // The raw parameter space (gsplat.h, gs_adam_rows_raw_device and the calls around it): Adam on log-scales, the logit of
+    // the opacity and the rotation before normalisation, with the listed rows of records rewritten as act(raw); the two
+    // conversions; the INRIA opacity reset.  All DEVICE pointers, enqueued on the context's stream without waiting.
+    static gs_adam_params defaultAdamParamsRaw() {
+        gs_adam_params p;
+        gs_default_adam_params_raw(&p);
+        return p;
+    }
+    int adamRowsRaw(float* raw, float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
+                    const uint32_t* count, uint32_t max_rows, const gs_adam_params& params) {
+        const int rc = gs_adam_rows_raw_device(ctx_, raw, records, m, v, n, ids, grad_rows, count, max_rows, &params);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int recordsFromRaw(const float* raw, float* records, uint32_t n) {
+        const int rc = gs_records_from_raw_device(ctx_, raw, records, n);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int rawFromRecords(const float* records, float* raw, uint32_t n) {
+        const int rc = gs_raw_from_records_device(ctx_, records, raw, n);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int resetOpacityRaw(float* raw, float* records, float* m, float* v, uint32_t n, float max_opacity = 0.01f) {
+        const int rc = gs_reset_opacity_raw_device(ctx_, raw, records, m, v, n, max_opacity);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    // rows [n][84] on the HOST -> a .ply gs_load_ply reads; space = GS_PLY_FROM_RECORDS or GS_PLY_FROM_RAW (no context needed)
+    static int writePly(const char* path, const float* rows, uint32_t n, uint32_t space) { return gs_write_ply(path, rows, n, space); }
+
     // Adaptive density control (gsplat.h, gs_densify_stats_device and gs_densify_device): the statistics of the step just
     // differentiated into the caller's DEVICE arrays [n], and the new cloud -- clones and split children beside their
     // parents -- into records_out / m_out / v_out [max_out][84]; counts_out[4] (device) = outputs, cloned, split, pruned.

@@ -6,9 +6,11 @@ gs_set_stream; every repetition is bracketed by HIP events (one pair per call, s
 alone), the two routes alternate repetition by repetition so that both see the same neighbours, and the means are over
 --iters repetitions after --warmup.  Bytes per row are what the Adam kernel has to move: the gradient's 59 fields read, and
 the 59 fields of records, m and v read and written (7 x 236); the upload reads a record (336) and writes 60 plane values
-(240), and both uploads then read 16 bytes per splat of the scene for the block bounds.
+(240), and both uploads then read 16 bytes per splat of the scene for the block bounds.  The raw-space step,
+gs_adam_rows_raw_device, runs beside the record-space one on the same rows in the same repetitions (--out-raw): it also
+writes the record's fields and reads its scale, rotation and opacity again (8 x 236 + 32 bytes per row).
 
-    python tools/adam_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/adam_cost.txt]"""
+    python tools/adam_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/adam_cost.txt] [--out-raw profiles/adam_raw_cost.txt]"""
 import argparse, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,6 +20,7 @@ ap.add_argument("--config", default="C")
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adam_cost.txt"))
+ap.add_argument("--out-raw", default=os.path.join(ROOT, "profiles", "adam_raw_cost.txt"))
 a = ap.parse_args()
 
 import numpy as np
@@ -26,6 +29,7 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import synth
 
 ADAM_BYTES_PER_ROW = 7 * 59 * 4
+ADAM_RAW_BYTES_PER_ROW = 8 * 59 * 4 + (3 + 4 + 1) * 4      # + the record's fields written, its scale, rotation and opacity read
 UPLOAD_BYTES_PER_ROW = 336 + 60 * 4
 
 aos, cfg = synth.generate_config(a.config)
@@ -81,15 +85,32 @@ def adam():
                      rows_listed, gs.default_adam_params(step=step[0]))
 
 
+# the raw route (gs_adam_rows_raw_device) on the same rows: its own raw / records / m / v, records == act(raw) from the start
+raw, raw_records = torch.zeros_like(records), torch.tensor(aos, device=dev)
+raw_m, raw_v = torch.zeros_like(records), torch.zeros_like(records)
+torch.cuda.synchronize()
+r.rawFromRecordsDevice(raw_records.data_ptr(), raw.data_ptr(), n)
+r.recordsFromRawDevice(raw.data_ptr(), raw_records.data_ptr(), n)
+r.synchronize()
+raw_step = [0]
+
+
+def adam_raw():
+    raw_step[0] += 1
+    r.adamRowsRawDevice(raw.data_ptr(), raw_records.data_ptr(), raw_m.data_ptr(), raw_v.data_ptr(), n, ids.data_ptr(), rows.data_ptr(),
+                        count.data_ptr(), rows_listed, gs.default_adam_params(space="raw", step=raw_step[0]))
+
+
 new_route = [adam, lambda: r.uploadRowsDevice(records.data_ptr(), n, ids.data_ptr(), count.data_ptr(), rows_listed)]
 old_route = [opt.step, lambda: r.uploadDevice(leaf.data_ptr(), n)]
-new_ms, old_ms = [], []
+new_ms, old_ms, raw_ms = [], [], []
 with torch.cuda.stream(stream):
     for k in range(a.warmup + a.iters):
-        t_new, t_old = timed(new_route), timed(old_route)
+        t_new, t_raw, t_old = timed(new_route), timed([adam_raw]), timed(old_route)
         if k >= a.warmup:
             new_ms.append(t_new)
             old_ms.append(t_old)
+            raw_ms.append(t_raw)
 torch.cuda.synchronize()
 r.setStream(None)
 r.cleanup()
@@ -121,3 +142,36 @@ with open(a.out, "w") as f:
             "# `iters` repetitions after `warmup`.  GPU times; the host-side wait for the count that the documented route also needs\n"
             "# (gs_visible_count, to size the COO tensor) is not in them.  Recorded numbers, not a bound.\n")
     f.write(json.dumps(line) + "\n")
+
+# the raw step beside the record step, the same rows in the same run
+raw_ms = np.array(raw_ms)
+raw_mean = mean(raw_ms[:, 0])
+raw_line = {"config": a.config, "width": w, "height": h, "gaussians": n, "rows": rows_listed, "iters": a.iters, "warmup": a.warmup,
+            "adam_rows_raw_ms_mean": raw_mean, "adam_rows_raw_ms_min_max": spread(raw_ms[:, 0]),
+            "adam_raw_bytes_per_row": ADAM_RAW_BYTES_PER_ROW,
+            "adam_raw_achieved_tbytes_per_s": round(rows_listed * ADAM_RAW_BYTES_PER_ROW / (raw_mean * 1e-3) / 1e12, 3),
+            "adam_rows_ms_mean": adam_ms, "adam_rows_ms_min_max": spread(new_ms[:, 0]), "adam_bytes_per_row": ADAM_BYTES_PER_ROW,
+            "adam_achieved_tbytes_per_s": line["adam_achieved_tbytes_per_s"],
+            "raw_over_records_ms": round(raw_mean / adam_ms, 3),
+            "raw_over_records_bytes": round(ADAM_RAW_BYTES_PER_ROW / ADAM_BYTES_PER_ROW, 3)}
+# the finding, from the two ratios: a kernel that moves its bytes at (nearly) its neighbour's rate is bound by them as that one is
+rate_ratio = raw_line["adam_raw_achieved_tbytes_per_s"] / raw_line["adam_achieved_tbytes_per_s"]
+raw_line["raw_rate_over_records_rate"] = round(rate_ratio, 3)
+raw_line["raw_is_bandwidth_bound_like_records"] = bool(rate_ratio >= 0.9)
+finding = (f"# Finding of this run: the times are in the ratio {raw_line['raw_over_records_ms']}, the bytes in the ratio "
+           f"{raw_line['raw_over_records_bytes']}; the raw kernel moves {raw_line['adam_raw_achieved_tbytes_per_s']} TB/s, "
+           f"{round(100 * rate_ratio, 1)} % of the record kernel's {raw_line['adam_achieved_tbytes_per_s']} TB/s in the same run: ")
+finding += ("the exps, the division and the square root did not make it VALU-bound.\n" if rate_ratio >= 0.9 else
+            "well below what the bytes say -- the arithmetic (four exps, a division and a square root per row) shows; "
+            "look at its VALU busy before trusting the byte count.\n")
+print(json.dumps(raw_line), flush=True)
+os.makedirs(os.path.dirname(os.path.abspath(a.out_raw)), exist_ok=True)
+with open(a.out_raw, "w") as f:
+    f.write("# tools/adam_cost.py on one MI355X: gs_adam_rows_raw_device beside gs_adam_rows_device, the same listed rows in the same run,\n"
+            "# the calls alternating; HIP events around every call, means (and min, max) over `iters` repetitions after `warmup`.\n"
+            "# Bytes per row: the raw kernel reads the gradient's 59 fields, reads and writes the 59 fields of raw, m and v, writes the\n"
+            "# record's 59 fields (8 x 236) and reads the record's scale, rotation and opacity again (32); the record kernel moves 7 x 236.\n"
+            "# It also evaluates four pinned exps per row.  Recorded numbers, not a bound; both kernels' times and the\n"
+            "# ratios are of this one run.\n")
+    f.write(finding)
+    f.write(json.dumps(raw_line) + "\n")

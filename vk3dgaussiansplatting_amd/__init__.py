@@ -19,6 +19,7 @@ from ._lib import (GS_OK, GS_WARN_OVERFLOW, GS_RENDER_EXACT, GS_RENDER_FAST, GS_
                    BUF_COUNT, BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE)
 from .renderer import (Camera, GpuSort, GsplatError, PlyScene, RadixSort, RadixSort8, Renderer, ResourceManager,
                        Scene, SimpleTestGaussiansScene, SphericalHarmonicsMode, TestSortScene,
-                       default_adam_params, makeGaussian, saveImage, savePpm)
+                       default_adam_params, makeGaussian, saveImage, savePpm, write_ply)
+from ._lib import GS_PLY_FROM_RECORDS, GS_PLY_FROM_RAW
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -43,6 +43,7 @@ RECORD_BYTES = 336
 # field groups of gs_adam_params (GS_ADAM_*): the 59 floats of the 84-float record gs_backward gives gradients to
 GS_ADAM_POSITION, GS_ADAM_SCALE, GS_ADAM_ROTATION, GS_ADAM_SH_DC, GS_ADAM_OPACITY, GS_ADAM_SH_REST = range(6)
 GS_ADAM_GROUPS = 6
+GS_PLY_FROM_RECORDS, GS_PLY_FROM_RAW = 0, 1   # gs_write_ply `space`: rows as the frame reads them / in the raw space
 # group of every float of a record; -1: one of the 25 floats gs_adam_rows_device and gs_upload_rows_device never touch
 ADAM_GROUP_OF_FLOAT = tuple(
     [GS_ADAM_POSITION] * 3 + [-1] + [GS_ADAM_SCALE] * 3 + [-1] + [GS_ADAM_ROTATION] * 4 + [GS_ADAM_SH_DC] * 3 + [GS_ADAM_OPACITY]
@@ -159,6 +160,8 @@ EXPORTS = [
     "gs_photometric_loss", "gs_photometric_loss_device",
     "gs_default_adam_params", "gs_adam_rows_device", "gs_upload_rows_device",
     "gs_densify_stats_device", "gs_default_densify_params", "gs_densify_device",
+    "gs_default_adam_params_raw", "gs_adam_rows_raw_device", "gs_records_from_raw_device", "gs_raw_from_records_device",
+    "gs_reset_opacity_raw_device", "gs_write_ply",
 ]
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -296,6 +299,13 @@ def lib() -> C.CDLL:
     L.gs_default_densify_params.argtypes = [C.POINTER(GsDensifyParams)]
     L.gs_default_densify_params.restype = None
     L.gs_densify_device.argtypes = [ctxp, vp, vp, vp, u32, vp, vp, vp, C.POINTER(GsDensifyParams), vp, vp, vp, u32, vp]
+    L.gs_default_adam_params_raw.argtypes = [C.POINTER(GsAdamParams)]
+    L.gs_default_adam_params_raw.restype = None
+    L.gs_adam_rows_raw_device.argtypes = [ctxp, vp, vp, vp, vp, u32, vp, vp, vp, u32, C.POINTER(GsAdamParams)]
+    L.gs_records_from_raw_device.argtypes = [ctxp, vp, vp, u32]
+    L.gs_raw_from_records_device.argtypes = [ctxp, vp, vp, u32]
+    L.gs_reset_opacity_raw_device.argtypes = [ctxp, vp, vp, vp, vp, u32, f32]
+    L.gs_write_ply.argtypes = [C.c_char_p, vp, u32, u32]
     _lib = L
     _check_hip_runtime(L)
     return L

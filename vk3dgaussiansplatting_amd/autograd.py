@@ -28,6 +28,9 @@ gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one 
     opt = VisibleAdam(records, renderer=r, track_density=True)                  # + gs_densify_stats_device in every step
     n_out, cloned, split, pruned = opt.densify(grad_threshold=2e-4)             # opt.records / m / v are the new cloud
 
+    opt = VisibleAdam(records, renderer=r, space="raw")                         # Adam on log-scale, logit-opacity, raw rotation
+    opt.reset_opacity(0.01); opt.save_ply("trained.ply")                        # the INRIA reset; a .ply gs_load_ply reads
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -38,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager, default_adam_params
+from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager, default_adam_params, write_ply
 
 
 def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
@@ -182,16 +185,25 @@ class VisibleAdam:
     the next step uploads everything.
 
     track_density=True: the optimiser also owns grad_accum, seen and max_radius (zeros of N), step() enqueues
-    gs_densify_stats_device right behind the backward, and densify() replaces the cloud."""
+    gs_densify_stats_device right behind the backward, and densify() replaces the cloud.
+
+    space="raw": the optimiser moves self.raw -- log-scales, the logit of the opacity, the rotation before normalisation:
+    the parameters a .ply stores, made from records by gs_raw_from_records_device -- and keeps records == act(raw) bit for
+    bit (records is rewritten once, here, as act(raw): its scales and opacity move by the rounding of one log and one
+    exp, its rotation becomes unit).  params default to default_adam_params(space="raw"): the INRIA rates, no clamps.
+    step() is the same chain with gs_adam_rows_raw_device as its last call; reset_opacity() and save_ply() complete the
+    trainer.  space="records" (the default) moves the record's own values."""
 
     def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, track_density: bool = False,
-                 **params):
+                 space: str = "records", **params):
         if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
             raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
         if not records.is_cuda or not records.is_contiguous() or records.requires_grad:
             raise ValueError("records must be a contiguous tensor on the GPU that does not require grad")
-        self.records, self.renderer = records, renderer
-        self.params = default_adam_params(**params)
+        if space not in ("records", "raw"):
+            raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
+        self.records, self.renderer, self.space = records, renderer, space
+        self.params = default_adam_params(space=space, **params)
         dev, n = records.device, records.shape[0]
         self.max_rows = n if max_rows is None else int(max_rows)
         self._rows_follow_n = max_rows is None
@@ -206,8 +218,19 @@ class VisibleAdam:
         self.t = 0
         self._full_upload = True
         self.stream = torch.cuda.Stream(device=dev)
+        self.raw = torch.zeros_like(records) if space == "raw" else None
         torch.cuda.synchronize(dev)                       # the zeros above; gs_set_stream waits for the context's stream itself
         renderer.setStream(self.stream.cuda_stream)
+        if space == "raw":
+            self._raw_from_records()
+            self.stream.synchronize()                     # once: records were rewritten, and the caller may read them anywhere
+
+    def _raw_from_records(self):
+        """self.raw <- the inverse of act on self.records, then self.records <- act(self.raw): from here on
+        records == act(raw) bit for bit, which the chain of every step stands on.  On self.stream."""
+        r, n = self.renderer, self.records.shape[0]
+        r.rawFromRecordsDevice(self.records.data_ptr(), self.raw.data_ptr(), n)
+        r.recordsFromRawDevice(self.raw.data_ptr(), self.records.data_ptr(), n)
 
     def _zero_stats(self, n: int, dev):
         self.grad_accum = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -219,7 +242,10 @@ class VisibleAdam:
         default_densify_params()'s overrides) -> (n_out, cloned, split, pruned).  self.records, self.m and self.v become new
         tensors of n_out rows, the children beside their parents; the statistics start again from zero; ids, rows and max_rows
         follow the new size (a max_rows given to the constructor stays); the next step uploads the whole cloud as a new scene.
-        t and the hyper-parameters stay.  Reading the four counts is the one host wait of this rare event."""
+        t and the hyper-parameters stay.  Reading the four counts is the one host wait of this rare event.
+        space="raw": density control runs on the records, then raw is made again from the new records and the records from
+        that raw.  A kept row's raw value therefore moves by the rounding of one log and one exp -- far below a step, at a
+        rare event -- and a split child starts from log(s / split_shrink)."""
         if not self.track_density:
             raise RuntimeError("VisibleAdam(track_density=True) gathers the statistics densify() goes by")
         p = _lib.default_densify_params(**params)
@@ -235,6 +261,9 @@ class VisibleAdam:
             if n_out == 0:
                 raise RuntimeError("densify() would prune every gaussian")
             self.records, self.m, self.v = (t[:n_out].clone() for t in out)
+            if self.space == "raw":
+                self.raw = torch.zeros_like(self.records)
+                self._raw_from_records()
             self._zero_stats(n_out, dev)
             if self._rows_follow_n:
                 self.max_rows = n_out
@@ -282,6 +311,29 @@ class VisibleAdam:
                                      self.seen.data_ptr(), self.max_radius.data_ptr())
             self.t += 1
             self.params.step = self.t
-            r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
-                             self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+            if self.space == "raw":
+                r.adamRowsRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n,
+                                    self.ids.data_ptr(), self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+            else:
+                r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
+                                 self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
         return numbers
+
+    def reset_opacity(self, max_opacity: float = 0.01):
+        """The INRIA opacity reset (space="raw" only; gs_reset_opacity_raw_device): every opacity above max_opacity goes back
+        to it, in records and as its logit in raw, and the opacity's moments of every row start again from zero.  The next
+        step uploads the whole cloud.  Nothing is waited for."""
+        if self.space != "raw":
+            raise RuntimeError("reset_opacity() needs VisibleAdam(space='raw'); in record space clamp records[:, 15] and call reset_upload()")
+        self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
+        self.renderer.resetOpacityRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                            self.records.shape[0], max_opacity)
+        self.reset_upload()
+
+    def save_ply(self, path: str):
+        """The cloud as a .ply the loader reads (gs_write_ply).  space="raw": the raw rows as they are, so the file holds
+        the trained parameters exactly; space="records": log and logit of the records.  Waits for self.stream and copies
+        the rows to the host."""
+        self.stream.synchronize()
+        rows = self.raw if self.space == "raw" else self.records
+        write_ply(path, rows.cpu().numpy(), self.space)

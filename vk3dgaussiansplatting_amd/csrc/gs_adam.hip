@@ -3,28 +3,11 @@
 // gradient row is read and the row's 59 fields of records, m and v are read and written (7 x 236 bytes; the other 25
 // floats of a row are never touched, so nothing wider than the fields is loaded or stored).
 #include "../../include/gsplat.h"
+#include "gs_adam_field.h"
 #include "gs_device_utils.h"
 #include "gs_internal.h"
 
 namespace gs {
-
-namespace {
-
-__device__ __forceinline__ float pick(const float (&t)[6], uint32_t g) {
-    return g == 0u ? t[0] : g == 1u ? t[1] : g == 2u ? t[2] : g == 3u ? t[3] : g == 4u ? t[4] : t[5];
-}
-
-// One field.  The order of the operations is the contract of the header (bitwise reproducible: the file is built with
-// -ffp-contract=off and correctly rounded division and square root).
-__device__ __forceinline__ void adam_field(float& p, float& m, float& v, float g, const AdamStep& a, float step, float lo,
-                                           float hi) {
-    m = a.beta1 * m + a.c1 * g;
-    v = a.beta2 * v + (a.c2 * g) * g;
-    const float q = p - step * (m / (sqrtf(v) + a.eps));
-    p = q < lo ? lo : (q > hi ? hi : q);        // every comparison with a NaN is false: a NaN stays
-}
-
-}  // namespace
 
 // A lane per (listed row, group of four floats): the lanes of a row read 304 consecutive bytes of the gradient row and of
 // the three rows of splat ids[row], ascending.  x, y, z of a group are fields of one GS_ADAM_* group in every group; w is a

@@ -725,12 +725,8 @@ void gs_default_adam_params(gs_adam_params* p) {
     p->lr[GS_ADAM_SH_REST] = 1.25e-4f;
 }
 
-int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_dev, uint32_t n, const uint32_t* ids_dev,
-                        const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, const gs_adam_params* p) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_adam_rows_device: ";
-    if (max_rows && (!records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
-        return fail(c, GS_ERR_INVALID, who + "null records, m, v, ids, grad_rows or count with max_rows > 0");
+// what gs_adam_rows_device and gs_adam_rows_raw_device check of their parameters, and the step they hand the kernel
+static int adam_step_of(gs_ctx* c, const std::string& who, uint32_t n, const gs_adam_params* p, AdamStep& a) {
     if (!p) return fail(c, GS_ERR_INVALID, who + "null gs_adam_params");
     if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
     if (p->struct_size != sizeof(gs_adam_params))
@@ -739,7 +735,6 @@ int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_de
     if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f) || !(p->beta2 >= 0.0f && p->beta2 < 1.0f))
         return fail(c, GS_ERR_INVALID, who + "beta1 and beta2 must be in [0, 1)");
     if (!(p->eps >= 0.0f) || !std::isfinite(p->eps)) return fail(c, GS_ERR_INVALID, who + "eps must be finite and not negative");
-    AdamStep a;
     a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps;
     a.c1 = 1.0f - p->beta1; a.c2 = 1.0f - p->beta2;
     // the bias correction of step t in double, rounded once per group
@@ -752,10 +747,87 @@ int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_de
         if (!std::isfinite(a.step[g])) return fail(c, GS_ERR_INVALID, who + "lr times the bias correction is not a finite float");
         a.lo[g] = p->lo[g]; a.hi[g] = p->hi[g];
     }
+    return GS_OK;
+}
+
+int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_dev, uint32_t n, const uint32_t* ids_dev,
+                        const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, const gs_adam_params* p) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_adam_rows_device: ";
+    if (max_rows && (!records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
+        return fail(c, GS_ERR_INVALID, who + "null records, m, v, ids, grad_rows or count with max_rows > 0");
+    AdamStep a;
+    if (int r = adam_step_of(c, who, n, p, a)) return r;
     if (!max_rows) return GS_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     launch_adam_rows(records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
     return check_launch(c, "gs_adam_rows_device");
+}
+
+// ---- the raw parameter space (gs_raw.hip) ----
+
+// two arrays of `bytes` bytes share at least one (a null array shares nothing)
+static bool arrays_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a && b && bytes && a0 < b0 + bytes && b0 < a0 + bytes;
+}
+
+void gs_default_adam_params_raw(gs_adam_params* p) {
+    if (!p) return;
+    gs_default_adam_params(p);
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
+}
+
+int gs_adam_rows_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                            const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows,
+                            const gs_adam_params* p) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_adam_rows_raw_device: ";
+    if (max_rows && (!raw_dev || !records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
+        return fail(c, GS_ERR_INVALID, who + "null raw, records, m, v, ids, grad_rows or count with max_rows > 0");
+    AdamStep a;
+    if (int r = adam_step_of(c, who, n, p, a)) return r;
+    const size_t bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES;
+    if (arrays_overlap(records_dev, raw_dev, bytes) || arrays_overlap(records_dev, m_dev, bytes) || arrays_overlap(records_dev, v_dev, bytes))
+        return fail(c, GS_ERR_INVALID, who + "records aliases raw, m or v");
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_adam_rows_raw(raw_dev, records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
+    return check_launch(c, "gs_adam_rows_raw_device");
+}
+
+static int convert_space(gs_ctx* c, const char* name, const float* src, float* dst, uint32_t n, bool to_raw) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = std::string(name) + ": ";
+    if (!src || !dst) return fail(c, GS_ERR_INVALID, who + "null raw or records");
+    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
+    if (arrays_overlap(src, dst, (size_t)n * GS_GAUSSIAN_RECORD_BYTES)) return fail(c, GS_ERR_INVALID, who + "raw aliases records");
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_convert_space(src, dst, n, to_raw, c->stream);
+    return check_launch(c, name);
+}
+
+int gs_records_from_raw_device(gs_ctx* c, const float* raw_dev, float* records_dev, uint32_t n) {
+    return convert_space(c, "gs_records_from_raw_device", raw_dev, records_dev, n, false);
+}
+
+int gs_raw_from_records_device(gs_ctx* c, const float* records_dev, float* raw_dev, uint32_t n) {
+    return convert_space(c, "gs_raw_from_records_device", records_dev, raw_dev, n, true);
+}
+
+int gs_reset_opacity_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                                float max_opacity) {
+    if (!c) return GS_ERR_INVALID;
+    const std::string who = "gs_reset_opacity_raw_device: ";
+    if (!raw_dev || !records_dev) return fail(c, GS_ERR_INVALID, who + "null raw or records");
+    if (!m_dev != !v_dev) return fail(c, GS_ERR_INVALID, who + "m and v must be given together or not at all");
+    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
+    if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, GS_ERR_INVALID, who + "max_opacity must lie strictly between 0 and 1");
+    const float logit = (float)std::log((double)max_opacity / (1.0 - (double)max_opacity));
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_reset_opacity_raw(raw_dev, records_dev, m_dev, v_dev, n, max_opacity, logit, c->stream);
+    return check_launch(c, "gs_reset_opacity_raw_device");
 }
 
 static hipError_t alloc_outputs(gs_ctx* c);

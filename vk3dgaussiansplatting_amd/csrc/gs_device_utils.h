@@ -87,6 +87,24 @@ __device__ __forceinline__ uint32_t f2u_sat(float x) {
     return (uint32_t)x;
 }
 
+// pinned exp: identical operation sequence to gso_exp() in oracle/gs_oracle.c, for every float: both clamps, so positive
+// arguments are served too (t = +-126 at the ends; a NaN fails `t > -126` and goes to the lower clamp, 2^-126)
+__device__ __forceinline__ float exp_pinned(float x) {
+    float t = x * 0x1.715476p+0f;
+    t = t > -126.0f ? t : -126.0f;
+    t = t < 126.0f ? t : 126.0f;
+    const float n = __builtin_rintf(t);
+    const float r = t - n;
+    float p = 0x1.42059ap-13f;
+    p = __builtin_fmaf(p, r, 0x1.5f3e12p-10f);
+    p = __builtin_fmaf(p, r, 0x1.3b2d40p-7f);
+    p = __builtin_fmaf(p, r, 0x1.c6aeeap-5f);
+    p = __builtin_fmaf(p, r, 0x1.ebfbdcp-3f);
+    p = __builtin_fmaf(p, r, 0x1.62e430p-1f);
+    p = __builtin_fmaf(p, r, 1.0f);
+    return __builtin_ldexpf(p, (int)n);
+}
+
 // exp_pinned_live of gs_render.hip (its scalar form, shared with the blend backward of gs_backward.hip): the pinned exp of
 // oracle/gs_oracle.h, bit for bit, for every x <= 0 (see exp_pinned2_live in gs_render.hip)
 __device__ __forceinline__ float exp_pinned_live(float x) {            // the scalar form of exp_pinned2_live

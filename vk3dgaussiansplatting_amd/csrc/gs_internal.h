@@ -333,6 +333,16 @@ struct AdamStep {
 };
 void launch_adam_rows(float* records, float* m, float* v, uint32_t n, const uint32_t* ids, const float* grad_rows,
                       const uint32_t* count, uint32_t max_rows, const AdamStep& a, hipStream_t stream);
+// The raw parameter space (gs_raw.hip).  launch_adam_rows_raw: launch_adam_rows on raw / m / v with the chain from the record
+// gradient in front and records[fields] = act(raw') behind.  launch_convert_space: dst = act(src) on the fields of n rows, or
+// with to_raw its inverse.  launch_reset_opacity_raw: float 15 of every row (m, v: both null or neither); logit = the raw
+// value a reset opacity gets.
+void launch_adam_rows_raw(float* raw, float* records, float* m, float* v, uint32_t n, const uint32_t* ids,
+                          const float* grad_rows, const uint32_t* count, uint32_t max_rows, const AdamStep& a,
+                          hipStream_t stream);
+void launch_convert_space(const float* src, float* dst, uint32_t n, bool to_raw, hipStream_t stream);
+void launch_reset_opacity_raw(float* raw, float* records, float* m, float* v, uint32_t n, float max_opacity, float logit,
+                              hipStream_t stream);
 // gs_densify_stats_device (gs_densify.hip): the listed ids of the frame, what its backward left, and the caller's arrays
 struct DensifyStatsArgs {
     const uint32_t* ids;

@@ -278,9 +278,79 @@ int convert(const char* path, float* records_out, size_t max_records, uint32_t& 
     });
 }
 
+// ---- the output side: 84-float rows -> an INRIA .ply (no reference counterpart) ------------------------------------------
+
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ != __ORDER_LITTLE_ENDIAN__
+#error "gs_write_ply writes the host's floats as binary_little_endian"
+#endif
+
+constexpr int kPlyProps = 62;     // x y z nx ny nz f_dc_0..2 f_rest_0..44 opacity scale_0..2 rot_0..3
+
+std::string ply_header(uint32_t n) {
+    std::string h = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(n) + "\n";
+    auto prop = [&](const std::string& name) { h += "property float " + name + "\n"; };
+    for (const char* name : {"x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"}) prop(name);
+    for (int i = 0; i < 45; ++i) prop("f_rest_" + std::to_string(i));
+    for (const char* name : {"opacity", "scale_0", "scale_1", "scale_2", "rot_0", "rot_1", "rot_2", "rot_3"}) prop(name);
+    return h + "end_header\n";
+}
+
+// the inverse of convert_row for one row r (record or raw: `raw` says which) -> the 62 values of a vertex
+inline void unconvert_row(const float* r, bool raw, float* o) {
+    o[0] = -r[0]; o[1] = -r[1]; o[2] = r[2];
+    o[3] = 0.0f; o[4] = 0.0f; o[5] = 0.0f;                                                     // normals
+    o[6] = r[12]; o[7] = r[13]; o[8] = r[14];
+    for (int c = 0; c < 15; ++c)
+        for (int ch = 0; ch < 3; ++ch) o[9 + c + 15 * ch] = r[16 + 4 * c + ch];
+    if (raw) {
+        o[54] = r[15];
+        for (int k = 0; k < 3; ++k) o[55 + k] = r[4 + k];
+    } else {                                                                                   // the clamps of gs_raw_from_records_device
+        const float op = r[15];
+        const float c = op < 0x1p-24f ? 0x1p-24f : (op > 0x1.fffffep-1f ? 0x1.fffffep-1f : op);
+        o[54] = std::log(c / (1.0f - c));
+        for (int k = 0; k < 3; ++k) {
+            const float s = r[4 + k];
+            o[55 + k] = std::log(s < std::numeric_limits<float>::min() ? std::numeric_limits<float>::min() : s);
+        }
+    }
+    o[58] = r[10]; o[59] = -r[11]; o[60] = -r[8]; o[61] = -r[9];
+}
+
+// Rows in the order given, a chunk of a few MB at a time: nothing of the cloud's size is held beside the caller's array.
+int write_ply(const char* path, const float* rows, uint32_t n, bool raw, std::string& err) {
+    const std::string head = ply_header(n);
+    const size_t chunk_rows = 16384;                                                            // 4 MB of output
+    std::vector<float> buf(std::min<size_t>(chunk_rows, n) * kPlyProps);
+    std::FILE* f = std::fopen(path, "wb");                                                      // nothing below throws
+    if (!f) { err = std::string("File cannot be created: ") + path; return GS_ERR_IO; }
+    bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
+    for (size_t i0 = 0; ok && i0 < n; i0 += chunk_rows) {
+        const size_t count = std::min<size_t>(chunk_rows, n - i0);
+        for (size_t i = 0; i < count; ++i) unconvert_row(rows + (i0 + i) * 84, raw, buf.data() + i * kPlyProps);
+        ok = std::fwrite(buf.data(), sizeof(float), count * kPlyProps, f) == count * kPlyProps;
+    }
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok) { err = std::string("File could not be written in full: ") + path; return GS_ERR_IO; }
+    return GS_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+int gs_write_ply(const char* path, const float* rows, uint32_t n, uint32_t space) {
+    if (!path || !rows || n == 0 || (space != GS_PLY_FROM_RECORDS && space != GS_PLY_FROM_RAW)) return GS_ERR_INVALID;
+    try {
+        return write_ply(path, rows, n, space == GS_PLY_FROM_RAW, g_ply_error);
+    } catch (const std::exception& ex) {
+        g_ply_error = std::string("ply writing failed: ") + ex.what();
+        return GS_ERR_IO;
+    } catch (...) {
+        g_ply_error = "ply writing failed";
+        return GS_ERR_IO;
+    }
+}
 
 // nothing may leave an extern "C" function as an exception (std::bad_alloc / length_error on a hostile header)
 static int convert_noexcept(const char* path, float* out, size_t max_records, uint32_t& n, std::vector<float>* grow) {

@@ -74,22 +74,7 @@ __global__ __launch_bounds__(256) void k_find_ranges(const uint32_t* __restrict_
     }
 }
 
-// pinned exp: identical operation sequence to gso_exp() in oracle/gs_oracle.c
-__device__ __forceinline__ float exp_pinned(float x) {
-    float t = x * 0x1.715476p+0f;
-    t = t > -126.0f ? t : -126.0f;
-    t = t < 126.0f ? t : 126.0f;
-    const float n = __builtin_rintf(t);
-    const float r = t - n;
-    float p = 0x1.42059ap-13f;
-    p = __builtin_fmaf(p, r, 0x1.5f3e12p-10f);
-    p = __builtin_fmaf(p, r, 0x1.3b2d40p-7f);
-    p = __builtin_fmaf(p, r, 0x1.c6aeeap-5f);
-    p = __builtin_fmaf(p, r, 0x1.ebfbdcp-3f);
-    p = __builtin_fmaf(p, r, 0x1.62e430p-1f);
-    p = __builtin_fmaf(p, r, 1.0f);
-    return __builtin_ldexpf(p, (int)n);
-}
+// exp_pinned (gs_device_utils.h) is the pinned exp of oracle/gs_oracle.c, gso_exp(), operation for operation.
 
 // The same pinned exp on two values at once: v_pk_mul / v_pk_add / v_pk_fma are IEEE per component, so
 // each component goes through exactly the operation sequence of exp_pinned().

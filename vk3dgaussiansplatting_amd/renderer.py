@@ -264,12 +264,31 @@ def saveImage(path: str, rgba: np.ndarray):
         raise GsplatError(rc, f"gs_write_image({path!r}) failed")
 
 
-def default_adam_params(**overrides) -> GsAdamParams:
+def write_ply(path: str, rows: np.ndarray, space: str = "records"):
+    """gs_write_ply: rows (float32 (n, 84), host) as a binary .ply in the INRIA layout that ResourceManager.loadGaussians
+    reads.  space="records": rows as the frame reads them (log and logit are taken here); space="raw": rows in the raw
+    space of gs_adam_rows_raw_device, written as they are -- a lossless checkpoint.  Raises GsplatError on failure."""
+    if space not in ("records", "raw"):
+        raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
+    a = np.ascontiguousarray(rows, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != FLOATS_PER_GAUSSIAN:
+        raise ValueError(f"rows must be (n, {FLOATS_PER_GAUSSIAN}), not {a.shape}")
+    L = _lib.lib()
+    rc = L.gs_write_ply(os.fsencode(path), _p(a), a.shape[0], _lib.GS_PLY_FROM_RAW if space == "raw" else _lib.GS_PLY_FROM_RECORDS)
+    if rc != 0:
+        raise GsplatError(rc, L.gs_ply_last_error().decode() if rc == _lib.GS_ERR_IO else f"gs_write_ply({path!r}): invalid argument")
+
+
+def default_adam_params(space: str = "records", **overrides) -> GsAdamParams:
     """gs_default_adam_params: step 1, beta1 0.9, beta2 0.999, eps 1e-15, the INRIA learning rates per GS_ADAM_* group
-    (acting on record-space values here) and the clamps scale >= 1e-7, opacity in [0, 1].  overrides: beta1, beta2, eps,
-    step as numbers; lr, lo, hi as a sequence of six or as {GS_ADAM_* group: value} for some of them."""
+    (acting on record-space values here) and the clamps scale >= 1e-7, opacity in [0, 1].  space="raw":
+    gs_default_adam_params_raw, the same without any clamp (for adamRowsRawDevice, where the rates act on log-scales and
+    logit-opacities).  overrides: beta1, beta2, eps, step as numbers; lr, lo, hi as a sequence of six or as {GS_ADAM_*
+    group: value} for some of them."""
+    if space not in ("records", "raw"):
+        raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
     p = GsAdamParams()
-    _lib.lib().gs_default_adam_params(C.byref(p))
+    (_lib.lib().gs_default_adam_params_raw if space == "raw" else _lib.lib().gs_default_adam_params)(C.byref(p))
     for name, value in overrides.items():
         if name in ("lr", "lo", "hi"):
             arr = getattr(p, name)
@@ -712,6 +731,39 @@ class Renderer:
         the records at ptr (float32 (n, 84), n = the scene's).  Enqueued on the context's stream without waiting."""
         vp = lambda a: C.c_void_p(a) if a else None
         self._ctx.check(_lib.lib().gs_upload_rows_device(self._ctx.handle, vp(ptr), int(n), vp(ids_ptr), vp(count_ptr), int(max_rows)))
+
+    # -- the raw parameter space (no reference counterpart; include/gsplat.h, gs_adam_rows_raw_device and the calls around it)
+    def adamRowsRawDevice(self, raw_ptr: int, records_ptr: int, m_ptr: int, v_ptr: int, n: int, ids_ptr: int, rows_ptr: int,
+                          count_ptr: int, max_rows: int, params: GsAdamParams):
+        """adamRowsDevice in raw space: the gradient rows (with respect to the records, as backwardVisibleDevice left them)
+        are chained to log-scale, logit-opacity and the rotation before normalisation, Adam moves raw, m and v (the
+        clamps of params apply to the raw values), and the listed rows of records are rewritten as act(raw).  params:
+        default_adam_params(space="raw").  Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_adam_rows_raw_device(
+            self._ctx.handle, vp(raw_ptr), vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(ids_ptr), vp(rows_ptr), vp(count_ptr),
+            int(max_rows), C.byref(params)))
+
+    def recordsFromRawDevice(self, raw_ptr: int, records_ptr: int, n: int):
+        """records = act(raw) on the 59 fields of all n rows (exp of the log-scales, sigmoid of the logit, the rotation
+        normalised).  Device addresses, float32 (n, 84).  Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_records_from_raw_device(self._ctx.handle, vp(raw_ptr), vp(records_ptr), int(n)))
+
+    def rawFromRecordsDevice(self, records_ptr: int, raw_ptr: int, n: int):
+        """The inverse: raw = (log of the scales, logit of the opacity clamped to [2^-24, 1 - 2^-24], everything else the
+        same bits).  Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_raw_from_records_device(self._ctx.handle, vp(records_ptr), vp(raw_ptr), int(n)))
+
+    def resetOpacityRawDevice(self, raw_ptr: int, records_ptr: int, m_ptr: int | None, v_ptr: int | None, n: int,
+                              max_opacity: float = 0.01):
+        """The INRIA opacity reset: every opacity above max_opacity becomes sigmoid(logit(max_opacity)) in records and its
+        logit in raw; float 15 of every row of m and v (both given or both None) becomes 0.  Follow it with a full upload.
+        Enqueued on the context's stream without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._ctx.check(_lib.lib().gs_reset_opacity_raw_device(self._ctx.handle, vp(raw_ptr), vp(records_ptr), vp(m_ptr), vp(v_ptr),
+                                                               int(n), float(max_opacity)))
 
     # -- adaptive density control (no reference counterpart; include/gsplat.h, gs_densify_stats_device / gs_densify_device)
     def densifyStatsDevice(self, ids_ptr: int, count_ptr: int, max_rows: int, n: int, grad_accum_ptr: int, seen_ptr: int,
