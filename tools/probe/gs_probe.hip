@@ -157,14 +157,14 @@ extern "C" {
 // Re-runs RenderGaussians of the last frame with per-tile
 // counters; out = uint32[tiles][8] {list length, splats visited, splats needing exp, clock ticks, entries staged, 0, 0, 0}.
 int gs_debug_render_stats(gs_ctx* c, const float* view, const float* proj, const float* cam_pos, uint32_t* out) {
-    if (!c || !out || !c->have_frame) return GS_ERR_INVALID;
+    if (!c || !out || c->last.kind != LastFrame::kFrame) return GS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     const FrameParams fp = make_frame_params(c, view, proj, cam_pos, 0);
     const size_t tiles = (size_t)c->grid_w * c->grid_h;
     uint4* d = nullptr;
     HIP_TRY(c, hipMalloc((void**)&d, tiles * 2 * sizeof(uint4)));
     HIP_TRY(c, hipMemsetAsync(d, 0, tiles * 2 * sizeof(uint4), c->stream));
-    launch_render_stats(fp, c->scratch.raster, c->sort.id[c->sorted_index], c->ranges, c->framebuffer, d, c->stream);
+    launch_render_stats(fp, c->scratch.raster, c->sort.id[c->last.sorted_index], c->ranges, c->framebuffer, d, c->stream);
     hipError_t e = hipMemcpyAsync(out, d, tiles * 2 * sizeof(uint4), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);

@@ -35,8 +35,6 @@ This module imports torch; `import vk3dgaussiansplatting_amd` does not import it
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -49,28 +47,18 @@ def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
     options (sort_algorithm, render_kernel, ...); render_mode must stay GS_RENDER_EXACT."""
     r = Renderer(width, height, device=device, record_timings=False, **kw)
     r.init(ResourceManager())
-    r._autograd_mask = None
-    r._autograd_frame = 0
     return r
 
 
 def _draw(r: Renderer, records: torch.Tensor, view, proj, cam_pos, sh_mode: int, want_depth: bool):
     """Upload records (device to device) and draw one frame; returns the host outputs."""
-    mask = _lib.GS_OUTPUT_RGBA32F | (_lib.GS_OUTPUT_DEPTH if want_depth else 0)
     torch.cuda.current_stream(records.device).synchronize()     # the library works on a stream of its own
     r.uploadDevice(records.data_ptr(), records.shape[0])
-    if getattr(r, "_autograd_mask", None) != mask:
-        r.setOutputs(rgba32f=True, depth=want_depth)
-        r._autograd_mask = mask
-    v = np.ascontiguousarray(view, dtype=np.float32).reshape(16)
-    p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
-    c = np.ascontiguousarray(cam_pos, dtype=np.float32).reshape(3)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-    r._ctx.check(_lib.lib().gs_render_device(r._ctx.handle, ptr(v), ptr(p), ptr(c), int(sh_mode), None))
-    r._autograd_frame = getattr(r, "_autograd_frame", 0) + 1
+    r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F | (_lib.GS_OUTPUT_DEPTH if want_depth else 0))
+    r.drawCamera(view, proj, cam_pos, sh_mode)
     rgba = r.readOutput(_lib.GS_OUTPUT_RGBA32F)
     depth = r.readOutput(_lib.GS_OUTPUT_DEPTH) if want_depth else None
-    return rgba, depth, r._autograd_frame
+    return rgba, depth, r.frameSerial
 
 
 class _Frame(torch.autograd.Function):
@@ -89,7 +77,7 @@ class _Frame(torch.autograd.Function):
     def backward(ctx, grad_rgba, grad_depth=None):
         (records,) = ctx.saved_tensors
         r = ctx.renderer
-        if r._autograd_frame != ctx.frame:          # another frame was drawn since: draw this one again
+        if r.frameSerial != ctx.frame:              # another frame was drawn since: draw this one again
             _draw(r, records.detach(), *ctx.args)
         g = (grad_rgba if grad_rgba is not None else torch.zeros(r.height, r.width, 4, device=records.device))
         g = g.to(device=records.device, dtype=torch.float32).contiguous()
@@ -211,9 +199,7 @@ class VisibleAdam:
         if self.track_density:
             self._zero_stats(n, dev)
         self.m, self.v = torch.zeros_like(records), torch.zeros_like(records)
-        self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)        # int32 storage for the library's uint32
-        self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
-        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._alloc_rows(dev)
         self.grad = torch.zeros(renderer.height, renderer.width, 4, dtype=torch.float32, device=dev)
         self.t = 0
         self._full_upload = True
@@ -231,6 +217,12 @@ class VisibleAdam:
         r, n = self.renderer, self.records.shape[0]
         r.rawFromRecordsDevice(self.records.data_ptr(), self.raw.data_ptr(), n)
         r.recordsFromRawDevice(self.raw.data_ptr(), self.records.data_ptr(), n)
+
+    def _alloc_rows(self, dev):
+        """What a step lists: ids and gradient rows (max_rows of them) and the count, all zero."""
+        self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)        # int32 storage for the library's uint32
+        self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def _zero_stats(self, n: int, dev):
         self.grad_accum = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -267,13 +259,10 @@ class VisibleAdam:
             self._zero_stats(n_out, dev)
             if self._rows_follow_n:
                 self.max_rows = n_out
-            self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)
-            self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
-            self.count.zero_()
+            self._alloc_rows(dev)
         self.stream.synchronize()
-        # another n is another scene: the next step uploads everything and sets the resolution and the RGBA32F output again
+        # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
         self._full_upload = True
-        r._autograd_mask = None
         return n_out, cloned, split, pruned
 
     def reset_upload(self):
@@ -285,24 +274,17 @@ class VisibleAdam:
         if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
             raise ValueError(f"target must be float32 {(r.height, r.width, 3)} on the GPU")
         target = target.contiguous()
-        v = np.ascontiguousarray(view, dtype=np.float32).reshape(16)
-        p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
-        c = np.ascontiguousarray(cam_pos, dtype=np.float32).reshape(3)
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
         self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
         with torch.cuda.stream(self.stream):
             numbers = torch.empty(3, dtype=torch.float32, device=self.records.device)
             target.record_stream(self.stream)
             if self._full_upload:
                 r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
-                if getattr(r, "_autograd_mask", None) != _lib.GS_OUTPUT_RGBA32F:
-                    r.setOutputs(rgba32f=True)
-                    r._autograd_mask = _lib.GS_OUTPUT_RGBA32F
+                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
                 self._full_upload = False
             else:
                 r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
-            r._ctx.check(_lib.lib().gs_render_device_async(r._ctx.handle, ptr(v), ptr(p), ptr(c), int(sh_mode), None))
-            r._autograd_frame = getattr(r, "_autograd_frame", 0) + 1
+            r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
             r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers.data_ptr(), self.grad.data_ptr())
             r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
                                     self.count.data_ptr())

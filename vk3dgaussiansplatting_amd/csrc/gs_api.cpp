@@ -1,24 +1,15 @@
-// gs_api.cpp -- host side of libgsplat_hip.so: the C-ABI of include/gsplat.h over the HIP kernels.
+// gs_api.cpp -- host side of libgsplat_hip.so: the C-ABI of include/gsplat.h over the HIP kernels, the part that has a
+// counterpart in the reference: context, scene, resolution, outputs, tile rows and the frame.  (gs_train.cpp: the training
+// calls; gs_debug.cpp: read-backs and micro-benchmarks.)
 // Mirrors the reference's frame orchestration (Engine/Graphics/Renderer.cpp, Subrenderer.cpp,
 // Sort/RadixSort.cpp) with HIP streams/events in place of Vulkan command buffers/timestamps.
 // There is NO CPU fallback: without a GPU every entry point that computes fails with
 // GS_ERR_NO_DEVICE / GS_ERR_HIP.
-#include "../../include/gsplat.h"
-#include "gs_internal.h"
 #include "gs_ctx.h"
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
 #include <cstddef>
-#include <cstdio>
-#include <cstring>
 #include <iterator>
-#include <limits>
 #include <new>
-#include <string>
-#include <vector>
 
 using namespace gs;
 
@@ -47,7 +38,6 @@ void free_resolution(gs_ctx* c) {
     c->bwd_mem.release();
     c->bwd_vis_rows = 0;
     c->loss_mem.release();
-    c->bwd_frame = false; c->bwd_rows = false;
     drop_sort_graph(c);
     c->res_mem.release();
     c->sort = SortBuffers{};          // fed[1], fed[2] point into the allocation of fed[0]
@@ -55,24 +45,26 @@ void free_resolution(gs_ctx* c) {
     // the strips of a sharded frame are sized by the resolution: gs_dist_shard_rows must be called again
     gsi_dist_free_buffers(c);
     c->capacity = 0; c->width = c->height = 0;
-    c->have_frame = false;
+    resolution_freed(c);
     if (c->elems_note) *(volatile uint32_t*)c->elems_note = 0u;     // (free_resolution's callers have waited for the stream)
 }
 
 // Renderer.cpp:703-710
 uint32_t ceil_pow2(uint32_t x) { uint32_t v = 1; while (v < x) v *= 2; return v; }
 
-// RadixSort.cpp:7-16 + 203-204
+inline bool sorts_splat_first(uint32_t algo) { return algo == GS_SORT_RADIX4_SPLAT_FIRST || algo == GS_SORT_RADIX8_SPLAT_FIRST; }
+inline uint32_t digit_bits_of(uint32_t algo) { return algo == GS_SORT_RADIX8 || algo == GS_SORT_RADIX8_SPLAT_FIRST ? 8u : (uint32_t)kRadixBits; }
+
+} // namespace
+
+// ---- what gs_train.cpp and gs_debug.cpp share with this file (declared in gs_ctx.h)
+
 uint32_t num_sort_bits_for(uint32_t num_tiles) {
     uint32_t x = num_tiles - 1u, bits = 0;
     for (int i = 31; i >= 0; --i) if ((x >> i) & 1u) { bits = (uint32_t)i + 1u; break; }
     return ((32u + bits + kRadixBits - 1u) / kRadixBits) * kRadixBits;
 }
 
-inline bool sorts_splat_first(uint32_t algo) { return algo == GS_SORT_RADIX4_SPLAT_FIRST || algo == GS_SORT_RADIX8_SPLAT_FIRST; }
-inline uint32_t digit_bits_of(uint32_t algo) { return algo == GS_SORT_RADIX8 || algo == GS_SORT_RADIX8_SPLAT_FIRST ? 8u : (uint32_t)kRadixBits; }
-
-// the sort buffers of a list of `capacity` elements, owned by `mem` (which the caller releases, after a failure too)
 int alloc_sort(gs_ctx* ctx, DeviceOwner& mem, SortBuffers& s, uint32_t capacity) {
     const size_t bytes = (size_t)capacity * sizeof(uint32_t);
     for (int k = 0; k < 2; ++k) {
@@ -102,8 +94,7 @@ int alloc_sort(gs_ctx* ctx, DeviceOwner& mem, SortBuffers& s, uint32_t capacity)
     return GS_OK;
 }
 
-// The run of the stand-alone sorters: the whole key over a list of n elements, nothing dropped.  They know their element
-// count: fed counts (gs_sort.hip) for short lists of the 4-bit sorter.
+// They know their element count: fed counts (gs_sort.hip) for short lists of the 4-bit sorter.
 SortRun whole_list_run(const gs_ctx* c, uint32_t n, uint32_t num_sort_bits) {
     const bool fed = digit_bits_of(c->cfg.sort_algorithm) == (uint32_t)kRadixBits &&
                      (c->cfg.count_launches == GS_COUNT_FED ||
@@ -116,6 +107,8 @@ int check_launch(gs_ctx* ctx, const char* what) {
     if (e != hipSuccess) return fail(ctx, GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     return GS_OK;
 }
+
+namespace {
 
 // ---- the stages of a frame behind project + scan (Renderer::recordCommandBuffer, Renderer.cpp:540-629), once per sorter:
 //      what a stage launches, the bucket of gs_timings its interval is booked under, the name check_launch reports it by,
@@ -222,6 +215,7 @@ int mark(gs_ctx* c, FrameBucket b) {
 
 int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* cam_pos,
                   uint32_t sh_mode, uint8_t* out_dev) {
+    list_launching(c);
     if (!c->n) return fail(c, GS_ERR_NO_SCENE, "gs_render: no gaussians uploaded");
     if (!c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_render: gs_set_resolution not called");
     if (!view || !proj || !cam_pos) return fail(c, GS_ERR_INVALID, "gs_render: null camera argument");
@@ -232,8 +226,6 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     const bool tm = c->cfg.record_timings != 0;
     hipStream_t st = c->stream;
 
-    c->unsorted_valid = false;
-    c->bwd_rows = false;          // from here on the rows scratch belongs to a frame that is no longer the current one
     c->num_marks = 0;
     if (tm) if (int r = mark(c, kBucketNone)) return r;
     // computeInitSortList (Subrenderer.cpp:37-170): per-frame resets, then the dispatch.  Only the
@@ -241,7 +233,7 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     // RadixSort.cpp:676-692) is unobservable once every later stage runs over E instead of C.
     // (the ranges and the sort's coarse totals are cleared inside k_scan_blocks: no fill launches in a frame)
     fp.parity = (c->emit_parity ^= 1u);
-    c->last_fp = fp;
+    const FrameParams listed = fp;      // what gs_backward* and the read-backs take the frame by
     const bool splat_first = sorts_splat_first(c->cfg.sort_algorithm);
     fp.splat_first = splat_first ? 1u : 0u;
     const bool bucket = c->cfg.sort_algorithm == GS_SORT_TILE_BUCKET;
@@ -313,17 +305,13 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
         if (chain) break;
         if (tm) if (int r = mark(c, s.bucket)) return r;
     }
-    c->sorted_index = f.sorted;
-    c->depth_dropped = !bucket;
     // computeRenderGaussians (Subrenderer.cpp:218-346), with the outputs of gs_set_outputs beside the image
     const RenderOutputs outs{reinterpret_cast<float4*>(c->out_rgba32f), c->out_depth, c->scratch.view_z};
-    launch_render(fp, c->scratch.raster, c->sort.id[c->sorted_index], c->ranges, f.ordered ? c->tile_order : nullptr,
+    launch_render(fp, c->scratch.raster, c->sort.id[f.sorted], c->ranges, f.ordered ? c->tile_order : nullptr,
                   out_dev ? out_dev : c->framebuffer, c->cfg.render_mode, c->cfg.render_kernel, st, outs);
     if (int r = check_launch(c, "RenderGaussians")) return r;
-    if (c->outputs) c->outputs_valid = true;
     if (tm) if (int r = mark(c, kBucketRender)) return r;
-    c->have_frame = true;
-    c->bwd_frame = true;
+    frame_enqueued(c, listed, f.sorted);
     return GS_OK;
 }
 
@@ -396,6 +384,17 @@ int finish_frame(gs_ctx* c) {
 
 // gs_dist.cpp: the buckets and the element count of the frame gs_render_sharded has just waited for (hidden: not an export)
 int gsi_finish_frame(gs_ctx* c) { return finish_frame(c); }
+
+int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** dev, size_t* size) {
+    if (which != GS_OUTPUT_RGBA32F && which != GS_OUTPUT_DEPTH)
+        return fail(c, GS_ERR_INVALID, std::string(who) + ": which must be GS_OUTPUT_RGBA32F or GS_OUTPUT_DEPTH");
+    if (!(c->outputs & which)) return fail(c, GS_ERR_INVALID, std::string(who) + ": that output is not enabled (gs_set_outputs)");
+    if (!c->capacity) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_set_resolution not called");
+    const size_t px = (size_t)c->width * c->height;
+    *dev = which == GS_OUTPUT_RGBA32F ? (void*)c->out_rgba32f : (void*)c->out_depth;
+    *size = px * (which == GS_OUTPUT_RGBA32F ? 4 * sizeof(float) : sizeof(float));
+    return GS_OK;
+}
 
 extern "C" {
 
@@ -618,12 +617,20 @@ static int new_scene(gs_ctx* c, uint32_t n, const char* who) {
     if (e == hipSuccess) e = mem.alloc(b.opacity, N * sizeof(float));
     if (e == hipSuccess) e = mem.alloc(b.sig2, N * sizeof(float));
     if (e == hipSuccess) e = mem.alloc(b.block_bounds, ((size_t)(n + 63u) / 64u + 4u) * 8 * sizeof(float));
-    if (e != hipSuccess) {
-        free_scene(c);
-        return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) { free_scene(c); return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
     c->scene = b;
     if (int r = alloc_scratch(c, n)) { free_scene(c); return r; }
+    return GS_OK;
+}
+
+// Behind the planes of a fresh scene (e: what writing them returned): the boxes of the blocks and a wait; then the scene is
+// the context's, or gone
+static int finish_new_scene(gs_ctx* c, uint32_t n, const char* who, hipError_t e) {
+    if (e == hipSuccess) launch_block_bounds(n, c->scene, c->stream);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { free_scene(c); return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
+    c->n = n;
     return GS_OK;
 }
 
@@ -640,28 +647,19 @@ int gs_upload_gaussians(gs_ctx* c, const void* aos336, uint32_t n) {
         return fail(c, GS_ERR_HIP, "gs_upload_gaussians: cannot allocate the staging buffer");
     }
     const char* src = static_cast<const char*>(aos336);
-    int rc = GS_OK;
-    for (uint32_t first = 0; first < n && rc == GS_OK; first += chunk) {
+    hipError_t e = hipSuccess;
+    for (uint32_t first = 0; first < n && e == hipSuccess; first += chunk) {
         const uint32_t cnt = (n - first) < chunk ? (n - first) : chunk;
-        hipError_t e = hipMemcpyAsync(staging, src + (size_t)first * GS_GAUSSIAN_RECORD_BYTES,
-                                      (size_t)cnt * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyHostToDevice, c->stream);
+        e = hipMemcpyAsync(staging, src + (size_t)first * GS_GAUSSIAN_RECORD_BYTES,
+                           (size_t)cnt * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) {
             launch_aos_to_soa(staging, first, cnt, n, c->scene, c->stream);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // staging is reused
-        if (e != hipSuccess) rc = fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians: ") + hipGetErrorString(e));
     }
     (void)hipFree(staging);
-    if (rc == GS_OK) {
-        launch_block_bounds(n, c->scene, c->stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) rc = fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians: ") + hipGetErrorString(e));
-    }
-    if (rc != GS_OK) { free_scene(c); return rc; }
-    c->n = n;
-    return GS_OK;
+    return finish_new_scene(c, n, "gs_upload_gaussians", e);
 }
 
 int gs_upload_gaussians_device(gs_ctx* c, const void* aos336_dev, uint32_t n) {
@@ -669,25 +667,15 @@ int gs_upload_gaussians_device(gs_ctx* c, const void* aos336_dev, uint32_t n) {
     if (!aos336_dev || n == 0) return fail(c, GS_ERR_INVALID, "gs_upload_gaussians_device: empty input");
     HIP_TRY(c, hipSetDevice(c->device));
     const float* src = static_cast<const float*>(aos336_dev);
-    if (c->shared && c->n == n) {
-        // the same scene size: the planes are rewritten in place behind whatever is enqueued on the stream, and every
-        // context that shares them renders the new values; resolution, scratch and captured graphs stay
-        launch_aos_to_soa(src, 0, n, n, c->scene, c->stream);
-        launch_block_bounds(n, c->scene, c->stream);
-        c->bwd_frame = false; c->bwd_rows = false;
-        HIP_TRY(c, hipGetLastError());
-        return GS_OK;
-    }
-    if (int r = new_scene(c, n, "gs_upload_gaussians_device")) return r;
+    // the same scene size: the planes are rewritten in place behind whatever is enqueued on the stream, and every
+    // context that shares them renders the new values; resolution, scratch and captured graphs stay
+    const bool in_place = c->shared && c->n == n;
+    if (!in_place) if (int r = new_scene(c, n, "gs_upload_gaussians_device")) return r;
     launch_aos_to_soa(src, 0, n, n, c->scene, c->stream);
+    if (!in_place) return finish_new_scene(c, n, "gs_upload_gaussians_device", hipGetLastError());
     launch_block_bounds(n, c->scene, c->stream);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        free_scene(c);
-        return fail(c, GS_ERR_HIP, std::string("gs_upload_gaussians_device: ") + hipGetErrorString(e));
-    }
-    c->n = n;
+    scene_or_rows_changed(c);
+    HIP_TRY(c, hipGetLastError());
     return GS_OK;
 }
 
@@ -705,132 +693,24 @@ int gs_upload_rows_device(gs_ctx* c, const void* aos336_dev, uint32_t n, const u
     // the listed planes in place, then the boxes of all blocks (16 bytes per splat read): what the full in-place upload leaves
     launch_upload_rows(static_cast<const float*>(aos336_dev), n, ids_dev, count_dev, max_rows, c->scene, c->stream);
     launch_block_bounds(n, c->scene, c->stream);
-    c->bwd_frame = false; c->bwd_rows = false;
+    scene_or_rows_changed(c);
     return check_launch(c, "gs_upload_rows_device");
 }
 
-void gs_default_adam_params(gs_adam_params* p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(*p);
-    p->step = 1;
-    p->beta1 = 0.9f; p->beta2 = 0.999f; p->eps = 1e-15f;
-    const float inf = std::numeric_limits<float>::infinity();
-    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
-    p->lr[GS_ADAM_POSITION] = 1.6e-4f;
-    p->lr[GS_ADAM_SCALE] = 5e-3f;     p->lo[GS_ADAM_SCALE] = 1e-7f;
-    p->lr[GS_ADAM_ROTATION] = 1e-3f;
-    p->lr[GS_ADAM_SH_DC] = 2.5e-3f;
-    p->lr[GS_ADAM_OPACITY] = 5e-2f;   p->lo[GS_ADAM_OPACITY] = 0.0f; p->hi[GS_ADAM_OPACITY] = 1.0f;
-    p->lr[GS_ADAM_SH_REST] = 1.25e-4f;
-}
-
-// what gs_adam_rows_device and gs_adam_rows_raw_device check of their parameters, and the step they hand the kernel
-static int adam_step_of(gs_ctx* c, const std::string& who, uint32_t n, const gs_adam_params* p, AdamStep& a) {
-    if (!p) return fail(c, GS_ERR_INVALID, who + "null gs_adam_params");
-    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
-    if (p->struct_size != sizeof(gs_adam_params))
-        return fail(c, GS_ERR_INVALID, who + "gs_adam_params.struct_size does not match this library (call gs_default_adam_params first)");
-    if (p->step == 0) return fail(c, GS_ERR_INVALID, who + "step counts from 1");
-    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f) || !(p->beta2 >= 0.0f && p->beta2 < 1.0f))
-        return fail(c, GS_ERR_INVALID, who + "beta1 and beta2 must be in [0, 1)");
-    if (!(p->eps >= 0.0f) || !std::isfinite(p->eps)) return fail(c, GS_ERR_INVALID, who + "eps must be finite and not negative");
-    a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps;
-    a.c1 = 1.0f - p->beta1; a.c2 = 1.0f - p->beta2;
-    // the bias correction of step t in double, rounded once per group
-    const double t = (double)p->step;
-    const double root2 = std::sqrt(1.0 - std::pow((double)p->beta2, t)), bias1 = 1.0 - std::pow((double)p->beta1, t);
-    for (int g = 0; g < GS_ADAM_GROUPS; ++g) {
-        if (!(p->lr[g] >= 0.0f) || !std::isfinite(p->lr[g])) return fail(c, GS_ERR_INVALID, who + "lr must be finite and not negative");
-        if (!(p->lo[g] <= p->hi[g])) return fail(c, GS_ERR_INVALID, who + "lo must not exceed hi, and neither may be a NaN");
-        a.step[g] = (float)((double)p->lr[g] * root2 / bias1);
-        if (!std::isfinite(a.step[g])) return fail(c, GS_ERR_INVALID, who + "lr times the bias correction is not a finite float");
-        a.lo[g] = p->lo[g]; a.hi[g] = p->hi[g];
+// The output buffers of the mask at the current resolution, zero-filled (rows a context does not own stay zero)
+static hipError_t alloc_outputs(gs_ctx* c) {
+    const size_t px = (size_t)c->width * c->height;
+    hipError_t e = hipSuccess;
+    if (px && (c->outputs & GS_OUTPUT_RGBA32F)) {
+        e = c->res_mem.alloc(c->out_rgba32f, px * 4 * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(c->out_rgba32f, 0, px * 4 * sizeof(float));
     }
-    return GS_OK;
+    if (e == hipSuccess && px && (c->outputs & GS_OUTPUT_DEPTH)) {
+        e = c->res_mem.alloc(c->out_depth, px * sizeof(float));
+        if (e == hipSuccess) e = hipMemset(c->out_depth, 0, px * sizeof(float));
+    }
+    return e;
 }
-
-int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_dev, uint32_t n, const uint32_t* ids_dev,
-                        const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, const gs_adam_params* p) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_adam_rows_device: ";
-    if (max_rows && (!records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
-        return fail(c, GS_ERR_INVALID, who + "null records, m, v, ids, grad_rows or count with max_rows > 0");
-    AdamStep a;
-    if (int r = adam_step_of(c, who, n, p, a)) return r;
-    if (!max_rows) return GS_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    launch_adam_rows(records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
-    return check_launch(c, "gs_adam_rows_device");
-}
-
-// ---- the raw parameter space (gs_raw.hip) ----
-
-// two arrays of `bytes` bytes share at least one (a null array shares nothing)
-static bool arrays_overlap(const void* a, const void* b, size_t bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && bytes && a0 < b0 + bytes && b0 < a0 + bytes;
-}
-
-void gs_default_adam_params_raw(gs_adam_params* p) {
-    if (!p) return;
-    gs_default_adam_params(p);
-    const float inf = std::numeric_limits<float>::infinity();
-    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
-}
-
-int gs_adam_rows_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
-                            const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows,
-                            const gs_adam_params* p) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_adam_rows_raw_device: ";
-    if (max_rows && (!raw_dev || !records_dev || !m_dev || !v_dev || !ids_dev || !grad_rows_dev || !count_dev))
-        return fail(c, GS_ERR_INVALID, who + "null raw, records, m, v, ids, grad_rows or count with max_rows > 0");
-    AdamStep a;
-    if (int r = adam_step_of(c, who, n, p, a)) return r;
-    const size_t bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES;
-    if (arrays_overlap(records_dev, raw_dev, bytes) || arrays_overlap(records_dev, m_dev, bytes) || arrays_overlap(records_dev, v_dev, bytes))
-        return fail(c, GS_ERR_INVALID, who + "records aliases raw, m or v");
-    if (!max_rows) return GS_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    launch_adam_rows_raw(raw_dev, records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
-    return check_launch(c, "gs_adam_rows_raw_device");
-}
-
-static int convert_space(gs_ctx* c, const char* name, const float* src, float* dst, uint32_t n, bool to_raw) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = std::string(name) + ": ";
-    if (!src || !dst) return fail(c, GS_ERR_INVALID, who + "null raw or records");
-    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
-    if (arrays_overlap(src, dst, (size_t)n * GS_GAUSSIAN_RECORD_BYTES)) return fail(c, GS_ERR_INVALID, who + "raw aliases records");
-    HIP_TRY(c, hipSetDevice(c->device));
-    launch_convert_space(src, dst, n, to_raw, c->stream);
-    return check_launch(c, name);
-}
-
-int gs_records_from_raw_device(gs_ctx* c, const float* raw_dev, float* records_dev, uint32_t n) {
-    return convert_space(c, "gs_records_from_raw_device", raw_dev, records_dev, n, false);
-}
-
-int gs_raw_from_records_device(gs_ctx* c, const float* records_dev, float* raw_dev, uint32_t n) {
-    return convert_space(c, "gs_raw_from_records_device", records_dev, raw_dev, n, true);
-}
-
-int gs_reset_opacity_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
-                                float max_opacity) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_reset_opacity_raw_device: ";
-    if (!raw_dev || !records_dev) return fail(c, GS_ERR_INVALID, who + "null raw or records");
-    if (!m_dev != !v_dev) return fail(c, GS_ERR_INVALID, who + "m and v must be given together or not at all");
-    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
-    if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return fail(c, GS_ERR_INVALID, who + "max_opacity must lie strictly between 0 and 1");
-    const float logit = (float)std::log((double)max_opacity / (1.0 - (double)max_opacity));
-    HIP_TRY(c, hipSetDevice(c->device));
-    launch_reset_opacity_raw(raw_dev, records_dev, m_dev, v_dev, n, max_opacity, logit, c->stream);
-    return check_launch(c, "gs_reset_opacity_raw_device");
-}
-
-static hipError_t alloc_outputs(gs_ctx* c);
 
 int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     if (!c) return GS_ERR_INVALID;
@@ -867,21 +747,6 @@ int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     return GS_OK;
 }
 
-// The output buffers of the mask at the current resolution, zero-filled (rows a context does not own stay zero)
-static hipError_t alloc_outputs(gs_ctx* c) {
-    const size_t px = (size_t)c->width * c->height;
-    hipError_t e = hipSuccess;
-    if (px && (c->outputs & GS_OUTPUT_RGBA32F)) {
-        e = c->res_mem.alloc(c->out_rgba32f, px * 4 * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(c->out_rgba32f, 0, px * 4 * sizeof(float));
-    }
-    if (e == hipSuccess && px && (c->outputs & GS_OUTPUT_DEPTH)) {
-        e = c->res_mem.alloc(c->out_depth, px * sizeof(float));
-        if (e == hipSuccess) e = hipMemset(c->out_depth, 0, px * sizeof(float));
-    }
-    return e;
-}
-
 // the three buffers of the mask, inside the lifetimes that hold them
 static void free_outputs(gs_ctx* c) {
     c->res_mem.free(c->out_rgba32f);
@@ -909,18 +774,6 @@ int gs_set_outputs(gs_ctx* c, uint32_t mask) {
         c->outputs = 0;
         return fail(c, GS_ERR_HIP, std::string("gs_set_outputs: ") + hipGetErrorString(e));
     }
-    return GS_OK;
-}
-
-// which: one GS_OUTPUT_* bit that is enabled and allocated -> its buffer and size; else fails
-static int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** dev, size_t* size) {
-    if (which != GS_OUTPUT_RGBA32F && which != GS_OUTPUT_DEPTH)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": which must be GS_OUTPUT_RGBA32F or GS_OUTPUT_DEPTH");
-    if (!(c->outputs & which)) return fail(c, GS_ERR_INVALID, std::string(who) + ": that output is not enabled (gs_set_outputs)");
-    if (!c->capacity) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_set_resolution not called");
-    const size_t px = (size_t)c->width * c->height;
-    *dev = which == GS_OUTPUT_RGBA32F ? (void*)c->out_rgba32f : (void*)c->out_depth;
-    *size = px * (which == GS_OUTPUT_RGBA32F ? 4 * sizeof(float) : sizeof(float));
     return GS_OK;
 }
 
@@ -953,326 +806,22 @@ int gs_output_device(gs_ctx* c, uint32_t which, void** dev_out, size_t* bytes) {
     return GS_OK;
 }
 
-// The buffers of a per-splat scan (gs_splat_scan.h) of K sums over n splats, into the lifetime `mem`
-static hipError_t alloc_splat_scan(DeviceOwner& mem, SplatScan& s, uint32_t n, uint32_t K) {
-    const size_t rows = (size_t)K * backward_blocks(n) * sizeof(uint32_t);
-    hipError_t e = mem.alloc(s.offsets, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.alloc(s.block_sums, rows);
-    if (e == hipSuccess) e = mem.alloc(s.block_offsets, rows);
-    if (e == hipSuccess) e = mem.alloc(s.totals, K * sizeof(uint32_t));
-    return e;
-}
-
-// gs_backward*: the refusals (nothing enqueued), then the scratch of the first call
-static int backward_prepare(gs_ctx* c, const char* who) {
-    if (c->cfg.render_mode != GS_RENDER_EXACT)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": only GS_RENDER_EXACT frames can be differentiated");
-    if (c->dist_sharded)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": a sharded context (gs_dist_shard_rows) cannot be differentiated");
-    if (!c->capacity || !c->n || !c->bwd_frame)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": no frame since the last gs_set_resolution, gs_set_tile_rows* or upload");
-    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->bwd.rows) {
-        DeviceOwner& mem = c->bwd_mem;
-        hipError_t e = mem.alloc(c->bwd.rows, backward_row_bytes(c->capacity));
-        if (e == hipSuccess) e = alloc_splat_scan(mem, c->bwd.scan, c->n, 2);
-        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            mem.release();
-            c->bwd_vis_rows = 0;
-            c->bwd_rows = false;
-            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-        }
-    }
-    return GS_OK;
-}
-
-// The last frame as the backward launchers take it
-static BackwardFrame backward_frame(const gs_ctx* c) {
-    return BackwardFrame{c->last_fp, c->scene, c->scratch, c->sort.id[c->sorted_index], c->ranges, c->bwd};
-}
-
-// Host gradients onto the device (bwd_host_in, allocated on first use), enqueued on the context's stream: the two host
-// pointers are replaced by their device copies (a null grad_depth stays null)
-static int stage_host_grads(gs_ctx* c, const float*& grad_rgba32f, const float*& grad_depth) {
-    const size_t px = (size_t)c->width * c->height;
-    if (!c->bwd_host_in) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_in, px * 5 * sizeof(float)));
-    float* din = c->bwd_host_in;
-    HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    grad_rgba32f = din;
-    if (grad_depth) grad_depth = din + px * 4;
-    return GS_OK;
-}
-
-// V of the last frame into bwd.vis_ids and |V| into *count, on the host: the scan, then a wait for the stream
-static int visible_count_sync(gs_ctx* c, const char* who, uint32_t* count) {
-    launch_backward_visible_scan(backward_frame(c), nullptr, 0u, nullptr, c->stream);
-    if (int r = check_launch(c, who)) return r;
-    HIP_TRY(c, hipMemcpyAsync(count, visible_count_of(c->bwd), 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GS_OK;
-}
-
-int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
-    if (!c) return GS_ERR_INVALID;
-    if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward_device: null gradient pointer");
-    if (int r = backward_prepare(c, "gs_backward_device")) return r;
-    launch_backward(backward_frame(c), grad_rgba32f, grad_depth, grad_records, c->stream);
-    c->bwd_rows = true;
-    return check_launch(c, "gs_backward_device");
-}
-
-int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
-    if (!c) return GS_ERR_INVALID;
-    if (!grad_rgba32f || !grad_records) return fail(c, GS_ERR_INVALID, "gs_backward: null gradient pointer");
-    if (int r = backward_prepare(c, "gs_backward")) return r;
-    if (!c->bwd_host_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES));
-    if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
-    launch_backward(backward_frame(c), grad_rgba32f, grad_depth, c->bwd_host_out, c->stream);
-    c->bwd_rows = true;
-    if (int r = check_launch(c, "gs_backward")) return r;
-    HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GS_OK;
-}
-
-// gs_photometric_loss*: the refusals (nothing enqueued), the image the call reads (rgba32f, or the context's own
-// GS_OUTPUT_RGBA32F buffer for NULL), then the scratch of the first call
-static int loss_prepare(gs_ctx* c, const char* who, const float*& rgba32f, const float* target_rgb, float lambda,
-                        const float* bg, const float* loss_out, const float* grad_rgba32f) {
-    if (!target_rgb || !loss_out) return fail(c, GS_ERR_INVALID, std::string(who) + ": null target_rgb or loss_out");
-    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(c, GS_ERR_INVALID, std::string(who) + ": lambda must be a finite value in [0, 1]");
-    if (bg && !(std::isfinite(bg[0]) && std::isfinite(bg[1]) && std::isfinite(bg[2])))
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": bg must be finite");
-    if (!c->capacity) return fail(c, GS_ERR_INVALID, std::string(who) + ": gs_set_resolution not called");
-    if (c->dist_sharded)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": a sharded context (gs_dist_shard_rows) has no whole frame to compare");
-    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": the context owns a subset of the tile rows");
-    if (!rgba32f) {
-        void* dev = nullptr;
-        size_t size = 0;
-        if (int r = output_buffer(c, GS_OUTPUT_RGBA32F, who, &dev, &size)) return r;
-        if (!c->outputs_valid)
-            return fail(c, GS_ERR_INVALID, std::string(who) + ": no frame rendered since the outputs were enabled or resized");
-        rgba32f = static_cast<const float*>(dev);
-    }
-    if (grad_rgba32f && grad_rgba32f == rgba32f)
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": grad_rgba32f must not be the image it differentiates");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->loss.maps) {
-        hipError_t e = c->loss_mem.alloc(c->loss.maps, loss_map_bytes(c->width, c->height));
-        if (e == hipSuccess) e = c->loss_mem.alloc(c->loss.tile_sums, loss_tile_bytes(c->width, c->height));
-        if (e != hipSuccess) {
-            c->loss_mem.release();
-            return fail(c, GS_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-        }
-    }
-    return GS_OK;
-}
-
-int gs_photometric_loss_device(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
-                               float* loss_out, float* grad_rgba32f) {
-    if (!c) return GS_ERR_INVALID;
-    if (int r = loss_prepare(c, "gs_photometric_loss_device", rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
-    launch_photometric_loss(c->loss, rgba32f, target_rgb, lambda, bg, c->width, c->height, loss_out, grad_rgba32f, c->stream);
-    return check_launch(c, "gs_photometric_loss_device");
-}
-
-int gs_photometric_loss(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
-                        float loss_out[3], float* grad_rgba32f) {
-    if (!c) return GS_ERR_INVALID;
-    const float* image = rgba32f;      // host, or (NULL form) the context's device buffer after loss_prepare
-    if (int r = loss_prepare(c, "gs_photometric_loss", image, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
-    // device copies: rgba [px][4] | gradient [px][4] | target [px][3] | the three numbers (+ 1: 16-byte multiples)
-    const size_t px = (size_t)c->width * c->height;
-    if (!c->loss_host) HIP_TRY(c, c->loss_mem.alloc(c->loss_host, (px * 11 + 4) * sizeof(float)));
-    float* d_rgba = c->loss_host, *d_grad = d_rgba + px * 4, *d_target = d_grad + px * 4, *d_loss = d_target + px * 3;
-    if (rgba32f) {
-        HIP_TRY(c, hipMemcpyAsync(d_rgba, rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        image = d_rgba;
-    }
-    HIP_TRY(c, hipMemcpyAsync(d_target, target_rgb, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    launch_photometric_loss(c->loss, image, d_target, lambda, bg, c->width, c->height, d_loss, grad_rgba32f ? d_grad : nullptr,
-                            c->stream);
-    if (int r = check_launch(c, "gs_photometric_loss")) return r;
-    HIP_TRY(c, hipMemcpyAsync(loss_out, d_loss, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    if (grad_rgba32f) HIP_TRY(c, hipMemcpyAsync(grad_rgba32f, d_grad, px * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return GS_OK;
-}
-
-int gs_visible_count(gs_ctx* c, uint32_t* count_out) {
-    if (!c) return GS_ERR_INVALID;
-    if (!count_out) return fail(c, GS_ERR_INVALID, "gs_visible_count: null count_out");
-    if (int r = backward_prepare(c, "gs_visible_count")) return r;
-    return visible_count_sync(c, "gs_visible_count", count_out);
-}
-
-static int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba32f, const uint32_t* ids_out,
-                                     const float* grad_rows_out, uint32_t max_rows, const uint32_t* count_out) {
-    if (!grad_rgba32f) return fail(c, GS_ERR_INVALID, std::string(who) + ": null gradient pointer");
-    if (!count_out) return fail(c, GS_ERR_INVALID, std::string(who) + ": null count_out");
-    if (max_rows && (!ids_out || !grad_rows_out))
-        return fail(c, GS_ERR_INVALID, std::string(who) + ": null ids_out or grad_rows_out with max_rows > 0");
-    return backward_prepare(c, who);
-}
-
-int gs_backward_visible_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
-                               float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
-    if (!c) return GS_ERR_INVALID;
-    if (int r = backward_visible_refusals(c, "gs_backward_visible_device", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
-        return r;
-    const BackwardFrame f = backward_frame(c);
-    launch_backward_visible_scan(f, ids_out, max_rows, count_out, c->stream);
-    if (max_rows) {
-        launch_backward_visible_rows(f, grad_rgba32f, grad_depth, max_rows, grad_rows_out, c->stream);
-        c->bwd_rows = true;
-    }
-    return check_launch(c, "gs_backward_visible_device");
-}
-
-int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
-                        float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
-    if (!c) return GS_ERR_INVALID;
-    if (int r = backward_visible_refusals(c, "gs_backward_visible", grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out))
-        return r;
-    // V and its size first (the count has to reach the host anyway), then exactly min(|V|, max_rows) rows
-    if (int r = visible_count_sync(c, "gs_backward_visible", count_out)) return r;
-    const uint32_t count = *count_out, k = count < max_rows ? count : max_rows;
-    if (k) {
-        if (c->bwd_vis_rows < k) {
-            c->bwd_mem.free(c->bwd_vis_out);
-            c->bwd_vis_rows = 0;
-            HIP_TRY(c, c->bwd_mem.alloc(c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
-            c->bwd_vis_rows = k;
-        }
-        if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
-        launch_backward_visible_rows(backward_frame(c), grad_rgba32f, grad_depth, k, c->bwd_vis_out, c->stream);
-        c->bwd_rows = true;
-        if (int r = check_launch(c, "gs_backward_visible")) return r;
-        HIP_TRY(c, hipMemcpyAsync(ids_out, c->bwd.vis_ids, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(grad_rows_out, c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    const bool count_only = !max_rows && !ids_out && !grad_rows_out;      // asked for no row: none is missing
-    return count > max_rows && !count_only ? GS_WARN_OVERFLOW : GS_OK;
-}
-
-int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,
-                            float* grad_accum, uint32_t* seen, float* max_radius) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_densify_stats_device";
-    if (max_rows && (!ids_dev || !count_dev || !grad_accum || !seen || !max_radius))
-        return fail(c, GS_ERR_INVALID, who + ": null ids, count, grad_accum, seen or max_radius with max_rows > 0");
-    if (int r = backward_prepare(c, who.c_str())) return r;
-    if (!c->bwd_rows) return fail(c, GS_ERR_INVALID, who + ": no gs_backward* on this frame");
-    if (n != c->n) return fail(c, GS_ERR_INVALID, who + ": n differs from the scene's");
-    if (!max_rows) return GS_OK;
-    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.scan.offsets, c->bwd.rows,
-                             c->scratch.raster, c->last_fp.capacity, c->last_fp.width, c->last_fp.height,
-                             grad_accum, seen, max_radius};
-    launch_densify_stats(a, c->stream);
-    return check_launch(c, who.c_str());
-}
-
-void gs_default_densify_params(gs_densify_params* p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->struct_size = (uint32_t)sizeof(*p);
-    p->grad_threshold = 2e-4f;
-    p->split_scale = 0.01f;
-    p->prune_opacity = 0.005f;
-    p->prune_scale = std::numeric_limits<float>::infinity();
-    p->prune_radius = std::numeric_limits<float>::infinity();
-    p->split_shrink = 1.6f;
-    p->seed = 0;
-}
-
-// the scratch of gs_densify_device for n splats, kept from call to call and grown when a larger cloud comes
-static int densify_scratch(gs_ctx* c, uint32_t n, const std::string& who) {
-    if (c->densify_cap >= n) return GS_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
-    DeviceOwner& mem = c->densify_mem;
-    mem.release();
-    c->densify_cap = 0;
-    const hipError_t e = alloc_splat_scan(mem, c->densify_scan, n, 4);
-    if (e != hipSuccess) {
-        mem.release();
-        return fail(c, GS_ERR_HIP, who + hipGetErrorString(e));
-    }
-    c->densify_cap = n;
-    return GS_OK;
-}
-
-int gs_densify_device(gs_ctx* c, const float* records, const float* m, const float* v, uint32_t n, const float* grad_accum,
-                      const uint32_t* seen, const float* max_radius, const gs_densify_params* p, float* records_out,
-                      float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out) {
-    if (!c) return GS_ERR_INVALID;
-    const std::string who = "gs_densify_device: ";
-    if (!records || !grad_accum || !seen || !max_radius || !counts_out)
-        return fail(c, GS_ERR_INVALID, who + "null records, grad_accum, seen, max_radius or counts_out");
-    if (max_out && !records_out) return fail(c, GS_ERR_INVALID, who + "null records_out with max_out > 0");
-    if (!p) return fail(c, GS_ERR_INVALID, who + "null gs_densify_params");
-    if (n == 0) return fail(c, GS_ERR_INVALID, who + "n is 0");
-    if (n >= 0x80000000u) return fail(c, GS_ERR_INVALID, who + "n must be below 2^31 (the outputs are counted in 32 bits)");
-    if (p->struct_size != sizeof(gs_densify_params))
-        return fail(c, GS_ERR_INVALID, who + "gs_densify_params.struct_size does not match this library (call gs_default_densify_params first)");
-    if (p->grad_threshold != p->grad_threshold) return fail(c, GS_ERR_INVALID, who + "grad_threshold is a NaN");
-    if (!(p->split_shrink > 0.0f)) return fail(c, GS_ERR_INVALID, who + "split_shrink must be greater than 0");
-    const bool moments = m || v || m_out || v_out;
-    if (moments && !(m && v && (!max_out || (m_out && v_out))))
-        return fail(c, GS_ERR_INVALID, who + "m, v, m_out and v_out must be given all together or not at all");
-    // no output may share bytes with an input, or with another output
-    struct Span { const void* at; size_t bytes; };
-    const size_t in_bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES, out_bytes = (size_t)max_out * GS_GAUSSIAN_RECORD_BYTES;
-    const Span ins[] = {{records, in_bytes}, {m, in_bytes}, {v, in_bytes}, {grad_accum, (size_t)n * 4}, {seen, (size_t)n * 4},
-                        {max_radius, (size_t)n * 4}};
-    const Span outs[] = {{records_out, out_bytes}, {m_out, out_bytes}, {v_out, out_bytes}, {counts_out, 16}};
-    auto overlap = [](const Span& a, const Span& b) {
-        const uintptr_t a0 = (uintptr_t)a.at, b0 = (uintptr_t)b.at;
-        return a.at && b.at && a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-    };
-    for (const Span& o : outs)
-        for (const Span& i : ins)
-            if (overlap(o, i)) return fail(c, GS_ERR_INVALID, who + "an output array aliases an input");
-    for (size_t o = 0; o < std::size(outs); ++o)
-        for (size_t k = o + 1; k < std::size(outs); ++k)
-            if (overlap(outs[o], outs[k])) return fail(c, GS_ERR_INVALID, who + "two output arrays alias each other");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int r = densify_scratch(c, n, who)) return r;
-    DensifyArgs a{};
-    a.records = records; a.m = m; a.v = v; a.n = n;
-    a.grad_accum = grad_accum; a.seen = seen; a.max_radius = max_radius;
-    a.rule = DensifyRule{p->grad_threshold, p->split_scale, p->prune_opacity, p->prune_scale, p->prune_radius};
-    a.split_shrink = p->split_shrink; a.seed = p->seed;
-    a.records_out = records_out; a.m_out = m_out; a.v_out = v_out; a.max_out = max_out;
-    a.scan = c->densify_scan;
-    launch_densify(a, counts_out, c->stream);
-    return check_launch(c, "gs_densify_device");
-}
-
 static int apply_tile_rows(gs_ctx* c, uint32_t row_begin, uint32_t row_end, uint32_t stride, uint32_t phase,
                            bool compact_out) {
+    // everything that can fail first: a context that reports an error keeps its old rows, with the sort bits and graphs of those
+    const bool graphs = c->run_graph[0].exec || c->run_graph[1].exec || c->chain_graph.exec;
+    if (c->elems_note || graphs) HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the note or execute a graph
+    // another band: another list length (GS_COUNT_AUTO learns it from the next frame)
+    if (c->elems_note) *(volatile uint32_t*)c->elems_note = 0u;
+    if (graphs) drop_sort_graph(c);
     c->row_begin = row_begin; c->row_end = row_end; c->row_stride = stride;
     c->first_row = row_begin + phase;
     c->rows_owned = c->first_row < row_end ? (row_end - c->first_row + stride - 1u) / stride : 0u;
     c->compact_out = compact_out;
-    c->bwd_frame = false; c->bwd_rows = false;
-    if (c->elems_note) {           // another band: another list length (GS_COUNT_AUTO learns it from the next frame)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // no frame in flight may still write the old one
-        *(volatile uint32_t*)c->elems_note = 0u;
-    }
+    scene_or_rows_changed(c);
     const uint32_t owned_tiles = c->rows_owned * c->grid_w;
     c->band_sort_bits = num_sort_bits_for(owned_tiles ? owned_tiles : 1u);
     c->hi16 = owned_tiles <= 65535u;
-    if (c->run_graph[0].exec || c->run_graph[1].exec || c->chain_graph.exec) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // the graph may still be executing
-        drop_sort_graph(c);
-    }
     return GS_OK;
 }
 
@@ -1337,28 +886,6 @@ int gs_render(gs_ctx* c, const float view[16], const float proj[16], const float
     return rc;
 }
 
-int gs_debug_init_sort_list(gs_ctx* c, const float view[16], const float proj[16],
-                            const float cam_pos[3], uint32_t sh_mode) {
-    if (!c) return GS_ERR_INVALID;
-    if (!c->n || !c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_debug_init_sort_list: scene/resolution not set");
-    if (!view || !proj || !cam_pos || sh_mode > 2u) return fail(c, GS_ERR_INVALID, "gs_debug_init_sort_list: bad argument");
-    HIP_TRY(c, hipSetDevice(c->device));
-    FrameParams fp = make_frame_params(c, view, proj, cam_pos, sh_mode);
-    fp.parity = (c->emit_parity ^= 1u);
-    c->last_fp = fp;
-    c->bwd_frame = false; c->bwd_rows = false;
-    launch_project(fp, c->scene, c->scratch, c->stream);
-    launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, c->stream);
-    launch_emit(fp, c->scratch, c->sort, c->stream);
-    if (int r = check_launch(c, "InitSortList")) return r;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->have_frame = false;
-    c->unsorted_valid = true;
-    SortParams sp{};
-    HIP_TRY(c, hipMemcpy(&sp, c->sort.params, sizeof(sp), hipMemcpyDeviceToHost));
-    return sp.overflow ? GS_WARN_OVERFLOW : GS_OK;
-}
-
 int gs_synchronize(gs_ctx* c) {
     if (!c) return GS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -1375,128 +902,6 @@ int gs_get_timings(const gs_ctx* c, gs_timings* out) {
 int gs_get_host_timings(const gs_ctx* c, gs_host_timings* out) {
     if (!c || !out) return GS_ERR_INVALID;
     *out = c->host;
-    return GS_OK;
-}
-
-// The sort list holds compact tile ids (uint16 or uint32, FrameParams) -> the uint32 GLOBAL tile ids callers expect
-static int read_tile_words(gs_ctx* c, const uint32_t* dev, uint32_t num_elems, void* dst, size_t bytes) {
-    if (bytes > (size_t)num_elems * sizeof(uint32_t)) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
-    const size_t cnt = bytes / sizeof(uint32_t);
-    uint32_t* out = static_cast<uint32_t*>(dst);
-    if (c->hi16) {
-        std::vector<uint16_t> h(num_elems);
-        if (num_elems) HIP_TRY(c, hipMemcpy(h.data(), dev, (size_t)num_elems * sizeof(uint16_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < cnt; ++i) out[i] = h[i];
-    } else if (cnt) {
-        HIP_TRY(c, hipMemcpy(out, dev, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    for (size_t i = 0; i < cnt; ++i) {
-        const uint32_t k = out[i] / c->grid_w, x = out[i] - k * c->grid_w;
-        out[i] = (c->first_row + k * c->row_stride) * c->grid_w + x;
-    }
-    return GS_OK;
-}
-
-int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
-    if (!c || !dst) return GS_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!c->have_frame && !c->unsorted_valid && which != GS_BUF_IMAGE) return fail(c, GS_ERR_NO_SCENE, "gs_debug_read: no frame rendered yet");
-    SortParams sp{};
-    HIP_TRY(c, hipMemcpy(&sp, c->sort.params, sizeof(sp), hipMemcpyDeviceToHost));
-    const size_t e_bytes = (size_t)sp.num_elems * sizeof(uint32_t);
-    const void* src = nullptr;
-    size_t avail = 0;
-    const int si = c->sorted_index;
-    switch (which) {
-        case GS_BUF_SORTED_TILE:
-            return read_tile_words(c, c->sort.hi[si], sp.num_elems, dst, bytes);
-        case GS_BUF_SORTED_DEPTH:
-            if (c->depth_dropped && c->have_frame && !c->unsorted_valid) {
-                // the frame path stops moving the depth words once they are sorted: rebuild them from the ids
-                if (bytes > e_bytes) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
-                std::vector<uint32_t> ids(sp.num_elems), depth(c->n);
-                if (sp.num_elems) HIP_TRY(c, hipMemcpy(ids.data(), c->sort.id[si], e_bytes, hipMemcpyDeviceToHost));
-                HIP_TRY(c, hipMemcpy(depth.data(), c->scratch.depth_key, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                uint32_t* out = static_cast<uint32_t*>(dst);
-                for (size_t i = 0; i < bytes / sizeof(uint32_t); ++i) out[i] = ids[i] < c->n ? depth[ids[i]] : 0u;
-                return GS_OK;
-            }
-            src = c->sort.lo[si]; avail = e_bytes; break;
-        case GS_BUF_SORTED_ID: src = c->sort.id[si]; avail = e_bytes; break;
-        case GS_BUF_RANGES: src = c->ranges; avail = (size_t)c->grid_w * c->grid_h * 8; break;
-        case GS_BUF_COUNT: {
-            if (bytes > sizeof(uint64_t)) return fail(c, GS_ERR_INVALID, "gs_debug_read: size");
-            std::memcpy(dst, &sp.counter, bytes);
-            return GS_OK;
-        }
-        case GS_BUF_IMAGE: src = c->framebuffer; avail = (size_t)c->width * c->height * 4; break;
-        case GS_BUF_UNSORTED_TILE:
-        case GS_BUF_UNSORTED_DEPTH:
-        case GS_BUF_UNSORTED_ID:
-            // the list as emitted lives in ping-pong half 0 and is overwritten by the second pass
-            if (!c->unsorted_valid)
-                return fail(c, GS_ERR_INVALID, "gs_debug_read: unsorted list only valid after gs_debug_init_sort_list");
-            if (which == GS_BUF_UNSORTED_TILE) return read_tile_words(c, c->sort.hi[0], sp.num_elems, dst, bytes);
-            src = which == GS_BUF_UNSORTED_DEPTH ? c->sort.lo[0] : c->sort.id[0];
-            avail = e_bytes;
-            break;
-        case GS_BUF_COLOR:
-        case GS_BUF_COV: {
-            const size_t need = (size_t)c->n * 4 * sizeof(float);
-            if (bytes > need) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
-            std::vector<SplatRaster> host(c->n);
-            HIP_TRY(c, hipMemcpy(host.data(), c->scratch.raster, (size_t)c->n * sizeof(SplatRaster), hipMemcpyDeviceToHost));
-            // color.a as the reference stores it (InitSortList.comp:126) is the opacity itself; the record's copy is
-            // already zeroed where the 2x2 determinant vanishes (RenderGaussians.comp:104), so it comes from the scene
-            std::vector<float> opacity;
-            std::vector<uint32_t> touched;
-            // N6 (InitSortList.comp:124-127): the reference stores colour for EVERY splat that passes the culls; the frame
-            // evaluates it for the emitting ones only, so the others are evaluated here, on demand, from the last frame's
-            // camera (k_debug_colour) -- in a context that owns the whole grid.  A context that owns a subset of the tile rows
-            // does not even project the splats that cannot reach its rows: there GS_BUF_COLOR stays what the frame stored.
-            std::vector<float> on_demand;
-            const bool whole_grid = c->row_begin == 0u && c->row_end == c->grid_h && c->row_stride == 1u;
-            if (which == GS_BUF_COLOR) {
-                opacity.resize(c->n); touched.resize(c->n);
-                HIP_TRY(c, hipMemcpy(opacity.data(), c->scene.opacity, (size_t)c->n * sizeof(float), hipMemcpyDeviceToHost));
-                HIP_TRY(c, hipMemcpy(touched.data(), c->scratch.tiles_touched, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                if (whole_grid) {
-                    float* dev = nullptr;
-                    HIP_TRY(c, hipMalloc((void**)&dev, need));
-                    launch_debug_colour(c->last_fp, c->scene, c->scratch, dev, c->stream);
-                    hipError_t e = hipGetLastError();
-                    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                    on_demand.resize((size_t)c->n * 4);
-                    if (e == hipSuccess) e = hipMemcpy(on_demand.data(), dev, need, hipMemcpyDeviceToHost);
-                    (void)hipFree(dev);
-                    HIP_TRY(c, e);
-                }
-            }
-            // records of a wave (64 consecutive splats) that k_project did not store this frame -- wholly culled, or with
-            // nothing to emit into this context's tile rows -- read back as zero, what a culled splat's scratch holds
-            std::vector<uint8_t> wrote((size_t)c->num_blocks * 4);
-            HIP_TRY(c, hipMemcpy(wrote.data(), c->scratch.wave_wrote, wrote.size(), hipMemcpyDeviceToHost));
-            std::vector<float> outv((size_t)c->n * 4, 0.0f);
-            for (uint32_t i = 0; i < c->n; ++i) {
-                if (!wrote[i / 64u]) continue;
-                const SplatRaster& r = host[i];
-                float* o = &outv[(size_t)i * 4];
-                if (which == GS_BUF_COLOR) {
-                    if (touched[i]) { o[0] = r.r; o[1] = r.g; o[2] = r.b; o[3] = opacity[i]; }       // what the frame stored and blended
-                    else if (!on_demand.empty() && on_demand[(size_t)i * 4 + 3] != 0.0f) {           // passed the culls, touched no tile
-                        o[0] = on_demand[(size_t)i * 4]; o[1] = on_demand[(size_t)i * 4 + 1]; o[2] = on_demand[(size_t)i * 4 + 2]; o[3] = opacity[i];
-                    }
-                }
-                else { o[0] = r.cx; o[1] = r.cy; o[2] = r.cz; o[3] = 0.0f; }
-            }
-            std::memcpy(dst, outv.data(), bytes);
-            return GS_OK;
-        }
-        default: return fail(c, GS_ERR_INVALID, "gs_debug_read: unknown buffer id");
-    }
-    if (bytes > avail) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
-    if (bytes) HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return GS_OK;
 }
 
@@ -1540,114 +945,6 @@ int gs_camera_matrices(const float pos[3], float yaw, float pitch, float aspect,
     proj[10] = far_plane / (near_plane - far_plane);
     proj[11] = -1.0f;
     proj[14] = -(far_plane * near_plane) / (far_plane - near_plane);
-    return GS_OK;
-}
-
-int gs_sort_host(gs_ctx* c, uint32_t* tile, uint32_t* depth, uint32_t* id, uint32_t n,
-                 uint32_t num_sort_bits) {
-    if (!c || !tile || !depth || !id) return GS_ERR_INVALID;
-    if (num_sort_bits == 0 || num_sort_bits > 64 || (num_sort_bits % kRadixBits) != 0)
-        return fail(c, GS_ERR_INVALID, "gs_sort_host: num_sort_bits must be a multiple of 4 in [4,64]");
-    if (n == 0) return GS_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    SortBuffers sb{};
-    DeviceOwner mem;
-    int rc = alloc_sort(c, mem, sb, n);
-    if (rc != GS_OK) { mem.release(); return rc; }
-    const size_t bytes = (size_t)n * sizeof(uint32_t);
-    hipError_t e = hipMemcpyAsync(sb.hi[0], tile, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sb.lo[0], depth, bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sb.id[0], id, bytes, hipMemcpyHostToDevice, c->stream);
-    int si = 0;
-    if (e == hipSuccess) {
-        launch_set_sort_params(sb.params, sb.coarse, n, c->stream);
-        si = launch_radix_sort(sb, whole_list_run(c, n, num_sort_bits), c->stream);
-        e = si < 0 ? hipErrorInvalidValue : hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(tile, sb.hi[si], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(depth, sb.lo[si], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(id, sb.id[si], bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    mem.release();
-    if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_sort_host: ") + hipGetErrorString(e));
-    return GS_OK;
-}
-
-int gs_sort_bench(gs_ctx* c, uint32_t n, uint32_t num_tiles, uint32_t iters, uint64_t seed,
-                  float* ms_per_sort, uint32_t* sorted_ok) {
-    if (!c || !ms_per_sort || n == 0 || num_tiles == 0 || iters == 0) return GS_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    SortBuffers sb{};
-    DeviceOwner mem;
-    int rc = alloc_sort(c, mem, sb, n);
-    if (rc != GS_OK) { mem.release(); return rc; }
-    const SortRun run = whole_list_run(c, n, num_sort_bits_for(num_tiles));
-    uint32_t* bad = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = mem.alloc(bad, sizeof(uint32_t));
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float total_ms = 0.0f;
-    int si = 0;
-    for (uint32_t it = 0; it < iters + 1 && e == hipSuccess; ++it) {   // iteration 0 = warm-up
-        launch_fill_random_keys(sb.lo[0], sb.hi[0], sb.id[0], n, num_tiles, seed + it, c->stream);
-        launch_set_sort_params(sb.params, sb.coarse, n, c->stream);
-        e = hipEventRecord(e0, c->stream);
-        if (e != hipSuccess) break;
-        si = launch_radix_sort(sb, run, c->stream);
-        if (si < 0) { si = 0; e = hipErrorInvalidValue; break; }
-        e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        float ms = 0.0f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (it > 0) total_ms += ms;
-    }
-    uint32_t bad_host = 0;
-    if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream);
-    if (e == hipSuccess) {
-        launch_check_sorted(sb.lo[si], sb.hi[si], n, bad, c->stream);
-        e = hipMemcpyAsync(&bad_host, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    mem.release();
-    if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_sort_bench: ") + hipGetErrorString(e));
-    *ms_per_sort = total_ms / (float)iters;
-    if (sorted_ok) *sorted_ok = bad_host == 0 ? 1u : 0u;
-    return GS_OK;
-}
-
-int gs_membench(gs_ctx* c, int kind, size_t bytes, uint32_t blocks, uint32_t iters, float* gbps, float* ms_out) {
-    if (!c || !gbps || bytes < 16 || iters == 0 || kind < 0 || kind > 12) return GS_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    bytes &= ~(size_t)15;
-    if (blocks == 0) blocks = 2048;
-    char *src = nullptr, *dst = nullptr;
-    DeviceOwner mem;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = mem.alloc(src, bytes + 65536);     // slack: the skewed scatter probes write a little past `bytes`
-    if (e == hipSuccess) e = mem.alloc(dst, bytes + 65536);
-    if (e == hipSuccess) e = hipMemsetAsync(src, 0x5A, bytes, c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dst, 0, bytes, c->stream);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float ms = 0.0f;
-    if (e == hipSuccess) {
-        for (int w = 0; w < 3; ++w) launch_stream_probe(kind, src, dst, bytes, blocks, c->stream);
-        e = hipEventRecord(e0, c->stream);
-        for (uint32_t i = 0; i < iters; ++i) launch_stream_probe(kind, src, dst, bytes, blocks, c->stream);
-        if (e == hipSuccess) e = hipEventRecord(e1, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    mem.release();
-    if (e != hipSuccess) return fail(c, GS_ERR_HIP, std::string("gs_membench: ") + hipGetErrorString(e));
-    const double moved = (double)bytes * ((kind & 1) || kind >= 4 ? 2.0 : 1.0) * iters;
-    *gbps = (float)(moved / (ms * 1e-3) / 1e9);
-    if (ms_out) *ms_out = ms / (float)iters;
     return GS_OK;
 }
 

@@ -1,6 +1,8 @@
 // gs_ctx.h -- the context behind the opaque gs_ctx handle of include/gsplat.h, the owner of its device memory
-// (DeviceOwner) and the one error exit of the host code (fail / HIP_TRY).  Internal: shared by gs_api.cpp, gs_dist.cpp and
-// the tuning probes of tools/probe (libgsplat_probe.so), which are built from this tree against the same layout.
+// (DeviceOwner), what the last frame left behind (LastFrame) and the one error exit of the host code (fail / HIP_TRY).
+// Internal: shared by the host files of the library (gs_api.cpp: context, scene, resolution, frame; gs_train.cpp: the training
+// calls; gs_debug.cpp: read-backs and micro-benchmarks; gs_dist.cpp) and the tuning probes of tools/probe (libgsplat_probe.so),
+// which are built from this tree against the same layout.
 #pragma once
 
 #include "../../include/gsplat.h"
@@ -52,6 +54,21 @@ struct SharedScene {
 };
 
 using HostClock = std::chrono::steady_clock;
+
+#define GS_HIDDEN __attribute__((visibility("hidden")))
+
+// What the last call that launched a sort list left behind.  Only the transitions behind gs_ctx write it; a call that is
+// about to launch a list first says so (list_launching), so nothing of an earlier frame stays readable or differentiable
+// when that call fails half way.
+struct LastFrame {
+    enum Kind : uint8_t { kNone, kUnsortedList, kFrame };
+    Kind kind = kNone;            // kUnsortedList: gs_debug_init_sort_list ran last; kFrame: a frame was enqueued last
+    bool differentiable = false;  // kFrame, and no upload or tile-row change since: gs_backward* may run
+    bool has_backward = false;    // bwd.rows holds a backward of this frame (a gs_backward* form ran the blend): what
+                                  // gs_densify_stats_device sums
+    int sorted_index = 0;         // kFrame: which ping-pong half holds the sorted list
+    gs::FrameParams fp{};         // of the InitSortList launch (gs_debug_read(GS_BUF_COLOR) evaluates colours on demand)
+};
 
 // A captured run of launches and what its capture returned (the ping-pong half that holds the sorted list)
 struct FrameGraph {
@@ -106,18 +123,13 @@ struct gs_ctx {
     float* out_rgba32f = nullptr;     // [H][W][4] while GS_OUTPUT_RGBA32F is on and a resolution is set
     float* out_depth = nullptr;       // [H][W] while GS_OUTPUT_DEPTH is on and a resolution is set
     bool outputs_valid = false;       // a frame has been enqueued since the mask or the resolution last changed
-    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity), freed with the resolution;
-    // bwd_frame = the last enqueued frame can be differentiated (no gs_set_resolution, gs_set_tile_rows*, upload or
-    // gs_debug_init_sort_list since)
+    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity), freed with the resolution
     gs::BackwardBuffers bwd{};
     DeviceOwner bwd_mem;              // of bwd and bwd_host_in / _out / bwd_vis_out
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
     float* bwd_host_out = nullptr;    // ... and the record gradients [N][84]
     float* bwd_vis_out = nullptr;     // gs_backward_visible (host pointers): bwd_vis_rows record gradients, grown on demand
     uint32_t bwd_vis_rows = 0;
-    bool bwd_frame = false;
-    bool bwd_rows = false;            // bwd.rows holds a backward of the current frame (a gs_backward* form ran the blend): what
-                                      // gs_densify_stats_device sums; cleared with bwd_frame, by a new frame and with bwd_mem
     // gs_densify_device: its scan (K = 4) for densify_cap splats; grown on demand, freed at gs_destroy
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
@@ -130,7 +142,6 @@ struct gs_ctx {
     uint32_t* ranges = nullptr;
     uint32_t* tile_order = nullptr;   // [tiles] RenderGaussians' dispatch order (GS_TILE_ORDER_LONGEST_FIRST)
     uint8_t* framebuffer = nullptr;
-    int sorted_index = 0;       // which ping-pong half holds the sorted list after the last frame
     // The radix passes of a frame (3 launches per pass, parameters fixed once resolution and band are) replayed
     // as one hipGraph launch: 36 launches -> 1 on the host side.  Built lazily, dropped when anything it baked in
     // changes.  Not used while per-Scatter events are recorded (record_timings == 2).
@@ -142,15 +153,12 @@ struct gs_ctx {
     uint32_t* elems_note = nullptr;   // pinned host word k_scan_blocks writes (element count + 1 of the latest list; 0: none
                                       // since the rows were set) -- what GS_COUNT_AUTO goes by
     bool sort_fed = false;        // the captured radix passes are the fed kind (k_scatter<.., FED>)
-    bool depth_dropped = false;   // last frame's tile-word passes did not carry the depth words (see k_scatter)
 
     gs_timings timings{};
     gs_host_timings host{};           // RECORD_CPU_TIMES (Renderer.cpp:299-456)
     HostClock::time_point last_entry{};
     bool have_entry = false;
-    bool have_frame = false;
-    bool unsorted_valid = false;   // last thing run was gs_debug_init_sort_list
-    gs::FrameParams last_fp{};     // of the last InitSortList launch (gs_debug_read(GS_BUF_COLOR) evaluates colours on demand)
+    LastFrame last;
 
     // gs_dist_init: the RCCL communicator of a multi-GPU frame (gs_dist.cpp)
     void* dist_comm = nullptr;
@@ -192,10 +200,41 @@ inline int fail(gs_ctx* ctx, int code, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(_e));                      \
     } while (0)
 
-// gs_dist.cpp: frees the buffers of a sharded frame (they are sized by the resolution); hidden: not an export.
-__attribute__((visibility("hidden"))) void gsi_dist_free_buffers(gs_ctx* c);
+// ---- the transitions of gs_ctx::last (and of outputs_valid, which lives as long as the mask: gs_set_outputs and the end of
+//      a resolution clear it too)
+// First statement of a call that launches a sort list: until it succeeds nothing is readable or differentiable
+GS_HIDDEN inline void list_launching(gs_ctx* c) {
+    c->last.kind = LastFrame::kNone;
+    c->last.differentiable = c->last.has_backward = c->outputs_valid = false;
+}
+GS_HIDDEN inline void frame_enqueued(gs_ctx* c, const gs::FrameParams& fp, int sorted_index) {
+    c->last = {LastFrame::kFrame, true, false, sorted_index, fp};
+    c->outputs_valid = c->outputs != 0u;
+}
+// gs_debug_init_sort_list succeeded; the list touches no output buffer: those are as valid as they were before it
+GS_HIDDEN inline void unsorted_list_ready(gs_ctx* c, const gs::FrameParams& fp, bool outputs_valid) {
+    c->last.kind = LastFrame::kUnsortedList;
+    c->last.fp = fp;
+    c->outputs_valid = outputs_valid;
+}
+// An in-place upload or a change of the tile rows: the lists stay readable, the frame is no longer the scene's
+GS_HIDDEN inline void scene_or_rows_changed(gs_ctx* c) { c->last.differentiable = c->last.has_backward = false; }
+GS_HIDDEN inline void backward_ran(gs_ctx* c) { c->last.has_backward = true; }
+GS_HIDDEN inline void resolution_freed(gs_ctx* c) { list_launching(c); }      // (its output buffers are gone with it)
+
+// gs_dist.cpp: frees the buffers of a sharded frame (they are sized by the resolution).
+GS_HIDDEN void gsi_dist_free_buffers(gs_ctx* c);
 // Renderer.cpp:458-475 for a frame enqueued with gs_render_device_async: wait, read the timestamps, fill gs_get_timings.
-__attribute__((visibility("hidden"))) int gsi_finish_frame(gs_ctx* c);
+GS_HIDDEN int gsi_finish_frame(gs_ctx* c);
+// gs_api.cpp, for gs_train.cpp and gs_debug.cpp: the error of the launches just made, under the name `what`
+GS_HIDDEN int check_launch(gs_ctx* ctx, const char* what);
+// ... the sort buffers of a list of `capacity` elements, owned by `mem` (which the caller releases, after a failure too)
+GS_HIDDEN int alloc_sort(gs_ctx* ctx, DeviceOwner& mem, gs::SortBuffers& s, uint32_t capacity);
+// ... the run of the stand-alone sorters: the whole key over a list of n elements, nothing dropped
+GS_HIDDEN gs::SortRun whole_list_run(const gs_ctx* c, uint32_t n, uint32_t num_sort_bits);
+GS_HIDDEN uint32_t num_sort_bits_for(uint32_t num_tiles);      // RadixSort.cpp:7-16 + 203-204
+// ... which: one GS_OUTPUT_* bit that is enabled and allocated -> its buffer and size; else fails
+GS_HIDDEN int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** dev, size_t* size);
 
 namespace gs {
 

@@ -374,7 +374,7 @@ int gs_convert_ply(const char* path, void* aos336_out, uint32_t max_records, uin
     return GS_OK;
 }
 
-// declared in gs_api.cpp's translation unit via gsplat.h
+// declared in gsplat.h beside the scene calls of gs_api.cpp
 int gs_load_ply(gs_ctx* ctx, const char* path) {
     if (!ctx || !path) return GS_ERR_INVALID;
     std::vector<float> rec;

@@ -1,0 +1,462 @@
+// gs_train.cpp -- the training calls of include/gsplat.h, which have no counterpart in the reference: Adam on listed rows,
+// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss* and density control.  Every entry point
+// refuses first (nothing enqueued, the context unchanged), then enqueues on the context's stream; a host-pointer form is
+// its _device twin between staging copies and a wait.
+#include "gs_ctx.h"
+
+#include <initializer_list>
+#include <iterator>
+#include <limits>
+
+using namespace gs;
+
+namespace {
+
+// ---- the vocabulary of the refusals: every text is "<entry point>: <what>", who = the entry point's __func__
+
+int refuse(gs_ctx* c, const std::string& who, const std::string& what, int code = GS_ERR_INVALID) {
+    return fail(c, code, who + ": " + what);
+}
+
+// rows are listed (max_rows > 0) and one of the arrays that hold them is null; names: those arrays as the text lists them
+int check_row_arrays(gs_ctx* c, const char* who, uint32_t max_rows, std::initializer_list<const void*> arrays, const char* names) {
+    const bool missing = max_rows && std::find(arrays.begin(), arrays.end(), nullptr) != arrays.end();
+    return missing ? refuse(c, who, std::string("null ") + names + " with max_rows > 0") : GS_OK;
+}
+
+// a gs_<kind>_params of another size than this library's
+int check_struct_size(gs_ctx* c, const char* who, const char* kind, uint32_t struct_size, size_t expected) {
+    if (struct_size == expected) return GS_OK;
+    return refuse(c, who, std::string("gs_") + kind + "_params.struct_size does not match this library (call gs_default_" + kind + "_params first)");
+}
+
+// two arrays share at least one byte (a null or empty array shares nothing)
+struct Span { const void* at; size_t bytes; };
+bool overlap(const Span& a, const Span& b) {
+    const uintptr_t a0 = (uintptr_t)a.at, b0 = (uintptr_t)b.at;
+    return a.at && b.at && a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+// The context holds a whole frame: not sharded (that refusal ends in sharded_tail), `ready` (else not_ready), all tile rows
+int check_whole_frame(gs_ctx* c, const char* who, const char* sharded_tail, bool ready = true, const char* not_ready = "") {
+    if (c->dist_sharded) return refuse(c, who, std::string("a sharded context (gs_dist_shard_rows) ") + sharded_tail);
+    if (!ready) return refuse(c, who, not_ready);
+    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
+        return refuse(c, who, "the context owns a subset of the tile rows");
+    return GS_OK;
+}
+
+// ---- Adam
+
+// what gs_adam_rows_device and gs_adam_rows_raw_device check of their parameters, and the step they hand the kernel
+int adam_step_of(gs_ctx* c, const char* who, uint32_t n, const gs_adam_params* p, AdamStep& a) {
+    if (!p) return refuse(c, who, "null gs_adam_params");
+    if (n == 0) return refuse(c, who, "n is 0");
+    if (int r = check_struct_size(c, who, "adam", p->struct_size, sizeof(gs_adam_params))) return r;
+    if (p->step == 0) return refuse(c, who, "step counts from 1");
+    if (!(p->beta1 >= 0.0f && p->beta1 < 1.0f) || !(p->beta2 >= 0.0f && p->beta2 < 1.0f))
+        return refuse(c, who, "beta1 and beta2 must be in [0, 1)");
+    if (!(p->eps >= 0.0f) || !std::isfinite(p->eps)) return refuse(c, who, "eps must be finite and not negative");
+    a.beta1 = p->beta1; a.beta2 = p->beta2; a.eps = p->eps;
+    a.c1 = 1.0f - p->beta1; a.c2 = 1.0f - p->beta2;
+    // the bias correction of step t in double, rounded once per group
+    const double t = (double)p->step;
+    const double root2 = std::sqrt(1.0 - std::pow((double)p->beta2, t)), bias1 = 1.0 - std::pow((double)p->beta1, t);
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) {
+        if (!(p->lr[g] >= 0.0f) || !std::isfinite(p->lr[g])) return refuse(c, who, "lr must be finite and not negative");
+        if (!(p->lo[g] <= p->hi[g])) return refuse(c, who, "lo must not exceed hi, and neither may be a NaN");
+        a.step[g] = (float)((double)p->lr[g] * root2 / bias1);
+        if (!std::isfinite(a.step[g])) return refuse(c, who, "lr times the bias correction is not a finite float");
+        a.lo[g] = p->lo[g]; a.hi[g] = p->hi[g];
+    }
+    return GS_OK;
+}
+
+// ---- the raw parameter space (gs_raw.hip)
+
+int convert_space(gs_ctx* c, const char* who, const float* src, float* dst, uint32_t n, bool to_raw) {
+    if (!c) return GS_ERR_INVALID;
+    if (!src || !dst) return refuse(c, who, "null raw or records");
+    if (n == 0) return refuse(c, who, "n is 0");
+    const size_t bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES;
+    if (overlap({src, bytes}, {dst, bytes})) return refuse(c, who, "raw aliases records");
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_convert_space(src, dst, n, to_raw, c->stream);
+    return check_launch(c, who);
+}
+
+// ---- gs_backward*
+
+// The buffers of a per-splat scan (gs_splat_scan.h) of K sums over n splats, into the lifetime `mem`
+hipError_t alloc_splat_scan(DeviceOwner& mem, SplatScan& s, uint32_t n, uint32_t K) {
+    const size_t rows = (size_t)K * backward_blocks(n) * sizeof(uint32_t);
+    hipError_t e = mem.alloc(s.offsets, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(s.block_sums, rows);
+    if (e == hipSuccess) e = mem.alloc(s.block_offsets, rows);
+    if (e == hipSuccess) e = mem.alloc(s.totals, K * sizeof(uint32_t));
+    return e;
+}
+
+// the refusals (nothing enqueued), then the scratch of the first call
+int backward_prepare(gs_ctx* c, const char* who) {
+    if (c->cfg.render_mode != GS_RENDER_EXACT) return refuse(c, who, "only GS_RENDER_EXACT frames can be differentiated");
+    const bool frame = c->capacity && c->n && c->last.differentiable;
+    const char* no_frame = "no frame since the last gs_set_resolution, gs_set_tile_rows* or upload";
+    if (int r = check_whole_frame(c, who, "cannot be differentiated", frame, no_frame)) return r;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->bwd.rows) {
+        DeviceOwner& mem = c->bwd_mem;
+        hipError_t e = mem.alloc(c->bwd.rows, backward_row_bytes(c->capacity));
+        if (e == hipSuccess) e = alloc_splat_scan(mem, c->bwd.scan, c->n, 2);
+        if (e == hipSuccess) e = mem.alloc(c->bwd.vis_ids, (size_t)c->n * sizeof(uint32_t));
+        if (e != hipSuccess) {
+            mem.release();
+            c->bwd_vis_rows = 0;
+            return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+        }
+    }
+    return GS_OK;
+}
+
+// The last frame as the backward launchers take it
+BackwardFrame backward_frame(const gs_ctx* c) {
+    return BackwardFrame{c->last.fp, c->scene, c->scratch, c->sort.id[c->last.sorted_index], c->ranges, c->bwd};
+}
+
+// Host gradients onto the device (bwd_host_in, allocated on first use), enqueued on the context's stream: the two host
+// pointers are replaced by their device copies (a null grad_depth stays null)
+int stage_host_grads(gs_ctx* c, const float*& grad_rgba32f, const float*& grad_depth) {
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->bwd_host_in) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_in, px * 5 * sizeof(float)));
+    float* din = c->bwd_host_in;
+    HIP_TRY(c, hipMemcpyAsync(din, grad_rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (grad_depth) HIP_TRY(c, hipMemcpyAsync(din + px * 4, grad_depth, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    grad_rgba32f = din;
+    if (grad_depth) grad_depth = din + px * 4;
+    return GS_OK;
+}
+
+// what gs_backward and gs_backward_device enqueue (device pointers)
+int enqueue_backward(gs_ctx* c, const char* who, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
+    launch_backward(backward_frame(c), grad_rgba32f, grad_depth, grad_records, c->stream);
+    backward_ran(c);
+    return check_launch(c, who);
+}
+
+// ... and both visible forms: the blend and the row sums of the first max_rows splats of V (which a scan has listed)
+int enqueue_visible_rows(gs_ctx* c, const char* who, const float* grad_rgba32f, const float* grad_depth, uint32_t max_rows,
+                         float* grad_rows) {
+    launch_backward_visible_rows(backward_frame(c), grad_rgba32f, grad_depth, max_rows, grad_rows, c->stream);
+    backward_ran(c);
+    return check_launch(c, who);
+}
+
+// V of the last frame into bwd.vis_ids and |V| into *count, on the host: the scan, then a wait for the stream
+int visible_count_sync(gs_ctx* c, const char* who, uint32_t* count) {
+    launch_backward_visible_scan(backward_frame(c), nullptr, 0u, nullptr, c->stream);
+    if (int r = check_launch(c, who)) return r;
+    HIP_TRY(c, hipMemcpyAsync(count, visible_count_of(c->bwd), 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba32f, const uint32_t* ids_out,
+                              const float* grad_rows_out, uint32_t max_rows, const uint32_t* count_out) {
+    if (!grad_rgba32f) return refuse(c, who, "null gradient pointer");
+    if (!count_out) return refuse(c, who, "null count_out");
+    if (int r = check_row_arrays(c, who, max_rows, {ids_out, grad_rows_out}, "ids_out or grad_rows_out")) return r;
+    return backward_prepare(c, who);
+}
+
+// ---- gs_photometric_loss*
+
+// the refusals (nothing enqueued), the image the call reads (rgba32f, or the context's own GS_OUTPUT_RGBA32F buffer for
+// NULL), then the scratch of the first call
+int loss_prepare(gs_ctx* c, const char* who, const float*& rgba32f, const float* target_rgb, float lambda,
+                 const float* bg, const float* loss_out, const float* grad_rgba32f) {
+    if (!target_rgb || !loss_out) return refuse(c, who, "null target_rgb or loss_out");
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return refuse(c, who, "lambda must be a finite value in [0, 1]");
+    if (bg && !(std::isfinite(bg[0]) && std::isfinite(bg[1]) && std::isfinite(bg[2]))) return refuse(c, who, "bg must be finite");
+    if (!c->capacity) return refuse(c, who, "gs_set_resolution not called");
+    if (int r = check_whole_frame(c, who, "has no whole frame to compare")) return r;
+    if (!rgba32f) {
+        void* dev = nullptr;
+        size_t size = 0;
+        if (int r = output_buffer(c, GS_OUTPUT_RGBA32F, who, &dev, &size)) return r;
+        if (!c->outputs_valid) return refuse(c, who, "no frame rendered since the outputs were enabled or resized");
+        rgba32f = static_cast<const float*>(dev);
+    }
+    if (grad_rgba32f && grad_rgba32f == rgba32f) return refuse(c, who, "grad_rgba32f must not be the image it differentiates");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->loss.maps) {
+        hipError_t e = c->loss_mem.alloc(c->loss.maps, loss_map_bytes(c->width, c->height));
+        if (e == hipSuccess) e = c->loss_mem.alloc(c->loss.tile_sums, loss_tile_bytes(c->width, c->height));
+        if (e != hipSuccess) {
+            c->loss_mem.release();
+            return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+        }
+    }
+    return GS_OK;
+}
+
+// what both forms enqueue (device pointers; bg is a host value)
+int enqueue_loss(gs_ctx* c, const char* who, const float* rgba32f, const float* target_rgb, float lambda, const float* bg,
+                 float* loss_out, float* grad_rgba32f) {
+    launch_photometric_loss(c->loss, rgba32f, target_rgb, lambda, bg, c->width, c->height, loss_out, grad_rgba32f, c->stream);
+    return check_launch(c, who);
+}
+
+// ---- density control
+
+// the scratch of gs_densify_device for n splats, kept from call to call and grown when a larger cloud comes
+int densify_scratch(gs_ctx* c, uint32_t n, const char* who) {
+    if (c->densify_cap >= n) return GS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
+    DeviceOwner& mem = c->densify_mem;
+    mem.release();
+    c->densify_cap = 0;
+    const hipError_t e = alloc_splat_scan(mem, c->densify_scan, n, 4);
+    if (e != hipSuccess) {
+        mem.release();
+        return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+    }
+    c->densify_cap = n;
+    return GS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+void gs_default_adam_params(gs_adam_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->step = 1;
+    p->beta1 = 0.9f; p->beta2 = 0.999f; p->eps = 1e-15f;
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
+    p->lr[GS_ADAM_POSITION] = 1.6e-4f;
+    p->lr[GS_ADAM_SCALE] = 5e-3f;     p->lo[GS_ADAM_SCALE] = 1e-7f;
+    p->lr[GS_ADAM_ROTATION] = 1e-3f;
+    p->lr[GS_ADAM_SH_DC] = 2.5e-3f;
+    p->lr[GS_ADAM_OPACITY] = 5e-2f;   p->lo[GS_ADAM_OPACITY] = 0.0f; p->hi[GS_ADAM_OPACITY] = 1.0f;
+    p->lr[GS_ADAM_SH_REST] = 1.25e-4f;
+}
+
+void gs_default_adam_params_raw(gs_adam_params* p) {
+    if (!p) return;
+    gs_default_adam_params(p);
+    const float inf = std::numeric_limits<float>::infinity();
+    for (int g = 0; g < GS_ADAM_GROUPS; ++g) { p->lo[g] = -inf; p->hi[g] = inf; }
+}
+
+int gs_adam_rows_device(gs_ctx* c, float* records_dev, float* m_dev, float* v_dev, uint32_t n, const uint32_t* ids_dev,
+                        const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, const gs_adam_params* p) {
+    if (!c) return GS_ERR_INVALID;
+    const char* rows = "records, m, v, ids, grad_rows or count";
+    if (int r = check_row_arrays(c, __func__, max_rows, {records_dev, m_dev, v_dev, ids_dev, grad_rows_dev, count_dev}, rows)) return r;
+    AdamStep a;
+    if (int r = adam_step_of(c, __func__, n, p, a)) return r;
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_adam_rows(records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_adam_rows_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                            const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows,
+                            const gs_adam_params* p) {
+    if (!c) return GS_ERR_INVALID;
+    const char* rows = "raw, records, m, v, ids, grad_rows or count";
+    if (int r = check_row_arrays(c, __func__, max_rows, {raw_dev, records_dev, m_dev, v_dev, ids_dev, grad_rows_dev, count_dev}, rows)) return r;
+    AdamStep a;
+    if (int r = adam_step_of(c, __func__, n, p, a)) return r;
+    const size_t bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES;
+    for (const float* other : {raw_dev, m_dev, v_dev})
+        if (overlap({records_dev, bytes}, {other, bytes})) return refuse(c, __func__, "records aliases raw, m or v");
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_adam_rows_raw(raw_dev, records_dev, m_dev, v_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, a, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_records_from_raw_device(gs_ctx* c, const float* raw_dev, float* records_dev, uint32_t n) {
+    return convert_space(c, "gs_records_from_raw_device", raw_dev, records_dev, n, false);
+}
+
+int gs_raw_from_records_device(gs_ctx* c, const float* records_dev, float* raw_dev, uint32_t n) {
+    return convert_space(c, "gs_raw_from_records_device", records_dev, raw_dev, n, true);
+}
+
+int gs_reset_opacity_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, float* m_dev, float* v_dev, uint32_t n,
+                                float max_opacity) {
+    if (!c) return GS_ERR_INVALID;
+    if (!raw_dev || !records_dev) return refuse(c, __func__, "null raw or records");
+    if (!m_dev != !v_dev) return refuse(c, __func__, "m and v must be given together or not at all");
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (!(max_opacity > 0.0f && max_opacity < 1.0f)) return refuse(c, __func__, "max_opacity must lie strictly between 0 and 1");
+    const float logit = (float)std::log((double)max_opacity / (1.0 - (double)max_opacity));
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_reset_opacity_raw(raw_dev, records_dev, m_dev, v_dev, n, max_opacity, logit, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
+    if (!c) return GS_ERR_INVALID;
+    if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");
+    if (int r = backward_prepare(c, __func__)) return r;
+    return enqueue_backward(c, __func__, grad_rgba32f, grad_depth, grad_records);
+}
+
+int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
+    if (!c) return GS_ERR_INVALID;
+    if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");
+    if (int r = backward_prepare(c, __func__)) return r;
+    const size_t bytes = (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES;
+    if (!c->bwd_host_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_out, bytes));
+    if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
+    if (int r = enqueue_backward(c, __func__, grad_rgba32f, grad_depth, c->bwd_host_out)) return r;
+    HIP_TRY(c, hipMemcpyAsync(grad_records, c->bwd_host_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_photometric_loss_device(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                               float* loss_out, float* grad_rgba32f) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = loss_prepare(c, __func__, rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
+    return enqueue_loss(c, __func__, rgba32f, target_rgb, lambda, bg, loss_out, grad_rgba32f);
+}
+
+int gs_photometric_loss(gs_ctx* c, const float* rgba32f, const float* target_rgb, float lambda, const float bg[3],
+                        float loss_out[3], float* grad_rgba32f) {
+    if (!c) return GS_ERR_INVALID;
+    const float* image = rgba32f;      // host, or (NULL form) the context's device buffer after loss_prepare
+    if (int r = loss_prepare(c, __func__, image, target_rgb, lambda, bg, loss_out, grad_rgba32f)) return r;
+    // device copies: rgba [px][4] | gradient [px][4] | target [px][3] | the three numbers (+ 1: 16-byte multiples)
+    const size_t px = (size_t)c->width * c->height;
+    if (!c->loss_host) HIP_TRY(c, c->loss_mem.alloc(c->loss_host, (px * 11 + 4) * sizeof(float)));
+    float* d_rgba = c->loss_host, *d_grad = d_rgba + px * 4, *d_target = d_grad + px * 4, *d_loss = d_target + px * 3;
+    if (rgba32f) {
+        HIP_TRY(c, hipMemcpyAsync(d_rgba, rgba32f, px * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        image = d_rgba;
+    }
+    HIP_TRY(c, hipMemcpyAsync(d_target, target_rgb, px * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int r = enqueue_loss(c, __func__, image, d_target, lambda, bg, d_loss, grad_rgba32f ? d_grad : nullptr)) return r;
+    HIP_TRY(c, hipMemcpyAsync(loss_out, d_loss, 3 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (grad_rgba32f) HIP_TRY(c, hipMemcpyAsync(grad_rgba32f, d_grad, px * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
+}
+
+int gs_visible_count(gs_ctx* c, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!count_out) return refuse(c, __func__, "null count_out");
+    if (int r = backward_prepare(c, __func__)) return r;
+    return visible_count_sync(c, __func__, count_out);
+}
+
+int gs_backward_visible_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
+                               float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_visible_refusals(c, __func__, grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out)) return r;
+    launch_backward_visible_scan(backward_frame(c), ids_out, max_rows, count_out, c->stream);
+    if (!max_rows) return check_launch(c, __func__);
+    return enqueue_visible_rows(c, __func__, grad_rgba32f, grad_depth, max_rows, grad_rows_out);
+}
+
+int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, uint32_t* ids_out,
+                        float* grad_rows_out, uint32_t max_rows, uint32_t* count_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_visible_refusals(c, __func__, grad_rgba32f, ids_out, grad_rows_out, max_rows, count_out)) return r;
+    // V and its size first (the count has to reach the host anyway), then exactly min(|V|, max_rows) rows
+    if (int r = visible_count_sync(c, __func__, count_out)) return r;
+    const uint32_t count = *count_out, k = count < max_rows ? count : max_rows;
+    if (k) {
+        if (c->bwd_vis_rows < k) {
+            c->bwd_mem.free(c->bwd_vis_out);
+            c->bwd_vis_rows = 0;
+            HIP_TRY(c, c->bwd_mem.alloc(c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES));
+            c->bwd_vis_rows = k;
+        }
+        if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
+        if (int r = enqueue_visible_rows(c, __func__, grad_rgba32f, grad_depth, k, c->bwd_vis_out)) return r;
+        HIP_TRY(c, hipMemcpyAsync(ids_out, c->bwd.vis_ids, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(grad_rows_out, c->bwd_vis_out, (size_t)k * GS_GAUSSIAN_RECORD_BYTES, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const bool count_only = !max_rows && !ids_out && !grad_rows_out;      // asked for no row: none is missing
+    return count > max_rows && !count_only ? GS_WARN_OVERFLOW : GS_OK;
+}
+
+int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,
+                            float* grad_accum, uint32_t* seen, float* max_radius) {
+    if (!c) return GS_ERR_INVALID;
+    const char* rows = "ids, count, grad_accum, seen or max_radius";
+    if (int r = check_row_arrays(c, __func__, max_rows, {ids_dev, count_dev, grad_accum, seen, max_radius}, rows)) return r;
+    if (int r = backward_prepare(c, __func__)) return r;
+    if (!c->last.has_backward) return refuse(c, __func__, "no gs_backward* on this frame");
+    if (n != c->n) return refuse(c, __func__, "n differs from the scene's");
+    if (!max_rows) return GS_OK;
+    const FrameParams& fp = c->last.fp;
+    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.scan.offsets, c->bwd.rows,
+                             c->scratch.raster, fp.capacity, fp.width, fp.height, grad_accum, seen, max_radius};
+    launch_densify_stats(a, c->stream);
+    return check_launch(c, __func__);
+}
+
+void gs_default_densify_params(gs_densify_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->grad_threshold = 2e-4f;
+    p->split_scale = 0.01f;
+    p->prune_opacity = 0.005f;
+    p->prune_scale = std::numeric_limits<float>::infinity();
+    p->prune_radius = std::numeric_limits<float>::infinity();
+    p->split_shrink = 1.6f;
+    p->seed = 0;
+}
+
+int gs_densify_device(gs_ctx* c, const float* records, const float* m, const float* v, uint32_t n, const float* grad_accum,
+                      const uint32_t* seen, const float* max_radius, const gs_densify_params* p, float* records_out,
+                      float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!records || !grad_accum || !seen || !max_radius || !counts_out)
+        return refuse(c, __func__, "null records, grad_accum, seen, max_radius or counts_out");
+    if (max_out && !records_out) return refuse(c, __func__, "null records_out with max_out > 0");
+    if (!p) return refuse(c, __func__, "null gs_densify_params");
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (n >= 0x80000000u) return refuse(c, __func__, "n must be below 2^31 (the outputs are counted in 32 bits)");
+    if (int r = check_struct_size(c, __func__, "densify", p->struct_size, sizeof(gs_densify_params))) return r;
+    if (p->grad_threshold != p->grad_threshold) return refuse(c, __func__, "grad_threshold is a NaN");
+    if (!(p->split_shrink > 0.0f)) return refuse(c, __func__, "split_shrink must be greater than 0");
+    const bool moments = m || v || m_out || v_out;
+    if (moments && !(m && v && (!max_out || (m_out && v_out))))
+        return refuse(c, __func__, "m, v, m_out and v_out must be given all together or not at all");
+    // no output may share bytes with an input, or with another output
+    const size_t in_bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES, out_bytes = (size_t)max_out * GS_GAUSSIAN_RECORD_BYTES;
+    const Span ins[] = {{records, in_bytes}, {m, in_bytes}, {v, in_bytes}, {grad_accum, (size_t)n * 4}, {seen, (size_t)n * 4},
+                        {max_radius, (size_t)n * 4}};
+    const Span outs[] = {{records_out, out_bytes}, {m_out, out_bytes}, {v_out, out_bytes}, {counts_out, 16}};
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlap(o, i)) return refuse(c, __func__, "an output array aliases an input");
+    for (size_t o = 0; o < std::size(outs); ++o)
+        for (size_t k = o + 1; k < std::size(outs); ++k)
+            if (overlap(outs[o], outs[k])) return refuse(c, __func__, "two output arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, __func__)) return r;
+    DensifyArgs a{};
+    a.records = records; a.m = m; a.v = v; a.n = n;
+    a.grad_accum = grad_accum; a.seen = seen; a.max_radius = max_radius;
+    a.rule = DensifyRule{p->grad_threshold, p->split_scale, p->prune_opacity, p->prune_scale, p->prune_radius};
+    a.split_shrink = p->split_shrink; a.seed = p->seed;
+    a.records_out = records_out; a.m_out = m_out; a.v_out = v_out; a.max_out = max_out;
+    a.scan = c->densify_scan;
+    launch_densify(a, counts_out, c->stream);
+    return check_launch(c, __func__);
+}
+
+} // extern "C"

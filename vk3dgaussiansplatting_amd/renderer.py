@@ -39,6 +39,11 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _vp(address: int | None):
+    """A device address as the library takes it; 0 and None are NULL."""
+    return C.c_void_p(address) if address else None
+
+
 class SphericalHarmonicsMode(enum.IntEnum):  # Camera.h:7-12
     ALL_BANDS = 0
     SKIP_FIRST_BAND = 1
@@ -435,6 +440,8 @@ class Renderer:
         self.resourceManager: ResourceManager | None = None
         self.numGaussians = 0
         self.numSortElements = 0
+        self.frameSerial = 0        # counts the calls that launched a sort list: what was drawn before the last is gone
+        self._outputs_mask = None   # the GS_OUTPUT_* mask setOutputs set last
         self.warmupFrames = self.WAIT_ELAPSED_WARMUP_FRAMES_FOR_AVG if warmup_frames is None else warmup_frames
         self._reset_avgs()
 
@@ -497,28 +504,36 @@ class Renderer:
 
     @staticmethod
     def _camera_args(cam: Camera):
-        """view, proj, pos (contiguous float32) and sh_mode, as gs_render* and gs_debug_init_sort_list take them."""
-        return (np.ascontiguousarray(cam.getViewMatrix(), dtype=np.float32),
-                np.ascontiguousarray(cam.getProjectionMatrix(), dtype=np.float32),
-                np.ascontiguousarray(cam.getPosition(), dtype=np.float32), int(cam.getShMode()))
+        """view, proj, pos and sh_mode of a Camera, as _launch takes them."""
+        return cam.getViewMatrix(), cam.getProjectionMatrix(), cam.getPosition(), int(cam.getShMode())
+
+    def _launch(self, fn, view, proj, cam_pos, sh_mode, *tail) -> int:
+        """fn = gs_render* or gs_debug_init_sort_list under the camera (view, proj: 16 floats, column-major; cam_pos: 3) with
+        the arguments behind sh_mode in tail; returns the checked status."""
+        v = np.ascontiguousarray(view, dtype=np.float32).reshape(16)
+        p = np.ascontiguousarray(proj, dtype=np.float32).reshape(16)
+        c = np.ascontiguousarray(cam_pos, dtype=np.float32).reshape(3)
+        self.frameSerial += 1
+        return self._ctx.check(fn(self._ctx.handle, _p(v), _p(p), _p(c), int(sh_mode), *tail))
+
+    def drawCamera(self, view, proj, cam_pos, sh_mode: int, device_ptr: int | None = None, sync: bool = True) -> int:
+        """drawDevice under a camera given by its matrices instead of a Scene; returns the status (also lastStatus)."""
+        fn = _lib.lib().gs_render_device if sync else _lib.lib().gs_render_device_async
+        self.lastStatus = self._launch(fn, view, proj, cam_pos, sh_mode, _vp(device_ptr))
+        return self.lastStatus
 
     # -- Renderer.cpp:297-515
     def draw(self, scene: Scene, out: np.ndarray | None = None) -> np.ndarray:
         if out is None:
             out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
-        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
-        self.lastStatus = self._ctx.check(_lib.lib().gs_render(
-            self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode, _p(out)))
+        self.lastStatus = self._launch(_lib.lib().gs_render, *self._camera_args(scene.getCamera()), _p(out))
         self._accumulate()
         return out
 
     def drawDevice(self, scene: Scene, device_ptr: int | None = None, sync: bool = True, compact_rows: bool = False):
         """Same frame with the image left in HBM (device_ptr = e.g. torch tensor .data_ptr()).  compact_rows only
         documents the call site: whether rows are packed is a property of the context (setTileRowsInterleaved)."""
-        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
-        fn = _lib.lib().gs_render_device if sync else _lib.lib().gs_render_device_async
-        self.lastStatus = self._ctx.check(fn(self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode,
-                                             C.c_void_p(device_ptr or 0)))
+        self.drawCamera(*self._camera_args(scene.getCamera()), device_ptr, sync)
         if sync:
             self._accumulate()
 
@@ -554,8 +569,7 @@ class Renderer:
 
     # -- stage-level read-back (no reference counterpart)
     def debugInitSortList(self, scene: Scene) -> int:
-        view, proj, pos, sh_mode = self._camera_args(scene.getCamera())
-        return self._ctx.check(_lib.lib().gs_debug_init_sort_list(self._ctx.handle, _p(view), _p(proj), _p(pos), sh_mode))
+        return self._launch(_lib.lib().gs_debug_init_sort_list, *self._camera_args(scene.getCamera()))
 
     def debugRead(self, which: int) -> np.ndarray:
         info = self.sceneInfo()
@@ -584,6 +598,12 @@ class Renderer:
         depth / alpha).  Both off (the default) = the RGBA8 frame alone."""
         mask = (_lib.GS_OUTPUT_RGBA32F if rgba32f else 0) | (_lib.GS_OUTPUT_DEPTH if depth else 0)
         self._ctx.check(_lib.lib().gs_set_outputs(self._ctx.handle, mask))
+        self._outputs_mask = mask
+
+    def ensureOutputs(self, mask: int):
+        """setOutputs for the GS_OUTPUT_* mask, unless it is the mask setOutputs set last (the call waits for the stream)."""
+        if mask != self._outputs_mask:
+            self.setOutputs(rgba32f=bool(mask & _lib.GS_OUTPUT_RGBA32F), depth=bool(mask & _lib.GS_OUTPUT_DEPTH))
 
     def readOutput(self, which: int) -> np.ndarray:
         """The last frame's GS_OUTPUT_RGBA32F (float32 (H, W, 4)) or GS_OUTPUT_DEPTH (float32 (H, W)) buffer."""
@@ -627,7 +647,7 @@ class Renderer:
         """The same with device addresses (float32 (H, W, 4), (H, W) or None, (N, 84)); enqueued on the context's stream
         without waiting (synchronize() waits)."""
         self._ctx.check(_lib.lib().gs_backward_device(self._ctx.handle, C.c_void_p(grad_rgba32f_ptr),
-                                                      C.c_void_p(grad_depth_ptr) if grad_depth_ptr else None,
+                                                      _vp(grad_depth_ptr),
                                                       C.c_void_p(grad_records_ptr)))
 
     def visibleCount(self) -> int:
@@ -659,9 +679,9 @@ class Renderer:
         enqueued on the context's stream without waiting.  The caller compares the count with max_rows after
         synchronize()."""
         self._ctx.check(_lib.lib().gs_backward_visible_device(
-            self._ctx.handle, C.c_void_p(grad_rgba32f_ptr), C.c_void_p(grad_depth_ptr) if grad_depth_ptr else None,
-            C.c_void_p(ids_ptr) if ids_ptr else None, C.c_void_p(rows_ptr) if rows_ptr else None, int(max_rows),
-            C.c_void_p(count_ptr) if count_ptr else None))
+            self._ctx.handle, C.c_void_p(grad_rgba32f_ptr), _vp(grad_depth_ptr),
+            _vp(ids_ptr), _vp(rows_ptr), int(max_rows),
+            _vp(count_ptr)))
 
     # -- photometric loss of a frame (no reference counterpart; include/gsplat.h, gs_photometric_loss*)
     @staticmethod
@@ -701,9 +721,9 @@ class Renderer:
         loss: 3 floats, grad: (H, W, 4) or None); bg stays a host value.  Enqueued on the context's stream without waiting."""
         b = self._bg_arg(bg)
         self._ctx.check(_lib.lib().gs_photometric_loss_device(
-            self._ctx.handle, C.c_void_p(rgba_ptr) if rgba_ptr else None, C.c_void_p(target_ptr) if target_ptr else None,
-            float(lam), None if b is None else _p(b), C.c_void_p(loss_ptr) if loss_ptr else None,
-            C.c_void_p(grad_ptr) if grad_ptr else None))
+            self._ctx.handle, _vp(rgba_ptr), _vp(target_ptr),
+            float(lam), None if b is None else _p(b), _vp(loss_ptr),
+            _vp(grad_ptr)))
 
     def uploadDevice(self, ptr: int, n: int):
         """Gaussian records (float32 (n, 84)) from device memory.  With the scene's n: rewritten in place on the context's
@@ -722,15 +742,13 @@ class Renderer:
         with the gradient rows (max_rows, 84); ids, rows and count as backwardVisibleDevice left them.  params:
         default_adam_params(), with `step` = the number of this step, counted from 1.  Enqueued on the context's stream
         without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_adam_rows_device(self._ctx.handle, vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(ids_ptr),
-                                                       vp(rows_ptr), vp(count_ptr), int(max_rows), C.byref(params)))
+        self._ctx.check(_lib.lib().gs_adam_rows_device(self._ctx.handle, _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(ids_ptr),
+                                                       _vp(rows_ptr), _vp(count_ptr), int(max_rows), C.byref(params)))
 
     def uploadRowsDevice(self, ptr: int, n: int, ids_ptr: int, count_ptr: int, max_rows: int):
         """uploadDevice for the listed rows alone: the planes of splats ids[i], i < min(count, max_rows), rewritten in place from
         the records at ptr (float32 (n, 84), n = the scene's).  Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_upload_rows_device(self._ctx.handle, vp(ptr), int(n), vp(ids_ptr), vp(count_ptr), int(max_rows)))
+        self._ctx.check(_lib.lib().gs_upload_rows_device(self._ctx.handle, _vp(ptr), int(n), _vp(ids_ptr), _vp(count_ptr), int(max_rows)))
 
     # -- the raw parameter space (no reference counterpart; include/gsplat.h, gs_adam_rows_raw_device and the calls around it)
     def adamRowsRawDevice(self, raw_ptr: int, records_ptr: int, m_ptr: int, v_ptr: int, n: int, ids_ptr: int, rows_ptr: int,
@@ -739,30 +757,26 @@ class Renderer:
         are chained to log-scale, logit-opacity and the rotation before normalisation, Adam moves raw, m and v (the
         clamps of params apply to the raw values), and the listed rows of records are rewritten as act(raw).  params:
         default_adam_params(space="raw").  Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
         self._ctx.check(_lib.lib().gs_adam_rows_raw_device(
-            self._ctx.handle, vp(raw_ptr), vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(ids_ptr), vp(rows_ptr), vp(count_ptr),
+            self._ctx.handle, _vp(raw_ptr), _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(ids_ptr), _vp(rows_ptr), _vp(count_ptr),
             int(max_rows), C.byref(params)))
 
     def recordsFromRawDevice(self, raw_ptr: int, records_ptr: int, n: int):
         """records = act(raw) on the 59 fields of all n rows (exp of the log-scales, sigmoid of the logit, the rotation
         normalised).  Device addresses, float32 (n, 84).  Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_records_from_raw_device(self._ctx.handle, vp(raw_ptr), vp(records_ptr), int(n)))
+        self._ctx.check(_lib.lib().gs_records_from_raw_device(self._ctx.handle, _vp(raw_ptr), _vp(records_ptr), int(n)))
 
     def rawFromRecordsDevice(self, records_ptr: int, raw_ptr: int, n: int):
         """The inverse: raw = (log of the scales, logit of the opacity clamped to [2^-24, 1 - 2^-24], everything else the
         same bits).  Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_raw_from_records_device(self._ctx.handle, vp(records_ptr), vp(raw_ptr), int(n)))
+        self._ctx.check(_lib.lib().gs_raw_from_records_device(self._ctx.handle, _vp(records_ptr), _vp(raw_ptr), int(n)))
 
     def resetOpacityRawDevice(self, raw_ptr: int, records_ptr: int, m_ptr: int | None, v_ptr: int | None, n: int,
                               max_opacity: float = 0.01):
         """The INRIA opacity reset: every opacity above max_opacity becomes sigmoid(logit(max_opacity)) in records and its
         logit in raw; float 15 of every row of m and v (both given or both None) becomes 0.  Follow it with a full upload.
         Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_reset_opacity_raw_device(self._ctx.handle, vp(raw_ptr), vp(records_ptr), vp(m_ptr), vp(v_ptr),
+        self._ctx.check(_lib.lib().gs_reset_opacity_raw_device(self._ctx.handle, _vp(raw_ptr), _vp(records_ptr), _vp(m_ptr), _vp(v_ptr),
                                                                int(n), float(max_opacity)))
 
     # -- adaptive density control (no reference counterpart; include/gsplat.h, gs_densify_stats_device / gs_densify_device)
@@ -772,9 +786,8 @@ class Renderer:
         for ids[i], i < min(count, max_rows), as backwardVisibleDevice left them for this frame, grad_accum += the norm of
         the screen-position gradient in NDC units, seen += 1, max_radius = max(itself, the screen radius in pixels).
         Enqueued on the context's stream without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._ctx.check(_lib.lib().gs_densify_stats_device(self._ctx.handle, vp(ids_ptr), vp(count_ptr), int(max_rows), int(n),
-                                                           vp(grad_accum_ptr), vp(seen_ptr), vp(max_radius_ptr)))
+        self._ctx.check(_lib.lib().gs_densify_stats_device(self._ctx.handle, _vp(ids_ptr), _vp(count_ptr), int(max_rows), int(n),
+                                                           _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr)))
 
     def densifyDevice(self, records_ptr: int, m_ptr: int | None, v_ptr: int | None, n: int, grad_accum_ptr: int, seen_ptr: int,
                       max_radius_ptr: int, params: GsDensifyParams, records_out_ptr: int, m_out_ptr: int | None,
@@ -783,10 +796,9 @@ class Renderer:
         records_out / m_out / v_out (max_out, 84), the children beside their parents; counts (4 uint32 on the device) =
         outputs (not truncated), cloned, split, pruned.  m, v, m_out and v_out: all given or all None.  params:
         default_densify_params().  Enqueued on the context's stream without waiting; needs no scene."""
-        vp = lambda a: C.c_void_p(a) if a else None
         self._ctx.check(_lib.lib().gs_densify_device(
-            self._ctx.handle, vp(records_ptr), vp(m_ptr), vp(v_ptr), int(n), vp(grad_accum_ptr), vp(seen_ptr), vp(max_radius_ptr),
-            C.byref(params), vp(records_out_ptr), vp(m_out_ptr), vp(v_out_ptr), int(max_out), vp(counts_ptr)))
+            self._ctx.handle, _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr),
+            C.byref(params), _vp(records_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
 
     # -- Renderer.cpp:230-270
     def cleanup(self):
