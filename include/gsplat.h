@@ -423,7 +423,7 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * gs_upload_gaussians.  Gradients go to the 59 fields a frame reads -- position.xyz, scale.xyz, rot (all four, used
  * unnormalised as getRotMat uses it), shCoeffs[k].rgb for the coefficients the frame's sh_mode uses (0: all 16, 1: 1..15,
  * 2: 0 only) and shCoeffs[0].a (opacity); every other float is 0, and so is the whole record of a splat that was culled or
- * emitted no element.  Camera gradients are not computed.
+ * emitted no element.  The camera's gradients are a call of their own behind this one: gs_backward_camera* below.
  * Boundary convention: the frame is piecewise smooth, and the gradient is the derivative of the branch the frame took with
  * every discrete decision held fixed -- the near-plane and NDC culls, tile boxes, depth keys and the sorted order; which
  * entries a pixel blends (f > 0 or alpha < 1/255 skip) and the entry it stops on (nextT < 1e-4, RenderGaussians.comp:127-140);
@@ -466,6 +466,36 @@ int gs_backward_visible(gs_ctx* ctx, const float* grad_rgba32f, const float* gra
                         uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
 int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth,
                                uint32_t* ids_out, float* grad_rows_out, uint32_t max_rows, uint32_t* count_out);
+
+/* Camera gradients of a frame (no reference counterpart; callers detect the two calls by their symbols, GS_API_VERSION is
+ * unchanged).  The call differentiates the last frame with the dL/d(outputs) the last gs_backward* call on this frame was
+ * given: it re-reads the per-element rows that call left in the context's scratch, so it works after any gs_backward* form
+ * that computed rows (dense or visible, host or device), and a visible call with max_rows < |V| still gives the full answer
+ * (the blend backward writes every element's row whatever max_rows is).
+ * Output: 35 floats.  [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos; element i of each block is the derivative
+ * with respect to element i of the float[16] / float[3] argument of gs_render* (column-major, view[c * 4 + r]).  The
+ * boundary convention is gs_backward's: every discrete decision of the frame is held fixed -- culls, tile boxes, keys and
+ * order, the blended entries and the stop entry, det == 0, max(colour, 0) and the IN_VIEW_LIMIT clamp.
+ * Two conventions:
+ *   - The view matrix is taken as affine.  Elements 3, 7, 11 and 15 (its bottom row) receive exactly +0.0f: a camera
+ *     never moves them.
+ *   - dL/dproj covers the screen-position path only.  The covariance's focal lengths come from gs_config.fov_y, not from
+ *     proj (the reference's own split, Common.glsl:53), and a frame never reads clip z: elements 2, 6, 10 and 14 of the
+ *     proj block (18, 22, 26 and 30 of the 35 floats) are exactly +0.0f.
+ * dL/dcam_pos is the SH direction's dependence on the camera position: exactly +0.0f in sh_mode 2.
+ * Bitwise reproducible: no atomics, a fixed-shape sum over the splats -- the same 35 words for every sorter, launch shape,
+ * tile order and GS_COUNT_* mode, after the dense and after the visible backward, from both entry points and from call to
+ * call.  A frame that drew nothing gives GS_OK and 35 zeros.
+ * Cost: a second pass over the rows (two launches); it is not fused into gs_backward*'s own row pass.  Scratch: 140 bytes
+ * per 256 gaussians plus 35 floats, allocated on this call's first use and freed with the resolution.
+ *   gs_backward_camera        : HOST pointer; synchronous.
+ *   gs_backward_camera_device : DEVICE pointer; enqueued on the context's stream, no host sync.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued and nothing written: a NULL grad_camera, everything
+ * gs_backward refuses (with its messages), and no gs_backward* form that computed rows on this frame ("no gs_backward* on
+ * this frame": gs_visible_count, or a visible call with max_rows == 0, computes none). */
+#define GS_CAMERA_GRAD_FLOATS 35u   /* [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos */
+int gs_backward_camera(gs_ctx* ctx, float grad_camera[GS_CAMERA_GRAD_FLOATS]);
+int gs_backward_camera_device(gs_ctx* ctx, float* grad_camera_dev);
 
 /* One optimiser step on the rows gs_backward_visible* lists (no reference counterpart), in two calls that keep no state
  * inside the library: an Adam step on the CALLER's records and moments, and the upload of the changed rows alone.

@@ -176,6 +176,15 @@ public:
         return rc;
     }
 
+    // The camera's gradients of the last frame (gsplat.h, gs_backward_camera), behind a backward() or backwardVisible() that
+    // computed rows: grad_camera[GS_CAMERA_GRAD_FLOATS] = dL/dview[16], dL/dproj[16], dL/dcam_pos[3] on the HOST;
+    // device = true: a device pointer, enqueued without waiting.
+    int backwardCamera(float* grad_camera, bool device = false) {
+        const int rc = device ? gs_backward_camera_device(ctx_, grad_camera) : gs_backward_camera(ctx_, grad_camera);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // L1 + D-SSIM of a frame against a target (gsplat.h, gs_photometric_loss): HOST rgba [H][W][4] (nullptr = the context's
     // own GS_OUTPUT_RGBA32F buffer), target [H][W][3], bg[3] (nullptr = black) -> loss_out[3] = {loss, L1, DSSIM} and
     // dloss/d(rgba) [H][W][4] (nullptr = the numbers only), which backward() takes as it is.

@@ -6,7 +6,9 @@ the blend backward (k_bwd_blend, with the three small kernels of the per-splat s
 and visible iterations alternating in one process so that both see the same neighbours; it runs the <true> instantiations
 of the same kernels, which the trace tells from the dense <false> ones by the template argument in the kernel name
 (k_splat_offsets<gs::BwdSource<true>>; k_bwd_blend is one kernel for both).  A trace in which a part of the split matches
-no kernel is an error, not a zero.  One JSON line per config.
+no kernel is an error, not a zero.  camera_ms is gs_backward_camera_device + gs_synchronize behind the visible backward
+of the same iteration (it re-reads that backward's rows), in the same alternating loop; the trace splits it into
+k_bwd_camera_blocks and k_bwd_camera_reduce.  One JSON line per config.
 
     python tools/backward_cost.py [C Chard ...] [--iters 20]"""
 import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile, time
@@ -67,30 +69,44 @@ def visible_ms(r, gr, gd, vis):
     return (time.perf_counter() - t0) * 1e3
 
 
+def camera_ms(r, cam):
+    t0 = time.perf_counter()
+    r.backwardCameraDevice(cam.data_ptr())
+    r.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
 if a.child:
     for name in a.configs:
         r, sc, gr, gd, out, n, w, h = setup(name)
         vis = visible_buffers(r, sc)
+        cam = torch.zeros(35, device="cuda")
         for _ in range(a.iters):
             backward_ms(r, gr, gd, out)
             visible_ms(r, gr, gd, vis)
+            camera_ms(r, cam)
         r.cleanup()
     sys.exit(0)
 
 for name in a.configs:
     r, sc, gr, gd, out, n, w, h = setup(name)
     vis = visible_buffers(r, sc)
-    fwd, bwd, bvis = [], [], []
+    fwd, bwd, bvis, bcam = [], [], [], []
+    cam = torch.zeros(35, device="cuda")
+    torch.cuda.synchronize()
     for _ in range(3):
         r.drawDevice(sc, None, sync=True)
         backward_ms(r, gr, gd, out)
         visible_ms(r, gr, gd, vis)
+        camera_ms(r, cam)
     for _ in range(a.iters):
         r.drawDevice(sc, None, sync=True)
         fwd.append(r.timings().total_ms)
         bwd.append(backward_ms(r, gr, gd, out))
         bvis.append(visible_ms(r, gr, gd, vis))
+        bcam.append(camera_ms(r, cam))
     assert int(vis[3].item()) == vis[0]
+    assert bool(torch.isfinite(cam).all()) and int((cam != 0).sum()) >= 20
     elems = r.timings().num_sort_elements
     r.cleanup()
     split = {}
@@ -117,9 +133,11 @@ for name in a.configs:
             split = {"blend_backward_ms": round(ms("k_bwd_blend") + scan("false"), 4),
                      "rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<false>"), 4),
                      "slot_offsets_ms": round(scan("false"), 4), "visible_scan_ms": round(scan("true"), 4),
-                     "visible_rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<true>"), 4)}
+                     "visible_rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<true>"), 4),
+                     "camera_blocks_ms": round(ms("k_bwd_camera_blocks"), 4), "camera_reduce_ms": round(ms("k_bwd_camera_reduce"), 4)}
         shutil.rmtree(d, ignore_errors=True)
     fm, bm, vm = float(np.median(fwd)), float(np.median(bwd)), float(np.median(bvis))
     print(json.dumps({"config": name, "width": w, "height": h, "gaussians": n, "elements": int(elems), "iters": a.iters,
                       "visible": vis[0], "forward_total_ms_median": round(fm, 4), "backward_ms_median": round(bm, 4),
-                      "backward_vs_forward": round(bm / fm, 3), "backward_visible_ms_median": round(vm, 4), **split}), flush=True)
+                      "backward_vs_forward": round(bm / fm, 3), "backward_visible_ms_median": round(vm, 4),
+                      "camera_ms": round(float(np.median(bcam)), 4), **split}), flush=True)

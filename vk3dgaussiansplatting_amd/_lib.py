@@ -162,7 +162,9 @@ EXPORTS = [
     "gs_densify_stats_device", "gs_default_densify_params", "gs_densify_device",
     "gs_default_adam_params_raw", "gs_adam_rows_raw_device", "gs_records_from_raw_device", "gs_raw_from_records_device",
     "gs_reset_opacity_raw_device", "gs_write_ply",
+    "gs_backward_camera", "gs_backward_camera_device",
 ]
+CAMERA_GRAD_FLOATS = 35    # GS_CAMERA_GRAD_FLOATS: [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
 DIST_UNIQUE_ID_BYTES = 128
@@ -306,6 +308,8 @@ def lib() -> C.CDLL:
     L.gs_raw_from_records_device.argtypes = [ctxp, vp, vp, u32]
     L.gs_reset_opacity_raw_device.argtypes = [ctxp, vp, vp, vp, vp, u32, f32]
     L.gs_write_ply.argtypes = [C.c_char_p, vp, u32, u32]
+    L.gs_backward_camera.argtypes = [ctxp, vp]
+    L.gs_backward_camera_device.argtypes = [ctxp, vp]
     _lib = L
     _check_hip_runtime(L)
     return L

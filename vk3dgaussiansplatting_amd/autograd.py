@@ -14,6 +14,9 @@ rasterised (gs_backward_visible_device): no N-sized gradient is written, and tor
 It is meant for a leaf `records`.  torch's backward formulas of the ops a non-leaf `records` comes from (cat, slicing) do
 not take sparse gradients, so a non-leaf input receives the same rows scattered into a dense [N, 84] tensor.
 
+view, proj and cam_pos may be numpy arrays or torch tensors (any device, any float dtype); tensors that require grad receive
+dL/dview, dL/dproj and dL/dcam_pos (gs_backward_camera_device, one call behind the record backward) for pose refinement.
+
     loss = photometric_loss(rgba, target, lambda_dssim=0.2, renderer=r)         # 0-dim: (1 - l) L1 + l (1 - SSIM)
 
 photometric_loss is the library's fused L1 + D-SSIM (gs_photometric_loss_device): the three numbers and dloss/d(rgba) come
@@ -50,6 +53,14 @@ def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
     return r
 
 
+def _camera_array(x) -> np.ndarray:
+    """A camera argument (numpy, a sequence, or a torch tensor on any device and of any float dtype) as the float32 host
+    array the library takes."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(x, dtype=np.float32)
+
+
 def _draw(r: Renderer, records: torch.Tensor, view, proj, cam_pos, sh_mode: int, want_depth: bool):
     """Upload records (device to device) and draw one frame; returns the host outputs."""
     torch.cuda.current_stream(records.device).synchronize()     # the library works on a stream of its own
@@ -64,6 +75,9 @@ def _draw(r: Renderer, records: torch.Tensor, view, proj, cam_pos, sh_mode: int,
 class _Frame(torch.autograd.Function):
     @staticmethod
     def forward(ctx, records, renderer, view, proj, cam_pos, sh_mode, want_depth, sparse_grad):
+        # tensor cameras that require grad receive gradients of their own shape, dtype and device (backward)
+        ctx.cameras = [(tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in (view, proj, cam_pos)]
+        view, proj, cam_pos = _camera_array(view), _camera_array(proj), _camera_array(cam_pos)
         rgba, depth, frame = _draw(renderer, records, view, proj, cam_pos, sh_mode, want_depth)
         ctx.renderer, ctx.frame, ctx.args = renderer, frame, (view, proj, cam_pos, sh_mode, want_depth)
         ctx.sparse_grad = sparse_grad
@@ -84,6 +98,16 @@ class _Frame(torch.autograd.Function):
         d = None
         if ctx.args[4] and grad_depth is not None:
             d = grad_depth.to(device=records.device, dtype=torch.float32).contiguous()
+        # one gs_backward_camera_device call behind the record backward, only when a camera tensor asks for its gradient
+        want_camera = any(ctx.needs_input_grad[2:5])
+        cam = torch.zeros(_lib.CAMERA_GRAD_FLOATS, dtype=torch.float32, device=records.device) if want_camera else None
+
+        def camera_grads():
+            if cam is None:
+                return None, None, None
+            blocks = (cam[0:16], cam[16:32], cam[32:35])
+            return tuple(b.reshape(c[0]).to(device=c[2], dtype=c[1]) if c is not None and need else None
+                         for b, c, need in zip(blocks, ctx.cameras, ctx.needs_input_grad[2:5]))
         if ctx.sparse_grad:
             count = r.visibleCount()
             # int32 storage for the library's uint32 ids (N < 2^31)
@@ -93,25 +117,32 @@ class _Frame(torch.autograd.Function):
             torch.cuda.current_stream(records.device).synchronize()
             r.backwardVisibleDevice(g.data_ptr(), None if d is None else d.data_ptr(), ids.data_ptr() if count else None,
                                     rows.data_ptr() if count else None, count, seen.data_ptr())
+            if want_camera and count:             # a frame that rasterised nothing has no rows: the zeros stand
+                r.backwardCameraDevice(cam.data_ptr())
             r.synchronize()
             if ctx.sparse_grad == "scatter":      # a non-leaf input
                 out = torch.zeros(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
                 out.index_copy_(0, ids.long(), rows)
             else:
                 out = torch.sparse_coo_tensor(ids.long()[None], rows, size=(records.shape[0], FLOATS_PER_GAUSSIAN))
-            return out, None, None, None, None, None, None, None
+            return (out, None) + camera_grads() + (None, None, None)
         out = torch.empty(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
         torch.cuda.current_stream(records.device).synchronize()
         r.backwardDevice(g.data_ptr(), None if d is None else d.data_ptr(), out.data_ptr())
+        if want_camera:
+            r.backwardCameraDevice(cam.data_ptr())
         r.synchronize()
-        return out, None, None, None, None, None, None, None
+        return (out, None) + camera_grads() + (None, None, None)
 
 
 def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: bool = False, *, renderer: Renderer,
            sparse_grad: bool = False):
     """The frame of `records` (float32 [N, 84], CUDA/HIP, on the renderer's device) under the camera (view, proj: 4 x 4
     column-major as Camera.getViewMatrix / getProjectionMatrix give them, cam_pos: 3): rgba32f [H, W, 4], and depth [H, W]
-    if asked, both differentiable w.r.t. records.  sparse_grad=True: records (meant to be a leaf) receives a sparse COO
+    if asked, both differentiable w.r.t. records.  view, proj and cam_pos may also be torch tensors, on any device and of any
+    float dtype: those that require grad receive dL/dview, dL/dproj, dL/dcam_pos in their own shape, dtype and device
+    (gs_backward_camera_device, with its two conventions: the view's bottom row and the projection's clip-z row get 0);
+    numpy cameras behave as before.  sparse_grad=True: records (meant to be a leaf) receives a sparse COO
     gradient over the splats the frame rasterised, with the values of the dense one; a non-leaf records receives those
     rows in a dense tensor."""
     if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
@@ -164,7 +195,8 @@ class VisibleAdam:
     step() enqueues, on self.stream (a torch stream handed to the renderer with gs_set_stream): the upload of the records
     -- in full the first time, afterwards of the rows the previous step moved (gs_upload_rows_device reads the ids and
     count that step left) --, the frame, gs_photometric_loss_device on the context's own RGBA32F buffer,
-    gs_backward_visible_device and gs_adam_rows_device.  It waits for nothing: self.stream is made to follow the caller's
+    gs_backward_visible_device (and, with camera_grad, gs_backward_camera_device) and gs_adam_rows_device.  It waits for
+    nothing: self.stream is made to follow the caller's
     current stream (so a target or records written there are seen), and the returned tensor {loss, L1, DSSIM} belongs to
     self.stream -- synchronise it, or make another stream wait for it, before the numbers are read.  Rows past max_rows
     are not updated (self.count holds |V| of the last step: compare after a synchronise).
@@ -269,8 +301,15 @@ class VisibleAdam:
         """The next step uploads every record (after the caller changed rows the last step did not list)."""
         self._full_upload = True
 
-    def step(self, view, proj, cam_pos, sh_mode: int, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None) -> torch.Tensor:
+    def step(self, view, proj, cam_pos, sh_mode: int, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None,
+             camera_grad: torch.Tensor | None = None) -> torch.Tensor:
+        """camera_grad: a float32 [35] tensor on the records' device, filled with dL/dview, dL/dproj, dL/dcam_pos of this
+        step's frame (gs_backward_camera_device) in the same enqueue chain, with no host wait; it belongs to self.stream
+        like the returned numbers.  Needs max_rows > 0."""
         r, n = self.renderer, self.records.shape[0]
+        if camera_grad is not None and (camera_grad.dtype != torch.float32 or tuple(camera_grad.shape) != (_lib.CAMERA_GRAD_FLOATS,)
+                                        or camera_grad.device != self.records.device or not camera_grad.is_contiguous()):
+            raise ValueError(f"camera_grad must be a contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}] tensor on the records' device")
         if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
             raise ValueError(f"target must be float32 {(r.height, r.width, 3)} on the GPU")
         target = target.contiguous()
@@ -288,6 +327,9 @@ class VisibleAdam:
             r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers.data_ptr(), self.grad.data_ptr())
             r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
                                     self.count.data_ptr())
+            if camera_grad is not None:
+                camera_grad.record_stream(self.stream)
+                r.backwardCameraDevice(camera_grad.data_ptr())
             if self.track_density:
                 r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
                                      self.seen.data_ptr(), self.max_radius.data_ptr())

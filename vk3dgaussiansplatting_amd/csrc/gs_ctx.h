@@ -65,7 +65,7 @@ struct LastFrame {
     Kind kind = kNone;            // kUnsortedList: gs_debug_init_sort_list ran last; kFrame: a frame was enqueued last
     bool differentiable = false;  // kFrame, and no upload or tile-row change since: gs_backward* may run
     bool has_backward = false;    // bwd.rows holds a backward of this frame (a gs_backward* form ran the blend): what
-                                  // gs_densify_stats_device sums
+                                  // gs_densify_stats_device and gs_backward_camera* sum
     int sorted_index = 0;         // kFrame: which ping-pong half holds the sorted list
     gs::FrameParams fp{};         // of the InitSortList launch (gs_debug_read(GS_BUF_COLOR) evaluates colours on demand)
 };
@@ -125,11 +125,13 @@ struct gs_ctx {
     bool outputs_valid = false;       // a frame has been enqueued since the mask or the resolution last changed
     // gs_backward*: scratch allocated on the first call (rows sized by the list capacity), freed with the resolution
     gs::BackwardBuffers bwd{};
-    DeviceOwner bwd_mem;              // of bwd and bwd_host_in / _out / bwd_vis_out
+    DeviceOwner bwd_mem;              // of bwd and bwd_host_in / _out / bwd_vis_out / bwd_cam_partials / bwd_cam_out
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
     float* bwd_host_out = nullptr;    // ... and the record gradients [N][84]
     float* bwd_vis_out = nullptr;     // gs_backward_visible (host pointers): bwd_vis_rows record gradients, grown on demand
     uint32_t bwd_vis_rows = 0;
+    float* bwd_cam_partials = nullptr;   // gs_backward_camera*: [35][blocks of 256 gaussians], allocated on its first call
+    float* bwd_cam_out = nullptr;        // gs_backward_camera (host pointer): the 35 floats on the device
     // gs_densify_device: its scan (K = 4) for densify_cap splats; grown on demand, freed at gs_destroy
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;

@@ -308,6 +308,10 @@ void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uin
                                   hipStream_t stream);
 void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
                                   uint32_t max_rows, float* grad_rows, hipStream_t stream);
+// gs_backward_camera* (gs_camera.hip): from the rows a launch_backward* left in bb.rows, grad_camera[35] = dL/dview[16],
+// dL/dproj[16], dL/dcam_pos[3] (device); partials: backward_camera_partial_bytes(N) of scratch, [35][backward_blocks(N)]
+size_t backward_camera_partial_bytes(uint32_t n);
+void launch_backward_camera(const BackwardFrame& f, float* partials, float* grad_camera, hipStream_t stream);
 // gs_photometric_loss* (gs_loss.hip): scratch of the loss, allocated on the first call and freed with the resolution
 struct LossBuffers {
     float* maps;              // [3][H][W][3]  A, B, E of gs_loss.hip: derivatives of ssim, scaled by -lambda / (3 H W)

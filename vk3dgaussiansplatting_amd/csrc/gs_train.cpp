@@ -160,6 +160,24 @@ int visible_count_sync(gs_ctx* c, const char* who, uint32_t* count) {
     return GS_OK;
 }
 
+// gs_backward_camera*: the refusals (nothing enqueued), then the scratch of the first call
+int backward_camera_prepare(gs_ctx* c, const char* who, const float* grad_camera) {
+    if (!grad_camera) return refuse(c, who, "null gradient pointer");
+    if (int r = backward_prepare(c, who)) return r;
+    if (!c->last.has_backward) return refuse(c, who, "no gs_backward* on this frame");
+    if (!c->bwd_cam_partials) {
+        const hipError_t e = c->bwd_mem.alloc(c->bwd_cam_partials, backward_camera_partial_bytes(c->n));
+        if (e != hipSuccess) return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+    }
+    return GS_OK;
+}
+
+// what both forms enqueue (a device pointer)
+int enqueue_backward_camera(gs_ctx* c, const char* who, float* grad_camera) {
+    launch_backward_camera(backward_frame(c), c->bwd_cam_partials, grad_camera, c->stream);
+    return check_launch(c, who);
+}
+
 int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba32f, const uint32_t* ids_out,
                               const float* grad_rows_out, uint32_t max_rows, const uint32_t* count_out) {
     if (!grad_rgba32f) return refuse(c, who, "null gradient pointer");
@@ -388,6 +406,23 @@ int gs_backward_visible(gs_ctx* c, const float* grad_rgba32f, const float* grad_
     }
     const bool count_only = !max_rows && !ids_out && !grad_rows_out;      // asked for no row: none is missing
     return count > max_rows && !count_only ? GS_WARN_OVERFLOW : GS_OK;
+}
+
+int gs_backward_camera_device(gs_ctx* c, float* grad_camera_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_camera_prepare(c, __func__, grad_camera_dev)) return r;
+    return enqueue_backward_camera(c, __func__, grad_camera_dev);
+}
+
+int gs_backward_camera(gs_ctx* c, float grad_camera[GS_CAMERA_GRAD_FLOATS]) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = backward_camera_prepare(c, __func__, grad_camera)) return r;
+    const size_t bytes = GS_CAMERA_GRAD_FLOATS * sizeof(float);
+    if (!c->bwd_cam_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_cam_out, bytes));
+    if (int r = enqueue_backward_camera(c, __func__, c->bwd_cam_out)) return r;
+    HIP_TRY(c, hipMemcpyAsync(grad_camera, c->bwd_cam_out, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return GS_OK;
 }
 
 int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,

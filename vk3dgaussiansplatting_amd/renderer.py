@@ -683,6 +683,19 @@ class Renderer:
             _vp(ids_ptr), _vp(rows_ptr), int(max_rows),
             _vp(count_ptr)))
 
+    def backwardCamera(self) -> np.ndarray:
+        """The camera's gradients of the last frame, float32 (35,): [0:16] dL/dview, [16:32] dL/dproj (both column-major, as
+        drawCamera takes the matrices), [32:35] dL/dcam_pos -- with the dL/d(outputs) the last backward*() on this frame was
+        given (gs_backward_camera; a backward form that computed rows must have run on the frame).  The view's bottom row and
+        the projection's clip-z row are exactly 0 (include/gsplat.h)."""
+        out = np.zeros(_lib.CAMERA_GRAD_FLOATS, dtype=np.float32)
+        self._ctx.check(_lib.lib().gs_backward_camera(self._ctx.handle, _p(out)))
+        return out
+
+    def backwardCameraDevice(self, grad_camera_ptr: int):
+        """The same into 35 float32 at a device address; enqueued on the context's stream without waiting."""
+        self._ctx.check(_lib.lib().gs_backward_camera_device(self._ctx.handle, _vp(grad_camera_ptr)))
+
     # -- photometric loss of a frame (no reference counterpart; include/gsplat.h, gs_photometric_loss*)
     @staticmethod
     def _bg_arg(bg):
