@@ -691,6 +691,58 @@ int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const f
                       const gs_densify_params* p,
                       float* records_out, float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out);
 
+/* A cloud from points (no reference counterpart): the first records of a training run from an SfM or LiDAR point cloud, what
+ * the INRIA trainer's create_from_pcd makes -- scale = the root of the mean squared distance to the three nearest other
+ * points, opacity 0.1, identity rotation, SH DC from the colour.  Both device calls work on the CALLER's device arrays, are
+ * enqueued on the context's stream without a host sync, need no scene and no resolution, keep no state in the library and
+ * are bitwise reproducible, the same for every sorter.  Callers detect them by their symbols (GS_API_VERSION is unchanged).
+ * Scratch: 45 bytes per point (24 of the sorter's lists, 16 of the sorted positions, 4 of the distances, 1 of the boxes and
+ * the sorter's tables together) plus 100 KB, the context's, grown on demand and freed by gs_destroy.
+ *
+ * gs_knn_mean_dist2_device: points_dev float[n][3]; for every point i, in input order,
+ *   d2(i, j) = (dx * dx + dy * dy) + dz * dz with dx = x_j - x_i, float32, never contracted, over all j != i -- a duplicate
+ *   point counts, with d2 = 0: only the index itself is excluded;
+ *   a <= b <= c the three smallest of those values;   dist2_out[i] = ((a + b) + c) / 3.0f.
+ * The result is exact: a function of the multiset of d2 values, so independent of search order and ties, and equal to a
+ * NumPy float32 brute force bit for bit (tests/test_init_cpu.py).  The search runs over the points in the loader's Morton
+ * order, a wave per 64 of them, and drops a box of 64 points only when a bound computed in the shape of d2 itself -- and so
+ * never above the d2 of any member -- exceeds the third best so far.
+ *
+ * gs_records_from_points_device: what gs_load_ply would make of the .ply an INRIA trainer writes at iteration 0.
+ * points_dev is in the .ply's frame; colors_dev is float[n][3] in [0, 1], or NULL.  The output rows are in the loader's
+ * Morton order, restated on the device over the flipped positions: bounds from the loader's start values (min from FLT_MAX,
+ * max from the smallest positive normal float, as written there), q_a = (pos_a - min_a) / delta_a * 1023.0f truncated to
+ * uint32 (a NaN and values <= 0 give 0, values >= 2^32 saturate; a flat axis gives 0 / 0 = NaN, then 0), the code
+ * (part(q2) << 2) + (part(q1) << 1) + part(q0), a stable sort over all 32 bits.  A cloud from this call is therefore already
+ * in the loader's order: written with gs_write_ply and loaded again, no row moves.  order_out[k] (may be NULL) = the input
+ * index of output row k.  Row r = records_out[k] of input i = order_out[k]:
+ *   r[0..2]  = (-x, -y, z)
+ *   r[4..6]  = s:  d = dist2[i] < min_dist2 ? min_dist2 : dist2[i];  s = sqrtf(d);  s = s > max_scale ? max_scale : s
+ *              (dist2 as gs_knn_mean_dist2_device defines it; sqrtf correctly rounded)
+ *   r[8..11] = (-0.0f, -0.0f, 1.0f, -0.0f): the loader's record of rot_0..3 = (1, 0, 0, 0), signs of zero included
+ *   r[12 + c] = (colour_c - 0.5f) / 0.28209479177387814f, c = 0..2 (correctly rounded); +0.0f with colors_dev == NULL
+ *   r[15]    = opacity
+ *   every other float of the 84: +0.0f.
+ * The call writes records, not raw rows: for the trainer's parameters follow it with gs_raw_from_records_device, then
+ * gs_records_from_raw_device ("Starting from points").
+ * Points must be finite.  With non-finite coordinates both calls still terminate -- every loop is bounded by n -- and the
+ * affected rows are unspecified.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued (a NULL ctx: the code alone): a NULL points_dev,
+ * dist2_out_dev or records_out_dev; n < 4 ("fewer than four points have no three neighbours") or n >= 2^31; a NULL
+ * gs_init_params or a wrong struct_size; an opacity that fails 0 < opacity < 1; a min_dist2 that is negative or not finite;
+ * a max_scale that fails max_scale > 0 (+inf is allowed); an output array that shares bytes with an input or with the other
+ * output. */
+typedef struct gs_init_params {
+    uint32_t struct_size;   /* sizeof(gs_init_params) of the caller's header: filled by gs_default_init_params, checked */
+    float opacity;          /* 0.1f: the record's opacity (float 15) */
+    float min_dist2;        /* 1e-7f: floor of the mean squared distance (INRIA's clamp_min) */
+    float max_scale;        /* +inf = none: cap of the initial scale */
+} gs_init_params;
+void gs_default_init_params(gs_init_params* p);
+int gs_knn_mean_dist2_device(gs_ctx* ctx, const float* points_dev, uint32_t n, float* dist2_out_dev);
+int gs_records_from_points_device(gs_ctx* ctx, const float* points_dev, const float* colors_dev, uint32_t n,
+                                  const gs_init_params* p, float* records_out_dev, uint32_t* order_out_dev);
+
 /* Photometric loss of a frame against a photograph (no reference counterpart): the number a 3DGS optimisation minimises,
  *   loss = (1 - lambda) * L1 + lambda * DSSIM,
  * and its gradient with respect to the frame, in the layout gs_backward* takes.  H and W are the context's resolution.

@@ -279,6 +279,27 @@ public:
         return rc;
     }
 
+    // A cloud from points (gsplat.h, gs_knn_mean_dist2_device and gs_records_from_points_device): the exact mean squared
+    // distance to the three nearest other points, in input order, and the first records of a training run -- rows in the
+    // loader's Morton order, order_out[k] (may be null) = the input index of row k.  All arrays on the DEVICE; both are
+    // enqueued on the context's stream without waiting and need no scene.
+    static gs_init_params defaultInitParams() {
+        gs_init_params p;
+        gs_default_init_params(&p);
+        return p;
+    }
+    int knnMeanDist2(const float* points, uint32_t n, float* dist2_out) {
+        const int rc = gs_knn_mean_dist2_device(ctx_, points, n, dist2_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int recordsFromPoints(const float* points, const float* colors, uint32_t n, const gs_init_params& params, float* records_out,
+                          uint32_t* order_out = nullptr) {
+        const int rc = gs_records_from_points_device(ctx_, points, colors, n, &params, records_out, order_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Renderer::cleanup (Renderer.cpp:230-270).  gs_destroy always frees the context (gsplat.h), so the handle is
     // dropped before the call and never touched afterwards.
     int cleanup() {

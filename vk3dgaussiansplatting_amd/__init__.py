@@ -15,6 +15,7 @@ from ._lib import (GS_OK, GS_WARN_OVERFLOW, GS_RENDER_EXACT, GS_RENDER_FAST, GS_
                    GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH,
                    GS_ADAM_POSITION, GS_ADAM_SCALE, GS_ADAM_ROTATION, GS_ADAM_SH_DC, GS_ADAM_OPACITY, GS_ADAM_SH_REST,
                    ADAM_GROUP_OF_FLOAT, GsAdamParams, GsDensifyParams, default_densify_params,
+                   GsInitParams, default_init_params,
                    BUF_SORTED_TILE, BUF_SORTED_DEPTH, BUF_SORTED_ID, BUF_RANGES, BUF_COLOR, BUF_COV,
                    BUF_COUNT, BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE)
 from .renderer import (Camera, GpuSort, GsplatError, PlyScene, RadixSort, RadixSort8, Renderer, ResourceManager,

@@ -134,6 +134,16 @@ class GsDensifyParams(C.Structure):
     ]
 
 
+class GsInitParams(C.Structure):
+    """gs_init_params: what gs_records_from_points_device gives every new record (filled by gs_default_init_params)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("opacity", C.c_float),
+        ("min_dist2", C.c_float),
+        ("max_scale", C.c_float),
+    ]
+
+
 class GsHostTimings(C.Structure):
     """gs_host_timings: the RECORD_CPU_TIMES figures (Renderer.cpp:399-456)."""
     _fields_ = [
@@ -163,6 +173,7 @@ EXPORTS = [
     "gs_default_adam_params_raw", "gs_adam_rows_raw_device", "gs_records_from_raw_device", "gs_raw_from_records_device",
     "gs_reset_opacity_raw_device", "gs_write_ply",
     "gs_backward_camera", "gs_backward_camera_device",
+    "gs_default_init_params", "gs_knn_mean_dist2_device", "gs_records_from_points_device",
 ]
 CAMERA_GRAD_FLOATS = 35    # GS_CAMERA_GRAD_FLOATS: [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
@@ -310,6 +321,10 @@ def lib() -> C.CDLL:
     L.gs_write_ply.argtypes = [C.c_char_p, vp, u32, u32]
     L.gs_backward_camera.argtypes = [ctxp, vp]
     L.gs_backward_camera_device.argtypes = [ctxp, vp]
+    L.gs_default_init_params.argtypes = [C.POINTER(GsInitParams)]
+    L.gs_default_init_params.restype = None
+    L.gs_knn_mean_dist2_device.argtypes = [ctxp, vp, u32, vp]
+    L.gs_records_from_points_device.argtypes = [ctxp, vp, vp, u32, C.POINTER(GsInitParams), vp, vp]
     _lib = L
     _check_hip_runtime(L)
     return L
@@ -327,6 +342,18 @@ def default_densify_params(**overrides) -> GsDensifyParams:
             setattr(p, name, float(value))
         else:
             raise TypeError(f"default_densify_params: unknown parameter {name!r}")
+    return p
+
+
+def default_init_params(**overrides) -> GsInitParams:
+    """gs_default_init_params: opacity 0.1, min_dist2 1e-7, max_scale +inf (none).  overrides: any of those fields by name."""
+    p = GsInitParams()
+    lib().gs_default_init_params(C.byref(p))
+    for name, value in overrides.items():
+        if name != "struct_size" and any(name == f[0] for f in GsInitParams._fields_):
+            setattr(p, name, float(value))
+        else:
+            raise TypeError(f"default_init_params: unknown parameter {name!r}")
     return p
 
 

@@ -34,6 +34,8 @@ gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one 
     opt = VisibleAdam(records, renderer=r, space="raw")                         # Adam on log-scale, logit-opacity, raw rotation
     opt.reset_opacity(0.01); opt.save_ply("trained.ply")                        # the INRIA reset; a .ply gs_load_ply reads
 
+    records, order = records_from_points(points, colors, renderer=r)            # a cloud from SfM points, in the loader's order
+
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
 """
 from __future__ import annotations
@@ -182,6 +184,31 @@ def photometric_loss(rgba: torch.Tensor, target: torch.Tensor, lambda_dssim: flo
         if not t.is_cuda:
             raise ValueError(f"{name} must be on the GPU")
     return _Loss.apply(rgba.contiguous(), target.detach().contiguous(), renderer, float(lambda_dssim), bg)
+
+
+def records_from_points(points: torch.Tensor, colors: torch.Tensor | None = None, *, renderer: Renderer, **params):
+    """The first records of a training run from a point cloud (gs_records_from_points_device) -> (records, order).
+
+    points: float32 [n, 3] on the renderer's GPU, in the .ply's frame; colors: float32 [n, 3] in [0, 1], or None.  params:
+    default_init_params()'s overrides (opacity, min_dist2, max_scale).  records: float32 [n, 84] in the loader's Morton
+    order -- scale from the three nearest neighbours, identity rotation, SH DC from the colour; order: int64 [n], the input
+    index of every row (records[k] is points[order[k]]).  Waits for the caller's stream before and for the renderer's
+    after the call: a rare event.  For the trainer's parameters hand records to VisibleAdam(space="raw")."""
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 3 or not points.is_cuda:
+        raise ValueError(f"points must be float32 [n, 3] on the GPU, not {points.dtype} {tuple(points.shape)}")
+    if colors is not None and (colors.dtype != torch.float32 or colors.shape != points.shape or colors.device != points.device):
+        raise ValueError("colors must be float32 [n, 3] on the points' device")
+    p = _lib.default_init_params(**params)
+    points = points.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    n, dev = points.shape[0], points.device
+    records = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+    order = torch.empty(n, dtype=torch.int32, device=dev)                           # int32 storage for the library's uint32
+    torch.cuda.current_stream(dev).synchronize()                # the library works on a stream of its own
+    renderer.recordsFromPointsDevice(points.data_ptr(), None if colors is None else colors.data_ptr(), n, p, records.data_ptr(),
+                                     order.data_ptr())
+    renderer.synchronize()
+    return records, order.to(torch.int64)
 
 
 class VisibleAdam:

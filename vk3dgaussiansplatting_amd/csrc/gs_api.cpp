@@ -519,6 +519,7 @@ int gs_destroy(gs_ctx* c) {
     free_resolution(c);
     free_scene(c);
     c->densify_mem.release();
+    c->init_mem.release();
     destroy_events(c->marks, kMaxFrameMarks);
     destroy_events(c->scatter_ev, 32);
     destroy_events(&c->fork_ev, 1);

@@ -136,6 +136,12 @@ struct gs_ctx {
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
     DeviceOwner densify_mem;
+    // gs_knn_mean_dist2_device / gs_records_from_points_device: scratch and sort buffers for init_cap points; grown on
+    // demand, freed at gs_destroy
+    gs::InitScratch init{};
+    gs::SortBuffers init_sort{};
+    uint32_t init_cap = 0;
+    DeviceOwner init_mem;
     // gs_photometric_loss*: scratch allocated on the first call (9 floats per pixel + 8 bytes per tile), freed with the
     // resolution; loss_host = the device copies of the host form's arguments (rgba, target, gradient, the three numbers)
     gs::LossBuffers loss{};

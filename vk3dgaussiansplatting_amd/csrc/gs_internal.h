@@ -380,6 +380,27 @@ struct DensifyArgs {
     SplatScan scan;                   // K = 4: outputs, cloned, split, pruned; offsets[g] = o(g), the index of g's first output
 };
 void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stream);
+// gs_knn_mean_dist2_device / gs_records_from_points_device (gs_init.hip): the context's scratch for n points, beside a
+// SortBuffers of capacity n (code, 0, input index)
+constexpr uint32_t kInitBoundBlocks = 256;      // partial boxes of the bounds reduction: a fixed shape
+struct InitScratch {
+    float* partial;           // [kInitBoundBlocks][6]  min xyz, max xyz
+    float* bounds;            // [6]  of the flipped positions, from the loader's start values
+    float4* sorted;           // [n]  flipped positions in sorted order, w = 0
+    float4* boxes;            // [ceil(n / 64)][2]  min, max of every 64 consecutive sorted positions
+    float* dist2;             // [n]  mean squared distance in sorted order (the row writer's input)
+    uint32_t* probe;          // null, or (a GS_INIT_PROBE build) [ceil(n / 64)][2] surviving boxes per wave: coarse, per lane
+};
+// Both enqueue bounds, codes, the sort of `run` over sb and the gather, then the search (and the rows); they return the
+// ping-pong half of sb that holds the sorted ids, or -1 with nothing of the search enqueued when sb cannot serve the run.
+int launch_knn_mean_dist2(const float* points, uint32_t n, const InitScratch& s, const SortBuffers& sb, const SortRun& run,
+                          float* dist2_out, hipStream_t stream);
+int launch_records_from_points(const float* points, const float* colors, uint32_t n, const InitScratch& s, const SortBuffers& sb,
+                               const SortRun& run, float opacity, float min_dist2, float max_scale, float* records_out,
+                               uint32_t* order_out, hipStream_t stream);
+#ifdef GS_INIT_PROBE
+hipError_t init_probe_ms(float ms[6]);      // a tuning build: milliseconds of the six launches of the last, completed call
+#endif
 void launch_stream_probe(int kind, const void* src, void* dst, size_t bytes, uint32_t blocks, hipStream_t stream);
 // helpers for the stand-alone sorter entry points
 void launch_set_sort_params(SortParams* params, uint32_t* coarse, uint32_t n, hipStream_t stream);

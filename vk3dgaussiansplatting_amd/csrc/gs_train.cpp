@@ -1,5 +1,5 @@
 // gs_train.cpp -- the training calls of include/gsplat.h, which have no counterpart in the reference: Adam on listed rows,
-// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss* and density control.  Every entry point
+// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control and a cloud from points.  Every entry point
 // refuses first (nothing enqueued, the context unchanged), then enqueues on the context's stream; a host-pointer form is
 // its _device twin between staging copies and a wait.
 #include "gs_ctx.h"
@@ -242,9 +242,103 @@ int densify_scratch(gs_ctx* c, uint32_t n, const char* who) {
     return GS_OK;
 }
 
+// ---- a cloud from points (gs_init.hip)
+
+// what both calls check of the points, in the header's order
+int check_points(gs_ctx* c, const char* who, bool arrays, uint32_t n) {
+    if (!arrays) return refuse(c, who, "null points, dist2_out or records_out");
+    if (n < 4u) return refuse(c, who, "fewer than four points have no three neighbours");
+    if (n >= 0x80000000u) return refuse(c, who, "n must be below 2^31");
+    return GS_OK;
+}
+
+// the scratch of both calls for n points (45 bytes per point), kept from call to call and grown when a larger cloud comes
+int init_scratch(gs_ctx* c, uint32_t n, const char* who) {
+    if (c->init_cap >= n) return GS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
+    DeviceOwner& mem = c->init_mem;
+    mem.release();
+    c->init_cap = 0;
+    InitScratch& s = c->init;
+    const size_t boxes = ((size_t)n + 63u) / 64u;
+    int rc = alloc_sort(c, mem, c->init_sort, n);
+    hipError_t e = hipSuccess;
+    if (rc == GS_OK) e = mem.alloc(s.partial, (size_t)kInitBoundBlocks * 6 * sizeof(float));
+    if (rc == GS_OK && e == hipSuccess) e = mem.alloc(s.bounds, 6 * sizeof(float));
+    if (rc == GS_OK && e == hipSuccess) e = mem.alloc(s.sorted, (size_t)n * sizeof(float4));
+    if (rc == GS_OK && e == hipSuccess) e = mem.alloc(s.boxes, boxes * 2 * sizeof(float4));
+    if (rc == GS_OK && e == hipSuccess) e = mem.alloc(s.dist2, (size_t)n * sizeof(float));
+#ifdef GS_INIT_PROBE
+    if (rc == GS_OK && e == hipSuccess) e = mem.alloc(s.probe, boxes * 2 * sizeof(uint32_t));
+#endif
+    if (rc == GS_OK && e != hipSuccess) rc = refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+    if (rc != GS_OK) { mem.release(); return rc; }
+    c->init_cap = n;
+    return GS_OK;
+}
+
 } // namespace
 
 extern "C" {
+
+void gs_default_init_params(gs_init_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->opacity = 0.1f;
+    p->min_dist2 = 1e-7f;
+    p->max_scale = std::numeric_limits<float>::infinity();
+}
+
+int gs_knn_mean_dist2_device(gs_ctx* c, const float* points_dev, uint32_t n, float* dist2_out_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = check_points(c, __func__, points_dev && dist2_out_dev, n)) return r;
+    if (overlap({points_dev, (size_t)n * 12}, {dist2_out_dev, (size_t)n * 4})) return refuse(c, __func__, "dist2_out aliases points");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = init_scratch(c, n, __func__)) return r;
+    if (launch_knn_mean_dist2(points_dev, n, c->init, c->init_sort, whole_list_run(c, n, 32u), dist2_out_dev, c->stream) < 0)
+        return refuse(c, __func__, "the sorter refused the run", GS_ERR_HIP);
+    return check_launch(c, __func__);
+}
+
+int gs_records_from_points_device(gs_ctx* c, const float* points_dev, const float* colors_dev, uint32_t n,
+                                  const gs_init_params* p, float* records_out_dev, uint32_t* order_out_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = check_points(c, __func__, points_dev && records_out_dev, n)) return r;
+    if (!p) return refuse(c, __func__, "null gs_init_params");
+    if (int r = check_struct_size(c, __func__, "init", p->struct_size, sizeof(gs_init_params))) return r;
+    if (!(p->opacity > 0.0f && p->opacity < 1.0f)) return refuse(c, __func__, "opacity must lie strictly between 0 and 1");
+    if (!(p->min_dist2 >= 0.0f) || !std::isfinite(p->min_dist2)) return refuse(c, __func__, "min_dist2 must be finite and not negative");
+    if (!(p->max_scale > 0.0f)) return refuse(c, __func__, "max_scale must be greater than 0");
+    // no output may share bytes with an input, or with the other output
+    const Span ins[] = {{points_dev, (size_t)n * 12}, {colors_dev, (size_t)n * 12}};
+    const Span outs[] = {{records_out_dev, (size_t)n * GS_GAUSSIAN_RECORD_BYTES}, {order_out_dev, (size_t)n * 4}};
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlap(o, i)) return refuse(c, __func__, "an output array aliases an input");
+    if (overlap(outs[0], outs[1])) return refuse(c, __func__, "two output arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = init_scratch(c, n, __func__)) return r;
+    if (launch_records_from_points(points_dev, colors_dev, n, c->init, c->init_sort, whole_list_run(c, n, 32u), p->opacity,
+                                   p->min_dist2, p->max_scale, records_out_dev, order_out_dev, c->stream) < 0)
+        return refuse(c, __func__, "the sorter refused the run", GS_ERR_HIP);
+    return check_launch(c, __func__);
+}
+
+#ifdef GS_INIT_PROBE
+// A tuning build only (tools/init_cost.py): the boxes that survived the coarse and the per-lane test of the last search,
+// summed over its waves, and the milliseconds of the last call's six launches.  Waits for the stream.
+int gs_init_probe_read(gs_ctx* c, uint32_t n, uint64_t* coarse_out, uint64_t* lane_out, float ms_out[6]) {
+    if (!c || !c->init.probe || n > c->init_cap) return GS_ERR_INVALID;
+    std::vector<uint32_t> h(((size_t)n + 63u) / 64u * 2);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, init_probe_ms(ms_out));
+    HIP_TRY(c, hipMemcpy(h.data(), c->init.probe, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *coarse_out = *lane_out = 0;
+    for (size_t i = 0; i < h.size(); i += 2) { *coarse_out += h[i]; *lane_out += h[i + 1]; }
+    return GS_OK;
+}
+#endif
 
 void gs_default_adam_params(gs_adam_params* p) {
     if (!p) return;

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import GsAdamParams, GsConfig, GsDensifyParams, GsHostTimings, GsSceneInfo, GsTimings
+from ._lib import GsAdamParams, GsConfig, GsDensifyParams, GsHostTimings, GsInitParams, GsSceneInfo, GsTimings
 
 FLOATS_PER_GAUSSIAN = 84
 GAUSSIAN_DTYPE = np.dtype([
@@ -812,6 +812,21 @@ class Renderer:
         self._ctx.check(_lib.lib().gs_densify_device(
             self._ctx.handle, _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr),
             C.byref(params), _vp(records_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
+
+    # -- a cloud from points (no reference counterpart; include/gsplat.h, gs_knn_mean_dist2_device / gs_records_from_points_device)
+    def knnMeanDist2Device(self, points_ptr: int, n: int, dist2_out_ptr: int):
+        """dist2_out[i] = the mean of the three smallest squared distances from point i to the other points, exact, in input
+        order.  Device addresses: float32 (n, 3) and (n,).  Enqueued on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_knn_mean_dist2_device(self._ctx.handle, _vp(points_ptr), int(n), _vp(dist2_out_ptr)))
+
+    def recordsFromPointsDevice(self, points_ptr: int, colors_ptr: int | None, n: int, params: GsInitParams, records_out_ptr: int,
+                                order_out_ptr: int | None = None):
+        """The first records of a training run from points in the .ply's frame (and colours in [0, 1], or None): scale from
+        the three nearest neighbours, params.opacity, identity rotation, SH DC from the colour, rows in the loader's
+        Morton order; order_out (uint32 (n,), or None) = the input index of every output row.  Device addresses; params:
+        default_init_params().  Enqueued on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_records_from_points_device(
+            self._ctx.handle, _vp(points_ptr), _vp(colors_ptr), int(n), C.byref(params), _vp(records_out_ptr), _vp(order_out_ptr)))
 
     # -- Renderer.cpp:230-270
     def cleanup(self):
