@@ -691,6 +691,45 @@ int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const f
                       const gs_densify_params* p,
                       float* records_out, float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out);
 
+/* Several views per optimiser step (no reference counterpart): the lists of two frames name different splats, so their rows
+ * cannot simply be added.  Two calls sum the (ids, rows, count) lists of any number of frames into one list over the union of
+ * their splats, which gs_adam_rows[_raw]_device, gs_upload_rows_device and gs_densify_stats_device take unchanged.  All arrays
+ * are the CALLER's, on the DEVICE: acc is float[n][84] in the record layout, mark is uint32[n].  Both calls are enqueued on the
+ * context's stream with no host sync, need no scene and no resolution, keep no state in the library and are bitwise
+ * reproducible; the host never reads a count.  Callers detect them by their symbols (GS_API_VERSION is unchanged).
+ *
+ * gs_rows_accumulate_device: ids_dev, grad_rows_dev and count_dev as gs_backward_visible_device leaves them.  For every
+ * i < min(*count_dev, max_rows), g = ids[i] (an id >= n is skipped: compared, never dereferenced; ids are distinct), and for
+ * each of the 59 fields f of the record (the floats the GS_ADAM_* groups name), float32, a multiply and then an add, never
+ * contracted:
+ *   mark[g] == 0 :  acc[g][f] = weight * row[i][f]                      (a store: the old value is not read)
+ *   otherwise    :  acc[g][f] = acc[g][f] + weight * row[i][f]
+ *   then            mark[g] += 1
+ * So acc needs no initialisation -- only mark starts as zeros --, a batch of one frame with weight == 1.0f reproduces that
+ * frame's rows bit for bit (-0.0f included), and mark[g] counts the lists that named g.  The other 25 floats of an acc row are
+ * never read or written; ids, grad_rows and count_dev are only read.  The sum of a batch depends on the order of its calls by
+ * float association alone.  The grid is sized from max_rows and the blocks past the count exit at once.  max_rows == 0:
+ * GS_OK, nothing launched.
+ * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued (a NULL ctx: the code alone): a NULL pointer with
+ * max_rows > 0, n == 0, a weight that is not finite, an acc that shares bytes with grad_rows.
+ *
+ * gs_rows_collect_device: let U = { g < n : mark[g] != 0 }, in ascending g.  *count_out_dev = |U|, not clamped.  For
+ * i < min(|U|, max_rows): ids_out[i] = the i-th member of U, and rows_out[i] = the 59 fields of acc[that g] bit for bit with
+ * +0.0f in the other 25 floats -- the row shape gs_backward_visible* writes.  Nothing past the written rows is touched.
+ * Afterwards mark[g] == 0 for every g < n, the members of U beyond max_rows included: THEIR SUMS ARE DROPPED with the batch
+ * (the count says how many there were), so size max_rows for the union, n at most.  acc is only read.  |U| == 0: count 0,
+ * nothing written.  max_rows == 0 is a count query that still clears mark; ids_out and rows_out may be NULL then.  Scratch:
+ * the context's per-splat scan buffers, shared with gs_densify_device (4 bytes per splat + 20 bytes per 256 splats), grown
+ * on demand and freed by gs_destroy.
+ * GS_ERR_INVALID (message, nothing enqueued; a NULL ctx: the code alone): a NULL acc, mark or count_out, n == 0 or n >= 2^31,
+ * a NULL ids_out or rows_out with max_rows > 0, a rows_out that shares bytes with acc, an ids_out or count_out that shares
+ * bytes with mark. */
+int gs_rows_accumulate_device(gs_ctx* ctx, float* acc_dev, uint32_t* mark_dev, uint32_t n,
+                              const uint32_t* ids_dev, const float* grad_rows_dev, const uint32_t* count_dev,
+                              uint32_t max_rows, float weight);
+int gs_rows_collect_device(gs_ctx* ctx, const float* acc_dev, uint32_t* mark_dev, uint32_t n,
+                           uint32_t* ids_out_dev, float* rows_out_dev, uint32_t max_rows, uint32_t* count_out_dev);
+
 /* A cloud from points (no reference counterpart): the first records of a training run from an SfM or LiDAR point cloud, what
  * the INRIA trainer's create_from_pcd makes -- scale = the root of the mean squared distance to the three nearest other
  * points, opacity 0.1, identity rotation, SH DC from the colour.  Both device calls work on the CALLER's device arrays, are

@@ -279,6 +279,23 @@ public:
         return rc;
     }
 
+    // Several views per optimiser step (gsplat.h, gs_rows_accumulate_device and gs_rows_collect_device): the listed rows of a
+    // frame, times weight, summed into the caller's DEVICE accumulator acc [n][84] with a touch count per splat in mark [n]
+    // (zeros before the first frame of a batch), then the touched rows as one ascending (ids, rows, count) list for adamRows
+    // and uploadRows, with mark cleared.  Both are enqueued on the context's stream without waiting and need no scene.
+    int rowsAccumulate(float* acc, uint32_t* mark, uint32_t n, const uint32_t* ids, const float* grad_rows, const uint32_t* count,
+                       uint32_t max_rows, float weight) {
+        const int rc = gs_rows_accumulate_device(ctx_, acc, mark, n, ids, grad_rows, count, max_rows, weight);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int rowsCollect(const float* acc, uint32_t* mark, uint32_t n, uint32_t* ids_out, float* rows_out, uint32_t max_rows,
+                    uint32_t* count_out) {
+        const int rc = gs_rows_collect_device(ctx_, acc, mark, n, ids_out, rows_out, max_rows, count_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // A cloud from points (gsplat.h, gs_knn_mean_dist2_device and gs_records_from_points_device): the exact mean squared
     // distance to the three nearest other points, in input order, and the first records of a training run -- rows in the
     // loader's Morton order, order_out[k] (may be null) = the input index of row k.  All arrays on the DEVICE; both are

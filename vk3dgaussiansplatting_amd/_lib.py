@@ -174,6 +174,7 @@ EXPORTS = [
     "gs_reset_opacity_raw_device", "gs_write_ply",
     "gs_backward_camera", "gs_backward_camera_device",
     "gs_default_init_params", "gs_knn_mean_dist2_device", "gs_records_from_points_device",
+    "gs_rows_accumulate_device", "gs_rows_collect_device",
 ]
 CAMERA_GRAD_FLOATS = 35    # GS_CAMERA_GRAD_FLOATS: [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
@@ -325,6 +326,8 @@ def lib() -> C.CDLL:
     L.gs_default_init_params.restype = None
     L.gs_knn_mean_dist2_device.argtypes = [ctxp, vp, u32, vp]
     L.gs_records_from_points_device.argtypes = [ctxp, vp, vp, u32, C.POINTER(GsInitParams), vp, vp]
+    L.gs_rows_accumulate_device.argtypes = [ctxp, vp, vp, u32, vp, vp, vp, u32, f32]
+    L.gs_rows_collect_device.argtypes = [ctxp, vp, vp, u32, vp, vp, u32, vp]
     _lib = L
     _check_hip_runtime(L)
     return L

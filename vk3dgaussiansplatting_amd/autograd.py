@@ -34,6 +34,8 @@ gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one 
     opt = VisibleAdam(records, renderer=r, space="raw")                         # Adam on log-scale, logit-opacity, raw rotation
     opt.reset_opacity(0.01); opt.save_ply("trained.ply")                        # the INRIA reset; a .ply gs_load_ply reads
 
+    numbers = opt.step_batch(cameras, targets, sh_mode)                         # one Adam step on the mean loss of B views: [B, 3]
+
     records, order = records_from_points(points, colors, renderer=r)            # a cloud from SfM points, in the loader's order
 
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
@@ -239,7 +241,10 @@ class VisibleAdam:
     bit (records is rewritten once, here, as act(raw): its scales and opacity move by the rounding of one log and one
     exp, its rotation becomes unit).  params default to default_adam_params(space="raw"): the INRIA rates, no clamps.
     step() is the same chain with gs_adam_rows_raw_device as its last call; reset_opacity() and save_ply() complete the
-    trainer.  space="records" (the default) moves the record's own values."""
+    trainer.  space="records" (the default) moves the record's own values.
+
+    step_batch() is one step on several views: the visible rows of every view summed on the device
+    (gs_rows_accumulate_device) and one Adam step on the union of their lists (gs_rows_collect_device)."""
 
     def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, track_density: bool = False,
                  space: str = "records", **params):
@@ -259,6 +264,7 @@ class VisibleAdam:
             self._zero_stats(n, dev)
         self.m, self.v = torch.zeros_like(records), torch.zeros_like(records)
         self._alloc_rows(dev)
+        self.acc = self.mark = None                       # step_batch's accumulator and marks: made on its first use
         self.grad = torch.zeros(renderer.height, renderer.width, 4, dtype=torch.float32, device=dev)
         self.t = 0
         self._full_upload = True
@@ -319,6 +325,8 @@ class VisibleAdam:
             if self._rows_follow_n:
                 self.max_rows = n_out
             self._alloc_rows(dev)
+            if self.acc is not None:
+                self._alloc_batch(dev)
         self.stream.synchronize()
         # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
         self._full_upload = True
@@ -360,6 +368,80 @@ class VisibleAdam:
             if self.track_density:
                 r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
                                      self.seen.data_ptr(), self.max_radius.data_ptr())
+            self.t += 1
+            self.params.step = self.t
+            if self.space == "raw":
+                r.adamRowsRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n,
+                                    self.ids.data_ptr(), self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+            else:
+                r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
+                                 self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+        return numbers
+
+    def _alloc_batch(self, dev):
+        """What step_batch sums into: the accumulator (never initialised: a first touch is a store) and the zero marks."""
+        n = self.records.shape[0]
+        self.acc = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+        self.mark = torch.zeros(n, dtype=torch.int32, device=dev)                   # int32 storage for the library's uint32
+
+    def step_batch(self, cameras, targets, sh_mode: int, lambda_dssim: float = 0.2, bg=None, weights=None,
+                   camera_grads=None) -> torch.Tensor:
+        """One Adam step on the weighted sum of the gradients of B views -> float32 [B, 3], {loss, L1, DSSIM} per view.
+
+        cameras: a sequence of (view, proj, cam_pos); targets: as many float32 [H, W, 3] tensors; weights: B floats, 1 / B
+        each by default (the mean of the losses); camera_grads: None, or B float32 [35] tensors (the rows of a [B, 35]
+        tensor serve), camera_grads[b] filled with the pose gradient of view b's own, unweighted loss.  One enqueue chain on
+        self.stream with no host wait: the upload (in full the first time, afterwards the rows of the previous step's
+        list, here the union), then per view the frame, the loss, gs_backward_visible_device into self.ids / rows / count
+        (with camera_grads gs_backward_camera_device, with track_density gs_densify_stats_device: seen counts views) and
+        gs_rows_accumulate_device into self.acc / self.mark; one gs_rows_collect_device back into self.ids / rows / count,
+        the ascending union; one gs_adam_rows[_raw]_device with t advanced once.  With B = 1 and weights = [1.0] it moves
+        records, m and v exactly as step() does.  max_rows bounds every view's list and the union; self.count holds the
+        size of the union afterwards.  The returned tensor belongs to self.stream, as step()'s does."""
+        r, n, dev = self.renderer, self.records.shape[0], self.records.device
+        B = len(cameras)
+        if B == 0 or len(targets) != B:
+            raise ValueError("step_batch needs at least one camera and a target for each")
+        weights = [1.0 / B] * B if weights is None else [float(w) for w in weights]
+        if len(weights) != B:
+            raise ValueError(f"weights must have {B} entries")
+        if camera_grads is not None:
+            if len(camera_grads) != B:
+                raise ValueError(f"camera_grads must have {B} entries")
+            for g in camera_grads:
+                if (g.dtype != torch.float32 or tuple(g.shape) != (_lib.CAMERA_GRAD_FLOATS,) or g.device != dev or not g.is_contiguous()):
+                    raise ValueError(f"camera_grads must hold contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}] tensors on the records' device")
+        for target in targets:
+            if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
+                raise ValueError(f"every target must be float32 {(r.height, r.width, 3)} on the GPU")
+        targets = [t.contiguous() for t in targets]
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            numbers = torch.empty(B, 3, dtype=torch.float32, device=dev)
+            if self.acc is None:
+                self._alloc_batch(dev)
+            if self._full_upload:
+                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
+                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
+                self._full_upload = False
+            else:
+                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+            for b, ((view, proj, cam_pos), target) in enumerate(zip(cameras, targets)):
+                target.record_stream(self.stream)
+                r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
+                r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers[b].data_ptr(), self.grad.data_ptr())
+                r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
+                                        self.count.data_ptr())
+                if camera_grads is not None:
+                    camera_grads[b].record_stream(self.stream)
+                    r.backwardCameraDevice(camera_grads[b].data_ptr())
+                if self.track_density:
+                    r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
+                                         self.seen.data_ptr(), self.max_radius.data_ptr())
+                r.rowsAccumulateDevice(self.acc.data_ptr(), self.mark.data_ptr(), n, self.ids.data_ptr(), self.rows.data_ptr(),
+                                       self.count.data_ptr(), self.max_rows, weights[b])
+            r.rowsCollectDevice(self.acc.data_ptr(), self.mark.data_ptr(), n, self.ids.data_ptr() if self.max_rows else None,
+                                self.rows.data_ptr() if self.max_rows else None, self.max_rows, self.count.data_ptr())
             self.t += 1
             self.params.step = self.t
             if self.space == "raw":

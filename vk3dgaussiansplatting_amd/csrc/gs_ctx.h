@@ -132,7 +132,7 @@ struct gs_ctx {
     uint32_t bwd_vis_rows = 0;
     float* bwd_cam_partials = nullptr;   // gs_backward_camera*: [35][blocks of 256 gaussians], allocated on its first call
     float* bwd_cam_out = nullptr;        // gs_backward_camera (host pointer): the 35 floats on the device
-    // gs_densify_device: its scan (K = 4) for densify_cap splats; grown on demand, freed at gs_destroy
+    // gs_densify_device (K = 4) and gs_rows_collect_device (K = 2): their scan for densify_cap splats; grown on demand, freed at gs_destroy
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
     DeviceOwner densify_mem;

@@ -380,6 +380,14 @@ struct DensifyArgs {
     SplatScan scan;                   // K = 4: outputs, cloned, split, pruned; offsets[g] = o(g), the index of g's first output
 };
 void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stream);
+// gs_rows_accumulate_device / gs_rows_collect_device (gs_batch.hip).  _accumulate: acc[ids[i]] (+)= weight * grad_rows[i] on the
+// fields, then mark[ids[i]] += 1, i < min(*count, max_rows); max_rows == 0 launches nothing.  _collect: the splats with a
+// non-zero mark, ascending, into ids_out / rows_out (both may be null with max_rows == 0) below max_rows, their number into
+// count_out, mark cleared; scan: K >= 2 rows for at least n splats.
+void launch_rows_accumulate(float* acc, uint32_t* mark, uint32_t n, const uint32_t* ids, const float* grad_rows,
+                            const uint32_t* count, uint32_t max_rows, float weight, hipStream_t stream);
+void launch_rows_collect(const float* acc, uint32_t* mark, uint32_t n, const SplatScan& scan, uint32_t* ids_out,
+                         float* rows_out, uint32_t max_rows, uint32_t* count_out, hipStream_t stream);
 // gs_knn_mean_dist2_device / gs_records_from_points_device (gs_init.hip): the context's scratch for n points, beside a
 // SortBuffers of capacity n (code, 0, input index)
 constexpr uint32_t kInitBoundBlocks = 256;      // partial boxes of the bounds reduction: a fixed shape

@@ -1,5 +1,5 @@
 // gs_train.cpp -- the training calls of include/gsplat.h, which have no counterpart in the reference: Adam on listed rows,
-// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control and a cloud from points.  Every entry point
+// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control, the rows of several views and a cloud from points.  Every entry point
 // refuses first (nothing enqueued, the context unchanged), then enqueues on the context's stream; a host-pointer form is
 // its _device twin between staging copies and a wait.
 #include "gs_ctx.h"
@@ -226,7 +226,7 @@ int enqueue_loss(gs_ctx* c, const char* who, const float* rgba32f, const float* 
 
 // ---- density control
 
-// the scratch of gs_densify_device for n splats, kept from call to call and grown when a larger cloud comes
+// the scratch of gs_densify_device and gs_rows_collect_device for n splats, kept from call to call and grown when a larger cloud comes
 int densify_scratch(gs_ctx* c, uint32_t n, const char* who) {
     if (c->densify_cap >= n) return GS_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
@@ -532,6 +532,39 @@ int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* 
     const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.scan.offsets, c->bwd.rows,
                              c->scratch.raster, fp.capacity, fp.width, fp.height, grad_accum, seen, max_radius};
     launch_densify_stats(a, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_rows_accumulate_device(gs_ctx* c, float* acc_dev, uint32_t* mark_dev, uint32_t n, const uint32_t* ids_dev,
+                              const float* grad_rows_dev, const uint32_t* count_dev, uint32_t max_rows, float weight) {
+    if (!c) return GS_ERR_INVALID;
+    const char* rows = "acc, mark, ids, grad_rows or count";
+    if (int r = check_row_arrays(c, __func__, max_rows, {acc_dev, mark_dev, ids_dev, grad_rows_dev, count_dev}, rows)) return r;
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (!std::isfinite(weight)) return refuse(c, __func__, "weight must be finite");
+    if (overlap({acc_dev, (size_t)n * GS_GAUSSIAN_RECORD_BYTES}, {grad_rows_dev, (size_t)max_rows * GS_GAUSSIAN_RECORD_BYTES}))
+        return refuse(c, __func__, "acc aliases grad_rows");
+    if (!max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_rows_accumulate(acc_dev, mark_dev, n, ids_dev, grad_rows_dev, count_dev, max_rows, weight, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_rows_collect_device(gs_ctx* c, const float* acc_dev, uint32_t* mark_dev, uint32_t n, uint32_t* ids_out_dev,
+                           float* rows_out_dev, uint32_t max_rows, uint32_t* count_out_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (!acc_dev || !mark_dev || !count_out_dev) return refuse(c, __func__, "null acc, mark or count_out");
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (n >= 0x80000000u) return refuse(c, __func__, "n must be below 2^31 (the rows are counted in 32 bits)");
+    if (int r = check_row_arrays(c, __func__, max_rows, {ids_out_dev, rows_out_dev}, "ids_out or rows_out")) return r;
+    if (overlap({rows_out_dev, (size_t)max_rows * GS_GAUSSIAN_RECORD_BYTES}, {acc_dev, (size_t)n * GS_GAUSSIAN_RECORD_BYTES}))
+        return refuse(c, __func__, "rows_out aliases acc");
+    const Span marks{mark_dev, (size_t)n * 4};
+    if (overlap({ids_out_dev, (size_t)max_rows * 4}, marks) || overlap({count_out_dev, 4}, marks))
+        return refuse(c, __func__, "ids_out or count_out aliases mark");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, __func__)) return r;
+    launch_rows_collect(acc_dev, mark_dev, n, c->densify_scan, ids_out_dev, rows_out_dev, max_rows, count_out_dev, c->stream);
     return check_launch(c, __func__);
 }
 

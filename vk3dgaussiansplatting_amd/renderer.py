@@ -813,6 +813,25 @@ class Renderer:
             self._ctx.handle, _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr),
             C.byref(params), _vp(records_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
 
+    # -- several views per optimiser step (no reference counterpart; include/gsplat.h, gs_rows_accumulate_device / gs_rows_collect_device)
+    def rowsAccumulateDevice(self, acc_ptr: int, mark_ptr: int, n: int, ids_ptr: int, rows_ptr: int, count_ptr: int, max_rows: int,
+                             weight: float = 1.0):
+        """The listed rows of one frame (ids, rows, count as backwardVisibleDevice left them) times weight, summed into the
+        caller's accumulator acc (float32 (n, 84)) on the 59 fields: a store where mark (uint32 (n,), zeros before the first
+        frame of a batch) is 0, an add elsewhere; then mark += 1 on the listed splats.  Device addresses.  Enqueued on the
+        context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_rows_accumulate_device(self._ctx.handle, _vp(acc_ptr), _vp(mark_ptr), int(n), _vp(ids_ptr),
+                                                             _vp(rows_ptr), _vp(count_ptr), int(max_rows), float(weight)))
+
+    def rowsCollectDevice(self, acc_ptr: int, mark_ptr: int, n: int, ids_out_ptr: int | None, rows_out_ptr: int | None, max_rows: int,
+                          count_out_ptr: int):
+        """The splats with a non-zero mark, ascending, as one list: ids_out (uint32 (max_rows,)), rows_out (float32 (max_rows, 84):
+        the fields of acc, +0 elsewhere) and count_out (their number, not clamped) -- what adamRowsDevice and uploadRowsDevice
+        take; mark is zero afterwards, and the sums of rows beyond max_rows are dropped.  max_rows == 0 with ids_out and
+        rows_out None only counts (and clears).  Enqueued on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_rows_collect_device(self._ctx.handle, _vp(acc_ptr), _vp(mark_ptr), int(n), _vp(ids_out_ptr),
+                                                          _vp(rows_out_ptr), int(max_rows), _vp(count_out_ptr)))
+
     # -- a cloud from points (no reference counterpart; include/gsplat.h, gs_knn_mean_dist2_device / gs_records_from_points_device)
     def knnMeanDist2Device(self, points_ptr: int, n: int, dist2_out_ptr: int):
         """dist2_out[i] = the mean of the three smallest squared distances from point i to the other points, exact, in input
