@@ -354,8 +354,28 @@ int gs_dist_bands(const gs_ctx* ctx, uint32_t* edges_out, uint32_t count);
  * same rule in Python). */
 int gs_balance_rows(const double* row_weights, uint32_t tiles_y, uint32_t world, uint32_t* edges_out);
 
+/* The sh_mode of a frame: which SH coefficients its colour sums.  0, 1 and 2 are the reference viewer's three
+ * (Camera.h:7-12); GS_SH_DEGREE_1 and GS_SH_DEGREE_2 are the degrees between them, which a trainer that raises the active
+ * degree step by step needs (no reference counterpart; callers detect them by the symbol gs_sh_mode_of_degree,
+ * GS_API_VERSION is unchanged).  The value 3 names no mode: it was refused before the degrees existed, callers were promised
+ * that refusal, and it stays refused.  Use the names, or gs_sh_mode_of_degree; the numbers do not follow the degree.
+ * With K = 4 (GS_SH_DEGREE_1) or K = 9 (GS_SH_DEGREE_2) the colour is GS_SH_ALL_BANDS's expression with the sum cut at K:
+ * res.c = sum over i < K of shCoeffs[i].c * basis[i] in ascending i, then + 0.5f, then max(res, 0) -- same arithmetic, same
+ * operand order.  A frame in these modes never reads the coefficients K..15 (no load is issued: a NaN there changes
+ * nothing), and neither do its gradients.  Every call that takes an sh_mode accepts all five (gs_render*,
+ * gs_render_sharded*, gs_debug_init_sort_list; gs_debug_read(GS_BUF_COLOR) follows the last frame's mode); the value 3 and
+ * every value of 6 or more are GS_ERR_INVALID with a message, nothing enqueued. */
+#define GS_SH_ALL_BANDS 0u        /* coefficients 0..15 (degree 3) */
+#define GS_SH_SKIP_FIRST_BAND 1u  /* coefficients 1..15, the reference's oddity as it is */
+#define GS_SH_ONLY_FIRST_BAND 2u  /* coefficient 0 (degree 0) */
+#define GS_SH_DEGREE_2 4u         /* coefficients 0..8 */
+#define GS_SH_DEGREE_1 5u         /* coefficients 0..3 */
+/* The mode of an active SH degree: 0, 1, 2, 3 -> GS_SH_ONLY_FIRST_BAND, GS_SH_DEGREE_1, GS_SH_DEGREE_2, GS_SH_ALL_BANDS.
+ * Pure host arithmetic, no context, no GPU.  GS_ERR_INVALID for degree > 3 or a NULL sh_mode_out (nothing written). */
+int gs_sh_mode_of_degree(uint32_t degree, uint32_t* sh_mode_out);
+
 /* Renderer::draw (Renderer.cpp:297-515): updateUniformBuffer(view, proj) (:531-538), the push
- * constants of Subrenderer.cpp:152-160 (camPos, shMode as an INTEGER 0/1/2), then the recorded
+ * constants of Subrenderer.cpp:152-160 (camPos, shMode as an INTEGER: one of GS_SH_* above), then the recorded
  * frame (:540-629).  rgba_out: height*width*4 bytes on the HOST, row-major, top row first,
  * R,G,B,A with A = 255 (the R8G8B8A8_UNORM storage image of Swapchain.cpp:27).  Synchronous. */
 int gs_render(gs_ctx* ctx, const float view[16], const float proj[16], const float cam_pos[3],
@@ -422,8 +442,10 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * NULL = zero), in real rows, top row first.  Output: dL/d(record) float[N][84] in the 336-byte layout and record order of
  * gs_upload_gaussians.  Gradients go to the 59 fields a frame reads -- position.xyz, scale.xyz, rot (all four, used
  * unnormalised as getRotMat uses it), shCoeffs[k].rgb for the coefficients the frame's sh_mode uses (0: all 16, 1: 1..15,
- * 2: 0 only) and shCoeffs[0].a (opacity); every other float is 0, and so is the whole record of a splat that was culled or
- * emitted no element.  The camera's gradients are a call of their own behind this one: gs_backward_camera* below.
+ * 2: 0 only, 4: 0..8, 5: 0..3) and shCoeffs[0].a (opacity); every other float is 0, and so is the whole record of a splat
+ * that was culled or emitted no element.  In GS_SH_DEGREE_1 / _2 the coefficient fields K..15 are exactly +0.0f, dL/d(position)
+ * carries the direction term of the K active coefficients only, and no inactive SH plane is read.  The camera's gradients
+ * are a call of their own behind this one: gs_backward_camera* below.
  * Boundary convention: the frame is piecewise smooth, and the gradient is the derivative of the branch the frame took with
  * every discrete decision held fixed -- the near-plane and NDC culls, tile boxes, depth keys and the sorted order; which
  * entries a pixel blends (f > 0 or alpha < 1/255 skip) and the entry it stops on (nextT < 1e-4, RenderGaussians.comp:127-140);
@@ -482,7 +504,8 @@ int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const flo
  *   - dL/dproj covers the screen-position path only.  The covariance's focal lengths come from gs_config.fov_y, not from
  *     proj (the reference's own split, Common.glsl:53), and a frame never reads clip z: elements 2, 6, 10 and 14 of the
  *     proj block (18, 22, 26 and 30 of the 35 floats) are exactly +0.0f.
- * dL/dcam_pos is the SH direction's dependence on the camera position: exactly +0.0f in sh_mode 2.
+ * dL/dcam_pos is the SH direction's dependence on the camera position, over the coefficients the frame's sh_mode uses
+ * (GS_SH_DEGREE_1 / _2: formed like mode 0's from the K active ones, no inactive plane read): exactly +0.0f in sh_mode 2 only.
  * Bitwise reproducible: no atomics, a fixed-shape sum over the splats -- the same 35 words for every sorter, launch shape,
  * tile order and GS_COUNT_* mode, after the dense and after the visible backward, from both entry points and from call to
  * call.  A frame that drew nothing gives GS_OK and 35 zeros.

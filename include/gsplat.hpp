@@ -73,7 +73,13 @@ public:
     }
 
     // Renderer::draw (Renderer.cpp:297-515).  view/proj: column-major float[16] (glm::mat4 memory);
-    // shMode 0/1/2 (Camera.h:7-12); rgbaOut: height*width*4 bytes, top row first.
+    // shMode: one of GS_SH_* (0/1/2 = Camera.h:7-12, 5/4 = SH degree 1 and 2); rgbaOut: height*width*4 bytes, top row first.
+    // The mode of an active SH degree 0..3 (gs_sh_mode_of_degree; a trainer's schedule: shModeOfDegree(min(3, t / 1000))),
+    // or -1 for a degree above 3.  No context, no GPU.
+    static int shModeOfDegree(uint32_t degree) {
+        uint32_t mode = 0;
+        return gs_sh_mode_of_degree(degree, &mode) == GS_OK ? (int)mode : -1;
+    }
     int draw(const float* view, const float* proj, const float* camPos, uint32_t shMode, uint8_t* rgbaOut) {
         return frameDone(gs_render(ctx_, view, proj, camPos, shMode, rgbaOut));
     }

@@ -175,7 +175,10 @@ EXPORTS = [
     "gs_backward_camera", "gs_backward_camera_device",
     "gs_default_init_params", "gs_knn_mean_dist2_device", "gs_records_from_points_device",
     "gs_rows_accumulate_device", "gs_rows_collect_device",
+    "gs_sh_mode_of_degree",
 ]
+# GS_SH_*: the sh_mode of a frame (0, 1, 2 = the reference's Camera.h modes; 5 and 4 = SH degree 1 and 2; 3 names none)
+GS_SH_ALL_BANDS, GS_SH_SKIP_FIRST_BAND, GS_SH_ONLY_FIRST_BAND, GS_SH_DEGREE_2, GS_SH_DEGREE_1 = 0, 1, 2, 4, 5
 CAMERA_GRAD_FLOATS = 35    # GS_CAMERA_GRAD_FLOATS: [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos
 ROWS_CONTIGUOUS, ROWS_INTERLEAVED, ROWS_BALANCED = 0, 1, 2   # GS_ROWS_*
 API_VERSION = 7            # GS_API_VERSION of include/gsplat.h this binding was written against
@@ -328,9 +331,18 @@ def lib() -> C.CDLL:
     L.gs_records_from_points_device.argtypes = [ctxp, vp, vp, u32, C.POINTER(GsInitParams), vp, vp]
     L.gs_rows_accumulate_device.argtypes = [ctxp, vp, vp, u32, vp, vp, vp, u32, f32]
     L.gs_rows_collect_device.argtypes = [ctxp, vp, vp, u32, vp, vp, u32, vp]
+    L.gs_sh_mode_of_degree.argtypes = [u32, C.POINTER(u32)]
     _lib = L
     _check_hip_runtime(L)
     return L
+
+
+def sh_mode_of_degree(degree: int) -> int:
+    """gs_sh_mode_of_degree: the frame mode (GS_SH_*) of an active SH degree 0..3 -> 2, 5, 4, 0.  No context, no GPU."""
+    mode = C.c_uint32()
+    if not 0 <= int(degree) <= 0xFFFFFFFF or lib().gs_sh_mode_of_degree(int(degree), C.byref(mode)) != GS_OK:
+        raise ValueError(f"sh_mode_of_degree: degree must be 0..3, got {degree!r}")
+    return int(mode.value)
 
 
 def default_densify_params(**overrides) -> GsDensifyParams:

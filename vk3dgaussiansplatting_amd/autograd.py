@@ -36,6 +36,10 @@ gradients and an Adam step on those rows (gs_adam_rows_device), enqueued on one 
 
     numbers = opt.step_batch(cameras, targets, sh_mode)                         # one Adam step on the mean loss of B views: [B, 3]
 
+    opt.sh_degree = 0                                                           # the INRIA schedule: start at the DC term ...
+    if it % 1000 == 0: opt.oneup_sh_degree()                                    # ... one degree up every 1000 iterations
+    numbers = opt.step(view, proj, cam_pos, None, target)                       # sh_mode None: the mode of opt.sh_degree
+
     records, order = records_from_points(points, colors, renderer=r)            # a cloud from SfM points, in the loader's order
 
 This module imports torch; `import vk3dgaussiansplatting_amd` does not import it.
@@ -332,16 +336,32 @@ class VisibleAdam:
         self._full_upload = True
         return n_out, cloned, split, pruned
 
+    # The INRIA schedule's active SH degree: a trainer starts at 0 and calls oneup_sh_degree() every 1000 iterations.  The
+    # default 3 (all 16 coefficients) is what a step drew before the degree existed.
+    sh_degree = 3
+
+    def oneup_sh_degree(self) -> int:
+        """Raise the active SH degree by one, up to 3 -> the new degree."""
+        self.sh_degree = min(int(self.sh_degree) + 1, 3)
+        return self.sh_degree
+
+    def frame_sh_mode(self, sh_mode: int | None = None) -> int:
+        """The sh_mode a step draws with: an explicit integer as it is, None = the mode of self.sh_degree
+        (gs_sh_mode_of_degree).  Host arithmetic: no context."""
+        return _lib.sh_mode_of_degree(self.sh_degree) if sh_mode is None else int(sh_mode)
+
     def reset_upload(self):
         """The next step uploads every record (after the caller changed rows the last step did not list)."""
         self._full_upload = True
 
-    def step(self, view, proj, cam_pos, sh_mode: int, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None,
+    def step(self, view, proj, cam_pos, sh_mode: int | None, target: torch.Tensor, lambda_dssim: float = 0.2, bg=None,
              camera_grad: torch.Tensor | None = None) -> torch.Tensor:
-        """camera_grad: a float32 [35] tensor on the records' device, filled with dL/dview, dL/dproj, dL/dcam_pos of this
+        """sh_mode: a GS_SH_* integer, or None for the mode of self.sh_degree (frame_sh_mode).
+        camera_grad: a float32 [35] tensor on the records' device, filled with dL/dview, dL/dproj, dL/dcam_pos of this
         step's frame (gs_backward_camera_device) in the same enqueue chain, with no host wait; it belongs to self.stream
         like the returned numbers.  Needs max_rows > 0."""
         r, n = self.renderer, self.records.shape[0]
+        sh_mode = self.frame_sh_mode(sh_mode)
         if camera_grad is not None and (camera_grad.dtype != torch.float32 or tuple(camera_grad.shape) != (_lib.CAMERA_GRAD_FLOATS,)
                                         or camera_grad.device != self.records.device or not camera_grad.is_contiguous()):
             raise ValueError(f"camera_grad must be a contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}] tensor on the records' device")
@@ -384,9 +404,10 @@ class VisibleAdam:
         self.acc = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
         self.mark = torch.zeros(n, dtype=torch.int32, device=dev)                   # int32 storage for the library's uint32
 
-    def step_batch(self, cameras, targets, sh_mode: int, lambda_dssim: float = 0.2, bg=None, weights=None,
+    def step_batch(self, cameras, targets, sh_mode: int | None = None, lambda_dssim: float = 0.2, bg=None, weights=None,
                    camera_grads=None) -> torch.Tensor:
         """One Adam step on the weighted sum of the gradients of B views -> float32 [B, 3], {loss, L1, DSSIM} per view.
+        sh_mode: a GS_SH_* integer, or None for the mode of self.sh_degree (frame_sh_mode).
 
         cameras: a sequence of (view, proj, cam_pos); targets: as many float32 [H, W, 3] tensors; weights: B floats, 1 / B
         each by default (the mean of the losses); camera_grads: None, or B float32 [35] tensors (the rows of a [B, 35]
@@ -400,6 +421,7 @@ class VisibleAdam:
         size of the union afterwards.  The returned tensor belongs to self.stream, as step()'s does."""
         r, n, dev = self.renderer, self.records.shape[0], self.records.device
         B = len(cameras)
+        sh_mode = self.frame_sh_mode(sh_mode)
         if B == 0 or len(targets) != B:
             raise ValueError("step_batch needs at least one camera and a target for each")
         weights = [1.0 / B] * B if weights is None else [float(w) for w in weights]

@@ -219,7 +219,7 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     if (!c->n) return fail(c, GS_ERR_NO_SCENE, "gs_render: no gaussians uploaded");
     if (!c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_render: gs_set_resolution not called");
     if (!view || !proj || !cam_pos) return fail(c, GS_ERR_INVALID, "gs_render: null camera argument");
-    if (sh_mode > 2u) return fail(c, GS_ERR_INVALID, "gs_render: sh_mode must be 0, 1 or 2");
+    if (!sh_mode_known(sh_mode)) return fail(c, GS_ERR_INVALID, "gs_render: " GS_SH_MODE_REFUSAL);
     Frame f{c, make_frame_params(c, view, proj, cam_pos, sh_mode)};
     FrameParams& fp = f.fp;
     if (!out_dev) fp.compact_out = 0u;   // the internal framebuffer is always a whole frame in real rows
@@ -399,6 +399,14 @@ int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** dev, size_t
 extern "C" {
 
 uint32_t gs_api_version(void) { return GS_API_VERSION; }
+
+// the frame mode of an active SH degree (host arithmetic: no context, no GPU)
+int gs_sh_mode_of_degree(uint32_t degree, uint32_t* sh_mode_out) {
+    static const uint32_t mode[4] = {GS_SH_ONLY_FIRST_BAND, GS_SH_DEGREE_1, GS_SH_DEGREE_2, GS_SH_ALL_BANDS};
+    if (degree > 3u || !sh_mode_out) return GS_ERR_INVALID;
+    *sh_mode_out = mode[degree];
+    return GS_OK;
+}
 
 int gs_runtime_versions(int* hip_build, int* hip_runtime, int* hip_driver) {
     if (hip_build) *hip_build = HIP_VERSION;

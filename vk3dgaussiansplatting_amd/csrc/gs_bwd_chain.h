@@ -208,7 +208,9 @@ __device__ __forceinline__ void bwd_chain(const FrameParams& fp, const SceneBuff
     const float dir[3] = {ddx / len, ddy / len, ddz / len};
     float b[16], bx[16], by[16], bz[16];
     sh_basis_grad(-dir[0], -dir[1], dir[2], b, bx, by, bz);
-    const int k_lo = fp.sh_mode == 1u ? 1 : 0, k_hi = fp.sh_mode == 2u ? 1 : 16;
+    // the coefficients [k_lo, k_hi) the frame's sh_mode uses (5 = GS_SH_DEGREE_1: 4, 4 = GS_SH_DEGREE_2: 9); no other plane is read
+    const int k_lo = fp.sh_mode == 1u ? 1 : 0;
+    const int k_hi = fp.sh_mode == 2u ? 1 : fp.sh_mode == 5u ? 4 : fp.sh_mode == 4u ? 9 : 16;
     float dres[3];
     {
         const float* shp = scene.sh + g;

@@ -246,6 +246,11 @@ GS_HIDDEN int output_buffer(gs_ctx* c, uint32_t which, const char* who, void** d
 
 namespace gs {
 
+// the five GS_SH_* modes; 3 names none (refused before the degrees existed, and still) -- what gs_render* and
+// gs_debug_init_sort_list refuse with GS_SH_MODE_REFUSAL behind their own name
+inline bool sh_mode_known(uint32_t sh_mode) { return sh_mode <= GS_SH_ONLY_FIRST_BAND || sh_mode == GS_SH_DEGREE_2 || sh_mode == GS_SH_DEGREE_1; }
+#define GS_SH_MODE_REFUSAL "sh_mode must be one of GS_SH_* (0, 1, 2, 4, 5)"
+
 inline FrameParams make_frame_params(const gs_ctx* c, const float* view, const float* proj,
                               const float* cam_pos, uint32_t sh_mode) {
     FrameParams fp{};

@@ -12,7 +12,8 @@ int gs_debug_init_sort_list(gs_ctx* c, const float view[16], const float proj[16
     const bool outputs_valid = c->outputs_valid;
     list_launching(c);
     if (!c->n || !c->capacity) return fail(c, GS_ERR_NO_SCENE, "gs_debug_init_sort_list: scene/resolution not set");
-    if (!view || !proj || !cam_pos || sh_mode > 2u) return fail(c, GS_ERR_INVALID, "gs_debug_init_sort_list: bad argument");
+    if (!view || !proj || !cam_pos) return fail(c, GS_ERR_INVALID, "gs_debug_init_sort_list: null camera argument");
+    if (!sh_mode_known(sh_mode)) return fail(c, GS_ERR_INVALID, "gs_debug_init_sort_list: " GS_SH_MODE_REFUSAL);
     HIP_TRY(c, hipSetDevice(c->device));
     FrameParams fp = make_frame_params(c, view, proj, cam_pos, sh_mode);
     fp.parity = (c->emit_parity ^= 1u);

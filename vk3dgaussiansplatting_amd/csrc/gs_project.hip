@@ -274,8 +274,11 @@ template <bool NT>
 __device__ __forceinline__ float sh_load(const float* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
 
 // colour of a splat, InitSortList.comp:124-126 + Common.glsl:141-170 (k_project for the splats that emit, k_debug_colour for
-// the others: one body, so both store the same bits)
-template <bool NT>
+// the others: one body, so both store the same bits).  K = 0: the reference's three modes behind a uniform branch on
+// fp.sh_mode, as ever.  K = 4 (GS_SH_DEGREE_1) and K = 9 (GS_SH_DEGREE_2): mode 0's sum cut at K coefficients -- the planes
+// 3K..47 are never loaded.  K is a template argument, not two more branches: with them k_project<*, false> went from 67 VGPRs
+// and no scratch to 70 VGPRs, 8 spilled and 36 bytes of scratch per lane (profiles/sh_degree_cost.txt).
+template <bool NT, int K>
 __device__ __forceinline__ void splat_colour(const FrameParams& fp, const float* shp, const uint32_t n, const float px, const float py,
                                              const float pz, float res[3]) {
     const float ddx = px - fp.cam_pos[0], ddy = py - fp.cam_pos[1], ddz = pz - fp.cam_pos[2];
@@ -283,7 +286,13 @@ __device__ __forceinline__ void splat_colour(const FrameParams& fp, const float*
     float basis[16];
     sh_eval4(ddx / len, ddy / len, ddz / len, basis);
     res[0] = 0.0f; res[1] = 0.0f; res[2] = 0.0f;
-    if (fp.sh_mode == 0u) {
+    if constexpr (K != 0) {
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                res[c] = res[c] + sh_load<NT>(shp + (size_t)(i * 3 + c) * n) * basis[i];
+    } else if (fp.sh_mode == 0u) {
 #pragma unroll
         for (int i = 0; i < 16; ++i)
 #pragma unroll
@@ -308,6 +317,9 @@ __device__ __forceinline__ void splat_colour(const FrameParams& fp, const float*
     }
 }
 
+// the K of splat_colour for a frame's sh_mode (5 = GS_SH_DEGREE_1, 4 = GS_SH_DEGREE_2)
+inline int sh_cut_of_mode(uint32_t sh_mode) { return sh_mode == 5u ? 4 : sh_mode == 4u ? 9 : 0; }
+
 // Seven workgroups per CU: left to itself the compiler hoists the 48 SH loads and takes 117 VGPRs (four waves per SIMD);
 // held to 72 it needs 65 without spilling, and the launch is 30 us shorter at config C (209 against 239 us).
 #ifndef GS_PROJECT_MINBLOCKS
@@ -318,8 +330,8 @@ __device__ __forceinline__ void splat_colour(const FrameParams& fp, const float*
 // the next anyway, while its other planes and the frame's lists can use the space (launch_project picks by scene size).
 // VIEW_Z (GS_OUTPUT_DEPTH on, SplatScratch::view_z allocated): also stores the view depth -viewSpacePos.z of every emitting
 // splat for the depth output -- an instantiation of its own, so that frames without it run the kernel as it was (a branch
-// in this kernel, at its SGPR limit, re-arranged the spills of the whole kernel).
-template <bool NT_SH, bool VIEW_Z>
+// in this kernel, at its SGPR limit, re-arranged the spills of the whole kernel).  SH_K: splat_colour's K, for the same reason.
+template <bool NT_SH, bool VIEW_Z, int SH_K>
 __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(const FrameParams fp,
                                                            const SceneBuffers scene,
                                                            const SplatScratch sc, const uint32_t num_blocks) {
@@ -437,7 +449,7 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                         rec0.z = inv_x; rec0.w = inv_y;
                         rec2.x = opacity;
                         float res[3];
-                        splat_colour<NT_SH>(fp, scene.sh + g, n, px, py, pz, res);
+                        splat_colour<NT_SH, SH_K>(fp, scene.sh + g, n, px, py, pz, res);
                         rec1 = make_float4(inv_z, res[0], res[1], res[2]);
                         sc.depth_key[g] = depth_key;
                         if constexpr (VIEW_Z) sc.view_z[g] = -vp[2];     // GS_OUTPUT_DEPTH: the z getDepthKey used
@@ -736,6 +748,18 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
     }
 }
 
+template <int SH_K>
+static void launch_project_cut(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, uint32_t blocks, bool nt_sh,
+                               hipStream_t stream) {
+    if (sc.view_z) {
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, true, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, true, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    } else {
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, false, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, false, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    }
+}
+
 void launch_project(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,
                     hipStream_t stream) {
     const uint32_t blocks = (fp.num_gaussians + kProjThreads - 1) / kProjThreads;
@@ -747,12 +771,10 @@ void launch_project(const FrameParams& fp, const SceneBuffers& scene, const Spla
 #define GS_PROJECT_NT_SH_ABOVE ((size_t)256u << 20)       /* scene bytes above which the SH planes are loaded non-temporally */
 #endif
     const bool nt_sh = (size_t)fp.num_gaussians * 236u > GS_PROJECT_NT_SH_ABOVE;
-    if (sc.view_z) {
-        if (nt_sh) hipLaunchKernelGGL((k_project<true, true>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-        else hipLaunchKernelGGL((k_project<false, true>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-    } else {
-        if (nt_sh) hipLaunchKernelGGL((k_project<true, false>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-        else hipLaunchKernelGGL((k_project<false, false>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+    switch (sh_cut_of_mode(fp.sh_mode)) {
+        case 4: launch_project_cut<4>(fp, scene, sc, blocks, nt_sh, stream); break;
+        case 9: launch_project_cut<9>(fp, scene, sc, blocks, nt_sh, stream); break;
+        default: launch_project_cut<0>(fp, scene, sc, blocks, nt_sh, stream); break;
     }
 }
 
@@ -761,6 +783,7 @@ void launch_project(const FrameParams& fp, const SceneBuffers& scene, const Spla
 // evaluates it only for the splats that emit (nothing else is ever read by a frame).  This fills in the others on demand,
 // from the last frame's camera: out[g] = (r, g, b, 1) for a splat whose record k_project stored (its covariance carries
 // the +0.3 dilation, so .cx != 0 marks it) but which touched no tile, (0, 0, 0, 0) otherwise.
+template <int SH_K>
 __global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, const SceneBuffers scene, const SplatScratch sc, float4* out) {
     const uint32_t n = fp.num_gaussians;
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
@@ -768,7 +791,7 @@ __global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, cons
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
     if (sc.wave_wrote[g >> 6] && sc.raster[g].cx != 0.0f && sc.tiles_touched[g] == 0u) {
         float res[3];
-        splat_colour<false>(fp, scene.sh + g, n, scene.pos[g], scene.pos[(size_t)n + g], scene.pos[2 * (size_t)n + g], res);
+        splat_colour<false, SH_K>(fp, scene.sh + g, n, scene.pos[g], scene.pos[(size_t)n + g], scene.pos[2 * (size_t)n + g], res);
         o = make_float4(res[0], res[1], res[2], 1.0f);
     }
     out[g] = o;
@@ -776,7 +799,13 @@ __global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, cons
 
 void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, float* out_rgba, hipStream_t stream) {
     const uint32_t blocks = (fp.num_gaussians + 255u) / 256u;
-    if (blocks) hipLaunchKernelGGL(k_debug_colour, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, reinterpret_cast<float4*>(out_rgba));
+    if (!blocks) return;
+    float4* out = reinterpret_cast<float4*>(out_rgba);
+    switch (sh_cut_of_mode(fp.sh_mode)) {
+        case 4: hipLaunchKernelGGL(k_debug_colour<4>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
+        case 9: hipLaunchKernelGGL(k_debug_colour<9>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
+        default: hipLaunchKernelGGL(k_debug_colour<0>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
+    }
 }
 
 void launch_scan_blocks(const FrameParams& fp, const SplatScratch& sc, SortParams* params,

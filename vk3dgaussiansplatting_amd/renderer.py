@@ -48,6 +48,9 @@ class SphericalHarmonicsMode(enum.IntEnum):  # Camera.h:7-12
     ALL_BANDS = 0
     SKIP_FIRST_BAND = 1
     ONLY_FIRST_BAND = 2
+    # no reference counterpart (GS_SH_DEGREE_1 / _2 of include/gsplat.h): the sum cut at 4 and at 9 coefficients
+    DEGREE_2 = 4
+    DEGREE_1 = 5
 
 
 class Camera:
