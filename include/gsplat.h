@@ -93,6 +93,10 @@ typedef struct gs_ctx gs_ctx;
 #define GS_COUNT_PER_PASS 1u  /* always a Count launch per pass */
 #define GS_COUNT_FED 2u       /* always fed (correct at every size; slow for long lists) */
 
+/* near_plane .. fov_y stand in for the reference's compile-time constants and hold for every frame of the context.
+ * gs_create refuses, with GS_ERR_INVALID and a message that names the field: any of the five that is not finite,
+ * near_plane <= 0, far_plane <= near_plane, ndc_cull <= 0, in_view_limit <= 0, and fov_y outside (0, pi) -- the tangent of
+ * its half angle must be finite and positive. */
 typedef struct gs_config {
     uint32_t struct_size;     /* sizeof(gs_config) as the CALLER's header declares it (gs_default_config fills it in).
                                  gs_create copies that many bytes and keeps its defaults for fields the caller's

@@ -273,7 +273,11 @@ def test_central_differences_for_cam_pos(scene):
     it."""
     aos, w, h, cam = load_scene(scene)
     sc = make_scene(aos, w, h, **cam)
-    r = make_renderer(sc, w, h)
+    check_cam_pos_central_differences(make_renderer(sc, w, h), sc, w, h, scene)
+
+
+def check_cam_pos_central_differences(r, sc, w, h, what):
+    """The body of test_central_differences_for_cam_pos on a renderer made for the scene sc (cleaned up here)."""
     r.setOutputs(rgba32f=True, depth=True)
     camera = sc.getCamera()
     view, proj, pos = camera.getViewMatrix(), camera.getProjectionMatrix(), np.asarray(camera.getPosition(), np.float32)
@@ -296,7 +300,7 @@ def test_central_differences_for_cam_pos(scene):
             fd[i, k] = (loss(hi) - loss(lo)) / (float(hi[k]) - float(lo[k]))
     r.cleanup()
     top = np.abs(fd[0]).max()
-    print(f"camera-grad-fd {scene}: fd(h) {fd[0]}, fd(2h) {fd[1]}, gradient {grad}")
+    print(f"camera-grad-fd {what}: fd(h) {fd[0]}, fd(2h) {fd[1]}, gradient {grad}")
     assert top > 0 and np.all(np.abs(fd[0] - fd[1]) <= 0.01 * top), (fd, top)
     assert np.all(np.abs(grad - fd[0]) <= 0.02 * top), (grad, fd[0], top)
 

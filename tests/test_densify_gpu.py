@@ -55,10 +55,11 @@ def radius_of(cov):
 class Frame:
     """A drawn frame with the visible-row backward done on it: the renderer, and ids / rows / count on the device."""
 
-    def __init__(self, aos, w, h, cam=None, sort=gs.GS_SORT_RADIX4, seed=1, grads=None):
+    def __init__(self, aos, w, h, cam=None, sort=gs.GS_SORT_RADIX4, seed=1, grads=None, sc=None, constants=None):
+        """sc: a scene with a camera of its own instead of make_scene(aos, w, h, **cam); constants: Renderer's camera constants."""
         self.n, self.w, self.h = len(aos), w, h
-        self.sc = make_scene(aos, w, h, **(cam or {}))
-        self.r = make_renderer(self.sc, w, h, sort=sort)
+        self.sc = sc if sc is not None else make_scene(aos, w, h, **(cam or {}))
+        self.r = make_renderer(self.sc, w, h, sort=sort, **(constants or {}))
         self.r.draw(self.sc)
         self.wr, self.wd = grads if grads is not None else weights(h, w, seed)
         self.g_rgba, self.g_depth = up(self.wr), up(self.wd)

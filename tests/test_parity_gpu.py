@@ -35,9 +35,10 @@ ALL_SORTS = (gs.GS_SORT_RADIX4, gs.GS_SORT_TILE_BUCKET, gs.GS_SORT_RADIX4_SPLAT_
 
 
 def make_renderer(sc, w, h, mode=gs.GS_RENDER_EXACT, sort=gs.GS_SORT_RADIX4, kernel=gs.GS_RENDER_KERNEL_AUTO,
-                  order=gs.GS_TILE_ORDER_LONGEST_FIRST, count=gs.GS_COUNT_AUTO):
+                  order=gs.GS_TILE_ORDER_LONGEST_FIRST, count=gs.GS_COUNT_AUTO, **constants):
+    """constants: Renderer's camera constants (near_plane, far_plane, ndc_cull, in_view_limit, fov_y); none = the defaults."""
     r = gs.Renderer(w, h, render_mode=mode, warmup_frames=0, sort_algorithm=sort, render_kernel=kernel, tile_order=order,
-                    count_launches=count)
+                    count_launches=count, **constants)
     r.init(sc.getResourceManager())
     r.initForScene(sc)
     return r

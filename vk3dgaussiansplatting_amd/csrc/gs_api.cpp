@@ -468,6 +468,20 @@ int gs_create(const gs_config* cfg_in, gs_ctx** out) {
         return fail(nullptr, GS_ERR_INVALID, "gs_create: unknown render_kernel");
     if (cfg.tile_order > GS_TILE_ORDER_RASTER) return fail(nullptr, GS_ERR_INVALID, "gs_create: unknown tile_order");
     if (cfg.count_launches > GS_COUNT_FED) return fail(nullptr, GS_ERR_INVALID, "gs_create: unknown count_launches");
+    // the five camera constants: every kernel that reads FrameParams divides by far - near, by tan(fov_y / 2) or by a
+    // limit derived from them, so a value that cannot be a camera's is refused here rather than rendered
+    const struct { const char* name; float value; } constants[5] = {
+        {"near_plane", cfg.near_plane}, {"far_plane", cfg.far_plane}, {"ndc_cull", cfg.ndc_cull},
+        {"in_view_limit", cfg.in_view_limit}, {"fov_y", cfg.fov_y}};
+    for (const auto& k : constants)
+        if (!std::isfinite(k.value)) return fail(nullptr, GS_ERR_INVALID, std::string("gs_create: ") + k.name + " is not finite");
+    if (cfg.near_plane <= 0.0f) return fail(nullptr, GS_ERR_INVALID, "gs_create: near_plane must be positive");
+    if (cfg.far_plane <= cfg.near_plane) return fail(nullptr, GS_ERR_INVALID, "gs_create: far_plane must be beyond near_plane");
+    if (cfg.ndc_cull <= 0.0f) return fail(nullptr, GS_ERR_INVALID, "gs_create: ndc_cull must be positive");
+    if (cfg.in_view_limit <= 0.0f) return fail(nullptr, GS_ERR_INVALID, "gs_create: in_view_limit must be positive");
+    // tan(fov_y / 2) must be finite and positive: the half angle inside (0, pi / 2)
+    if (cfg.fov_y <= 0.0f || (double)cfg.fov_y >= 3.14159265358979323846)
+        return fail(nullptr, GS_ERR_INVALID, "gs_create: fov_y must lie in (0, pi)");
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0)
@@ -749,6 +763,9 @@ int gs_set_resolution(gs_ctx* c, uint32_t width, uint32_t height) {
     if (e == hipSuccess) e = hipMemset(c->ranges, 0, (size_t)gw * gh * 2 * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(c->framebuffer, 0, (size_t)width * height * 4);
     if (e == hipSuccess) e = alloc_outputs(c);
+    // hipMemset returns before a device fill is done, and the null stream it ran on is not ordered with the context's
+    // non-blocking stream: wait for the fills, or a short first frame can store its outputs before the zeros land
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
         free_resolution(c);
         return fail(c, GS_ERR_HIP, std::string("gs_set_resolution: ") + hipGetErrorString(e));
@@ -778,6 +795,9 @@ int gs_set_outputs(gs_ctx* c, uint32_t mask) {
         if (e == hipSuccess) e = hipMemset(c->scratch.view_z, 0, (size_t)c->n * sizeof(float));
     }
     if (e == hipSuccess) e = alloc_outputs(c);
+    // hipMemset returns before a device fill is done, and the null stream it ran on is not ordered with the context's
+    // non-blocking stream: wait for the fills, or a short first frame can store its outputs before the zeros land
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {   // back to RGBA8-only frames rather than half set up
         free_outputs(c);
         c->outputs = 0;

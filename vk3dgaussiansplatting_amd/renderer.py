@@ -314,22 +314,39 @@ def default_adam_params(space: str = "records", **overrides) -> GsAdamParams:
     return p
 
 
+CAMERA_CONSTANTS = ("near_plane", "far_plane", "ndc_cull", "in_view_limit", "fov_y")   # the five floats of gs_config
+
+
+def _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
+            near_plane=None, far_plane=None, ndc_cull=None, in_view_limit=None, fov_y=None) -> GsConfig:
+    """gs_default_config with these fields written over it; a camera constant that is None keeps its default."""
+    cfg = GsConfig()
+    _lib.lib().gs_default_config(C.byref(cfg))
+    cfg.device_ordinal = device
+    cfg.render_mode = render_mode
+    cfg.sort_algorithm = sort_algorithm
+    cfg.render_kernel = render_kernel
+    cfg.tile_order = tile_order
+    cfg.count_launches = count_launches
+    cfg.record_timings = int(record_timings)   # 0 off, 1 buckets, 2 buckets + per-Scatter events
+    for name, value in zip(CAMERA_CONSTANTS, (near_plane, far_plane, ndc_cull, in_view_limit, fov_y)):
+        if value is not None:
+            setattr(cfg, name, float(value))
+    return cfg
+
+
 class _Context:
-    """Owns one gs_ctx."""
+    """Owns one gs_ctx.  near_plane .. fov_y: the camera constants of gs_config (include/gsplat.h); None keeps what
+    gs_default_config wrote."""
 
     def __init__(self, device: int = 0, render_mode: int = _lib.GS_RENDER_EXACT, record_timings=True,
                  sort_algorithm: int = _lib.GS_SORT_RADIX4, render_kernel: int = _lib.GS_RENDER_KERNEL_AUTO,
-                 tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO):
+                 tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO,
+                 near_plane: float | None = None, far_plane: float | None = None, ndc_cull: float | None = None,
+                 in_view_limit: float | None = None, fov_y: float | None = None):
         L = _lib.lib()
-        cfg = GsConfig()
-        L.gs_default_config(C.byref(cfg))
-        cfg.device_ordinal = device
-        cfg.render_mode = render_mode
-        cfg.sort_algorithm = sort_algorithm
-        cfg.render_kernel = render_kernel
-        cfg.tile_order = tile_order
-        cfg.count_launches = count_launches
-        cfg.record_timings = int(record_timings)   # 0 off, 1 buckets, 2 buckets + per-Scatter events
+        cfg = _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
+                      near_plane, far_plane, ndc_cull, in_view_limit, fov_y)
         self.cfg = cfg
         self.handle = C.c_void_p()
         rc = L.gs_create(C.byref(cfg), C.byref(self.handle))
@@ -432,8 +449,16 @@ class Renderer:
                  render_mode: int = _lib.GS_RENDER_EXACT, record_timings: bool = True,
                  warmup_frames: int | None = None, sort_algorithm: int = _lib.GS_SORT_RADIX4,
                  render_kernel: int = _lib.GS_RENDER_KERNEL_AUTO,
-                 tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO):
+                 tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO,
+                 near_plane: float | None = None, far_plane: float | None = None, ndc_cull: float | None = None,
+                 in_view_limit: float | None = None, fov_y: float | None = None):
+        """near_plane, far_plane, ndc_cull, in_view_limit, fov_y: the camera constants of gs_config, fixed for the life of
+        the context (None: gs_default_config's, the reference's).  proj drives the screen position, fov_y the covariance's
+        focal lengths: INTEGRATION.md, "Real cameras".  self.cfg is the gs_config init() hands to gs_create."""
         self.width, self.height = int(width), int(height)   # swapchain extent (Engine.cpp:35)
+        self._constants = (near_plane, far_plane, ndc_cull, in_view_limit, fov_y)
+        self.cfg = _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
+                           *self._constants)
         self._render_kernel = render_kernel
         self._tile_order = tile_order
         self._count_launches = count_launches     # GS_COUNT_*: a Count launch per radix pass, or per sort (short lists)
@@ -457,7 +482,8 @@ class Renderer:
     def init(self, resourceManager: ResourceManager):
         self.resourceManager = resourceManager
         self._ctx = _Context(self._device, self._render_mode, self._record, self._sort_algorithm,
-                             self._render_kernel, self._tile_order, self._count_launches)
+                             self._render_kernel, self._tile_order, self._count_launches, *self._constants)
+        self.cfg = self._ctx.cfg
 
     # -- Renderer.cpp:696-710
     def getNumTiles(self) -> int:
