@@ -718,6 +718,59 @@ int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const f
                       const gs_densify_params* p,
                       float* records_out, float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out);
 
+/* Pruning by contribution (no reference counterpart): which splats does any picture ever show?  The blend weight
+ * w = T * alpha is known to the blend alone; a splat behind an opaque surface in every view passes the opacity, scale and
+ * radius tests of gs_densify_device and is still projected, sorted and walked in every frame.  Two calls: the per-splat blend
+ * statistics of a frame, accumulated over any number of frames, and a stable compaction of the cloud by a per-splat score.
+ * All arrays are the CALLER's, on the DEVICE; the library keeps no training state.  Callers detect both calls by their symbols
+ * (GS_API_VERSION is unchanged).
+ *
+ * gs_contrib_device works on the last frame enqueued on the context.  Take every pair (pixel p, entry i of the list of p's
+ * tile) in which the entry adds its colour to the pixel -- the entry a pixel stops on included, the entries behind it not
+ * (tests/host/blend_trace_ref.c flags exactly these 1 or 2).  w = T_i * alpha_i, the float32 product of the forward's own
+ * transmittance in front of the entry and its own alpha (same expressions, same pinned exp).  Per splat g with at least one
+ * such pair in the frame (wmax, wsum: float[n], pixels: uint32[n], n the scene's):
+ *   wmax[g]   = M > wmax[g] ? M : wmax[g]                M = the largest w of g in the frame
+ *   wsum[g]   = wsum[g] + S                              S = the frame's sum in the fixed order below
+ *   pixels[g] = min(pixels[g] + count, 2^32 - 1)         count = the number of pairs; the sum is formed in 64 bits
+ * A splat without such a pair is neither read nor written in any of the three arrays: culled splats, splats that emit no
+ * element, splats wholly past an overflowed list, entries with det == 0, entries no pixel reaches and entries behind every
+ * pixel's stop.  The arrays start as zeros and accumulate over any number of frames.  wsum_dev and pixels_dev may each be
+ * NULL: that statistic is not formed.
+ * The fixed order of S (no float atomics; restated bit for bit by tests/host/contrib_ref.c):
+ *   per list element  e = ((W0 + W1) + W2) + W3, Ww = the sum over the 64 pixels of wave w of the element's tile: pixel rows
+ *                     4 w .. 4 w + 3 of the tile, lane = (ly & 3) * 16 + lx, as a balanced tree -- lanes 2 k and 2 k + 1
+ *                     first, then adjacent pair sums, six levels; a pixel that does not blend the entry, or lies outside
+ *                     the image, adds +0.0f;
+ *   per splat         S = 0.0f; S = S + e over the splat's list elements in slot order = tile raster order inside its box
+ *                     (the order of the backward's row sums), over the slots below the list capacity.
+ * Weights are finite and positive whenever opacities are finite; with non-finite opacities the call still terminates and
+ * the affected splats' values are unspecified.  Enqueued on the context's stream, no host sync; bitwise reproducible, the
+ * same for every sorter, launch shape, tile order and GS_COUNT_* mode.  Scratch: the per-splat slot offsets -- the
+ * backward's own where a gs_backward* form has allocated them (the values are identical), else 4 bytes per splat of this
+ * call's -- plus 12 bytes per list element of capacity, allocated on first use and freed with the resolution; never the
+ * backward's 40-byte rows.  The call leaves what a backward left behind as it is: between gs_backward_visible_device and
+ * gs_backward_camera_device or gs_densify_stats_device it changes neither result by a bit.
+ * GS_ERR_INVALID (message in gs_last_error, nothing enqueued; a NULL ctx: the code alone): everything gs_backward refuses,
+ * with its words behind this call's name (no frame since the last gs_set_resolution / gs_set_tile_rows* / upload /
+ * gs_debug_init_sort_list, a GS_RENDER_FAST context, a context that owns a subset of the tile rows, a sharded context); a
+ * NULL wmax_dev; an n other than the scene's. */
+int gs_contrib_device(gs_ctx* ctx, uint32_t n, float* wmax_dev, float* wsum_dev, uint32_t* pixels_dev);
+/* gs_prune_below_device: keep(g) = score[g] >= threshold, exactly as written (a NaN score is dropped).  The kept rows of
+ * records / raw / m / v (float[n][84], all 84 floats) are copied bit for bit to rows [0, kept) of their outputs, in ascending
+ * g.  counts_out[2] (DEVICE): [0] the number kept, not truncated; [1] the number dropped.  Rows with index >= max_out are not
+ * written and nothing past the written rows is touched.  raw, m and v are optional one by one, each NULL together with its
+ * own output; records_out (and the outputs of the arrays given) may be NULL with max_out == 0, a count query.  Bitwise
+ * reproducible; enqueued on the context's stream, no host sync; needs no scene and no resolution.  Scratch: the context's
+ * per-splat scan buffers, shared with gs_densify_device.
+ * GS_ERR_INVALID (message, nothing enqueued; a NULL ctx: the code alone): a NULL score, records or counts_out, a NULL
+ * records_out with max_out > 0, n == 0 or n >= 2^31, a NaN threshold, an input NULL without its output or the reverse, an
+ * output that shares bytes with an input, with the score or with another output. */
+int gs_prune_below_device(gs_ctx* ctx, const float* score_dev, float threshold, uint32_t n,
+                          const float* records, const float* raw, const float* m, const float* v,
+                          float* records_out, float* raw_out, float* m_out, float* v_out,
+                          uint32_t max_out, uint32_t* counts_out_dev /* [2] */);
+
 /* Several views per optimiser step (no reference counterpart): the lists of two frames name different splats, so their rows
  * cannot simply be added.  Two calls sum the (ids, rows, count) lists of any number of frames into one list over the union of
  * their splats, which gs_adam_rows[_raw]_device, gs_upload_rows_device and gs_densify_stats_device take unchanged.  All arrays

@@ -285,6 +285,25 @@ public:
         return rc;
     }
 
+    // Pruning by contribution (gsplat.h, gs_contrib_device and gs_prune_below_device): the blend weights of the last frame
+    // accumulated per splat into the caller's DEVICE arrays wmax / wsum / pixels [n] (wsum and pixels may be null), and the
+    // rows whose score reaches the threshold copied, in order, into records_out / raw_out / m_out / v_out [max_out][84] (raw,
+    // m and v each null together with its output); counts_out[2] (device) = kept, dropped.  Both are enqueued on the
+    // context's stream without waiting.
+    int contrib(uint32_t n, float* wmax, float* wsum, uint32_t* pixels) {
+        const int rc = gs_contrib_device(ctx_, n, wmax, wsum, pixels);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int pruneBelow(const float* score, float threshold, uint32_t n, const float* records, const float* raw, const float* m,
+                   const float* v, float* records_out, float* raw_out, float* m_out, float* v_out, uint32_t max_out,
+                   uint32_t* counts_out) {
+        const int rc = gs_prune_below_device(ctx_, score, threshold, n, records, raw, m, v, records_out, raw_out, m_out, v_out,
+                                             max_out, counts_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Several views per optimiser step (gsplat.h, gs_rows_accumulate_device and gs_rows_collect_device): the listed rows of a
     // frame, times weight, summed into the caller's DEVICE accumulator acc [n][84] with a touch count per splat in mark [n]
     // (zeros before the first frame of a batch), then the touched rows as one ascending (ids, rows, count) list for adamRows

@@ -336,6 +336,62 @@ class VisibleAdam:
         self._full_upload = True
         return n_out, cloned, split, pruned
 
+    def prune_by_contribution(self, cameras, threshold: float, sh_mode: int | None = None):
+        """Drop every gaussian whose largest blend weight w = T * alpha over the given views stays below threshold
+        (gs_contrib_device per view, then gs_prune_below_device with score = wmax) -> (n_out, dropped).
+
+        cameras: a sequence of (view, proj, cam_pos); sh_mode as in step().  On self.stream: the pending upload (in full, or
+        the rows the last step moved), then per view a frame and its contributions into zeroed self.wmax / self.wsum /
+        self.pixels (float32 / float32 / uint32-in-int32 of the OLD n: they stay readable until the next call), with no loss
+        and no optimiser step; then the kept rows of records, m, v and (space="raw") raw copied bit for bit, in order, into
+        new tensors -- raw makes no log/exp round trip, unlike densify().  The density statistics start again from zero;
+        ids, rows and max_rows follow the new size (a max_rows given to the constructor stays); the next step uploads the
+        whole cloud as a new scene.  t and the hyper-parameters stay.  Reading the two counts is the one host wait.
+        threshold has no default: no good value has been measured; the smallest positive float drops exactly the splats no
+        view shows, which leaves the frames of these views bit for bit as they were while no list overflows."""
+        cameras = list(cameras)
+        if not cameras:
+            raise ValueError("prune_by_contribution needs at least one camera")
+        r, dev, n = self.renderer, self.records.device, self.records.shape[0]
+        sh_mode = self.frame_sh_mode(sh_mode)
+        self.stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(self.stream):
+            if self._full_upload:
+                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
+                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
+                self._full_upload = False
+            else:
+                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+            self.wmax = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.wsum = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.pixels = torch.zeros(n, dtype=torch.int32, device=dev)             # int32 storage for the library's uint32
+            for view, proj, cam_pos in cameras:
+                r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
+                r.contribDevice(n, self.wmax.data_ptr(), self.wsum.data_ptr(), self.pixels.data_ptr())
+            raw = self.space == "raw"
+            out = [torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(4 if raw else 3)]
+            counts = torch.zeros(2, dtype=torch.int32, device=dev)
+            r.pruneBelowDevice(self.wmax.data_ptr(), float(threshold), n, self.records.data_ptr(),
+                               self.raw.data_ptr() if raw else None, self.m.data_ptr(), self.v.data_ptr(), out[0].data_ptr(),
+                               out[3].data_ptr() if raw else None, out[1].data_ptr(), out[2].data_ptr(), n, counts.data_ptr())
+            n_out, dropped = (int(x) for x in counts.cpu().numpy().view(np.uint32))      # waits for the stream
+            if n_out == 0:
+                raise RuntimeError("prune_by_contribution() would prune every gaussian")
+            self.records, self.m, self.v = (t[:n_out].clone() for t in out[:3])
+            if raw:
+                self.raw = out[3][:n_out].clone()
+            if self.track_density:
+                self._zero_stats(n_out, dev)
+            if self._rows_follow_n:
+                self.max_rows = n_out
+            self._alloc_rows(dev)
+            if self.acc is not None:
+                self._alloc_batch(dev)
+        self.stream.synchronize()
+        # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
+        self._full_upload = True
+        return n_out, dropped
+
     # The INRIA schedule's active SH degree: a trainer starts at 0 and calls oneup_sh_degree() every 1000 iterations.  The
     # default 3 (all 16 coefficients) is what a step drew before the degree existed.
     sh_degree = 3

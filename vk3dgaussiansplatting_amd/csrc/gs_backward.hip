@@ -274,9 +274,13 @@ __global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, 
     bwd_chain<false>(fp, scene, g, any, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats), nullptr);
 }
 
+void launch_slot_offsets(const uint32_t* tiles_touched, uint32_t n, const SplatScan& scan, hipStream_t stream) {
+    launch_splat_scan(BwdSource<false>{tiles_touched, nullptr, nullptr, 0u}, n, scan, nullptr, stream);
+}
+
 void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
                      hipStream_t stream) {
-    launch_splat_scan(BwdSource<false>{f.sc.tiles_touched, nullptr, nullptr, 0u}, f.fp.num_gaussians, f.bb.scan, nullptr, stream);
+    launch_slot_offsets(f.sc.tiles_touched, f.fp.num_gaussians, f.bb.scan, stream);
     launch_blend(f, grad_rgba, grad_depth, stream);
     hipLaunchKernelGGL(k_bwd_rowsum_chain<false>, dim3(backward_blocks(f.fp.num_gaussians)), dim3(256), 0, stream, f.fp,
                        f.scene, f.sc.tiles_touched, f.bb.scan.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);

@@ -132,7 +132,11 @@ struct gs_ctx {
     uint32_t bwd_vis_rows = 0;
     float* bwd_cam_partials = nullptr;   // gs_backward_camera*: [35][blocks of 256 gaussians], allocated on its first call
     float* bwd_cam_out = nullptr;        // gs_backward_camera (host pointer): the 35 floats on the device
-    // gs_densify_device (K = 4) and gs_rows_collect_device (K = 2): their scan for densify_cap splats; grown on demand, freed at gs_destroy
+    // gs_contrib_device: 12 bytes per list element of capacity, and slot offsets of its own (K = 1) while no backward has
+    // allocated bwd.scan, which it shares from then on; both owned by bwd_mem (allocated on first use, freed with the resolution)
+    uint32_t* contrib_rows = nullptr;
+    gs::SplatScan contrib_scan{};
+    // gs_densify_device (K = 4), gs_rows_collect_device and gs_prune_below_device (K = 2): their scan for densify_cap splats; grown on demand, freed at gs_destroy
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
     DeviceOwner densify_mem;

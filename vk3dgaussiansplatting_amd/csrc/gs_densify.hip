@@ -6,8 +6,10 @@
 //                   outputs k(g), and the four totals (outputs, cloned, split, pruned), and k_dens_write moves the records: a
 //                   lane per (input splat, quad), so a wave reads 1 KiB of consecutive bytes of records, m and v and writes
 //                   the outputs of g next to those of g - 1 -- the children sit beside their parent, and the storage order
-//                   keeps its locality.
-// No float atomics, nothing read back by the host: both calls are bitwise reproducible.
+//                   keeps its locality;
+//   gs_prune_below_device   : the stable compaction of the cloud by a per-splat score -- the same scan over PruneSource (kept,
+//                   dropped) and k_prune_write, k_dens_write's mapping with plain copies.
+// No float atomics, nothing read back by the host: all three calls are bitwise reproducible.
 #include "gs_splat_math.h"
 #include "gs_splat_scan.h"
 
@@ -158,6 +160,51 @@ void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stre
     const uint64_t wblocks = ((uint64_t)a.n * kRecordQuads + 255u) / 256u;       // < 2^28 for n < 2^31
     if (a.m) hipLaunchKernelGGL(k_dens_write<true>, dim3((uint32_t)wblocks), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_dens_write<false>, dim3((uint32_t)wblocks), dim3(256), 0, stream, a);
+}
+
+// ---- pruning by a score -------------------------------------------------------------------------------------------
+
+namespace {
+
+// The comparison of the header as it writes it: a NaN score compares false and is dropped
+__device__ __forceinline__ bool prune_keeps(const float* __restrict__ score, uint32_t g, float threshold) {
+    return score[g] >= threshold;
+}
+
+// The rows of the scan: kept, dropped (both totals are the call's counts)
+struct PruneSource {
+    static constexpr uint32_t K = 2u, kPlaced = 1u, kTotalsFrom = 0u;
+    const float* score;
+    float threshold;
+    __device__ void counts(uint32_t g, uint32_t (&c)[K]) const {
+        c[0] = prune_keeps(score, g, threshold) ? 1u : 0u;
+        c[1] = 1u - c[0];
+    }
+};
+
+}  // namespace
+
+// A lane per (input splat g, group q of four floats), like k_dens_write: a kept g below max_out has its quads copied to row
+// offsets[g] of every output that is given.
+__global__ __launch_bounds__(256) void k_prune_write(const PruneArgs a) {
+    const uint64_t item = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t g = (uint32_t)(item / kRecordQuads), q = (uint32_t)(item % kRecordQuads);
+    if (g >= a.n) return;
+    if (!prune_keeps(a.score, g, a.threshold)) return;
+    const uint32_t o = a.scan.offsets[g];
+    if (o >= a.max_out) return;
+    const size_t at = (size_t)o * kRecordQuads + q;
+    reinterpret_cast<float4*>(a.records_out)[at] = reinterpret_cast<const float4*>(a.records)[item];
+    if (a.raw) reinterpret_cast<float4*>(a.raw_out)[at] = reinterpret_cast<const float4*>(a.raw)[item];
+    if (a.m) reinterpret_cast<float4*>(a.m_out)[at] = reinterpret_cast<const float4*>(a.m)[item];
+    if (a.v) reinterpret_cast<float4*>(a.v_out)[at] = reinterpret_cast<const float4*>(a.v)[item];
+}
+
+void launch_prune_below(const PruneArgs& a, uint32_t* counts_out, hipStream_t stream) {
+    launch_splat_scan(PruneSource{a.score, a.threshold}, a.n, a.scan, counts_out, stream);   // n < 2^31: nothing saturates
+    if (a.max_out == 0) return;
+    const uint64_t wblocks = ((uint64_t)a.n * kRecordQuads + 255u) / 256u;       // < 2^28 for n < 2^31
+    hipLaunchKernelGGL(k_prune_write, dim3((uint32_t)wblocks), dim3(256), 0, stream, a);
 }
 
 }  // namespace gs

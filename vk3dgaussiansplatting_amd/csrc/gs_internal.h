@@ -308,6 +308,16 @@ void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uin
                                   hipStream_t stream);
 void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth,
                                   uint32_t max_rows, float* grad_rows, hipStream_t stream);
+// The slot offsets alone (row 0 of the scan, what launch_backward runs first): scan.offsets[g] = the first slot of splat g.
+// Over the buffers of a backward's scan it rewrites the values that are there and leaves V and |V| alone.
+void launch_slot_offsets(const uint32_t* tiles_touched, uint32_t n, const SplatScan& scan, hipStream_t stream);
+// gs_contrib_device (gs_contrib.hip): a row {sum, max, count} of the blend weights of one list element, in its slot
+constexpr int kContribRowWords = 3;
+inline size_t contrib_row_bytes(uint32_t capacity) { return (size_t)capacity * kContribRowWords * sizeof(uint32_t); }
+// wmax / wsum / pixels [N] (device; wsum and pixels may be null) accumulate the frame's blend weights per splat; offsets:
+// the slot offsets of the frame, rows: contrib_row_bytes(capacity) of scratch.  f.bb is not used.
+void launch_contrib(const BackwardFrame& f, const uint32_t* offsets, uint32_t* rows, float* wmax, float* wsum,
+                    uint32_t* pixels, hipStream_t stream);
 // gs_backward_camera* (gs_camera.hip): from the rows a launch_backward* left in bb.rows, grad_camera[35] = dL/dview[16],
 // dL/dproj[16], dL/dcam_pos[3] (device); partials: backward_camera_partial_bytes(N) of scratch, [35][backward_blocks(N)]
 size_t backward_camera_partial_bytes(uint32_t n);
@@ -380,6 +390,17 @@ struct DensifyArgs {
     SplatScan scan;                   // K = 4: outputs, cloned, split, pruned; offsets[g] = o(g), the index of g's first output
 };
 void launch_densify(const DensifyArgs& a, uint32_t* counts_out, hipStream_t stream);
+// gs_prune_below_device: the rows g with score[g] >= threshold, ascending, into rows [0, kept) of every output below max_out
+struct PruneArgs {
+    const float* score;
+    float threshold;
+    uint32_t n;
+    const float *records, *raw, *m, *v;            // raw, m, v: each null together with its output
+    float *records_out, *raw_out, *m_out, *v_out;
+    uint32_t max_out;
+    SplatScan scan;                   // K = 2: kept, dropped; offsets[g] = the output row of a kept g
+};
+void launch_prune_below(const PruneArgs& a, uint32_t* counts_out, hipStream_t stream);
 // gs_rows_accumulate_device / gs_rows_collect_device (gs_batch.hip).  _accumulate: acc[ids[i]] (+)= weight * grad_rows[i] on the
 // fields, then mark[ids[i]] += 1, i < min(*count, max_rows); max_rows == 0 launches nothing.  _collect: the splats with a
 // non-zero mark, ascending, into ids_out / rows_out (both may be null with max_rows == 0) below max_rows, their number into

@@ -1,5 +1,5 @@
 // gs_train.cpp -- the training calls of include/gsplat.h, which have no counterpart in the reference: Adam on listed rows,
-// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control, the rows of several views and a cloud from points.  Every entry point
+// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control, pruning by contribution, the rows of several views and a cloud from points.  Every entry point
 // refuses first (nothing enqueued, the context unchanged), then enqueues on the context's stream; a host-pointer form is
 // its _device twin between staging copies and a wait.
 #include "gs_ctx.h"
@@ -97,12 +97,17 @@ hipError_t alloc_splat_scan(DeviceOwner& mem, SplatScan& s, uint32_t n, uint32_t
     return e;
 }
 
-// the refusals (nothing enqueued), then the scratch of the first call
-int backward_prepare(gs_ctx* c, const char* who) {
+// what gs_backward* and gs_contrib_device refuse of the context (nothing enqueued)
+int backward_refusals(gs_ctx* c, const char* who) {
     if (c->cfg.render_mode != GS_RENDER_EXACT) return refuse(c, who, "only GS_RENDER_EXACT frames can be differentiated");
     const bool frame = c->capacity && c->n && c->last.differentiable;
     const char* no_frame = "no frame since the last gs_set_resolution, gs_set_tile_rows* or upload";
-    if (int r = check_whole_frame(c, who, "cannot be differentiated", frame, no_frame)) return r;
+    return check_whole_frame(c, who, "cannot be differentiated", frame, no_frame);
+}
+
+// the refusals, then the scratch of the first call
+int backward_prepare(gs_ctx* c, const char* who) {
+    if (int r = backward_refusals(c, who)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->bwd.rows) {
         DeviceOwner& mem = c->bwd_mem;
@@ -517,6 +522,62 @@ int gs_backward_camera(gs_ctx* c, float grad_camera[GS_CAMERA_GRAD_FLOATS]) {
     HIP_TRY(c, hipMemcpyAsync(grad_camera, c->bwd_cam_out, bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return GS_OK;
+}
+
+int gs_contrib_device(gs_ctx* c, uint32_t n, float* wmax_dev, float* wsum_dev, uint32_t* pixels_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (!wmax_dev) return refuse(c, __func__, "null wmax");
+    if (int r = backward_refusals(c, __func__)) return r;
+    if (n != c->n) return refuse(c, __func__, "n differs from the scene's");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the slot offsets: the backward's scan where one exists (the same values), else a scan of this call's own
+    const bool own_scan = !c->bwd.rows;
+    DeviceOwner& mem = c->bwd_mem;
+    hipError_t e = hipSuccess;
+    if (!c->contrib_rows) e = mem.alloc(c->contrib_rows, contrib_row_bytes(c->capacity));
+    if (e == hipSuccess && own_scan && !c->contrib_scan.totals) {
+        e = alloc_splat_scan(mem, c->contrib_scan, c->n, 1);
+        if (e != hipSuccess) {       // `totals` is allocated last: without it the next call starts over
+            SplatScan& s = c->contrib_scan;
+            mem.free(s.offsets); mem.free(s.block_sums); mem.free(s.block_offsets); mem.free(s.totals);
+        }
+    }
+    if (e != hipSuccess) return refuse(c, __func__, hipGetErrorString(e), GS_ERR_HIP);
+    const SplatScan& scan = own_scan ? c->contrib_scan : c->bwd.scan;
+    launch_slot_offsets(c->scratch.tiles_touched, c->n, scan, c->stream);
+    launch_contrib(backward_frame(c), scan.offsets, c->contrib_rows, wmax_dev, wsum_dev, pixels_dev, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_prune_below_device(gs_ctx* c, const float* score_dev, float threshold, uint32_t n, const float* records,
+                          const float* raw, const float* m, const float* v, float* records_out, float* raw_out, float* m_out,
+                          float* v_out, uint32_t max_out, uint32_t* counts_out_dev) {
+    if (!c) return GS_ERR_INVALID;
+    if (!score_dev || !records || !counts_out_dev) return refuse(c, __func__, "null score, records or counts_out");
+    if (max_out && !records_out) return refuse(c, __func__, "null records_out with max_out > 0");
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (n >= 0x80000000u) return refuse(c, __func__, "n must be below 2^31 (the outputs are counted in 32 bits)");
+    if (threshold != threshold) return refuse(c, __func__, "threshold is a NaN");
+    // with max_out == 0 no row is written and an output may stay away; an output without its input never
+    const bool paired = (raw || !raw_out) && (m || !m_out) && (v || !v_out) &&
+                        (!max_out || ((!raw || raw_out) && (!m || m_out) && (!v || v_out)));
+    if (!paired) return refuse(c, __func__, "raw, m and v must each be null together with their own output");
+    // no output may share bytes with an input, with the score or with another output
+    const size_t in_bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES, out_bytes = (size_t)max_out * GS_GAUSSIAN_RECORD_BYTES;
+    const Span ins[] = {{records, in_bytes}, {raw, in_bytes}, {m, in_bytes}, {v, in_bytes}, {score_dev, (size_t)n * 4}};
+    const Span outs[] = {{records_out, out_bytes}, {raw_out, out_bytes}, {m_out, out_bytes}, {v_out, out_bytes}, {counts_out_dev, 8}};
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlap(o, i)) return refuse(c, __func__, "an output array aliases an input");
+    for (size_t o = 0; o < std::size(outs); ++o)
+        for (size_t k = o + 1; k < std::size(outs); ++k)
+            if (overlap(outs[o], outs[k])) return refuse(c, __func__, "two output arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, __func__)) return r;
+    // with max_out == 0 the writer is not launched: its pointers may be anything
+    const PruneArgs a{score_dev, threshold, n, records, raw, m, v, records_out, raw_out, m_out, v_out, max_out, c->densify_scan};
+    launch_prune_below(a, counts_out_dev, c->stream);
+    return check_launch(c, __func__);
 }
 
 int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,

@@ -842,6 +842,25 @@ class Renderer:
             self._ctx.handle, _vp(records_ptr), _vp(m_ptr), _vp(v_ptr), int(n), _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr),
             C.byref(params), _vp(records_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
 
+    # -- pruning by contribution (no reference counterpart; include/gsplat.h, gs_contrib_device / gs_prune_below_device)
+    def contribDevice(self, n: int, wmax_ptr: int, wsum_ptr: int | None = None, pixels_ptr: int | None = None):
+        """The blend weights w = T * alpha of the last frame, per splat, accumulated into the caller's device arrays of n
+        (zeros before the first frame): wmax (float32) = max(itself, the largest w), wsum (float32, or None) += the sum in
+        the header's fixed order, pixels (uint32, or None) += the number of (pixel, entry) pairs, saturating.  A splat that
+        adds colour to no pixel is not touched.  Enqueued on the context's stream without waiting."""
+        self._ctx.check(_lib.lib().gs_contrib_device(self._ctx.handle, int(n), _vp(wmax_ptr), _vp(wsum_ptr), _vp(pixels_ptr)))
+
+    def pruneBelowDevice(self, score_ptr: int, threshold: float, n: int, records_ptr: int, raw_ptr: int | None, m_ptr: int | None,
+                         v_ptr: int | None, records_out_ptr: int | None, raw_out_ptr: int | None, m_out_ptr: int | None,
+                         v_out_ptr: int | None, max_out: int, counts_ptr: int):
+        """The rows g with score[g] >= threshold (score: float32 (n,); a NaN is dropped) of records / raw / m / v (n, 84)
+        copied bit for bit, in order, to the first rows of records_out / raw_out / m_out / v_out (max_out, 84); counts (2
+        uint32 on the device) = kept (not truncated), dropped.  raw, m and v: each None together with its output.  Enqueued
+        on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_prune_below_device(
+            self._ctx.handle, _vp(score_ptr), float(threshold), int(n), _vp(records_ptr), _vp(raw_ptr), _vp(m_ptr), _vp(v_ptr),
+            _vp(records_out_ptr), _vp(raw_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
+
     # -- several views per optimiser step (no reference counterpart; include/gsplat.h, gs_rows_accumulate_device / gs_rows_collect_device)
     def rowsAccumulateDevice(self, acc_ptr: int, mark_ptr: int, n: int, ids_ptr: int, rows_ptr: int, count_ptr: int, max_rows: int,
                              weight: float = 1.0):
