@@ -8,9 +8,10 @@
 //                   below the capacity, and every such slot is an element of the list.  VIS carries a second row beside
 //                   the first, the flag tiles_touched != 0: its exclusive scan is the position of g in V (ascending g by
 //                   construction), vis_ids[position] = g, and its total is |V| (visible_count_of);
-//   k_bwd_blend   : per tile, the blend of RenderGaussians.comp:112-142 replayed front to back in the EXACT arithmetic
-//                   (same expressions, same pinned exp: the same entries contribute and each pixel stops on the same
-//                   entry K with the same T_K), then walked back to front with the colour behind every entry as a running
+//   k_bwd_blend   : per tile, the blend of RenderGaussians.comp:112-142 replayed front to back with the pieces of
+//                   gs_tile_replay.h (the staging, the entry test and the transmittance step, shared with k_contrib_blend
+//                   of gs_contrib.hip: the same entries contribute and each pixel stops on the same entry K with the same
+//                   T_K).  What this kernel adds: the walk back to front with the colour behind every entry as a running
 //                   sum; the 256 pixels' derivatives of each list entry are reduced on chip in a fixed tree and stored as
 //                   one 10-float row in the slot of the entry, with plain stores;
 //   k_bwd_rowsum_chain<VIS> : per splat, its rows summed in slot order (= tile raster order inside its box), then the sum
@@ -25,6 +26,7 @@
 // the forward (they depend on the sorted list and the pixels only).
 #include "gs_bwd_chain.h"
 #include "gs_splat_scan.h"
+#include "gs_tile_replay.h"
 
 namespace gs {
 
@@ -56,95 +58,41 @@ struct BwdSource {
 
 // ---- blend backward -----------------------------------------------------------------------------------------------
 
-struct BwdBlendArgs {
-    const SplatRaster* raster;
-    const uint32_t* sorted_id;
-    const uint32_t* ranges;
-    const float* pos;               // SceneBuffers::pos (the view depth of an entry, with grad_depth)
+struct BwdBlendArgs : TileListArgs {
+    const float* pos;               // SceneBuffers::pos (the view depth of an entry) with grad_depth, else null
     const float4* grad_rgba;        // [H][W] dL/dRGBA32F
     const float* grad_depth;        // [H][W] dL/dDEPTH or null
-    const uint32_t* offsets;        // [N] BackwardBuffers::scan.offsets
-    const uint2* extents;           // SplatScratch::extents
     float* rows;                    // [capacity][kRowFloats]
-    uint32_t capacity;
 };
 
-// The exponent of RenderGaussians.comp:119-123 in the operand order of k_render / blend_pair (contraction is off)
-__device__ __forceinline__ float blend_exponent(float sx, float sy, float ix, float iy, float iz, float fpx, float fpy,
-                                                float& ex, float& ey) {
-    ex = sx - fpx;
-    ey = -(sy - fpy);
-    return -0.5f * (ix * ex * ex + iz * ey * ey) - iy * ex * ey;
-}
-
-// One 256-thread workgroup per tile, one pixel per lane (wave w: pixel rows 4 w .. 4 w + 3).
+// One 256-thread workgroup per tile, one pixel per lane: the replay of gs_tile_replay.h, then its walk back
 __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const BwdBlendArgs a) {
-    // staged entries: sx, sy, ix, iy, iz, alpha0, r, g, b, z, slot (bits), -
-    __shared__ float s_e[kBwdBatch][12];
+    __shared__ float s_e[kBwdBatch][12];                 // staged entries, with colour and depth
     __shared__ float s_part[4][kBwdBatch][kRowFloats];   // per-wave sums of an entry's row
     __shared__ uint32_t s_kend;
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t tile = blockIdx.x;                                // a full grid: compact id == global id
-    const uint32_t ty = tile / fp.grid_w, tx = tile % fp.grid_w;
-    const uint32_t start = a.ranges[tile * 2 + 0], end = a.ranges[tile * 2 + 1];
-    const uint32_t px = tx * kTile + (uint32_t)(tid & 15), py = ty * kTile + (uint32_t)(tid >> 4);
-    const bool inside = px < fp.width && py < fp.height;
-    const float fpx = (float)px, fpy = (float)py;
-    const bool want_z = a.grad_depth != nullptr;
-    if (tid == 0) s_kend = 0u;
-
-    // stages entries [i0, i0 + count) of the list into s_e (threads 0 .. count - 1)
-    auto stage = [&](uint32_t i0, uint32_t count) {
-        if ((uint32_t)tid < count) {
-            const uint32_t gi = a.sorted_id[i0 + tid];
-            const float4* rp = reinterpret_cast<const float4*>(a.raster + gi);
-            const float4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
-            float z = 0.0f;
-            if (want_z) {   // -viewSpacePos.z as k_project computes it (mat4_mul_vec4, row 2)
-                const size_t n = fp.num_gaussians;
-                float acc = fp.view[2] * a.pos[gi];
-                acc = acc + fp.view[6] * a.pos[n + gi];
-                acc = acc + fp.view[10] * a.pos[2 * n + gi];
-                acc = acc + fp.view[14] * 1.0f;
-                z = -acc;
-            }
-            const uint2 ext = a.extents[gi];
-            const uint32_t min_x = ext.x & 0xFFFFu, k0 = ext.x >> 16, max_x = ext.y & 0xFFFFu;
-            const uint64_t slot = (uint64_t)a.offsets[gi] + (uint64_t)(ty - k0) * (max_x - min_x) + (tx - min_x);
-            float* e = s_e[tid];
-            e[0] = r0.x; e[1] = r0.y; e[2] = r0.z; e[3] = r0.w; e[4] = r1.x;
-            e[5] = r2.x; e[6] = r1.y; e[7] = r1.z; e[8] = r1.w; e[9] = z;
-            e[10] = __uint_as_float(slot < a.capacity ? (uint32_t)slot : 0xFFFFFFFFu);
-        }
-    };
-    // the entry's test and alpha, bit for bit those of the forward: contributes = !(f > 0) && !(alpha < 1/255)
-    auto entry_alpha = [&](const float* e, float& ex, float& ey, float& expf_, bool& contributes) {
-        const float f = blend_exponent(e[0], e[1], e[2], e[3], e[4], fpx, fpy, ex, ey);
-        expf_ = exp_pinned_live(f);
-        const float alpha = e[5] * expf_;
-        contributes = !(f > 0.0f) && !(alpha < 1.0f / 255.0f);
-        return alpha;
-    };
+    const TilePixel t = tile_pixel(fp, a.ranges);
+    const uint32_t start = t.start, end = t.end;
+    if (t.tid == 0) s_kend = 0u;
 
     // 1. forward replay: the last contributing entry K of the pixel and the transmittance T_K in front of it
     uint32_t last = 0xFFFFFFFFu;
     float T = 1.0f, TK = 0.0f;
-    bool done = !inside;
+    bool done = !t.inside;
     for (uint32_t i0 = start; i0 < end; i0 += kBwdBatch) {
         const uint32_t cnt = end - i0 < (uint32_t)kBwdBatch ? end - i0 : (uint32_t)kBwdBatch;
-        stage(i0, cnt);
+        stage_entries<true>(s_e, t, fp, a, a.pos, i0, cnt);
         __syncthreads();
         if (!done) {
             for (uint32_t j = 0; j < cnt; ++j) {
-                float ex, ey, ef;
+                float ex, ey, ef, next_t;
                 bool contributes;
-                const float alpha = entry_alpha(s_e[j], ex, ey, ef, contributes);
+                const float alpha = entry_alpha(s_e[j], t, ex, ey, ef, contributes);
                 if (!contributes) continue;
-                const float next_t = T * (1.0f - alpha);                       // :133
+                const bool stops = transmittance_step(T, alpha, next_t);
                 last = i0 + j;
                 TK = T;
-                if (next_t < 0.0001f) { done = true; break; }                  // :136-140, colour already added
+                if (stops) { done = true; break; }
                 T = next_t;
             }
         }
@@ -157,23 +105,23 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
     // 2. back to front over [start, kend)
     float4 gc = make_float4(0.f, 0.f, 0.f, 0.f);
     float gd = 0.0f;
-    if (inside && last != 0xFFFFFFFFu) {
-        gc = a.grad_rgba[(size_t)py * fp.width + px];
-        if (want_z) gd = a.grad_depth[(size_t)py * fp.width + px];
+    if (t.inside && last != 0xFFFFFFFFu) {
+        gc = a.grad_rgba[(size_t)t.py * fp.width + t.px];
+        if (a.pos) gd = a.grad_depth[(size_t)t.py * fp.width + t.px];
     }
     float Tcur = TK;                                  // T in front of the entry processed last (walking back)
     float Sr = 0.f, Sg = 0.f, Sb = 0.f, Sa = 0.f, Sz = 0.f;   // colour, alpha, depth behind it (divided by its T)
     for (uint32_t i1 = kend; i1 > start;) {
         const uint32_t i0 = i1 - start > (uint32_t)kBwdBatch ? i1 - (uint32_t)kBwdBatch : start;
         const uint32_t cnt = i1 - i0;
-        stage(i0, cnt);
+        stage_entries<true>(s_e, t, fp, a, a.pos, i0, cnt);
         __syncthreads();
         for (int j = (int)cnt - 1; j >= 0; --j) {
             const uint32_t i = i0 + (uint32_t)j;
             const float* e = s_e[j];
             float ex, ey, ef;
             bool contributes;
-            const float alpha = entry_alpha(e, ex, ey, ef, contributes);
+            const float alpha = entry_alpha(e, t, ex, ey, ef, contributes);
             contributes = contributes && last != 0xFFFFFFFFu && i <= last;
             float v[kRowFloats];
 #pragma unroll
@@ -181,12 +129,12 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
             if (contributes) {
                 const float one_m = 1.0f - alpha;                              // the forward's own (1 - alpha)
                 const float Ti = i == last ? TK : Tcur / one_m;                // T_{i+1} >= 1e-4 here: no early-out before K
-                const float cr = e[6], cg = e[7], cb = e[8], z = e[9];
+                const float cr = e[kEntColour], cg = e[kEntColour + 1], cb = e[kEntColour + 2], z = e[kEntDepth];
                 const float dalpha = Ti * (gc.x * (cr - Sr) + gc.y * (cg - Sg) + gc.z * (cb - Sb) + gc.w * (1.0f - Sa) +
                                            gd * (z - Sz));
                 const float w = Ti * alpha;
                 const float df = dalpha * alpha;                               // alpha = a * exp(f)
-                const float ix = e[2], iy = e[3], iz = e[4];
+                const float ix = e[kEntIx], iy = e[kEntIy], iz = e[kEntIz];
                 v[0] = df * (-(ix * ex) - iy * ey);                            // d f / d sx  (ex = sx - px)
                 v[1] = df * (iz * ey + iy * ex);                               // d f / d sy  (ey = py - sy)
                 v[2] = df * (-0.5f * ex * ex);
@@ -205,43 +153,31 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
             // the wave's sum in a fixed butterfly (every lane ends with the same bits), then one lane parks it
             if (__ballot(contributes) != 0ull) {
 #pragma unroll
-                for (int k = 0; k < kRowFloats; ++k) {
-#pragma unroll
-                    for (int off = 1; off < 64; off <<= 1) v[k] += __shfl_xor(v[k], off, 64);
-                }
+                for (int k = 0; k < kRowFloats; ++k) v[k] = wave_tree(v[k], [](float x, float y) { return x + y; });
             }
-            if (lane == 0) {
+            if (t.lane == 0) {
 #pragma unroll
-                for (int k = 0; k < kRowFloats; ++k) s_part[wave][j][k] = v[k];
+                for (int k = 0; k < kRowFloats; ++k) s_part[t.wave][j][k] = v[k];
             }
         }
         __syncthreads();
-        // the four waves' sums in a fixed order -> the entry's row, in its slot
-        for (uint32_t q = (uint32_t)tid; q < cnt * kRowFloats; q += 256u) {
+        // the four waves' sums -> the entry's row, in its slot
+        for (uint32_t q = (uint32_t)t.tid; q < cnt * kRowFloats; q += 256u) {
             const uint32_t j = q / kRowFloats, k = q % kRowFloats;
-            const uint32_t slot = __float_as_uint(s_e[j][10]);
+            const uint32_t slot = __float_as_uint(s_e[j][kEntSlot<true>]);
             const float sum = ((s_part[0][j][k] + s_part[1][j][k]) + s_part[2][j][k]) + s_part[3][j][k];
-            if (slot != 0xFFFFFFFFu) a.rows[(size_t)slot * kRowFloats + k] = sum;
+            if (slot != kNoSlot) a.rows[(size_t)slot * kRowFloats + k] = sum;
         }
         __syncthreads();
         i1 = i0;
     }
-    // 3. entries no pixel of the tile reaches: zero rows
-    for (uint32_t i0 = kend; i0 < end; i0 += kBwdBatch) {
-        const uint32_t cnt = end - i0 < (uint32_t)kBwdBatch ? end - i0 : (uint32_t)kBwdBatch;
-        stage(i0, cnt);
-        __syncthreads();
-        for (uint32_t q = (uint32_t)tid; q < cnt * kRowFloats; q += 256u) {
-            const uint32_t slot = __float_as_uint(s_e[q / kRowFloats][10]);
-            if (slot != 0xFFFFFFFFu) a.rows[(size_t)slot * kRowFloats + q % kRowFloats] = 0.0f;
-        }
-        __syncthreads();
-    }
+    // 3. entries no pixel of the tile reaches
+    zero_rows<kRowFloats, kBwdBatch>(t, a, kend, a.rows);
 }
 
 static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, hipStream_t stream) {
-    const BwdBlendArgs args{f.sc.raster, f.sorted_id, f.ranges, f.scene.pos, reinterpret_cast<const float4*>(grad_rgba),
-                            grad_depth, f.bb.scan.offsets, f.sc.extents, f.bb.rows, f.fp.capacity};
+    const BwdBlendArgs args{{f.sc.raster, f.sorted_id, f.ranges, f.bb.scan.offsets, f.sc.extents, f.fp.capacity},
+                            grad_depth ? f.scene.pos : nullptr, reinterpret_cast<const float4*>(grad_rgba), grad_depth, f.bb.rows};
     hipLaunchKernelGGL(k_bwd_blend, dim3(f.fp.grid_w * f.fp.grid_h), dim3(256), 0, stream, f.fp, args);
 }
 

@@ -62,6 +62,27 @@ __device__ __forceinline__ uint64_t wave_inclusive_scan64(uint64_t v) {
     return v;
 }
 
+// The value of another lane of the row of 16 by DPP (pure VALU, no LDS crossbar); every lane of the wave must be active
+template <int CTRL>
+__device__ __forceinline__ float row_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+
+// A six-level butterfly over the wave, lanes 2 k and 2 k + 1 first, then adjacent pair results: lane l combines with lane
+// l ^ 1, ^ 2, ^ 4, ^ 8 by DPP -- quad_perm [1,0,3,2] and [2,3,0,1], then row_half_mirror and row_mirror: once the lanes of a
+// group of 4 (8) hold the same bits, the mirrored lane holds those of the group l ^ 4 (l ^ 8) lies in -- and with l ^ 16,
+// ^ 32 by shuffles.  Both operands of every level are the same two values in either order, so with a commutative op every
+// lane ends with the same bits.
+template <class Op>
+__device__ __forceinline__ float wave_tree(float v, Op op) {
+    v = op(v, row_dpp<0xB1>(v));
+    v = op(v, row_dpp<0x4E>(v));
+    v = op(v, row_dpp<0x141>(v));
+    v = op(v, row_dpp<0x140>(v));
+    v = op(v, __shfl_xor(v, 16, 64));
+    return op(v, __shfl_xor(v, 32, 64));
+}
+
 // GLSL clamp(x, lo, hi) = min(max(x, lo), hi) with the comparison forms the oracle uses.
 __device__ __forceinline__ float clampf(float x, float lo, float hi) {
     float t = x > lo ? x : lo;
