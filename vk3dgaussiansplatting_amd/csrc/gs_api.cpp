@@ -276,14 +276,19 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
                   (c->cfg.count_launches == GS_COUNT_AUTO && note != 0u &&
                    note - 1u <= (c->sort_fed ? limit : limit - limit / 16u));
         }
-        if (fed != c->sort_fed) {
+        // the packed payload of the depth passes (gs_sort_words.h): the contractual sorter over 16-bit tile ids and 24-bit
+        // splat indices; sort_pass() checks what the run itself must offer.  Like the fed counts it is part of the capture.
+        const bool packed = c->cfg.sort_algorithm == GS_SORT_RADIX4 && frame_packs_payload(c->hi16, c->n, c->cfg.record_timings);
+        if (fed != c->sort_fed || packed != c->sort_packed) {
             if (c->run_graph[0].exec || c->chain_graph.exec) HIP_TRY(c, hipStreamSynchronize(st));   // the graph may still be executing (rare: the mode flips)
             drop_sort_graph(c);
             c->sort_fed = fed;
+            c->sort_packed = packed;
         }
+        fp.packed = packed ? 1u : 0u;
         // the bucket sorter runs the tile-word passes alone and carries the depth words through them
         c->runs[0] = {.capacity = c->capacity, .first_bit = bucket ? 32u : 0u, .num_sort_bits = c->band_sort_bits,
-                      .drop_depth_payload = !bucket, .hi16 = c->hi16, .share = tile_share, .fed = fed,
+                      .drop_depth_payload = !bucket, .hi16 = c->hi16, .packed = packed, .share = tile_share, .fed = fed,
                       .scatter_events = pass_events};
         c->num_runs = 1;
     }
@@ -362,7 +367,7 @@ int finish_frame(gs_ctx* c) {
                 const SortPass p = sort_pass(run, c->sort.digit_bits, k);
                 const int which = p.lo_in == 0 && p.lo_out == 0 ? 1 : 0;
                 sum_ms[which] += ms;
-                sum_bytes[which] += (float)(p.lo_in + p.lo_out) + 2.0f * (run.hi16 ? 2.0f : 4.0f) + 8.0f;   // depth + tile + id, r + w
+                sum_bytes[which] += (float)sort_pass_bytes(p, run.hi16);   // depth + tile + id (or the packed payload), r + w
                 ++n[which];
             }
         }

@@ -165,6 +165,7 @@ struct gs_ctx {
     uint32_t* elems_note = nullptr;   // pinned host word k_scan_blocks writes (element count + 1 of the latest list; 0: none
                                       // since the rows were set) -- what GS_COUNT_AUTO goes by
     bool sort_fed = false;        // the captured radix passes are the fed kind (k_scatter<.., FED>)
+    bool sort_packed = false;     // ... and carry the packed payload through the depth passes (SortRun::packed)
 
     gs_timings timings{};
     gs_host_timings host{};           // RECORD_CPU_TIMES (Renderer.cpp:299-456)

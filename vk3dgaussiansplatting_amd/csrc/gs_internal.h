@@ -77,6 +77,8 @@ struct FrameParams {
     uint32_t parity;      // InitSortList launches alternate between the two helper counters of SplatScratch
     uint32_t splat_first; // GS_SORT_RADIX4_SPLAT_FIRST: k_project also counts the emitting splats per block and leaves the
                           // helper records of k_emit to k_gather_sorted
+    uint32_t packed;      // k_emit writes the packed payload (SortRun::packed, gs_sort_words.h): pk32 into the id plane, pk8
+                          // into a byte plane in the storage of the tile words
 };
 
 // Device-side dispatch record: the role of RadixIndirectDispatch (ShaderStructs.h:45-57) +
@@ -185,6 +187,8 @@ struct SortRun {
     const SortParams* params = nullptr;   // dispatch record of this list (null: SortBuffers::params)
     bool drop_depth_payload = false;   // frame path: a pass carries only the depth bytes that later passes still read
     bool hi16 = false;                 // frame path: the hi arrays hold 16-bit tile ids (at most 65535 owned tiles)
+    bool packed = false;               // frame path, 4-bit digits, hi16, first_bit == 0, at least 32 sort bits, at most 2^24
+                                       // splats: through the depth passes the payload travels as pk32 + pk8 (gs_sort_words.h)
     float share = 1.0f;                // the context's share of the tiles: below one half the grids shrink with it
     bool fed = false;                  // 4-bit digits only -- one Count launch for the whole run, every Scatter feeds the next
                                        // pass's counts (k_scatter<.., FED>); same output, meant for at most kFedMaxGroups groups
@@ -200,8 +204,24 @@ struct SortPass {
                              // half of the depth word once the lower half is consumed (gs_sort_words.h)
     uint32_t word_shift;     // of the digit within the word as stored (= word_shift_of, gs_sort_words.h)
     int lo_in, lo_out;       // bytes of the depth word read / written per element (LO_IN / LO_OUT of gs_sort_words.h)
+    int pk_in, pk_out;       // form of the payload read / written (kPk*; PK_IN / PK_OUT of gs_sort_words.h)
     bool last;
 };
+// The payload of an element: kPkNone = tile word + 32-bit splat index; else pk32 = tile16 << 16 | (id & 0xFFFF) in the id
+// plane and pk8 = id >> 16 either in a byte plane (kPkPlane) or in the lowest byte of the stored depth word, once a
+// pass has consumed that byte (kPkWord).
+constexpr int kPkNone = 0, kPkPlane = 1, kPkWord = 2;
+#ifndef GS_SORT_PACKED_PAYLOAD
+#define GS_SORT_PACKED_PAYLOAD 1    /* tuning: 0 = a frame never packs the payload of its depth passes (the layouts before) */
+#endif
+constexpr uint32_t kPackedMaxSplats = 1u << 24;   // pk32 + pk8 hold a 24-bit splat index
+// SortRun::packed of a frame of the contractual sorter (enqueue_frame): 16-bit tile ids, splat indices below 2^24.  A
+// frame with per-pass timers (record_timings >= 2: nothing captured, an event pair around every Scatter launch) sorts in
+// the unpacked layouts: its scatter_bytes_per_elem and scatter_ms_avg are the figures of the word layouts alone, which
+// the recorded per-pass profiles and tests/test_parity_gpu.py (17.5 bytes for this sorter) are stated in.
+inline bool frame_packs_payload(bool hi16, uint32_t num_gaussians, uint32_t record_timings) {
+    return GS_SORT_PACKED_PAYLOAD != 0 && hi16 && num_gaussians <= kPackedMaxSplats && record_timings < 2u;
+}
 inline uint32_t sort_pass_count(const SortRun& r, uint32_t digit_bits) {
     return r.num_sort_bits > r.first_bit ? (r.num_sort_bits - r.first_bit + digit_bits - 1u) / digit_bits : 0u;
 }
@@ -220,10 +240,33 @@ inline SortPass sort_pass(const SortRun& r, uint32_t digit_bits, uint32_t k) {
             p.lo_out = p.shift + digit_bits >= 32u ? 0 : (p.shift + digit_bits >= 16u ? 2 : 4);
         }
     }
+    p.pk_in = kPkNone; p.pk_out = kPkNone;
+    if (r.packed && r.drop_depth_payload && r.hi16 && r.first_bit == 0u && r.num_sort_bits >= 32u && digit_bits == 4u &&
+        !p.tile_word) {
+        // pk8 rides in byte 0 of the depth word as stored once the passes before have consumed that byte: key bits
+        // 0-7 of a 32-bit word, 16-23 of the upper half; the last depth pass unpacks.  A fed run (short lists, bound by
+        // latency) keeps the unpacked element where the byte plane would lie beside a 16-bit depth word, out of passes 3
+        // and 4: those two launches measured 1.1 - 1.8 us slower with it at config A (profiles/packed_words_cost.txt)
+        const bool fed = r.fed;
+        auto form = [fed](uint32_t first_live_bit) {
+            if (first_live_bit >= 32u) return kPkNone;
+            if ((first_live_bit & 15u) >= 8u) return kPkWord;
+            return fed && first_live_bit >= 16u ? kPkNone : kPkPlane;
+        };
+        p.pk_in = form(p.shift);
+        p.pk_out = form(p.shift + digit_bits);
+    }
     const bool lo16 = !p.tile_word && p.lo_in == 2;
     p.word16 = (p.tile_word && r.hi16) || lo16;
     p.word_shift = lo16 ? p.shift - 16u : p.shift & 31u;
     return p;
+}
+// Bytes of an element on one side of a Scatter launch: `lo` depth bytes + the payload in form `pk`; of pass p: read + written
+inline uint32_t sort_elem_bytes(int lo, int pk, bool hi16) {
+    return (uint32_t)lo + (pk == kPkNone ? (hi16 ? 2u : 4u) + 4u : (pk == kPkPlane ? 1u + 4u : 4u));
+}
+inline uint32_t sort_pass_bytes(const SortPass& p, bool hi16) {
+    return sort_elem_bytes(p.lo_in, p.pk_in, hi16) + sort_elem_bytes(p.lo_out, p.pk_out, hi16);
 }
 
 // ---- launchers (each enqueues on `stream`, no host sync) ------------------------------------

@@ -737,10 +737,19 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
                 const uint32_t tile_key = (y0 + ry) * fp.grid_w + (min_x + (uint32_t)rx);
                 const uint64_t out = (uint64_t)base + j;
                 if (out < fp.capacity) {                                  // :143
-                    if (fp.hi16) reinterpret_cast<uint16_t*>(out_hi)[out] = (uint16_t)tile_key;
-                    else out_hi[out] = tile_key;
-                    if constexpr (SORTED) out_id[out] = s_depth[s];
-                    else { out_lo[out] = s_depth[s]; out_id[out] = g0 + s; }
+                    if (!SORTED && fp.packed) {
+                        // the packed payload of the depth passes (gs_sort_words.h): pk32, and pk8 into the byte plane
+                        // that uses the storage of the tile words
+                        const uint32_t id = g0 + s;
+                        out_lo[out] = s_depth[s];
+                        out_id[out] = (tile_key << 16) | (id & 0xFFFFu);
+                        reinterpret_cast<uint8_t*>(out_hi)[out] = (uint8_t)(id >> 16);
+                    } else {
+                        if (fp.hi16) reinterpret_cast<uint16_t*>(out_hi)[out] = (uint16_t)tile_key;
+                        else out_hi[out] = tile_key;
+                        if constexpr (SORTED) out_id[out] = s_depth[s];
+                        else { out_lo[out] = s_depth[s]; out_id[out] = g0 + s; }
+                    }
                 }
             }
         }

@@ -232,17 +232,19 @@ static_assert((1u << kSortTileLog2) == (uint32_t)kSortTile, "destination group o
 // clears its own row of (p + 2) % 3; pass 0's rows come from k_count (one launch per sort instead of one per pass).
 // In this mode the kernel's `table` argument is the row set read, `seg_sum` the set added into (null in the last
 // pass) and `coarse` the set cleared.
-template <int LO_IN, int LO_OUT, bool HI16, bool FULL, bool FED>
+// PK_IN, PK_OUT: the form of the payload (gs_sort_words.h).  A packed pass is a depth pass: its digit never lies in `hi`,
+// which carries pk8 of a kPkPlane element instead (loaded from the byte plane in the storage of in_hi).
+template <int LO_IN, int LO_OUT, bool HI16, bool FULL, bool FED, int PK_IN, int PK_OUT>
 __device__ __forceinline__ void scatter_group(
     uint32_t e, uint32_t G, uint32_t K, uint32_t grp, const uint32_t* __restrict__ in_lo,
     const uint32_t* __restrict__ in_hi, const uint32_t* __restrict__ in_id,
     uint32_t* __restrict__ out_lo, uint32_t* __restrict__ out_hi, uint32_t* __restrict__ out_id,
     const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_sum, const uint32_t* __restrict__ coarse,
-    uint32_t shift, uint2* s_slot, third_word<HI16>* s_third,
+    uint32_t shift, uint2* s_slot, third_word<HI16, PK_IN>* s_third,
     uint32_t* s_wcnt, uint32_t* s_pre, uint32_t* s_next, uint32_t* s_first) {
     constexpr int R = kSortKeysPerThread;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool use_hi = shift >= 32u;
+    const bool use_hi = PK_IN == kPkNone && shift >= 32u;
     const uint32_t sh = word_shift_of<LO_IN>(shift);
     const uint32_t tile_base = grp * kSortTile;
     const uint32_t base = tile_base + (uint32_t)wave * (R * 64) + lane;
@@ -285,11 +287,14 @@ __device__ __forceinline__ void scatter_group(
     {
         const uint16_t* lo16 = reinterpret_cast<const uint16_t*>(in_lo) + base;
         const uint16_t* hi16 = reinterpret_cast<const uint16_t*>(in_hi) + base;
+        const uint8_t* hi8 = reinterpret_cast<const uint8_t*>(in_hi) + base;
         const uint32_t *lo32 = in_lo + base, *hi32 = in_hi + base, *id32 = in_id + base;
 #pragma unroll
         for (int r = 0; r < R; ++r) {   // coalesced: 64 consecutive elements per wave-instruction
             const bool ok = FULL || base + r * 64 < e;
-            if constexpr (HI16) hi[r] = ok ? (uint32_t)GS_KEY_LOAD(&hi16[r * 64]) : 0xFFFFu;
+            if constexpr (PK_IN == kPkPlane) hi[r] = ok ? (uint32_t)GS_KEY_LOAD(&hi8[r * 64]) : 0xFFu;
+            else if constexpr (PK_IN == kPkWord) hi[r] = 0u;
+            else if constexpr (HI16) hi[r] = ok ? (uint32_t)GS_KEY_LOAD(&hi16[r * 64]) : 0xFFFFu;
             else hi[r] = ok ? GS_KEY_LOAD(&hi32[r * 64]) : 0xFFFFFFFFu;
             if constexpr (LO_IN == 4) lo[r] = ok ? GS_KEY_LOAD(&lo32[r * 64]) : 0xFFFFFFFFu;
             else if constexpr (LO_IN == 2) lo[r] = ok ? (uint32_t)GS_KEY_LOAD(&lo16[r * 64]) : 0xFFFFu;
@@ -415,7 +420,7 @@ __device__ __forceinline__ void scatter_group(
     for (int r = 0; r < R; ++r) {
         const uint32_t dg = digit_of(use_hi ? hi[r] : lo[r], sh);
         const uint32_t p = (uint32_t)__shfl((int)wbase, (int)dg, 64) + rank[r];
-        if (FULL || base + r * 64 < e) stage_elem<LO_IN, HI16>(s_slot, s_third, p, id[r], lo[r], hi[r]);
+        if (FULL || base + r * 64 < e) stage_elem<LO_IN, HI16, PK_IN>(s_slot, s_third, p, id[r], lo[r], hi[r]);
     }
     __syncthreads();
 
@@ -425,10 +430,10 @@ __device__ __forceinline__ void scatter_group(
     for (int r = 0; r < R; ++r) {
         const uint32_t p = (uint32_t)r * kSortThreads + tid;
         uint32_t l, h;
-        const uint32_t id_p = unstage_elem<LO_IN, HI16>(s_slot, s_third, p, l, h);
+        const uint32_t id_p = unstage_elem<LO_IN, HI16, PK_IN>(s_slot, s_third, p, l, h);
         const uint32_t d = digit_of(use_hi ? h : l, sh);
         const uint32_t o = (uint32_t)__shfl((int)gofs, (int)d, 64) + p;
-        if (FULL || p < valid) store_elem<LO_IN, LO_OUT, HI16>(out_lo, out_hi, out_id, o, id_p, l, h);
+        if (FULL || p < valid) store_elem<LO_IN, LO_OUT, HI16, PK_IN, PK_OUT>(out_lo, out_hi, out_id, o, id_p, l, h);
         if constexpr (FED) {
             if (seg_sum) {   // not the last pass: the key's NEXT digit, counted under (run, destination group)
                 // Lanes hold consecutive sorted positions, and in the depth passes the elements of one splat lie side by side
@@ -436,7 +441,8 @@ __device__ __forceinline__ void scatter_group(
                 // equal neighbours are added once: a lane whose counter differs from its left neighbour's (inside its row of
                 // 16 lanes) heads a run and adds the run's length -- the distance to the next head in the ballot.
                 const uint32_t ns = shift + (uint32_t)kRadixBits;
-                const uint32_t nd = ns >= 32u ? digit_of(h, ns - 32u) : digit_of(l, LO_IN == 2 ? ns - 16u : ns);
+                const uint32_t tile = PK_IN != kPkNone ? id_p >> 16 : h;                          // packed: the upper half of pk32
+                const uint32_t nd = ns >= 32u ? digit_of(tile, ns - 32u) : digit_of(l, LO_IN == 2 ? ns - 16u : ns);
                 const uint32_t j = (o >> kSortTileLog2) - (s_first[d] >> kSortTileLog2);          // 0 or 1 for a stored element
                 const bool stored = FULL || p < valid;
                 const uint32_t ctr = stored ? (((d * 2u + j) << kRadixBits) | nd) : 0xFFFFFFFFu;
@@ -469,7 +475,7 @@ __device__ __forceinline__ void scatter_group(
 
 // (the fed kind keeps a batch of count rows in registers beside the keys: four workgroups per CU, 128 VGPRs -- its lists
 // are short, a CU never holds more than four of its workgroups anyway)
-template <int LO_IN, int LO_OUT, bool HI16, bool FED>
+template <int LO_IN, int LO_OUT, bool HI16, bool FED, int PK_IN = kPkNone, int PK_OUT = kPkNone>
 __global__ __launch_bounds__(kSortThreads, FED ? 4 : ((LO_IN == 4 || (LO_IN == 2 && !HI16)) ? GS_SCATTER_MINWAVES_KEY : GS_SCATTER_MINWAVES_SMALL))
 void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict__ in_lo,
                const uint32_t* __restrict__ in_hi, const uint32_t* __restrict__ in_id,
@@ -477,7 +483,7 @@ void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict
                const uint32_t* __restrict__ table, const uint32_t* __restrict__ seg_sum,
                const uint32_t* __restrict__ coarse, uint32_t shift) {
     __shared__ uint2 s_slot[kSortTile];
-    __shared__ third_word<HI16> s_third[has_third(LO_IN, HI16) ? kSortTile : 1];
+    __shared__ third_word<HI16, PK_IN> s_third[has_third(LO_IN, HI16, PK_IN) ? kSortTile : 1];
     __shared__ __attribute__((aligned(16))) uint32_t s_wcnt[kBins * kSortWaves];
     __shared__ __attribute__((aligned(16))) uint32_t s_pre[FED ? 2 * kBins * kSortWaves : 2 * kBins];
     __shared__ uint32_t s_next[FED ? 2 * kBins * kBins : 1];      // [run][destination group 0 / 1][next digit]
@@ -491,10 +497,10 @@ void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict
         if (again) __syncthreads();   // LDS is reused
         again = true;
         if (grp * kSortTile + kSortTile <= e)
-            scatter_group<LO_IN, LO_OUT, HI16, true, FED>(e, G, K, grp, in_lo, in_hi, in_id, out_lo, out_hi, out_id, table,
+            scatter_group<LO_IN, LO_OUT, HI16, true, FED, PK_IN, PK_OUT>(e, G, K, grp, in_lo, in_hi, in_id, out_lo, out_hi, out_id, table,
                                                           seg_sum, coarse, shift, s_slot, s_third, s_wcnt, s_pre, s_next, s_first);
         else
-            scatter_group<LO_IN, LO_OUT, HI16, false, FED>(e, G, K, grp, in_lo, in_hi, in_id, out_lo, out_hi, out_id, table,
+            scatter_group<LO_IN, LO_OUT, HI16, false, FED, PK_IN, PK_OUT>(e, G, K, grp, in_lo, in_hi, in_id, out_lo, out_hi, out_id, table,
                                                            seg_sum, coarse, shift, s_slot, s_third, s_wcnt, s_pre, s_next, s_first);
     }
 }
@@ -531,9 +537,9 @@ int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t str
             });
         }
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
-        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16) {
+        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16, auto pk_in, auto pk_out) {
             with_bool(fed, [&](auto f) {
-                hipLaunchKernelGGL((k_scatter<lo_in.value, lo_out.value, h16.value, f.value>), dim3(max_groups),
+                hipLaunchKernelGGL((k_scatter<lo_in.value, lo_out.value, h16.value, f.value, pk_in.value, pk_out.value>), dim3(max_groups),
                                    dim3(kSortThreads), 0, stream, params, sb.lo[src], sb.hi[src], sb.id[src], sb.lo[dst],
                                    sb.hi[dst], sb.id[dst], fed ? rows_in : sb.table, fed ? rows_next : sb.seg_sum,
                                    fed ? rows_zero : coarse, p.shift);

@@ -335,7 +335,7 @@ int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t st
         }); }); });
         hipLaunchKernelGGL(k_scan8, dim3(kBins8), dim3(kSegments), 0, stream, sb.seg_sum, seg_base, totals);
         if (run.scatter_events) (void)hipEventRecord(run.scatter_events[2 * pass], stream);
-        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16) {
+        with_word_layout(p, hi16, [&](auto lo_in, auto lo_out, auto h16, auto, auto) {   // sort_pass() packs no 8-bit pass
             with_bool(small, [&](auto sm) {
                 hipLaunchKernelGGL((k_scatter8<lo_in.value, lo_out.value, h16.value, sm.value ? kSort8KeysSmall : kSort8KeysPerThread>),
                                    dim3(max_groups), dim3(kSort8Threads), 0, stream, params, sb.lo[src], sb.hi[src], sb.id[src],

@@ -13,6 +13,20 @@
 // sort_pass() (gs_internal.h) derives the pair of a pass; with_word_layout() below turns it into template arguments.
 // HI16: the tile words are 16-bit compact tile ids (at most 65535 owned tiles): 2 bytes less read and 2 less written
 // per element in every pass.
+// PK_IN / PK_OUT (SortRun::packed; kPk* of gs_internal.h): the depth passes never look at the payload, so with 16-bit
+// tile ids and at most 2^24 splats the 4-bit sorter of a frame carries it in 5 bytes instead of 6:
+//   pk32 = tile16 << 16 | (id & 0xFFFF) in the id plane, pk8 = id >> 16 in a byte plane that uses the storage of the
+//   tile words (kPkPlane) or, as soon as a pass has consumed that byte, in the lowest byte of the stored depth word
+//   (kPkWord).  Count reads the same word at the same shift either way.  Bytes per element read -> written:
+//     k_emit -> 9 | pass 0  9 -> 9 <4, 4, plane, plane> | pass 1  9 -> 8 <4, 4, plane, word> | pass 2  8 -> 8 <4, 4, word, word>
+//     pass 3  8 -> 7 <4, 2, word, plane> | pass 4  7 -> 7 <2, 2, plane, plane> | pass 5  7 -> 6 <2, 2, plane, word>
+//     pass 6  6 -> 6 <2, 2, word, word>  | pass 7  6 -> 6 <2, 0, word, none>: tile u16 + id u32, what every later stage reads
+//   117 bytes per element over the eight depth passes where the unpacked layouts move 140.  A fed run (SortRun::fed:
+//   short lists, every launch bound by latency) does not use the byte plane beside a 16-bit depth word: pass 3 unpacks
+//   <4, 2, word, none>, pass 4 runs unpacked <2, 2, none, none>, pass 5 packs again <2, 2, none, word> (121 bytes).
+//   Everything else -- more than 65535 owned tiles, more than 2^24 splats, a frame with per-pass timers (record_timings
+//   >= 2, frame_packs_payload()), the stand-alone sorter, the other sorters -- stays unpacked (sort_pass() decides; a
+//   GS_SORT_PACKED_PAYLOAD=0 build never packs).
 // FULL: the group holds all its keys (every group but the last): no per-element bounds logic.
 #pragma once
 
@@ -79,38 +93,72 @@ __device__ __forceinline__ uint32_t word_shift_of(uint32_t shift) {
 // LDS staging: one 8-byte slot {id, word} per element.  Nothing travels beside it when the element is id + one 32-bit
 // word (tile-word passes; depth passes whose depth and tile words are both 16 bits wide), else the tile word does,
 // in s_third.
-template <bool HI16>
-using third_word = typename std::conditional<HI16, uint16_t, uint32_t>::type;
-constexpr bool has_third(int lo_in, bool hi16) { return lo_in == 4 || (lo_in == 2 && !hi16); }
-
-template <int LO_IN, bool HI16>
-__device__ __forceinline__ void stage_elem(uint2* s_slot, third_word<HI16>* s_third, uint32_t p, uint32_t id,
-                                           uint32_t lo, uint32_t hi) {
-    if constexpr (LO_IN == 0) s_slot[p] = make_uint2(id, hi);
-    else if constexpr (!has_third(LO_IN, HI16)) s_slot[p] = make_uint2(id, lo | (hi << 16));
-    else { s_slot[p] = make_uint2(id, lo); s_third[p] = (third_word<HI16>)hi; }
+// Packed payload (PK_IN != kPkNone, HI16 only; the header comment): the slot is {pk32, depth word as stored}; pk8 is
+// part of that word (kPkWord), sits beside a 16-bit depth word in the slot (kPkPlane, LO_IN == 2) or travels in
+// s_third, one byte wide (kPkPlane, LO_IN == 4).  In registers `hi` carries pk8 of a kPkPlane element.
+template <bool HI16, int PK_IN = kPkNone>
+using third_word = typename std::conditional<PK_IN != kPkNone, uint8_t,
+                                             typename std::conditional<HI16, uint16_t, uint32_t>::type>::type;
+constexpr bool has_third(int lo_in, bool hi16, int pk_in = kPkNone) {
+    return pk_in != kPkNone ? (pk_in == kPkPlane && lo_in == 4) : (lo_in == 4 || (lo_in == 2 && !hi16));
 }
 
-// -> the id; l, h = the depth and tile words as loaded
-template <int LO_IN, bool HI16>
-__device__ __forceinline__ uint32_t unstage_elem(const uint2* s_slot, const third_word<HI16>* s_third, uint32_t p,
+template <int LO_IN, bool HI16, int PK_IN = kPkNone>
+__device__ __forceinline__ void stage_elem(uint2* s_slot, third_word<HI16, PK_IN>* s_third, uint32_t p, uint32_t id,
+                                           uint32_t lo, uint32_t hi) {
+    if constexpr (PK_IN == kPkWord) s_slot[p] = make_uint2(id, lo);
+    else if constexpr (LO_IN == 0) s_slot[p] = make_uint2(id, hi);
+    else if constexpr (!has_third(LO_IN, HI16, PK_IN)) s_slot[p] = make_uint2(id, lo | (hi << 16));
+    else { s_slot[p] = make_uint2(id, lo); s_third[p] = (third_word<HI16, PK_IN>)hi; }
+}
+
+// -> the id (packed: pk32); l, h = the depth and tile words as loaded (packed: h = pk8)
+template <int LO_IN, bool HI16, int PK_IN = kPkNone>
+__device__ __forceinline__ uint32_t unstage_elem(const uint2* s_slot, const third_word<HI16, PK_IN>* s_third, uint32_t p,
                                                  uint32_t& l, uint32_t& h) {
     const uint2 sl = s_slot[p];
-    if constexpr (LO_IN == 0) { l = 0u; h = sl.y; }
-    else if constexpr (!has_third(LO_IN, HI16)) { l = sl.y & 0xFFFFu; h = sl.y >> 16; }
+    if constexpr (PK_IN == kPkWord) { l = sl.y; h = sl.y & 0xFFu; }
+    else if constexpr (LO_IN == 0) { l = 0u; h = sl.y; }
+    else if constexpr (!has_third(LO_IN, HI16, PK_IN)) { l = sl.y & 0xFFFFu; h = sl.y >> 16; }
     else { l = sl.y; h = s_third[p]; }
     return sl.x;
 }
 
-// Element to index o of the destination; <4, 2> keeps the upper half of the depth word.
-template <int LO_IN, int LO_OUT, bool HI16>
+// Element to index o of the destination; <4, 2> keeps the upper half of the depth word.  Packed: pk8 goes to the byte
+// plane (the storage of out_hi) or over the consumed low byte of the depth word written.  A pass may unpack (PK_OUT ==
+// kPkNone: the 16-bit tile word and the 32-bit splat index, as the last depth pass writes them) or pack what it read
+// unpacked (PK_IN == kPkNone; a fed run does both, sort_pass()).
+template <int LO_IN, int LO_OUT, bool HI16, int PK_IN = kPkNone, int PK_OUT = kPkNone>
 __device__ __forceinline__ void store_elem(uint32_t* out_lo, uint32_t* out_hi, uint32_t* out_id, uint32_t o,
                                            uint32_t id, uint32_t l, uint32_t h) {
-    if constexpr (LO_OUT == 4) out_lo[o] = l;
-    else if constexpr (LO_OUT == 2) reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)(LO_IN == 4 ? l >> 16 : l);
-    if constexpr (HI16) reinterpret_cast<uint16_t*>(out_hi)[o] = (uint16_t)h;
-    else out_hi[o] = h;
-    out_id[o] = id;
+    if constexpr (PK_IN != kPkNone || PK_OUT != kPkNone) {
+        static_assert(HI16, "the packed payload holds a 16-bit tile id");
+        const uint32_t w = LO_IN == 4 && LO_OUT == 2 ? l >> 16 : l;          // the depth word in its width of the output
+        const uint32_t pk32 = PK_IN != kPkNone ? id : (h << 16) | (id & 0xFFFFu);
+        const uint32_t pk8 = PK_IN != kPkNone ? h : (id >> 16) & 0xFFu;
+        if constexpr (PK_OUT == kPkWord) {
+            static_assert(LO_OUT == LO_IN && LO_OUT != 0, "pk8 replaces the low byte of a word that keeps its width");
+            if constexpr (LO_OUT == 4) out_lo[o] = (w & 0xFFFFFF00u) | pk8;
+            else reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)((w & 0xFF00u) | pk8);
+            out_id[o] = pk32;
+        } else if constexpr (PK_OUT == kPkPlane) {
+            if constexpr (LO_OUT == 4) out_lo[o] = w;
+            else reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)w;
+            reinterpret_cast<uint8_t*>(out_hi)[o] = (uint8_t)pk8;
+            out_id[o] = pk32;
+        } else {
+            if constexpr (LO_OUT == 4) out_lo[o] = w;
+            else if constexpr (LO_OUT == 2) reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)w;
+            reinterpret_cast<uint16_t*>(out_hi)[o] = (uint16_t)(pk32 >> 16);
+            out_id[o] = (pk8 << 16) | (pk32 & 0xFFFFu);
+        }
+    } else {
+        if constexpr (LO_OUT == 4) out_lo[o] = l;
+        else if constexpr (LO_OUT == 2) reinterpret_cast<uint16_t*>(out_lo)[o] = (uint16_t)(LO_IN == 4 ? l >> 16 : l);
+        if constexpr (HI16) reinterpret_cast<uint16_t*>(out_hi)[o] = (uint16_t)h;
+        else out_hi[o] = h;
+        out_id[o] = id;
+    }
 }
 
 // The walk of a Scatter workgroup over the groups: virtual blocks vb = blockIdx.x, + gridDim.x, ... below 8 per_xcd,
@@ -141,12 +189,32 @@ inline void with_bool(bool b, F&& f) {
     if (b) f(std::true_type{}); else f(std::false_type{});
 }
 
-// f(LO_IN, LO_OUT, HI16) as std::integral_constants, for the word layout of pass p
+// f(LO_IN, LO_OUT, HI16, PK_IN, PK_OUT) as std::integral_constants, for the word layout of pass p
 template <class F>
 inline void with_word_layout(const SortPass& p, bool hi16, F&& f) {
-    auto pair = [&](auto lo_in, auto lo_out) { with_bool(hi16, [&](auto h16) { f(lo_in, lo_out, h16); }); };
     using I0 = std::integral_constant<int, 0>; using I2 = std::integral_constant<int, 2>;
     using I4 = std::integral_constant<int, 4>;
+    using None = std::integral_constant<int, kPkNone>; using Plane = std::integral_constant<int, kPkPlane>;
+    using Word = std::integral_constant<int, kPkWord>;
+    if (p.pk_in != kPkNone || p.pk_out != kPkNone) {   // sort_pass() packs under hi16 alone, in these ten combinations
+        const std::true_type h16{};
+        const int in = p.pk_in, out = p.pk_out;
+        if (p.lo_in == 4 && p.lo_out == 4) {
+            if (in == kPkPlane && out == kPkPlane) f(I4{}, I4{}, h16, Plane{}, Plane{});
+            else if (in == kPkPlane) f(I4{}, I4{}, h16, Plane{}, Word{});
+            else f(I4{}, I4{}, h16, Word{}, Word{});
+        } else if (p.lo_in == 4) {
+            if (out == kPkPlane) f(I4{}, I2{}, h16, Word{}, Plane{});
+            else f(I4{}, I2{}, h16, Word{}, None{});              // a fed run unpacks here ...
+        } else if (p.lo_out == 2) {
+            if (in == kPkPlane && out == kPkPlane) f(I2{}, I2{}, h16, Plane{}, Plane{});
+            else if (in == kPkPlane) f(I2{}, I2{}, h16, Plane{}, Word{});
+            else if (in == kPkNone) f(I2{}, I2{}, h16, None{}, Word{});   // ... and packs again here
+            else f(I2{}, I2{}, h16, Word{}, Word{});
+        } else f(I2{}, I0{}, h16, Word{}, None{});
+        return;
+    }
+    auto pair = [&](auto lo_in, auto lo_out) { with_bool(hi16, [&](auto h16) { f(lo_in, lo_out, h16, None{}, None{}); }); };
     if (p.lo_in == 4 && p.lo_out == 4) pair(I4{}, I4{});
     else if (p.lo_in == 4 && p.lo_out == 2) pair(I4{}, I2{});
     else if (p.lo_in == 2 && p.lo_out == 2) pair(I2{}, I2{});
