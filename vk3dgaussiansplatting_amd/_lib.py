@@ -348,31 +348,49 @@ def sh_mode_of_degree(degree: int) -> int:
     return int(mode.value)
 
 
+def _default_params(who: str, struct, fill, overrides: dict):
+    """A parameter struct as `fill` (its gs_default_*_params) writes it, with keyword overrides by field name: an integer field takes
+    int(value), a float field float(value), an array of floats a sequence of its length or {index: value} for some of its
+    elements.  struct_size, or a name the struct does not have: TypeError."""
+    p = struct()
+    fill(C.byref(p))
+    kinds = {name: kind for name, kind in struct._fields_ if name != "struct_size"}
+    for name, value in overrides.items():
+        kind = kinds.get(name)
+        if kind is None:
+            raise TypeError(f"{who}: unknown parameter {name!r}")
+        if issubclass(kind, C.Array):
+            if not isinstance(value, dict) and len(value) != kind._length_:
+                raise ValueError(f"{name} needs {kind._length_} values or a dict of groups")
+            arr = getattr(p, name)
+            for g, x in (value.items() if isinstance(value, dict) else enumerate(value)):
+                arr[int(g)] = float(x)
+        else:
+            setattr(p, name, float(value) if kind is C.c_float else int(value))
+    return p
+
+
+def default_adam_params(space: str = "records", **overrides) -> GsAdamParams:
+    """gs_default_adam_params: step 1, beta1 0.9, beta2 0.999, eps 1e-15, the INRIA learning rates per GS_ADAM_* group
+    (acting on record-space values here) and the clamps scale >= 1e-7, opacity in [0, 1].  space="raw":
+    gs_default_adam_params_raw, the same without any clamp (for adamRowsRawDevice, where the rates act on log-scales and
+    logit-opacities).  overrides: beta1, beta2, eps, step as numbers; lr, lo, hi as a sequence of six or as {GS_ADAM_*
+    group: value} for some of them."""
+    if space not in ("records", "raw"):
+        raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
+    fill = lib().gs_default_adam_params_raw if space == "raw" else lib().gs_default_adam_params
+    return _default_params("default_adam_params", GsAdamParams, fill, overrides)
+
+
 def default_densify_params(**overrides) -> GsDensifyParams:
     """gs_default_densify_params: grad_threshold 2e-4, split_scale 0.01, prune_opacity 0.005, prune_scale and prune_radius
     +inf (none), split_shrink 1.6, seed 0.  overrides: any of those fields by name."""
-    p = GsDensifyParams()
-    lib().gs_default_densify_params(C.byref(p))
-    for name, value in overrides.items():
-        if name == "seed":
-            p.seed = int(value)
-        elif name != "struct_size" and any(name == f[0] for f in GsDensifyParams._fields_):
-            setattr(p, name, float(value))
-        else:
-            raise TypeError(f"default_densify_params: unknown parameter {name!r}")
-    return p
+    return _default_params("default_densify_params", GsDensifyParams, lib().gs_default_densify_params, overrides)
 
 
 def default_init_params(**overrides) -> GsInitParams:
     """gs_default_init_params: opacity 0.1, min_dist2 1e-7, max_scale +inf (none).  overrides: any of those fields by name."""
-    p = GsInitParams()
-    lib().gs_default_init_params(C.byref(p))
-    for name, value in overrides.items():
-        if name != "struct_size" and any(name == f[0] for f in GsInitParams._fields_):
-            setattr(p, name, float(value))
-        else:
-            raise TypeError(f"default_init_params: unknown parameter {name!r}")
-    return p
+    return _default_params("default_init_params", GsInitParams, lib().gs_default_init_params, overrides)
 
 
 def hip_runtime_path() -> str | None:

@@ -61,6 +61,43 @@ def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
     return r
 
 
+def _u32(n: int, dev, zero: bool = True) -> torch.Tensor:
+    """n of the library's uint32 (ids, counts, marks) in int32 storage: every value here stays below 2^31, and a host
+    copy is read with .view(np.uint32)."""
+    return (torch.zeros if zero else torch.empty)(n, dtype=torch.int32, device=dev)
+
+
+def _check_records(records: torch.Tensor, plain: bool = False):
+    """records must be float32 [N, 84] on the GPU; plain: also contiguous and outside autograd, as VisibleAdam updates them."""
+    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
+        raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
+    if plain:
+        if not records.is_cuda or not records.is_contiguous() or records.requires_grad:
+            raise ValueError("records must be a contiguous tensor on the GPU that does not require grad")
+    elif not records.is_cuda:
+        raise ValueError("records must be on the GPU")
+
+
+def _check_image(name: str, t: torch.Tensor, shape: tuple, apart: bool = False):
+    """t must be float32 of `shape` ([H, W, C]) on the GPU; apart: a wrong shape or dtype and a host tensor are worded apart."""
+    fits = t.dtype == torch.float32 and tuple(t.shape) == shape
+    if apart:
+        if not fits:
+            raise ValueError(f"{name} must be float32 {shape}, not {t.dtype} {tuple(t.shape)}")
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be on the GPU")
+    elif not fits or not t.is_cuda:
+        raise ValueError(f"{name} must be float32 {shape} on the GPU")
+
+
+def _check_camera_grad(g: torch.Tensor, dev, one_of_many: bool = False):
+    """g must be a contiguous float32 [35] tensor on dev: what gs_backward_camera_device fills."""
+    if g.dtype != torch.float32 or tuple(g.shape) != (_lib.CAMERA_GRAD_FLOATS,) or g.device != dev or not g.is_contiguous():
+        form = f"contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}]"
+        raise ValueError(f"camera_grads must hold {form} tensors on the records' device" if one_of_many else
+                         f"camera_grad must be a {form} tensor on the records' device")
+
+
 def _camera_array(x) -> np.ndarray:
     """A camera argument (numpy, a sequence, or a torch tensor on any device and of any float dtype) as the float32 host
     array the library takes."""
@@ -98,49 +135,42 @@ class _Frame(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_rgba, grad_depth=None):
         (records,) = ctx.saved_tensors
-        r = ctx.renderer
+        r, dev, size = ctx.renderer, records.device, (records.shape[0], FLOATS_PER_GAUSSIAN)
         if r.frameSerial != ctx.frame:              # another frame was drawn since: draw this one again
             _draw(r, records.detach(), *ctx.args)
-        g = (grad_rgba if grad_rgba is not None else torch.zeros(r.height, r.width, 4, device=records.device))
-        g = g.to(device=records.device, dtype=torch.float32).contiguous()
+        g = (grad_rgba if grad_rgba is not None else torch.zeros(r.height, r.width, 4, device=dev))
+        g = g.to(device=dev, dtype=torch.float32).contiguous()
         d = None
         if ctx.args[4] and grad_depth is not None:
-            d = grad_depth.to(device=records.device, dtype=torch.float32).contiguous()
+            d = grad_depth.to(device=dev, dtype=torch.float32).contiguous()
         # one gs_backward_camera_device call behind the record backward, only when a camera tensor asks for its gradient
-        want_camera = any(ctx.needs_input_grad[2:5])
-        cam = torch.zeros(_lib.CAMERA_GRAD_FLOATS, dtype=torch.float32, device=records.device) if want_camera else None
-
-        def camera_grads():
-            if cam is None:
-                return None, None, None
-            blocks = (cam[0:16], cam[16:32], cam[32:35])
-            return tuple(b.reshape(c[0]).to(device=c[2], dtype=c[1]) if c is not None and need else None
-                         for b, c, need in zip(blocks, ctx.cameras, ctx.needs_input_grad[2:5]))
+        cam = torch.zeros(_lib.CAMERA_GRAD_FLOATS, dtype=torch.float32, device=dev) if any(ctx.needs_input_grad[2:5]) else None
+        # the row form is all that differs: every row of the cloud, or the rows of the splats the frame rasterised
         if ctx.sparse_grad:
             count = r.visibleCount()
-            # int32 storage for the library's uint32 ids (N < 2^31)
-            ids = torch.empty(count, dtype=torch.int32, device=records.device)
-            rows = torch.empty(count, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
-            seen = torch.empty(1, dtype=torch.int32, device=records.device)
-            torch.cuda.current_stream(records.device).synchronize()
-            r.backwardVisibleDevice(g.data_ptr(), None if d is None else d.data_ptr(), ids.data_ptr() if count else None,
-                                    rows.data_ptr() if count else None, count, seen.data_ptr())
-            if want_camera and count:             # a frame that rasterised nothing has no rows: the zeros stand
-                r.backwardCameraDevice(cam.data_ptr())
-            r.synchronize()
-            if ctx.sparse_grad == "scatter":      # a non-leaf input
-                out = torch.zeros(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
-                out.index_copy_(0, ids.long(), rows)
-            else:
-                out = torch.sparse_coo_tensor(ids.long()[None], rows, size=(records.shape[0], FLOATS_PER_GAUSSIAN))
-            return (out, None) + camera_grads() + (None, None, None)
-        out = torch.empty(records.shape[0], FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=records.device)
-        torch.cuda.current_stream(records.device).synchronize()
-        r.backwardDevice(g.data_ptr(), None if d is None else d.data_ptr(), out.data_ptr())
-        if want_camera:
+            ids, seen = _u32(count, dev, zero=False), _u32(1, dev, zero=False)
+            rows = torch.empty(count, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+            rows_form = (r.backwardVisibleDevice, ids.data_ptr() if count else None, rows.data_ptr() if count else None, count,
+                         seen.data_ptr())
+        else:
+            count = records.shape[0]
+            out = torch.empty(size, dtype=torch.float32, device=dev)
+            rows_form = (r.backwardDevice, out.data_ptr())
+        torch.cuda.current_stream(dev).synchronize()
+        rows_form[0](g.data_ptr(), None if d is None else d.data_ptr(), *rows_form[1:])
+        if cam is not None and count:               # a frame that rasterised nothing has no rows: the zeros stand
             r.backwardCameraDevice(cam.data_ptr())
         r.synchronize()
-        return (out, None) + camera_grads() + (None, None, None)
+        if ctx.sparse_grad == "scatter":            # a non-leaf input
+            out = torch.zeros(size, dtype=torch.float32, device=dev)
+            out.index_copy_(0, ids.long(), rows)
+        elif ctx.sparse_grad:
+            out = torch.sparse_coo_tensor(ids.long()[None], rows, size=size)
+        camera = (None, None, None)
+        if cam is not None:
+            camera = tuple(b.reshape(c[0]).to(device=c[2], dtype=c[1]) if c is not None and need else None
+                           for b, c, need in zip((cam[0:16], cam[16:32], cam[32:35]), ctx.cameras, ctx.needs_input_grad[2:5]))
+        return (out, None) + camera + (None, None, None)
 
 
 def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: bool = False, *, renderer: Renderer,
@@ -153,10 +183,7 @@ def render(records: torch.Tensor, view, proj, cam_pos, sh_mode: int = 0, depth: 
     numpy cameras behave as before.  sparse_grad=True: records (meant to be a leaf) receives a sparse COO
     gradient over the splats the frame rasterised, with the values of the dense one; a non-leaf records receives those
     rows in a dense tensor."""
-    if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
-        raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
-    if not records.is_cuda:
-        raise ValueError("records must be on the GPU")
+    _check_records(records)
     mode = ("sparse" if records.grad_fn is None else "scatter") if sparse_grad else None
     return _Frame.apply(records.contiguous(), renderer, view, proj, cam_pos, int(sh_mode), bool(depth), mode)
 
@@ -183,12 +210,8 @@ def photometric_loss(rgba: torch.Tensor, target: torch.Tensor, lambda_dssim: flo
     quantities, e.g. render()'s output) composited over bg (3 floats, None = black) against target (float32 [H, W, 3]), as a
     0-dim tensor, differentiable w.r.t. rgba.  H and W are the renderer's resolution; the renderer must hold a scene (any
     render() gives it one).  The definition is that of gs_photometric_loss in include/gsplat.h."""
-    shape = (renderer.height, renderer.width)
-    for name, t, ch in (("rgba", rgba, 4), ("target", target, 3)):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape + (ch,):
-            raise ValueError(f"{name} must be float32 {shape + (ch,)}, not {t.dtype} {tuple(t.shape)}")
-        if not t.is_cuda:
-            raise ValueError(f"{name} must be on the GPU")
+    _check_image("rgba", rgba, (renderer.height, renderer.width, 4), apart=True)
+    _check_image("target", target, (renderer.height, renderer.width, 3), apart=True)
     return _Loss.apply(rgba.contiguous(), target.detach().contiguous(), renderer, float(lambda_dssim), bg)
 
 
@@ -209,7 +232,7 @@ def records_from_points(points: torch.Tensor, colors: torch.Tensor | None = None
     colors = None if colors is None else colors.contiguous()
     n, dev = points.shape[0], points.device
     records = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
-    order = torch.empty(n, dtype=torch.int32, device=dev)                           # int32 storage for the library's uint32
+    order = _u32(n, dev, zero=False)
     torch.cuda.current_stream(dev).synchronize()                # the library works on a stream of its own
     renderer.recordsFromPointsDevice(points.data_ptr(), None if colors is None else colors.data_ptr(), n, p, records.data_ptr(),
                                      order.data_ptr())
@@ -252,10 +275,7 @@ class VisibleAdam:
 
     def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, track_density: bool = False,
                  space: str = "records", **params):
-        if records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != FLOATS_PER_GAUSSIAN:
-            raise ValueError(f"records must be float32 [N, {FLOATS_PER_GAUSSIAN}], not {records.dtype} {tuple(records.shape)}")
-        if not records.is_cuda or not records.is_contiguous() or records.requires_grad:
-            raise ValueError("records must be a contiguous tensor on the GPU that does not require grad")
+        _check_records(records, plain=True)
         if space not in ("records", "raw"):
             raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
         self.records, self.renderer, self.space = records, renderer, space
@@ -289,14 +309,84 @@ class VisibleAdam:
 
     def _alloc_rows(self, dev):
         """What a step lists: ids and gradient rows (max_rows of them) and the count, all zero."""
-        self.ids = torch.zeros(self.max_rows, dtype=torch.int32, device=dev)        # int32 storage for the library's uint32
+        self.ids = _u32(self.max_rows, dev)
         self.rows = torch.zeros(self.max_rows, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
-        self.count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.count = _u32(1, dev)
 
     def _zero_stats(self, n: int, dev):
         self.grad_accum = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.seen = torch.zeros(n, dtype=torch.int32, device=dev)                   # int32 storage for the library's uint32
+        self.seen = _u32(n, dev)
         self.max_radius = torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def _alloc_batch(self, dev):
+        """What step_batch sums into: the accumulator (never initialised: a first touch is a store) and the zero marks."""
+        n = self.records.shape[0]
+        self.acc = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
+        self.mark = _u32(n, dev)
+
+    def _enqueue(self):
+        """`with self._enqueue():` -- self.stream is made to follow the caller's current stream (so a target or records
+        written there are seen) and is current inside the block: what the block allocates and enqueues belongs to it."""
+        self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
+        return torch.cuda.stream(self.stream)
+
+    def _upload_pending(self):
+        """The records as the context must see them before a frame: in full the first time and after reset_upload(),
+        afterwards the rows the previous step moved (gs_upload_rows_device reads the ids and count that step left)."""
+        r, n = self.renderer, self.records.shape[0]
+        if self._full_upload:
+            r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
+            r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
+            self._full_upload = False
+        else:
+            r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+
+    def _view(self, view, proj, cam_pos, sh_mode: int, target: torch.Tensor, numbers_ptr: int, lambda_dssim: float, bg,
+              camera_grad: torch.Tensor | None):
+        """One view's chain: the frame, gs_photometric_loss_device on the context's own RGBA32F buffer ({loss, L1, DSSIM}
+        to numbers_ptr, the image gradient to self.grad), gs_backward_visible_device into self.ids / rows / count, with
+        camera_grad gs_backward_camera_device, with track_density gs_densify_stats_device.  target and camera_grad may be
+        the caller's own stream's: they are kept alive until self.stream is past them."""
+        r = self.renderer
+        target.record_stream(self.stream)
+        r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
+        r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers_ptr, self.grad.data_ptr())
+        r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
+                                self.count.data_ptr())
+        if camera_grad is not None:
+            camera_grad.record_stream(self.stream)
+            r.backwardCameraDevice(camera_grad.data_ptr())
+        if self.track_density:
+            r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, self.records.shape[0],
+                                 self.grad_accum.data_ptr(), self.seen.data_ptr(), self.max_radius.data_ptr())
+
+    def _adam(self):
+        """t advanced once, then gs_adam_rows_device, or gs_adam_rows_raw_device in raw space, on self.ids / rows / count."""
+        r, n = self.renderer, self.records.shape[0]
+        self.t += 1
+        self.params.step = self.t
+        if self.space == "raw":
+            r.adamRowsRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n,
+                                self.ids.data_ptr(), self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+        else:
+            r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
+                             self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+
+    def _resized(self):
+        """After self.records / m / v (and raw) became tensors of another n, inside _enqueue: the density statistics start
+        again from zero, ids, rows and max_rows follow the new size (a max_rows given to the constructor stays), and so do
+        step_batch's buffers once they exist; then self.stream is waited for, and the next step uploads the whole cloud."""
+        dev = self.records.device
+        if self.track_density:
+            self._zero_stats(self.records.shape[0], dev)
+        if self._rows_follow_n:
+            self.max_rows = self.records.shape[0]
+        self._alloc_rows(dev)
+        if self.acc is not None:
+            self._alloc_batch(dev)
+        self.stream.synchronize()
+        # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
+        self._full_upload = True
 
     def densify(self, **params):
         """Clone, split and prune by the statistics gathered since the last call (gs_densify_device, params:
@@ -311,10 +401,9 @@ class VisibleAdam:
             raise RuntimeError("VisibleAdam(track_density=True) gathers the statistics densify() goes by")
         p = _lib.default_densify_params(**params)
         r, dev, n = self.renderer, self.records.device, self.records.shape[0]
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self.stream):
+        with self._enqueue():
             out = [torch.empty(2 * n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(3)]
-            counts = torch.zeros(4, dtype=torch.int32, device=dev)
+            counts = _u32(4, dev)
             r.densifyDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.grad_accum.data_ptr(),
                             self.seen.data_ptr(), self.max_radius.data_ptr(), p, out[0].data_ptr(), out[1].data_ptr(),
                             out[2].data_ptr(), 2 * n, counts.data_ptr())
@@ -325,15 +414,7 @@ class VisibleAdam:
             if self.space == "raw":
                 self.raw = torch.zeros_like(self.records)
                 self._raw_from_records()
-            self._zero_stats(n_out, dev)
-            if self._rows_follow_n:
-                self.max_rows = n_out
-            self._alloc_rows(dev)
-            if self.acc is not None:
-                self._alloc_batch(dev)
-        self.stream.synchronize()
-        # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
-        self._full_upload = True
+            self._resized()
         return n_out, cloned, split, pruned
 
     def prune_by_contribution(self, cameras, threshold: float, sh_mode: int | None = None):
@@ -354,23 +435,17 @@ class VisibleAdam:
             raise ValueError("prune_by_contribution needs at least one camera")
         r, dev, n = self.renderer, self.records.device, self.records.shape[0]
         sh_mode = self.frame_sh_mode(sh_mode)
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self.stream):
-            if self._full_upload:
-                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
-                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
-                self._full_upload = False
-            else:
-                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+        with self._enqueue():
+            self._upload_pending()
             self.wmax = torch.zeros(n, dtype=torch.float32, device=dev)
             self.wsum = torch.zeros(n, dtype=torch.float32, device=dev)
-            self.pixels = torch.zeros(n, dtype=torch.int32, device=dev)             # int32 storage for the library's uint32
+            self.pixels = _u32(n, dev)
             for view, proj, cam_pos in cameras:
                 r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
                 r.contribDevice(n, self.wmax.data_ptr(), self.wsum.data_ptr(), self.pixels.data_ptr())
             raw = self.space == "raw"
             out = [torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(4 if raw else 3)]
-            counts = torch.zeros(2, dtype=torch.int32, device=dev)
+            counts = _u32(2, dev)
             r.pruneBelowDevice(self.wmax.data_ptr(), float(threshold), n, self.records.data_ptr(),
                                self.raw.data_ptr() if raw else None, self.m.data_ptr(), self.v.data_ptr(), out[0].data_ptr(),
                                out[3].data_ptr() if raw else None, out[1].data_ptr(), out[2].data_ptr(), n, counts.data_ptr())
@@ -380,16 +455,7 @@ class VisibleAdam:
             self.records, self.m, self.v = (t[:n_out].clone() for t in out[:3])
             if raw:
                 self.raw = out[3][:n_out].clone()
-            if self.track_density:
-                self._zero_stats(n_out, dev)
-            if self._rows_follow_n:
-                self.max_rows = n_out
-            self._alloc_rows(dev)
-            if self.acc is not None:
-                self._alloc_batch(dev)
-        self.stream.synchronize()
-        # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
-        self._full_upload = True
+            self._resized()
         return n_out, dropped
 
     # The INRIA schedule's active SH degree: a trainer starts at 0 and calls oneup_sh_degree() every 1000 iterations.  The
@@ -416,49 +482,17 @@ class VisibleAdam:
         camera_grad: a float32 [35] tensor on the records' device, filled with dL/dview, dL/dproj, dL/dcam_pos of this
         step's frame (gs_backward_camera_device) in the same enqueue chain, with no host wait; it belongs to self.stream
         like the returned numbers.  Needs max_rows > 0."""
-        r, n = self.renderer, self.records.shape[0]
         sh_mode = self.frame_sh_mode(sh_mode)
-        if camera_grad is not None and (camera_grad.dtype != torch.float32 or tuple(camera_grad.shape) != (_lib.CAMERA_GRAD_FLOATS,)
-                                        or camera_grad.device != self.records.device or not camera_grad.is_contiguous()):
-            raise ValueError(f"camera_grad must be a contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}] tensor on the records' device")
-        if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
-            raise ValueError(f"target must be float32 {(r.height, r.width, 3)} on the GPU")
+        if camera_grad is not None:
+            _check_camera_grad(camera_grad, self.records.device)
+        _check_image("target", target, (self.renderer.height, self.renderer.width, 3))
         target = target.contiguous()
-        self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
-        with torch.cuda.stream(self.stream):
+        with self._enqueue():
             numbers = torch.empty(3, dtype=torch.float32, device=self.records.device)
-            target.record_stream(self.stream)
-            if self._full_upload:
-                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
-                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
-                self._full_upload = False
-            else:
-                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
-            r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
-            r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers.data_ptr(), self.grad.data_ptr())
-            r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
-                                    self.count.data_ptr())
-            if camera_grad is not None:
-                camera_grad.record_stream(self.stream)
-                r.backwardCameraDevice(camera_grad.data_ptr())
-            if self.track_density:
-                r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
-                                     self.seen.data_ptr(), self.max_radius.data_ptr())
-            self.t += 1
-            self.params.step = self.t
-            if self.space == "raw":
-                r.adamRowsRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n,
-                                    self.ids.data_ptr(), self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
-            else:
-                r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
-                                 self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+            self._upload_pending()
+            self._view(view, proj, cam_pos, sh_mode, target, numbers.data_ptr(), lambda_dssim, bg, camera_grad)
+            self._adam()
         return numbers
-
-    def _alloc_batch(self, dev):
-        """What step_batch sums into: the accumulator (never initialised: a first touch is a store) and the zero marks."""
-        n = self.records.shape[0]
-        self.acc = torch.empty(n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev)
-        self.mark = torch.zeros(n, dtype=torch.int32, device=dev)                   # int32 storage for the library's uint32
 
     def step_batch(self, cameras, targets, sh_mode: int | None = None, lambda_dssim: float = 0.2, bg=None, weights=None,
                    camera_grads=None) -> torch.Tensor:
@@ -487,47 +521,24 @@ class VisibleAdam:
             if len(camera_grads) != B:
                 raise ValueError(f"camera_grads must have {B} entries")
             for g in camera_grads:
-                if (g.dtype != torch.float32 or tuple(g.shape) != (_lib.CAMERA_GRAD_FLOATS,) or g.device != dev or not g.is_contiguous()):
-                    raise ValueError(f"camera_grads must hold contiguous float32 [{_lib.CAMERA_GRAD_FLOATS}] tensors on the records' device")
+                _check_camera_grad(g, dev, one_of_many=True)
+        shape = (r.height, r.width, 3)
         for target in targets:
-            if target.dtype != torch.float32 or tuple(target.shape) != (r.height, r.width, 3) or not target.is_cuda:
-                raise ValueError(f"every target must be float32 {(r.height, r.width, 3)} on the GPU")
+            _check_image("every target", target, shape)
         targets = [t.contiguous() for t in targets]
-        self.stream.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self.stream):
+        with self._enqueue():
             numbers = torch.empty(B, 3, dtype=torch.float32, device=dev)
             if self.acc is None:
                 self._alloc_batch(dev)
-            if self._full_upload:
-                r.uploadDevice(self.records.data_ptr(), n)             # a context without this scene: a new one (waits once)
-                r.ensureOutputs(_lib.GS_OUTPUT_RGBA32F)
-                self._full_upload = False
-            else:
-                r.uploadRowsDevice(self.records.data_ptr(), n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows)
+            self._upload_pending()
             for b, ((view, proj, cam_pos), target) in enumerate(zip(cameras, targets)):
-                target.record_stream(self.stream)
-                r.drawCamera(view, proj, cam_pos, sh_mode, sync=False)
-                r.photometricLossDevice(None, target.data_ptr(), float(lambda_dssim), bg, numbers[b].data_ptr(), self.grad.data_ptr())
-                r.backwardVisibleDevice(self.grad.data_ptr(), None, self.ids.data_ptr(), self.rows.data_ptr(), self.max_rows,
-                                        self.count.data_ptr())
-                if camera_grads is not None:
-                    camera_grads[b].record_stream(self.stream)
-                    r.backwardCameraDevice(camera_grads[b].data_ptr())
-                if self.track_density:
-                    r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, n, self.grad_accum.data_ptr(),
-                                         self.seen.data_ptr(), self.max_radius.data_ptr())
+                self._view(view, proj, cam_pos, sh_mode, target, numbers[b].data_ptr(), lambda_dssim, bg,
+                           None if camera_grads is None else camera_grads[b])
                 r.rowsAccumulateDevice(self.acc.data_ptr(), self.mark.data_ptr(), n, self.ids.data_ptr(), self.rows.data_ptr(),
                                        self.count.data_ptr(), self.max_rows, weights[b])
             r.rowsCollectDevice(self.acc.data_ptr(), self.mark.data_ptr(), n, self.ids.data_ptr() if self.max_rows else None,
                                 self.rows.data_ptr() if self.max_rows else None, self.max_rows, self.count.data_ptr())
-            self.t += 1
-            self.params.step = self.t
-            if self.space == "raw":
-                r.adamRowsRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n,
-                                    self.ids.data_ptr(), self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
-            else:
-                r.adamRowsDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.ids.data_ptr(),
-                                 self.rows.data_ptr(), self.count.data_ptr(), self.max_rows, self.params)
+            self._adam()
         return numbers
 
     def reset_opacity(self, max_opacity: float = 0.01):
@@ -536,9 +547,9 @@ class VisibleAdam:
         step uploads the whole cloud.  Nothing is waited for."""
         if self.space != "raw":
             raise RuntimeError("reset_opacity() needs VisibleAdam(space='raw'); in record space clamp records[:, 15] and call reset_upload()")
-        self.stream.wait_stream(torch.cuda.current_stream(self.records.device))
-        self.renderer.resetOpacityRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                            self.records.shape[0], max_opacity)
+        with self._enqueue():
+            self.renderer.resetOpacityRawDevice(self.raw.data_ptr(), self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                                self.records.shape[0], max_opacity)
         self.reset_upload()
 
     def save_ply(self, path: str):

@@ -19,7 +19,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import GsAdamParams, GsConfig, GsDensifyParams, GsHostTimings, GsInitParams, GsSceneInfo, GsTimings
+from ._lib import GsAdamParams, GsConfig, GsDensifyParams, GsHostTimings, GsInitParams, GsSceneInfo, GsTimings, default_adam_params  # noqa: F401
 
 FLOATS_PER_GAUSSIAN = 84
 GAUSSIAN_DTYPE = np.dtype([
@@ -287,47 +287,23 @@ def write_ply(path: str, rows: np.ndarray, space: str = "records"):
         raise GsplatError(rc, L.gs_ply_last_error().decode() if rc == _lib.GS_ERR_IO else f"gs_write_ply({path!r}): invalid argument")
 
 
-def default_adam_params(space: str = "records", **overrides) -> GsAdamParams:
-    """gs_default_adam_params: step 1, beta1 0.9, beta2 0.999, eps 1e-15, the INRIA learning rates per GS_ADAM_* group
-    (acting on record-space values here) and the clamps scale >= 1e-7, opacity in [0, 1].  space="raw":
-    gs_default_adam_params_raw, the same without any clamp (for adamRowsRawDevice, where the rates act on log-scales and
-    logit-opacities).  overrides: beta1, beta2, eps, step as numbers; lr, lo, hi as a sequence of six or as {GS_ADAM_*
-    group: value} for some of them."""
-    if space not in ("records", "raw"):
-        raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
-    p = GsAdamParams()
-    (_lib.lib().gs_default_adam_params_raw if space == "raw" else _lib.lib().gs_default_adam_params)(C.byref(p))
-    for name, value in overrides.items():
-        if name in ("lr", "lo", "hi"):
-            arr = getattr(p, name)
-            items = value.items() if isinstance(value, dict) else enumerate(value)
-            if not isinstance(value, dict) and len(value) != _lib.GS_ADAM_GROUPS:
-                raise ValueError(f"{name} needs {_lib.GS_ADAM_GROUPS} values or a dict of groups")
-            for g, x in items:
-                arr[int(g)] = float(x)
-        elif name in ("beta1", "beta2", "eps"):
-            setattr(p, name, float(value))
-        elif name == "step":
-            p.step = int(value)
-        else:
-            raise TypeError(f"default_adam_params: unknown parameter {name!r}")
-    return p
-
-
 CAMERA_CONSTANTS = ("near_plane", "far_plane", "ndc_cull", "in_view_limit", "fov_y")   # the five floats of gs_config
 
 
-def _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
+def _config(device: int = 0, render_mode: int = _lib.GS_RENDER_EXACT, record_timings=True,
+            sort_algorithm: int = _lib.GS_SORT_RADIX4, render_kernel: int = _lib.GS_RENDER_KERNEL_AUTO,
+            tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO,
             near_plane=None, far_plane=None, ndc_cull=None, in_view_limit=None, fov_y=None) -> GsConfig:
-    """gs_default_config with these fields written over it; a camera constant that is None keeps its default."""
+    """gs_default_config with these fields written over it.  near_plane .. fov_y: the camera constants of gs_config
+    (include/gsplat.h); None keeps what gs_default_config wrote."""
     cfg = GsConfig()
     _lib.lib().gs_default_config(C.byref(cfg))
     cfg.device_ordinal = device
     cfg.render_mode = render_mode
-    cfg.sort_algorithm = sort_algorithm
+    cfg.sort_algorithm = sort_algorithm     # GPU_SORT_ALGORITHM, Renderer.h:33
     cfg.render_kernel = render_kernel
     cfg.tile_order = tile_order
-    cfg.count_launches = count_launches
+    cfg.count_launches = count_launches     # GS_COUNT_*: a Count launch per radix pass, or per sort (short lists)
     cfg.record_timings = int(record_timings)   # 0 off, 1 buckets, 2 buckets + per-Scatter events
     for name, value in zip(CAMERA_CONSTANTS, (near_plane, far_plane, ndc_cull, in_view_limit, fov_y)):
         if value is not None:
@@ -335,18 +311,14 @@ def _config(device, render_mode, record_timings, sort_algorithm, render_kernel, 
     return cfg
 
 
-class _Context:
-    """Owns one gs_ctx.  near_plane .. fov_y: the camera constants of gs_config (include/gsplat.h); None keeps what
-    gs_default_config wrote."""
+_CONFIG_OPTIONS = _config.__code__.co_varnames[:_config.__code__.co_argcount]     # the names of _config's parameters
 
-    def __init__(self, device: int = 0, render_mode: int = _lib.GS_RENDER_EXACT, record_timings=True,
-                 sort_algorithm: int = _lib.GS_SORT_RADIX4, render_kernel: int = _lib.GS_RENDER_KERNEL_AUTO,
-                 tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO,
-                 near_plane: float | None = None, far_plane: float | None = None, ndc_cull: float | None = None,
-                 in_view_limit: float | None = None, fov_y: float | None = None):
+
+class _Context:
+    """Owns one gs_ctx, made from a finished gs_config (_config)."""
+
+    def __init__(self, cfg: GsConfig):
         L = _lib.lib()
-        cfg = _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
-                      near_plane, far_plane, ndc_cull, in_view_limit, fov_y)
         self.cfg = cfg
         self.handle = C.c_void_p()
         rc = L.gs_create(C.byref(cfg), C.byref(self.handle))
@@ -394,7 +366,7 @@ class RadixSort(GpuSort):
     SORT_ALGORITHM = _lib.GS_SORT_RADIX4
 
     def __init__(self, device: int = 0, count_launches: int = _lib.GS_COUNT_AUTO):
-        self._ctx = _Context(device, sort_algorithm=self.SORT_ALGORITHM, count_launches=count_launches)
+        self._ctx = _Context(_config(device, sort_algorithm=self.SORT_ALGORITHM, count_launches=count_launches))
         self.maxNumSortElements = 0
         self.radixSortNumSortBits = 0
 
@@ -455,15 +427,9 @@ class Renderer:
         """near_plane, far_plane, ndc_cull, in_view_limit, fov_y: the camera constants of gs_config, fixed for the life of
         the context (None: gs_default_config's, the reference's).  proj drives the screen position, fov_y the covariance's
         focal lengths: INTEGRATION.md, "Real cameras".  self.cfg is the gs_config init() hands to gs_create."""
+        given = locals()                                     # _config's options are arguments here under their own names
+        self.cfg = _config(**{name: given[name] for name in _CONFIG_OPTIONS})
         self.width, self.height = int(width), int(height)   # swapchain extent (Engine.cpp:35)
-        self._constants = (near_plane, far_plane, ndc_cull, in_view_limit, fov_y)
-        self.cfg = _config(device, render_mode, record_timings, sort_algorithm, render_kernel, tile_order, count_launches,
-                           *self._constants)
-        self._render_kernel = render_kernel
-        self._tile_order = tile_order
-        self._count_launches = count_launches     # GS_COUNT_*: a Count launch per radix pass, or per sort (short lists)
-        self._device, self._render_mode, self._record = device, render_mode, record_timings
-        self._sort_algorithm = sort_algorithm   # GPU_SORT_ALGORITHM, Renderer.h:33
         self._ctx: _Context | None = None
         self.resourceManager: ResourceManager | None = None
         self.numGaussians = 0
@@ -481,9 +447,7 @@ class Renderer:
     # -- Renderer.cpp:688-694
     def init(self, resourceManager: ResourceManager):
         self.resourceManager = resourceManager
-        self._ctx = _Context(self._device, self._render_mode, self._record, self._sort_algorithm,
-                             self._render_kernel, self._tile_order, self._count_launches, *self._constants)
-        self.cfg = self._ctx.cfg
+        self._ctx = _Context(self.cfg)
 
     # -- Renderer.cpp:696-710
     def getNumTiles(self) -> int:
