@@ -771,6 +771,87 @@ int gs_prune_below_device(gs_ctx* ctx, const float* score_dev, float threshold, 
                           float* records_out, float* raw_out, float* m_out, float* v_out,
                           uint32_t max_out, uint32_t* counts_out_dev /* [2] */);
 
+/* MCMC (no reference counterpart): the other strategy for the set of gaussians, 3DGS-MCMC (Kheradmand et al. 2024).  Dead
+ * splats are relocated onto live ones sampled in proportion to their opacity, the cloud grows by a chosen number of rows up to
+ * a chosen cap, and noise shaped like each splat's covariance explores the positions.  Relocation keeps n: it runs in place
+ * and lists the rows it changed for gs_upload_rows_device, so the scene, the resolution and the scratch stay.  All arrays are
+ * the CALLER's, on the DEVICE; every call is enqueued on the context's stream with no host sync, needs no scene and no
+ * resolution, keeps no state in the library and is bitwise reproducible, the same for every sorter (up to the device's
+ * log1pf / expm1f / logf / cosf).  Callers detect the calls by their symbols (GS_API_VERSION is unchanged).  Scratch: 12 bytes
+ * per splat + 16 bytes per 256 splats + 11 KB, beside the per-splat scan buffers shared with gs_densify_device; the
+ * context's, grown on demand and freed by gs_destroy.
+ *
+ * The sampler (gs_relocate_device and gs_grow_device), integer arithmetic throughout:
+ *   alive(g) = records[g][15] > min_opacity, exactly as written (a NaN opacity is dead)
+ *   w(g)     = alive(g) ? (uint32)(min(o, 1.0f) * 16777216.0f) : 0        (the conversion truncates)
+ *   P(g)     = the exclusive prefix sum of w in 64 bits; total = the sum
+ *   draw i:    h = mix(mix(i ^ (uint32)seed) + (uint32)(seed >> 32))      (mix: gs_densify_device's)
+ *              r64 = ((uint64)mix(h + 0x9E3779B9) << 32) | mix(h + 2 * 0x9E3779B9)
+ *              t = (uint64)(((unsigned __int128)r64 * total) >> 64), in [0, total)
+ *              the source is the one g with P(g) <= t < P(g) + w(g): never a splat of weight zero
+ *   cnt[g]   = the number of draws whose source is g; with total == 0 no draw is made.
+ *
+ * The relocation values of a source g with cnt[g] > 0: r = min(cnt[g] + 1, 51), o and s_k the record's current opacity and
+ * scales, hi = 0x1.fffffep-1f; float32, never contracted, in exactly this order:
+ *   o1 = -expm1f(log1pf(-min(o, hi)) / (float)r)          (the device's functions: 1 - (1 - o)^(1 / r), well conditioned)
+ *   oc = o1 < min_opacity ? min_opacity : (o1 > hi ? hi : o1)
+ *   records alone: o' = oc.  With raw: raw[15] = logf(oc / (1.0f - oc)) and o' = 1.0f / (1.0f + E(-raw[15])) (act).
+ *   D = 0;  for i = 1 .. r: { p = o'; sg = 1;  for k = 0 .. i - 1: { D = D + B[i - 1][k] * ((sg * Q[k]) * p);  p = p * o';
+ *   sg = -sg } }          B[a][b] = (float)C(a, b) from the exact integer, Q[k] = (float)(1.0 / sqrt((double)(k + 1)))
+ *   c = o / D;  s'_k = c * s_k.  Records alone: the record stores s'_k.  With raw: raw[4 + k] = logf(max(s'_k, FLT_MIN)) and
+ *   the record stores E(raw[4 + k]).  The record stores o'.
+ * For o' in [0.005, hi] and every r, D > 0 and 0 < c <= 1 (tests/test_mcmc_cpu.py).  Two deliberate differences from the CUDA
+ * original keep the stored pair consistent: the clamp comes BEFORE the scale -- the scale belongs to the opacity that is
+ * stored --, and the opacity is not computed with powf.
+ *
+ * gs_relocate_device, in place, n fixed.  Every dead d makes draw i = d; call its source src(d).  Then, in this order:
+ *   1. every source gets the new opacity and scales, in records and (if given) raw; its m and v rows become zero;
+ *   2. every dead d gets all 84 floats of records[src(d)], and of raw[src(d)], as they now stand; its m and v rows become
+ *      zero.
+ * No other float is touched.  ids_out receives, ascending, the changed rows -- the dead splats and the sources --, at most
+ * max_rows of them; counts_out[3] (DEVICE) = {changed (not clamped), dead, sources}: ids_out and counts_out are what
+ * gs_upload_rows_device takes.  With total == 0 or no dead splat the counts are {0, dead, 0} and nothing changes.
+ * max_rows == 0 with a NULL ids_out is legal (the caller uploads in full).  raw may be NULL; m and v NULL together.
+ * GS_ERR_INVALID (message in gs_last_error, nothing enqueued; a NULL ctx: the code alone): a NULL records or counts_out, one of
+ * m and v without the other, n == 0 or n >= 2^31, a min_opacity that fails 0x1p-24f <= min_opacity < 1, a NULL ids_out with
+ * max_rows > 0, arrays that share bytes.
+ *
+ * gs_grow_device, out of place like gs_densify_device.  Draws i = 0 .. n_add - 1 give cnt.  Input g has 1 + cnt[g] outputs at
+ * rows [o(g), o(g) + 1 + cnt[g]), o = the exclusive scan: the copies sit beside their source, and the storage order keeps its
+ * locality.  A g with cnt[g] == 0: its rows of records, raw, m and v copied bit for bit.  A g with cnt[g] > 0: all its
+ * outputs identical, the source's row with the relocation values for r = min(cnt[g] + 1, 51), and zero m and v rows.
+ * counts_out[2] (DEVICE) = {outputs, sources}; outputs = n + n_add when total > 0, else n.  Rows with index >= max_out are not
+ * written.  raw, m and v are each NULL together with their own output; n_add == 0 is a plain copy.
+ * GS_ERR_INVALID: what gs_relocate_device refuses of records, counts_out, m, v, n and min_opacity; n + n_add >= 2^31; a NULL
+ * records_out with max_out > 0; an input NULL without its output or the reverse; an output that shares bytes with an input or
+ * with another output.
+ *
+ * gs_position_noise_device.  With ids the listing rules of gs_adam_rows_device: rows i < min(*count_dev, max_rows), an id >= n
+ * compared and never dereferenced, the grid sized from max_rows, count_dev never read by the host; with a NULL ids every g < n
+ * (count_dev and max_rows are ignored).  For a listed g, float32, never contracted:
+ *   z_a  = gs_densify_device's normal of (seed, g, child 0, axis a);  R = the rotation matrix of the record's own rot as the
+ *          frame builds it, R[row][col];  s = the record's scales, o = its opacity
+ *   gate = 1.0f / (1.0f + E(-(gate_k * ((1.0f - o) - gate_x0))))                  (3DGS-MCMC: gate_k = 100, gate_x0 = 0.995)
+ *   a_k   = s_k * ((R[0][k] * z_0 + R[1][k] * z_1) + R[2][k] * z_2)
+ *   off_i = ((R[i][0] * s_0) * a_0 + (R[i][1] * s_1) * a_1) + (R[i][2] * s_2) * a_2          (Sigma z, Sigma = M M^T)
+ *   pos_i = pos_i + (off_i * gate) * scale
+ * written to records and, the same bits, to raw (may be NULL).  scale is the caller's noise_lr * lr[GS_ADAM_POSITION].
+ * GS_ERR_INVALID: a NULL records, n == 0, a scale, gate_k or gate_x0 that is not finite, a NULL count_dev with ids given and
+ * max_rows > 0.  ids with max_rows == 0: GS_OK, nothing launched.
+ *
+ * Out of scope: the opacity and scale regularisers of the MCMC loss are constant gradients the caller adds to the rows, and
+ * no schedule is built in. */
+int gs_relocate_device(gs_ctx* ctx, float* records, float* raw, float* m, float* v, uint32_t n,
+                       float min_opacity, uint64_t seed,
+                       uint32_t* ids_out, uint32_t max_rows, uint32_t* counts_out /* [3] */);
+int gs_grow_device(gs_ctx* ctx, const float* records, const float* raw, const float* m, const float* v, uint32_t n,
+                   float min_opacity, uint64_t seed, uint32_t n_add,
+                   float* records_out, float* raw_out, float* m_out, float* v_out,
+                   uint32_t max_out, uint32_t* counts_out /* [2] */);
+int gs_position_noise_device(gs_ctx* ctx, float* records, float* raw, uint32_t n, const uint32_t* ids,
+                             const uint32_t* count_dev, uint32_t max_rows, float scale, float gate_k, float gate_x0,
+                             uint64_t seed);
+
 /* Several views per optimiser step (no reference counterpart): the lists of two frames name different splats, so their rows
  * cannot simply be added.  Two calls sum the (ids, rows, count) lists of any number of frames into one list over the union of
  * their splats, which gs_adam_rows[_raw]_device, gs_upload_rows_device and gs_densify_stats_device take unchanged.  All arrays

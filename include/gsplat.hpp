@@ -304,6 +304,32 @@ public:
         return rc;
     }
 
+    // MCMC (gsplat.h, gs_relocate_device, gs_grow_device and gs_position_noise_device): dead splats moved onto live ones in
+    // place (ids_out / counts_out[3] = changed, dead, sources: what uploadRows takes), the cloud grown by n_add rows into
+    // records_out / raw_out / m_out / v_out [max_out][84] (counts_out[2] = outputs, sources), and covariance-shaped noise on
+    // the positions of the listed rows (ids null: every row).  All arrays on the DEVICE; enqueued on the context's stream
+    // without waiting.
+    int relocate(float* records, float* raw, float* m, float* v, uint32_t n, float min_opacity, uint64_t seed, uint32_t* ids_out,
+                 uint32_t max_rows, uint32_t* counts_out) {
+        const int rc = gs_relocate_device(ctx_, records, raw, m, v, n, min_opacity, seed, ids_out, max_rows, counts_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int grow(const float* records, const float* raw, const float* m, const float* v, uint32_t n, float min_opacity, uint64_t seed,
+             uint32_t n_add, float* records_out, float* raw_out, float* m_out, float* v_out, uint32_t max_out,
+             uint32_t* counts_out) {
+        const int rc = gs_grow_device(ctx_, records, raw, m, v, n, min_opacity, seed, n_add, records_out, raw_out, m_out, v_out,
+                                      max_out, counts_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int positionNoise(float* records, float* raw, uint32_t n, const uint32_t* ids, const uint32_t* count, uint32_t max_rows,
+                      float scale, float gate_k = 100.0f, float gate_x0 = 0.995f, uint64_t seed = 0) {
+        const int rc = gs_position_noise_device(ctx_, records, raw, n, ids, count, max_rows, scale, gate_k, gate_x0, seed);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Several views per optimiser step (gsplat.h, gs_rows_accumulate_device and gs_rows_collect_device): the listed rows of a
     // frame, times weight, summed into the caller's DEVICE accumulator acc [n][84] with a touch count per splat in mark [n]
     // (zeros before the first frame of a batch), then the touched rows as one ascending (ids, rows, count) list for adamRows

@@ -270,6 +270,10 @@ class VisibleAdam:
     step() is the same chain with gs_adam_rows_raw_device as its last call; reset_opacity() and save_ply() complete the
     trainer.  space="records" (the default) moves the record's own values.
 
+    relocate(), grow() and add_noise() are the 3DGS-MCMC strategy (gs_relocate_device, gs_grow_device,
+    gs_position_noise_device): dead splats moved onto live ones in place with no host wait and no new scene, the cloud grown
+    to a cap, covariance-shaped noise on the positions.  They need no track_density.
+
     step_batch() is one step on several views: the visible rows of every view summed on the device
     (gs_rows_accumulate_device) and one Adam step on the union of their lists (gs_rows_collect_device)."""
 
@@ -457,6 +461,75 @@ class VisibleAdam:
                 self.raw = out[3][:n_out].clone()
             self._resized()
         return n_out, dropped
+
+    # -- MCMC (3DGS-MCMC; include/gsplat.h, gs_relocate_device / gs_grow_device / gs_position_noise_device)
+    # seed=None of the three methods is self.t with the call's own number in the upper word: the random words of relocate(),
+    # grow() and add_noise() of one iteration are then different streams (the hash mixes the upper word in separately)
+    _SEED_RELOCATE, _SEED_GROW, _SEED_NOISE = 0, 1 << 32, 2 << 32
+    relocated = None       # relocate(): {changed, dead, sources} of the last call, on the device
+    relocated_ids = None   # ... and the rows it changed, ascending (the first min(changed, n))
+
+    def relocate(self, min_opacity: float = 0.005, seed: int | None = None):
+        """Move every splat whose opacity is <= min_opacity onto a live one drawn in proportion to its opacity, in place
+        (gs_relocate_device), opacity and scales of every copy corrected so that the picture stays; the moments of the changed
+        rows start again from zero.  On self.stream: the pending upload, the call, then gs_upload_rows_device with the call's
+        own ids and count -- n, the scene, the resolution and the scratch stay.  Nothing is waited for: self.relocated is the
+        device tensor {changed, dead, sources}, self.relocated_ids the changed rows.  seed=None: self.t."""
+        r, dev, n = self.renderer, self.records.device, self.records.shape[0]
+        with self._enqueue():
+            self._upload_pending()
+            if self.relocated_ids is None or self.relocated_ids.shape[0] != n:
+                self.relocated_ids = _u32(n, dev)
+            self.relocated = _u32(3, dev)
+            r.relocateDevice(self.records.data_ptr(), self.raw.data_ptr() if self.space == "raw" else None, self.m.data_ptr(),
+                             self.v.data_ptr(), n, min_opacity, self.t | self._SEED_RELOCATE if seed is None else seed, self.relocated_ids.data_ptr(),
+                             n, self.relocated.data_ptr())
+            r.uploadRowsDevice(self.records.data_ptr(), n, self.relocated_ids.data_ptr(), self.relocated.data_ptr(), n)
+
+    def grow(self, n_add: int | None = None, cap_max: int | None = None, factor: float = 1.05, min_opacity: float = 0.005,
+             seed: int | None = None):
+        """Grow the cloud by n_add rows (gs_grow_device) -> (n_out, sources): n_add live splats drawn in proportion to their
+        opacity, the copies beside their sources with the relocation values and zero moments, every other row copied bit for
+        bit.  n_add=None: min(cap_max, int(factor * n)) - n (cap_max=None: no cap).  self.records, self.m, self.v and
+        (space="raw") self.raw become new tensors -- raw travels through the call, no log/exp round trip --; the rest is
+        densify()'s bookkeeping: the next step uploads the whole cloud as a new scene, t and the hyper-parameters stay.
+        Reading the two counts is the one host wait of this rare event.  seed=None: self.t + 2^32, not relocate()'s stream."""
+        r, dev, n = self.renderer, self.records.device, self.records.shape[0]
+        if n_add is None:
+            target = int(factor * n)
+            n_add = (target if cap_max is None else min(int(cap_max), target)) - n
+        n_add = max(int(n_add), 0)
+        raw = self.space == "raw"
+        with self._enqueue():
+            out = [torch.empty(n + n_add, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(4 if raw else 3)]
+            counts = _u32(2, dev)
+            r.growDevice(self.records.data_ptr(), self.raw.data_ptr() if raw else None, self.m.data_ptr(), self.v.data_ptr(), n,
+                         min_opacity, self.t | self._SEED_GROW if seed is None else seed, n_add, out[0].data_ptr(),
+                         out[3].data_ptr() if raw else None, out[1].data_ptr(), out[2].data_ptr(), n + n_add, counts.data_ptr())
+            n_out, sources = (int(x) for x in counts.cpu().numpy().view(np.uint32))      # waits for the stream
+            self.records, self.m, self.v = (t if n_out == t.shape[0] else t[:n_out].clone() for t in out[:3])
+            if raw:
+                self.raw = out[3] if n_out == out[3].shape[0] else out[3][:n_out].clone()
+            self.relocated_ids = None
+            self._resized()
+        return n_out, sources
+
+    def add_noise(self, noise_lr: float, all_rows: bool = False, seed: int | None = None):
+        """3DGS-MCMC exploration noise (gs_position_noise_device) with scale = noise_lr * lr[GS_ADAM_POSITION], on the rows the
+        last step listed -- the next step's upload covers exactly those -- or, all_rows=True, on every row, followed by
+        reset_upload().  Nothing is waited for.  seed=None: self.t + 2^33."""
+        r, n = self.renderer, self.records.shape[0]
+        scale = float(noise_lr) * float(self.params.lr[_lib.GS_ADAM_POSITION])
+        seed = self.t | self._SEED_NOISE if seed is None else seed
+        raw = self.raw.data_ptr() if self.space == "raw" else None
+        with self._enqueue():
+            if all_rows:
+                r.positionNoiseDevice(self.records.data_ptr(), raw, n, None, None, 0, scale, seed=seed)
+            else:
+                r.positionNoiseDevice(self.records.data_ptr(), raw, n, self.ids.data_ptr(), self.count.data_ptr(), self.max_rows,
+                                      scale, seed=seed)
+        if all_rows:
+            self.reset_upload()
 
     # The INRIA schedule's active SH degree: a trainer starts at 0 and calls oneup_sh_degree() every 1000 iterations.  The
     # default 3 (all 16 coefficients) is what a step drew before the degree existed.

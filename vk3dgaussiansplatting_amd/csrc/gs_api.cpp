@@ -546,6 +546,7 @@ int gs_destroy(gs_ctx* c) {
     free_resolution(c);
     free_scene(c);
     c->densify_mem.release();
+    c->mcmc_mem.release();
     c->init_mem.release();
     destroy_events(c->marks, kMaxFrameMarks);
     destroy_events(c->scatter_ev, 32);

@@ -140,6 +140,11 @@ struct gs_ctx {
     gs::SplatScan densify_scan{};
     uint32_t densify_cap = 0;
     DeviceOwner densify_mem;
+    // gs_relocate_device / gs_grow_device: the sampler's scratch for mcmc_cap splats (12 bytes per splat + 16 bytes per 256
+    // splats + the two tables); grown on demand, freed at gs_destroy.  Their per-splat scan is densify_scan.
+    gs::McmcScratch mcmc{};
+    uint32_t mcmc_cap = 0;
+    DeviceOwner mcmc_mem;
     // gs_knn_mean_dist2_device / gs_records_from_points_device: scratch and sort buffers for init_cap points; grown on
     // demand, freed at gs_destroy
     gs::InitScratch init{};

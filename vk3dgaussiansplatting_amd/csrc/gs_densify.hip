@@ -48,20 +48,6 @@ struct DensifySource {
     }
 };
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
-// The standard normal of (seed, g, child, axis): Box-Muller on two counter-based words
-__device__ __forceinline__ float densify_normal(uint32_t h, uint32_t child, uint32_t axis) {
-    const uint32_t w0 = mix32(h + (child * 6u + axis * 2u + 1u) * 0x9E3779B9u);
-    const uint32_t w1 = mix32(h + (child * 6u + axis * 2u + 2u) * 0x9E3779B9u);
-    const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f;         // (0, 1]
-    const float u2 = (float)(w1 >> 8) * 0x1p-24f;                // [0, 1)
-    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
-}
-
 }  // namespace
 
 // ---- statistics of one step ---------------------------------------------------------------------------------------

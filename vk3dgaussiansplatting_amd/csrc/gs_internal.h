@@ -444,6 +444,37 @@ struct PruneArgs {
     SplatScan scan;                   // K = 2: kept, dropped; offsets[g] = the output row of a kept g
 };
 void launch_prune_below(const PruneArgs& a, uint32_t* counts_out, hipStream_t stream);
+// gs_relocate_device / gs_grow_device / gs_position_noise_device (gs_mcmc.hip).  The sampler's scratch for n splats, in blocks
+// of 256 splats: w(g) is never stored, P(g) = block_prefix[g / 256] + within[g]
+constexpr uint32_t kMcmcMaxRatio = 51;          // r = min(cnt + 1, kMcmcMaxRatio)
+constexpr uint32_t kMcmcTableFloats = kMcmcMaxRatio * kMcmcMaxRatio + kMcmcMaxRatio;    // B[51][51], then Q[51]
+constexpr uint32_t kMcmcAlive = 0xFFFFFFFFu, kMcmcDeadNoDraw = 0xFFFFFFFEu;             // McmcScratch::src_of of a row that is no copy
+struct McmcScratch {
+    uint32_t* within;         // [n]  the exclusive sum of w inside the splat's block (at most 255 * 2^24)
+    uint64_t* block_sums;     // [ceil(n / 256)]
+    uint64_t* block_prefix;   // [ceil(n / 256) + 1]  exclusive scan of block_sums; the last entry is `total`
+    uint32_t* cnt;            // [n]  draws that chose g
+    uint32_t* src_of;         // [n]  gs_relocate_device: src(d) of a dead d that drew, kMcmcDeadNoDraw of a dead d with
+                              //      total == 0, kMcmcAlive of an alive g
+    float* tables;            // [kMcmcTableFloats]  B and Q of the header, made on the host (mcmc_fill_tables)
+};
+void mcmc_fill_tables(float* host_tables);      // kMcmcTableFloats floats
+struct McmcArgs {
+    float *records, *raw, *m, *v;     // raw: null or given; m, v: both null or neither
+    uint32_t n;
+    float min_opacity;
+    uint64_t seed;
+    McmcScratch s;
+    SplatScan scan;                   // relocate K = 3: changed, dead, sources; grow K = 2: outputs, sources
+};
+// ids_out: the changed rows below max_rows, ascending; counts_out[3] = {changed, dead, sources}
+void launch_relocate(const McmcArgs& a, uint32_t* ids_out, uint32_t max_rows, uint32_t* counts_out, hipStream_t stream);
+// a.records / raw / m / v are only read; counts_out[2] = {outputs, sources}
+void launch_grow(const McmcArgs& a, uint32_t n_add, float* records_out, float* raw_out, float* m_out, float* v_out,
+                 uint32_t max_out, uint32_t* counts_out, hipStream_t stream);
+// ids == null: every g < n (count and max_rows unused)
+void launch_position_noise(float* records, float* raw, uint32_t n, const uint32_t* ids, const uint32_t* count, uint32_t max_rows,
+                           float scale, float gate_k, float gate_x0, uint64_t seed, hipStream_t stream);
 // gs_rows_accumulate_device / gs_rows_collect_device (gs_batch.hip).  _accumulate: acc[ids[i]] (+)= weight * grad_rows[i] on the
 // fields, then mark[ids[i]] += 1, i < min(*count, max_rows); max_rows == 0 launches nothing.  _collect: the splats with a
 // non-zero mark, ascending, into ids_out / rows_out (both may be null with max_rows == 0) below max_rows, their number into

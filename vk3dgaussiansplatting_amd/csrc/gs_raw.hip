@@ -3,46 +3,13 @@
 // gs_records_from_raw_device, gs_raw_from_records_device, gs_reset_opacity_raw_device.  No reference counterpart.  All four
 // are bandwidth-bound and touch nothing but the 59 fields of a row (gs_record.h); every kernel runs a lane per (row, group of
 // four floats), like k_adam_rows, so the scale's three and the rotation's four components sit in one lane.
-#include <float.h>
-
 #include "../../include/gsplat.h"
 #include "gs_adam_field.h"
-#include "gs_device_utils.h"
-#include "gs_internal.h"
+#include "gs_splat_math.h"
 
 namespace gs {
 
 namespace {
-
-constexpr uint32_t kQuadScale = kRecScale / 4u, kQuadRot = kRecRot / 4u, kQuadDc = kRecSh / 4u;   // the quads act() changes
-static_assert(kRecOpacity == kQuadDc * 4u + 3u, "the opacity is the w of the SH-DC quad");
-
-// 1 / |q| in the association of the loader (gs_ply.cpp convert_row, glm::normalize)
-__device__ __forceinline__ float inv_length4(float x, float y, float z, float w) {
-    const float t0 = x * x, t1 = y * y, t2 = z * z, t3 = w * w;
-    return 1.0f / sqrtf((t0 + t1) + (t2 + t3));
-}
-
-__device__ __forceinline__ float sigmoid_pinned(float x) { return 1.0f / (1.0f + exp_pinned(-x)); }
-
-// act(raw) on one leading quad, in place: the header's expressions in the header's order
-__device__ __forceinline__ void act_quad(uint32_t quad, float3& p, float& w) {
-    if (quad == kQuadScale) {
-        p.x = exp_pinned(p.x); p.y = exp_pinned(p.y); p.z = exp_pinned(p.z);
-    } else if (quad == kQuadRot) {
-        const float inv = inv_length4(p.x, p.y, p.z, w);
-        p.x = p.x * inv; p.y = p.y * inv; p.z = p.z * inv; w = w * inv;
-    } else if (quad == kQuadDc) {
-        w = sigmoid_pinned(w);
-    }
-}
-
-// the inverse, with the device's logf and the two clamps of the header
-__device__ __forceinline__ float log_scale(float s) { return logf(s < FLT_MIN ? FLT_MIN : s); }
-__device__ __forceinline__ float logit_opacity(float o) {
-    const float c = o < 0x1p-24f ? 0x1p-24f : (o > 0x1.fffffep-1f ? 0x1.fffffep-1f : o);
-    return logf(c / (1.0f - c));
-}
 
 struct Quad {
     float3 p;

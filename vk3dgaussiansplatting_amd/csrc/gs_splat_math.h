@@ -1,8 +1,11 @@
 // gs_splat_math.h -- the per-splat expressions more than one kernel file evaluates, each written once (device).  Every
 // .hip file is built with -ffp-contract=off and correctly rounded division and square root, so an expression of this header
 // gives the same floats wherever it is compiled: the frame (gs_project.hip), its backward (gs_backward.hip), the upload
-// (gs_upload.hip) and density control (gs_densify.hip) agree bit for bit because they call the same function.
+// (gs_upload.hip), density control (gs_densify.hip), the raw space (gs_raw.hip) and MCMC (gs_mcmc.hip) agree bit for bit
+// because they call the same function.
 #pragma once
+
+#include <float.h>
 
 #include "gs_device_utils.h"
 #include "gs_internal.h"
@@ -47,6 +50,54 @@ __device__ __forceinline__ float tile_extent_radius(float cx, float cy, float cz
     const float lambda0 = m + sqrtf(maxf(m * m - det, 0.0f));
     const float lambda1 = m - sqrtf(maxf(m * m - det, 0.0f));
     return ceilf(3.0f * sqrtf(maxf(lambda0, lambda1)));
+}
+
+// ---- the counter-based random words of gs_densify.hip and gs_mcmc.hip (the header's mix)
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+// The standard normal of (seed, g, child, axis): Box-Muller on two counter-based words
+__device__ __forceinline__ float densify_normal(uint32_t h, uint32_t child, uint32_t axis) {
+    const uint32_t w0 = mix32(h + (child * 6u + axis * 2u + 1u) * 0x9E3779B9u);
+    const uint32_t w1 = mix32(h + (child * 6u + axis * 2u + 2u) * 0x9E3779B9u);
+    const float u1 = (float)((w0 >> 8) + 1u) * 0x1p-24f;         // (0, 1]
+    const float u2 = (float)(w1 >> 8) * 0x1p-24f;                // [0, 1)
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.2831855f * u2);
+}
+
+// ---- the raw parameter space of gs_raw.hip and gs_mcmc.hip: act() of the header and its inverse
+
+constexpr uint32_t kQuadScale = kRecScale / 4u, kQuadRot = kRecRot / 4u, kQuadDc = kRecSh / 4u;   // the quads act() changes
+static_assert(kRecOpacity == kQuadDc * 4u + 3u, "the opacity is the w of the SH-DC quad");
+
+// 1 / |q| in the association of the loader (gs_ply.cpp convert_row, glm::normalize)
+__device__ __forceinline__ float inv_length4(float x, float y, float z, float w) {
+    const float t0 = x * x, t1 = y * y, t2 = z * z, t3 = w * w;
+    return 1.0f / sqrtf((t0 + t1) + (t2 + t3));
+}
+
+__device__ __forceinline__ float sigmoid_pinned(float x) { return 1.0f / (1.0f + exp_pinned(-x)); }
+
+// act(raw) on one leading quad, in place: the header's expressions in the header's order
+__device__ __forceinline__ void act_quad(uint32_t quad, float3& p, float& w) {
+    if (quad == kQuadScale) {
+        p.x = exp_pinned(p.x); p.y = exp_pinned(p.y); p.z = exp_pinned(p.z);
+    } else if (quad == kQuadRot) {
+        const float inv = inv_length4(p.x, p.y, p.z, w);
+        p.x = p.x * inv; p.y = p.y * inv; p.z = p.z * inv; w = w * inv;
+    } else if (quad == kQuadDc) {
+        w = sigmoid_pinned(w);
+    }
+}
+
+// the inverse, with the device's logf and the two clamps of the header
+__device__ __forceinline__ float log_scale(float s) { return logf(s < FLT_MIN ? FLT_MIN : s); }
+__device__ __forceinline__ float logit_opacity(float o) {
+    const float c = o < 0x1p-24f ? 0x1p-24f : (o > 0x1.fffffep-1f ? 0x1.fffffep-1f : o);
+    return logf(c / (1.0f - c));
 }
 
 // The first COLS columns of splat g's rows (BackwardBuffers::rows) summed in slot order, from 0.0f, over the slots below the

@@ -1,5 +1,5 @@
 // gs_train.cpp -- the training calls of include/gsplat.h, which have no counterpart in the reference: Adam on listed rows,
-// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control, pruning by contribution, the rows of several views and a cloud from points.  Every entry point
+// the raw parameter space, gs_backward*, gs_visible_count, gs_photometric_loss*, density control, pruning by contribution, the MCMC strategy, the rows of several views and a cloud from points.  Every entry point
 // refuses first (nothing enqueued, the context unchanged), then enqueues on the context's stream; a host-pointer form is
 // its _device twin between staging copies and a wait.
 #include "gs_ctx.h"
@@ -244,6 +244,46 @@ int densify_scratch(gs_ctx* c, uint32_t n, const char* who) {
         return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
     }
     c->densify_cap = n;
+    return GS_OK;
+}
+
+// ---- MCMC (gs_mcmc.hip)
+
+// the sampler's scratch of gs_relocate_device and gs_grow_device for n splats, kept from call to call and grown when a larger
+// cloud comes; the two tables go up once per allocation
+int mcmc_scratch(gs_ctx* c, uint32_t n, const char* who) {
+    if (c->mcmc_cap >= n) return GS_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // an earlier call may still be running on the old arrays
+    DeviceOwner& mem = c->mcmc_mem;
+    mem.release();
+    c->mcmc_cap = 0;
+    McmcScratch& s = c->mcmc;
+    const size_t blocks = backward_blocks(n);
+    hipError_t e = mem.alloc(s.within, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(s.block_sums, blocks * sizeof(uint64_t));
+    if (e == hipSuccess) e = mem.alloc(s.block_prefix, (blocks + 1) * sizeof(uint64_t));
+    if (e == hipSuccess) e = mem.alloc(s.cnt, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(s.src_of, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = mem.alloc(s.tables, kMcmcTableFloats * sizeof(float));
+    if (e == hipSuccess) {
+        float tables[kMcmcTableFloats];
+        mcmc_fill_tables(tables);
+        e = hipMemcpy(s.tables, tables, sizeof(tables), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        mem.release();
+        return refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+    }
+    c->mcmc_cap = n;
+    return GS_OK;
+}
+
+// what gs_relocate_device and gs_grow_device check of the cloud and the threshold
+int check_mcmc_cloud(gs_ctx* c, const char* who, const float* m, const float* v, uint32_t n, float min_opacity) {
+    if (!m != !v) return refuse(c, who, "m and v must be given together or not at all");
+    if (n == 0) return refuse(c, who, "n is 0");
+    if (n >= 0x80000000u) return refuse(c, who, "n must be below 2^31 (the rows are counted in 32 bits)");
+    if (!(min_opacity >= 0x1p-24f && min_opacity < 1.0f)) return refuse(c, who, "min_opacity must lie in [2^-24, 1)");
     return GS_OK;
 }
 
@@ -679,6 +719,71 @@ int gs_densify_device(gs_ctx* c, const float* records, const float* m, const flo
     a.records_out = records_out; a.m_out = m_out; a.v_out = v_out; a.max_out = max_out;
     a.scan = c->densify_scan;
     launch_densify(a, counts_out, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_relocate_device(gs_ctx* c, float* records, float* raw, float* m, float* v, uint32_t n, float min_opacity, uint64_t seed,
+                       uint32_t* ids_out, uint32_t max_rows, uint32_t* counts_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!records || !counts_out) return refuse(c, __func__, "null records or counts_out");
+    if (int r = check_mcmc_cloud(c, __func__, m, v, n, min_opacity)) return r;
+    if (int r = check_row_arrays(c, __func__, max_rows, {ids_out}, "ids_out")) return r;
+    const size_t bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES;
+    const Span arrays[] = {{records, bytes}, {raw, bytes}, {m, bytes}, {v, bytes}, {ids_out, (size_t)max_rows * 4}, {counts_out, 12}};
+    for (size_t a = 0; a < std::size(arrays); ++a)
+        for (size_t b = a + 1; b < std::size(arrays); ++b)
+            if (overlap(arrays[a], arrays[b])) return refuse(c, __func__, "two arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, __func__)) return r;
+    if (int r = mcmc_scratch(c, n, __func__)) return r;
+    const McmcArgs a{records, raw, m, v, n, min_opacity, seed, c->mcmc, c->densify_scan};
+    launch_relocate(a, ids_out, max_rows, counts_out, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_grow_device(gs_ctx* c, const float* records, const float* raw, const float* m, const float* v, uint32_t n,
+                   float min_opacity, uint64_t seed, uint32_t n_add, float* records_out, float* raw_out, float* m_out,
+                   float* v_out, uint32_t max_out, uint32_t* counts_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (!records || !counts_out) return refuse(c, __func__, "null records or counts_out");
+    if (max_out && !records_out) return refuse(c, __func__, "null records_out with max_out > 0");
+    // with max_out == 0 no row is written and an output may stay away; an output without its input never
+    const bool paired = (raw || !raw_out) && (m || !m_out) && (v || !v_out) &&
+                        (!max_out || ((!raw || raw_out) && (!m || m_out) && (!v || v_out)));
+    if (!paired) return refuse(c, __func__, "raw, m and v must each be null together with their own output");
+    if (int r = check_mcmc_cloud(c, __func__, m, v, n, min_opacity)) return r;
+    if ((uint64_t)n + n_add >= 0x80000000ull) return refuse(c, __func__, "n + n_add must be below 2^31 (the outputs are counted in 32 bits)");
+    // no output may share bytes with an input, or with another output
+    const size_t in_bytes = (size_t)n * GS_GAUSSIAN_RECORD_BYTES, out_bytes = (size_t)max_out * GS_GAUSSIAN_RECORD_BYTES;
+    const Span ins[] = {{records, in_bytes}, {raw, in_bytes}, {m, in_bytes}, {v, in_bytes}};
+    const Span outs[] = {{records_out, out_bytes}, {raw_out, out_bytes}, {m_out, out_bytes}, {v_out, out_bytes}, {counts_out, 8}};
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlap(o, i)) return refuse(c, __func__, "an output array aliases an input");
+    for (size_t o = 0; o < std::size(outs); ++o)
+        for (size_t k = o + 1; k < std::size(outs); ++k)
+            if (overlap(outs[o], outs[k])) return refuse(c, __func__, "two output arrays alias each other");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int r = densify_scratch(c, n, __func__)) return r;
+    if (int r = mcmc_scratch(c, n, __func__)) return r;
+    // the kernels only read the inputs: one argument struct serves both calls
+    const McmcArgs a{const_cast<float*>(records), const_cast<float*>(raw), const_cast<float*>(m), const_cast<float*>(v), n,
+                     min_opacity, seed, c->mcmc, c->densify_scan};
+    launch_grow(a, n_add, records_out, raw_out, m_out, v_out, max_out, counts_out, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_position_noise_device(gs_ctx* c, float* records, float* raw, uint32_t n, const uint32_t* ids, const uint32_t* count_dev,
+                             uint32_t max_rows, float scale, float gate_k, float gate_x0, uint64_t seed) {
+    if (!c) return GS_ERR_INVALID;
+    if (!records) return refuse(c, __func__, "null records");
+    if (n == 0) return refuse(c, __func__, "n is 0");
+    if (!std::isfinite(scale) || !std::isfinite(gate_k) || !std::isfinite(gate_x0))
+        return refuse(c, __func__, "scale, gate_k and gate_x0 must be finite");
+    if (ids && max_rows && !count_dev) return refuse(c, __func__, "null count with ids and max_rows > 0");
+    if (ids && !max_rows) return GS_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    launch_position_noise(records, raw, n, ids, count_dev, max_rows, scale, gate_k, gate_x0, seed, c->stream);
     return check_launch(c, __func__);
 }
 

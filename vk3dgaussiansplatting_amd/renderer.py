@@ -825,6 +825,39 @@ class Renderer:
             self._ctx.handle, _vp(score_ptr), float(threshold), int(n), _vp(records_ptr), _vp(raw_ptr), _vp(m_ptr), _vp(v_ptr),
             _vp(records_out_ptr), _vp(raw_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr), int(max_out), _vp(counts_ptr)))
 
+    # -- MCMC (no reference counterpart; include/gsplat.h, gs_relocate_device / gs_grow_device / gs_position_noise_device)
+    def relocateDevice(self, records_ptr: int, raw_ptr: int | None, m_ptr: int | None, v_ptr: int | None, n: int,
+                       min_opacity: float, seed: int, ids_out_ptr: int | None, max_rows: int, counts_ptr: int):
+        """3DGS-MCMC relocation in place on records / raw / m / v (n, 84; raw None, m and v None together): every splat with
+        opacity <= min_opacity receives the row of a live one drawn in proportion to its opacity, the opacity and scales of
+        every copy corrected so that the picture stays.  ids_out (max_rows uint32) = the changed rows, ascending; counts (3
+        uint32 on the device) = changed (not truncated), dead, sources -- what uploadRowsDevice takes.  Enqueued on the
+        context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_relocate_device(
+            self._ctx.handle, _vp(records_ptr), _vp(raw_ptr), _vp(m_ptr), _vp(v_ptr), int(n), float(min_opacity),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _vp(ids_out_ptr), int(max_rows), _vp(counts_ptr)))
+
+    def growDevice(self, records_ptr: int, raw_ptr: int | None, m_ptr: int | None, v_ptr: int | None, n: int, min_opacity: float,
+                   seed: int, n_add: int, records_out_ptr: int | None, raw_out_ptr: int | None, m_out_ptr: int | None,
+                   v_out_ptr: int | None, max_out: int, counts_ptr: int):
+        """The cloud grown by n_add rows (gs_grow_device): n_add live splats drawn in proportion to their opacity, every
+        drawn splat's copies beside it in records_out / raw_out / m_out / v_out (max_out, 84) with the relocation values and
+        zero moments, every other row copied bit for bit; counts (2 uint32 on the device) = outputs, sources.  raw, m and v:
+        each None together with its output.  Enqueued on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_grow_device(
+            self._ctx.handle, _vp(records_ptr), _vp(raw_ptr), _vp(m_ptr), _vp(v_ptr), int(n), float(min_opacity),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(n_add), _vp(records_out_ptr), _vp(raw_out_ptr), _vp(m_out_ptr), _vp(v_out_ptr),
+            int(max_out), _vp(counts_ptr)))
+
+    def positionNoiseDevice(self, records_ptr: int, raw_ptr: int | None, n: int, ids_ptr: int | None, count_ptr: int | None,
+                            max_rows: int, scale: float, gate_k: float = 100.0, gate_x0: float = 0.995, seed: int = 0):
+        """3DGS-MCMC exploration noise on the positions of rows ids[i], i < min(count, max_rows) -- every row with ids None --
+        of records and (the same bits) raw: Sigma z of the splat's own covariance, gated by its opacity, times scale (the
+        caller's noise_lr * lr[GS_ADAM_POSITION]).  Enqueued on the context's stream without waiting; needs no scene."""
+        self._ctx.check(_lib.lib().gs_position_noise_device(
+            self._ctx.handle, _vp(records_ptr), _vp(raw_ptr), int(n), _vp(ids_ptr), _vp(count_ptr), int(max_rows), float(scale),
+            float(gate_k), float(gate_x0), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
     # -- several views per optimiser step (no reference counterpart; include/gsplat.h, gs_rows_accumulate_device / gs_rows_collect_device)
     def rowsAccumulateDevice(self, acc_ptr: int, mark_ptr: int, n: int, ids_ptr: int, rows_ptr: int, count_ptr: int, max_rows: int,
                              weight: float = 1.0):
