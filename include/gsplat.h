@@ -465,7 +465,7 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  *   gs_backward_device : the same arguments as DEVICE pointers; enqueued on the context's stream, no host sync.
  * GS_ERR_INVALID with a message in gs_last_error, nothing enqueued: a NULL grad_rgba32f or grad_records, no frame since the
  * last gs_set_resolution, gs_set_tile_rows*, gs_debug_init_sort_list or upload, a GS_RENDER_FAST context, a context that
- * owns a subset of the tile rows, a sharded context (gs_dist_shard_rows). */
+ * owns a subset of the tile rows (unless gs_set_band_gradients is on: see there), a sharded context (gs_dist_shard_rows). */
 int gs_backward(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
 int gs_backward_device(gs_ctx* ctx, const float* grad_rgba32f, const float* grad_depth, float* grad_records);
 
@@ -523,6 +523,45 @@ int gs_backward_visible_device(gs_ctx* ctx, const float* grad_rgba32f, const flo
 #define GS_CAMERA_GRAD_FLOATS 35u   /* [0..15] dL/dview, [16..31] dL/dproj, [32..34] dL/dcam_pos */
 int gs_backward_camera(gs_ctx* ctx, float grad_camera[GS_CAMERA_GRAD_FLOATS]);
 int gs_backward_camera_device(gs_ctx* ctx, float* grad_camera_dev);
+
+/* Gradients of a band of tile rows (no reference counterpart; callers detect the call by its symbol, GS_API_VERSION is
+ * unchanged).  The loss of a frame is a sum over its pixels, so dL/d(record) is a sum over its tile rows: a context that
+ * owns a band (gs_set_tile_rows, any [row_begin, row_end) including the empty one, or gs_set_tile_rows_interleaved)
+ * computes the terms of its own pixels, and the rows of the R bands of a frame, summed, are the frame's gradient.  What a
+ * band context returns is therefore a PARTIAL SUM, not dL/d(record) -- which is why the calls refuse a band until the caller
+ * says so:
+ *   gs_set_band_gradients(ctx, 1) : gs_backward, gs_backward_device, gs_visible_count, gs_backward_visible,
+ *                                   gs_backward_visible_device, gs_backward_camera, gs_backward_camera_device and
+ *                                   gs_contrib_device accept a context that owns a subset of the tile rows;
+ *   gs_set_band_gradients(ctx, 0) : (default) they refuse it with "the context owns a subset of the tile rows".
+ * A host flag: nothing is enqueued or waited for; legal any time after gs_create; survives gs_set_resolution,
+ * gs_set_tile_rows* and uploads.  GS_ERR_INVALID for a NULL ctx (the code alone) and for enable > 1 (with a message).  A
+ * context that owns every row computes the same bits with the flag on as off.  Still refused with their messages, flag on
+ * or off: a sharded context (gs_dist_shard_rows), a GS_RENDER_FAST context, a context without a frame since the last
+ * change, and in a band gs_densify_stats_device (its sqrt(gx^2 + gy^2) and seen += 1 do not decompose over bands: a sum of
+ * norms is not the norm of the sum) and gs_photometric_loss* (the 11 x 11 SSIM window crosses the band's edge).
+ * The contract of a band:
+ *   - Owned pixels: P = the pixels of the owned tile rows that lie in the image.
+ *   - What is read: grad_rgba32f and grad_depth are addressed as for the whole frame, float[H][W][4] and float[H][W], real
+ *     rows, top row first -- also under gs_set_tile_rows_interleaved(.., compact_output = 1).  Only the values at P are read.
+ *   - Dense form: grad_records is the whole frame's gradient with dL/d(outputs) set to zero outside P, in the same
+ *     arithmetic and the same order of sums: per splat, the rows of its list elements in the owned tiles are summed in slot
+ *     order (tile raster order inside its tile box clipped to the owned rows), and the sum goes through the per-splat chain.
+ *     A splat with no element in the band gets an all-zero record.
+ *   - Visible form: V_band = the splats with at least one tile in the owned rows in this frame, ascending g.  ids, count
+ *     and max_rows follow gs_backward_visible's rules, the rows are the dense band rows bit for bit, gs_visible_count
+ *     returns |V_band|.  The union of V_band over the bands of a dealing is V of the whole frame.
+ *   - Camera form: the 35 floats from the band's rows, by the same fixed-shape sum over g < N.
+ *   - Contributions: gs_contrib_device takes the pairs (pixel of P, entry) alone.  The per-element sums are the whole
+ *     frame's bit for bit, S runs over the band's slots in order, and a splat with no pair in the band is not touched.
+ *     wmax and pixels accumulated over the bands of a dealing equal the whole frame's; wsum differs by the association of a
+ *     float32 sum.
+ *   - Overflow: a band whose own list overflowed is differentiated as drawn, by the same slot-below-capacity rule.
+ *   - Reproducibility: bitwise, the same for every sorter, launch shape, tile order and GS_COUNT_* mode.
+ *   - Scratch: as for the whole frame, sized by the band context's own capacity.
+ * Moving the lists of the bands between GPUs is the caller's job; gs_rows_accumulate_device / gs_rows_collect_device sum
+ * lists over different splat sets, and gs_adam_rows*_device / gs_upload_rows_device take the result unchanged. */
+int gs_set_band_gradients(gs_ctx* ctx, uint32_t enable);
 
 /* One optimiser step on the rows gs_backward_visible* lists (no reference counterpart), in two calls that keep no state
  * inside the library: an Adam step on the CALLER's records and moments, and the upload of the changed rows alone.
@@ -753,8 +792,8 @@ int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const f
  * gs_backward_camera_device or gs_densify_stats_device it changes neither result by a bit.
  * GS_ERR_INVALID (message in gs_last_error, nothing enqueued; a NULL ctx: the code alone): everything gs_backward refuses,
  * with its words behind this call's name (no frame since the last gs_set_resolution / gs_set_tile_rows* / upload /
- * gs_debug_init_sort_list, a GS_RENDER_FAST context, a context that owns a subset of the tile rows, a sharded context); a
- * NULL wmax_dev; an n other than the scene's. */
+ * gs_debug_init_sort_list, a GS_RENDER_FAST context, a context that owns a subset of the tile rows unless
+ * gs_set_band_gradients is on, a sharded context); a NULL wmax_dev; an n other than the scene's. */
 int gs_contrib_device(gs_ctx* ctx, uint32_t n, float* wmax_dev, float* wsum_dev, uint32_t* pixels_dev);
 /* gs_prune_below_device: keep(g) = score[g] >= threshold, exactly as written (a NaN score is dropped).  The kept rows of
  * records / raw / m / v (float[n][84], all 84 floats) are copied bit for bit to rows [0, kept) of their outputs, in ascending

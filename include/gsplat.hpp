@@ -164,6 +164,14 @@ public:
         return rc;
     }
 
+    // A context that owns a band of tile rows serves backward*, visibleCount and contribDevice with the terms of its own
+    // pixels (gsplat.h, gs_set_band_gradients): partial sums, which the caller adds up over the bands of the frame.
+    int setBandGradients(bool enable) {
+        const int rc = gs_set_band_gradients(ctx_, enable ? 1u : 0u);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // |V| of the last frame: the splats it rasterised (gsplat.h, gs_visible_count); 0 with error() set on a refusal.
     uint32_t visibleCount() {
         uint32_t count = 0;

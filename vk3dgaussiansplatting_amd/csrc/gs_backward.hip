@@ -1,7 +1,9 @@
 // gs_backward.hip -- gradients of the last GS_RENDER_EXACT frame w.r.t. the uploaded gaussians (gs_backward*,
 // include/gsplat.h), as five launches after the frame's own kernels.  The dense form (gs_backward*: a record gradient for
 // every splat) and the visible form (gs_backward_visible*: for the splats of V = { g : tiles_touched[g] != 0 } alone, with
-// their ids) run the same kernels; where they differ the kernel is a template on VIS:
+// their ids) run the same kernels; where they differ the kernel is a template on VIS.  tiles_touched[g] is everywhere the
+// count of THIS frame, SplatCounts::of (gs_internal.h): in a band of tile rows the stored word of a culled block is stale.
+// A band context (gs_set_band_gradients) runs the same launches over its own tiles: the result is the sum over its pixels.
 //   the per-splat scan of gs_splat_scan.h over BwdSource<VIS> (three launches): offset[g] = sum of tiles_touched over the
 //                   splats before g, the splat-order position of g's first element -- the position InitSortList's truncation
 //                   goes by (k_emit, k_gather_sorted), so an element of the list has offset[g] + (its tile's index in g's box)
@@ -39,11 +41,11 @@ constexpr int kBwdBatch = 64;             // list entries staged per step of k_b
 template <bool VIS>
 struct BwdSource {
     static constexpr uint32_t K = VIS ? 2u : 1u, kPlaced = K, kTotalsFrom = 1u;
-    const uint32_t* touched;
+    SplatCounts frame;
     uint32_t *vis_ids, *ids_out;
     uint32_t max_rows;
     __device__ void counts(uint32_t g, uint32_t (&c)[K]) const {
-        c[0] = touched[g];
+        c[0] = frame.of(g);
         if constexpr (VIS) c[1] = c[0] != 0u ? 1u : 0u;
     }
     __device__ void place(uint32_t g, const uint32_t (&c)[K], const uint32_t (&pos)[K]) const {
@@ -65,7 +67,7 @@ struct BwdBlendArgs : TileListArgs {
     float* rows;                    // [capacity][kRowFloats]
 };
 
-// One 256-thread workgroup per tile, one pixel per lane: the replay of gs_tile_replay.h, then its walk back
+// One 256-thread workgroup per owned tile, one pixel per lane: the replay of gs_tile_replay.h, then its walk back
 __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const BwdBlendArgs a) {
     __shared__ float s_e[kBwdBatch][12];                 // staged entries, with colour and depth
     __shared__ float s_part[4][kBwdBatch][kRowFloats];   // per-wave sums of an entry's row
@@ -178,7 +180,8 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
 static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, hipStream_t stream) {
     const BwdBlendArgs args{{f.sc.raster, f.sorted_id, f.ranges, f.bb.scan.offsets, f.sc.extents, f.fp.capacity},
                             grad_depth ? f.scene.pos : nullptr, reinterpret_cast<const float4*>(grad_rgba), grad_depth, f.bb.rows};
-    hipLaunchKernelGGL(k_bwd_blend, dim3(f.fp.grid_w * f.fp.grid_h), dim3(256), 0, stream, f.fp, args);
+    if (!f.fp.rows_owned) return;                     // an empty band: no tile, no element, no row
+    hipLaunchKernelGGL(k_bwd_blend, replay_grid(f.fp), dim3(256), 0, stream, f.fp, args);
 }
 
 // ---- per splat ----------------------------------------------------------------------------------------------------
@@ -188,7 +191,7 @@ static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const f
 // min(N, max_rows) (|V| lives on the device, in *vis_count) and the threads beyond the count leave.
 template <bool VIS>
 __global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, const SceneBuffers scene,
-                                                           const uint32_t* __restrict__ touched,
+                                                           const SplatCounts counts,
                                                            const uint32_t* __restrict__ offsets,
                                                            const float* __restrict__ rows,
                                                            const uint32_t* __restrict__ vis_ids,
@@ -203,28 +206,28 @@ __global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, 
         g = vis_ids[i];
     } else {
         if (g >= fp.num_gaussians) return;
-        any = touched[g] != 0u;
+        any = counts.of(g) != 0u;
     }
     float row[kRowFloats];
-    splat_row_sum(touched, offsets, rows, g, fp.capacity, row);
+    splat_row_sum(counts, offsets, rows, g, fp.capacity, row);
     bwd_chain<false>(fp, scene, g, any, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats), nullptr);
 }
 
-void launch_slot_offsets(const uint32_t* tiles_touched, uint32_t n, const SplatScan& scan, hipStream_t stream) {
-    launch_splat_scan(BwdSource<false>{tiles_touched, nullptr, nullptr, 0u}, n, scan, nullptr, stream);
+void launch_slot_offsets(const SplatCounts& counts, uint32_t n, const SplatScan& scan, hipStream_t stream) {
+    launch_splat_scan(BwdSource<false>{counts, nullptr, nullptr, 0u}, n, scan, nullptr, stream);
 }
 
 void launch_backward(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, float* grad_records,
                      hipStream_t stream) {
-    launch_slot_offsets(f.sc.tiles_touched, f.fp.num_gaussians, f.bb.scan, stream);
+    launch_slot_offsets(splat_counts_of(f.sc, f.fp), f.fp.num_gaussians, f.bb.scan, stream);
     launch_blend(f, grad_rgba, grad_depth, stream);
     hipLaunchKernelGGL(k_bwd_rowsum_chain<false>, dim3(backward_blocks(f.fp.num_gaussians)), dim3(256), 0, stream, f.fp,
-                       f.scene, f.sc.tiles_touched, f.bb.scan.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);
+                       f.scene, splat_counts_of(f.sc, f.fp), f.bb.scan.offsets, f.bb.rows, nullptr, nullptr, 0u, grad_records);
 }
 
 void launch_backward_visible_scan(const BackwardFrame& f, uint32_t* ids_out, uint32_t max_rows, uint32_t* count_out,
                                   hipStream_t stream) {
-    launch_splat_scan(BwdSource<true>{f.sc.tiles_touched, f.bb.vis_ids, ids_out, max_rows}, f.fp.num_gaussians, f.bb.scan, count_out,
+    launch_splat_scan(BwdSource<true>{splat_counts_of(f.sc, f.fp), f.bb.vis_ids, ids_out, max_rows}, f.fp.num_gaussians, f.bb.scan, count_out,
                       stream);
 }
 
@@ -233,7 +236,7 @@ void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba
     const uint32_t n = f.fp.num_gaussians;
     launch_blend(f, grad_rgba, grad_depth, stream);
     hipLaunchKernelGGL(k_bwd_rowsum_chain<true>, dim3(backward_blocks(n < max_rows ? n : max_rows)), dim3(256), 0, stream,
-                       f.fp, f.scene, f.sc.tiles_touched, f.bb.scan.offsets, f.bb.rows, f.bb.vis_ids, visible_count_of(f.bb),
+                       f.fp, f.scene, splat_counts_of(f.sc, f.fp), f.bb.scan.offsets, f.bb.rows, f.bb.vis_ids, visible_count_of(f.bb),
                        max_rows, grad_rows);
 }
 

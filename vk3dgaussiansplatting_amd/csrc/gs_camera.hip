@@ -36,7 +36,7 @@ __device__ __forceinline__ float wave_sum_f32_to_lane63(float v) {
 
 // Thread g of the grid backward_blocks(N) x 256.  No thread leaves early: every lane takes part in the wave sums.
 __global__ __launch_bounds__(256) void k_bwd_camera_blocks(const FrameParams fp, const SceneBuffers scene,
-                                                            const uint32_t* __restrict__ touched,
+                                                            const SplatCounts counts,
                                                             const uint32_t* __restrict__ offsets,
                                                             const float* __restrict__ rows, float* __restrict__ partials) {
     __shared__ float s_part[4][kCamFloats];
@@ -44,9 +44,9 @@ __global__ __launch_bounds__(256) void k_bwd_camera_blocks(const FrameParams fp,
     float cg[kCamFloats];
 #pragma unroll
     for (int k = 0; k < kCamFloats; ++k) cg[k] = 0.0f;
-    if (g < fp.num_gaussians && touched[g] != 0u) {
+    if (g < fp.num_gaussians && counts.of(g) != 0u) {
         float row[kRowFloats];
-        splat_row_sum(touched, offsets, rows, g, fp.capacity, row);
+        splat_row_sum(counts, offsets, rows, g, fp.capacity, row);
         bwd_chain<true>(fp, scene, g, true, row, nullptr, cg);       // a zero row leaves the zeros
     }
     const int lane = lane_id(), wave = wave_id();
@@ -95,7 +95,7 @@ size_t backward_camera_partial_bytes(uint32_t n) { return (size_t)kCamFloats * b
 
 void launch_backward_camera(const BackwardFrame& f, float* partials, float* grad_camera, hipStream_t stream) {
     const uint32_t blocks = backward_blocks(f.fp.num_gaussians);
-    hipLaunchKernelGGL(k_bwd_camera_blocks, dim3(blocks), dim3(256), 0, stream, f.fp, f.scene, f.sc.tiles_touched,
+    hipLaunchKernelGGL(k_bwd_camera_blocks, dim3(blocks), dim3(256), 0, stream, f.fp, f.scene, splat_counts_of(f.sc, f.fp),
                        f.bb.scan.offsets, f.bb.rows, partials);
     hipLaunchKernelGGL(k_bwd_camera_reduce, dim3(1), dim3(1024), 0, stream, partials, blocks, grad_camera);
 }

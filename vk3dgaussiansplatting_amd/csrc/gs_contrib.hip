@@ -27,7 +27,7 @@ struct ContribBlendArgs : TileListArgs {
 
 }  // namespace
 
-// One 256-thread workgroup per tile, one pixel per lane: the replay of gs_tile_replay.h, every entry reduced over the wave
+// One 256-thread workgroup per owned tile, one pixel per lane: the replay of gs_tile_replay.h, every entry reduced over the wave
 __global__ __launch_bounds__(256) void k_contrib_blend(const FrameParams fp, const ContribBlendArgs a) {
     __shared__ float s_e[kContribBatch][8];                           // staged entries, the prefix alone
     __shared__ uint32_t s_part[4][kContribBatch][kContribRowWords];   // per-wave sum, max, count of an entry
@@ -94,16 +94,16 @@ __global__ __launch_bounds__(256) void k_contrib_blend(const FrameParams fp, con
     zero_rows<kContribRowWords, kContribBatch>(t, a, i0, a.rows);
 }
 
-// Thread g < N combines the rows of splat g in slot order, over the slots below the capacity.  A splat that emits nothing,
-// lies past the capacity or has no pair in the frame leaves without a load or a store on the caller's arrays.
-__global__ __launch_bounds__(256) void k_contrib_rowsum(uint32_t n, uint32_t capacity, const uint32_t* __restrict__ touched,
+// Thread g < N combines the rows of splat g in slot order, over the slots below the capacity.  A splat that emits nothing
+// in this frame (SplatCounts::of), lies past the capacity or has no pair leaves without a load or a store on the caller's arrays.
+__global__ __launch_bounds__(256) void k_contrib_rowsum(uint32_t n, uint32_t capacity, const SplatCounts counts,
                                                          const uint32_t* __restrict__ offsets,
                                                          const uint32_t* __restrict__ rows, float* __restrict__ wmax,
                                                          float* __restrict__ wsum, uint32_t* __restrict__ pixels) {
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n) return;
     const uint64_t o = offsets[g];
-    const uint64_t e = o + touched[g];
+    const uint64_t e = o + counts.of(g);
     const uint64_t stop = e < capacity ? e : capacity;
     float S = 0.0f, M = 0.0f;
     uint64_t count = 0;
@@ -126,9 +126,10 @@ __global__ __launch_bounds__(256) void k_contrib_rowsum(uint32_t n, uint32_t cap
 void launch_contrib(const BackwardFrame& f, const uint32_t* offsets, uint32_t* rows, float* wmax, float* wsum,
                     uint32_t* pixels, hipStream_t stream) {
     const ContribBlendArgs args{{f.sc.raster, f.sorted_id, f.ranges, offsets, f.sc.extents, f.fp.capacity}, rows};
-    hipLaunchKernelGGL(k_contrib_blend, dim3(f.fp.grid_w * f.fp.grid_h), dim3(256), 0, stream, f.fp, args);
+    if (!f.fp.rows_owned) return;                     // an empty band: no pair, nothing of the caller's is touched
+    hipLaunchKernelGGL(k_contrib_blend, replay_grid(f.fp), dim3(256), 0, stream, f.fp, args);
     hipLaunchKernelGGL(k_contrib_rowsum, dim3(backward_blocks(f.fp.num_gaussians)), dim3(256), 0, stream, f.fp.num_gaussians,
-                       f.fp.capacity, f.sc.tiles_touched, offsets, rows, wmax, wsum, pixels);
+                       f.fp.capacity, splat_counts_of(f.sc, f.fp), offsets, rows, wmax, wsum, pixels);
 }
 
 }  // namespace gs

@@ -110,6 +110,7 @@ struct gs_ctx {
     // tile rows of this context: first_row + k * row_stride < row_end, k < rows_owned (FrameParams)
     uint32_t row_begin = 0, row_end = 0, row_stride = 1, first_row = 0, rows_owned = 0;
     bool compact_out = false;
+    bool band_gradients = false;      // gs_set_band_gradients: gs_backward* and gs_contrib_device serve a band of tile rows
     uint32_t capacity = 0, num_sort_bits = 0;
     // what the sort of the owned tiles runs over: compact tile ids, so ceil((32 + bits(T_owned - 1)) / 4) passes
     // (the reference's formula, RadixSort.cpp:203-204, for the context's own tile count)

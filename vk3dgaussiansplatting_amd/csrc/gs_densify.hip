@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_densify_stats(const DensifyStatsArgs a)
     const uint32_t g = a.ids[i];
     if (g >= a.n) return;
     float ds[2];
-    splat_row_sum(a.touched, a.offsets, a.rows, g, a.capacity, ds);
+    splat_row_sum(a.counts, a.offsets, a.rows, g, a.capacity, ds);
     const float gx = ds[0] * 0.5f * (float)a.width, gy = ds[1] * 0.5f * (float)a.height;
     const float norm = sqrtf(gx * gx + gy * gy);
     a.grad_accum[g] = a.grad_accum[g] + norm;

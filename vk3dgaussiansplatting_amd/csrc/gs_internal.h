@@ -331,8 +331,25 @@ struct BackwardBuffers {
 inline const uint32_t* visible_count_of(const BackwardBuffers& bb) { return bb.scan.totals + 1; }
 inline size_t backward_row_bytes(uint32_t capacity) { return (size_t)capacity * kRowFloats * sizeof(float); }
 inline uint32_t backward_blocks(uint32_t n) { return (n + 255u) / 256u; }   // 256 splats per block of the per-splat kernels
-// The frame a backward pass differentiates: its FrameParams (full grid, GS_RENDER_EXACT), the scene, what its forward left
-// (scratch, sorted list, ranges) and the backward's own scratch
+// The tile count of splat g in the last frame, as every kernel behind the frame reads it.  In a contiguous band of tile rows
+// k_band_cull rejects whole project blocks: such a block gets a zero block sum and nothing else, so the tiles_touched (and
+// extents, and raster records) of its 256 splats are whatever an earlier frame on the context left.  A block that runs
+// writes the count of every one of its splats (0 for a skipped wave).  Hence the count of this frame is block_sums[g /
+// kProjThreads] != 0 ? tiles_touched[g] : 0.  Every other frame (the whole grid, interleaved rows) runs every block:
+// block_sums is null there and the count is the stored word, at no cost.
+struct SplatCounts {
+    const uint32_t* touched;          // SplatScratch::tiles_touched
+    const uint32_t* block_sums;       // SplatScratch::block_sums, per kProjThreads splats, or null: no block was culled
+    __device__ __forceinline__ uint32_t of(uint32_t g) const {
+        return block_sums && block_sums[g / (uint32_t)kProjThreads] == 0u ? 0u : touched[g];
+    }
+};
+inline SplatCounts splat_counts_of(const SplatScratch& sc, const FrameParams& fp) {
+    const bool culled = !(fp.row_begin == 0u && fp.row_end == fp.grid_h) && fp.row_stride == 1u;   // launch_project ran k_band_cull
+    return SplatCounts{sc.tiles_touched, culled ? sc.block_sums : nullptr};
+}
+// The frame a backward pass differentiates: its FrameParams (GS_RENDER_EXACT; the whole grid, or the tile rows of a band
+// context), the scene, what its forward left (scratch, sorted list, ranges) and the backward's own scratch
 struct BackwardFrame {
     FrameParams fp;
     SceneBuffers scene;
@@ -353,7 +370,7 @@ void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba
                                   uint32_t max_rows, float* grad_rows, hipStream_t stream);
 // The slot offsets alone (row 0 of the scan, what launch_backward runs first): scan.offsets[g] = the first slot of splat g.
 // Over the buffers of a backward's scan it rewrites the values that are there and leaves V and |V| alone.
-void launch_slot_offsets(const uint32_t* tiles_touched, uint32_t n, const SplatScan& scan, hipStream_t stream);
+void launch_slot_offsets(const SplatCounts& counts, uint32_t n, const SplatScan& scan, hipStream_t stream);
 // gs_contrib_device (gs_contrib.hip): a row {sum, max, count} of the blend weights of one list element, in its slot
 constexpr int kContribRowWords = 3;
 inline size_t contrib_row_bytes(uint32_t capacity) { return (size_t)capacity * kContribRowWords * sizeof(uint32_t); }
@@ -405,7 +422,7 @@ struct DensifyStatsArgs {
     const uint32_t* ids;
     const uint32_t* count;
     uint32_t max_rows, n;
-    const uint32_t* touched;          // SplatScratch::tiles_touched
+    SplatCounts counts;               // splat_counts_of(the frame's scratch)
     const uint32_t* offsets;          // BackwardBuffers::scan.offsets
     const float* rows;                // BackwardBuffers::rows
     const SplatRaster* raster;

@@ -101,15 +101,15 @@ __device__ __forceinline__ float logit_opacity(float o) {
 }
 
 // The first COLS columns of splat g's rows (BackwardBuffers::rows) summed in slot order, from 0.0f, over the slots below the
-// capacity; zero for a splat that emits nothing.  Only the summed columns are read.
+// capacity; zero for a splat that emits nothing in this frame (SplatCounts::of).  Only the summed columns are read.
 template <int COLS>
-__device__ __forceinline__ void splat_row_sum(const uint32_t* __restrict__ touched, const uint32_t* __restrict__ offsets,
+__device__ __forceinline__ void splat_row_sum(const SplatCounts& counts, const uint32_t* __restrict__ offsets,
                                               const float* __restrict__ rows, uint32_t g, uint32_t capacity,
                                               float (&acc)[COLS]) {
 #pragma unroll
     for (int k = 0; k < COLS; ++k) acc[k] = 0.0f;
     const uint64_t o = offsets[g];
-    const uint64_t e = o + touched[g];
+    const uint64_t e = o + counts.of(g);
     const uint64_t stop = e < capacity ? e : capacity;
     for (uint64_t s = o; s < stop; ++s) {
         const float* r = rows + s * kRowFloats;

@@ -1,6 +1,7 @@
 // gs_tile_replay.h -- what the kernels that replay the blend of a GS_RENDER_EXACT frame evaluate alike, each written once
-// (device): k_bwd_blend of gs_backward.hip and k_contrib_blend of gs_contrib.hip.  One 256-thread workgroup per tile of a
-// full grid, one pixel per lane; the tile's list entries are staged in LDS a batch at a time and every pixel walks them
+// (device): k_bwd_blend of gs_backward.hip and k_contrib_blend of gs_contrib.hip.  One 256-thread workgroup per tile the
+// context owns (the whole grid, or the tile rows of a band: replay_grid), one pixel per lane; the tile's list entries are
+// staged in LDS a batch at a time and every pixel walks them
 // front to back in the EXACT arithmetic of RenderGaussians.comp:112-142 (same expressions, same pinned exp), so a replay
 // makes the forward's decision for every (entry, pixel) pair -- the entry contributes or not, the pixel stops on it or
 // not -- because it calls the same functions.  What a kernel does with a pair, its loop over the batches and the row it
@@ -30,19 +31,28 @@ struct TileListArgs {
     uint32_t capacity;
 };
 
-// The workgroup's tile and this thread's pixel of it (wave w: pixel rows 4 w .. 4 w + 3)
+// The workgroup's tile and this thread's pixel of it (wave w: pixel rows 4 w .. 4 w + 3).  A launch is replay_grid(fp):
+// grid_w x rows_owned workgroups, dispatched in the raster order of the owned tiles.  Workgroup (x, k) takes column x of the
+// k-th owned row, which is row first_row + k * row_stride of the grid (global_tile of gs_render.hip; the identity for a
+// context that owns every row).  ranges[] and the pixels go by the row of the grid, the slot by k (SplatScratch::extents
+// holds compact rows).  Two grid dimensions, not one divided by grid_w: the load of the tile's range, which everything
+// waits for, then hangs on a multiply-add of kernel arguments instead of on the division (with it k_bwd_blend measured
+// 2 % slower at config C, profiles/band_backward_cost.txt).
 struct TilePixel {
     int tid, lane, wave;
-    uint32_t tx, ty, start, end;    // the tile and its range of the list
+    uint32_t tx, ty, start, end;    // the tile (ty: its row of the grid) and its range of the list
+    uint32_t ky;                    // the row's index among the owned rows
     uint32_t px, py;
     bool inside;                    // the pixel lies in the frame
     float fpx, fpy;
 };
+inline dim3 replay_grid(const FrameParams& fp) { return dim3(fp.grid_w, fp.rows_owned); }   // rows_owned == 0 (an empty band): no launch
 __device__ __forceinline__ TilePixel tile_pixel(const FrameParams& fp, const uint32_t* ranges) {
     TilePixel t;
     t.tid = threadIdx.x; t.lane = t.tid & 63; t.wave = t.tid >> 6;
-    const uint32_t tile = blockIdx.x;                                // a full grid: compact id == global id
-    t.ty = tile / fp.grid_w; t.tx = tile % fp.grid_w;
+    t.tx = blockIdx.x; t.ky = blockIdx.y;
+    t.ty = fp.first_row + t.ky * fp.row_stride;
+    const uint32_t tile = t.ty * fp.grid_w + t.tx;
     t.start = ranges[tile * 2 + 0]; t.end = ranges[tile * 2 + 1];
     t.px = t.tx * kTile + (uint32_t)(t.tid & 15); t.py = t.ty * kTile + (uint32_t)(t.tid >> 4);
     t.inside = t.px < fp.width && t.py < fp.height;
@@ -50,12 +60,12 @@ __device__ __forceinline__ TilePixel tile_pixel(const FrameParams& fp, const uin
     return t;
 }
 
-// The slot of splat gi's list element in tile (tx, ty): its offset + the tile's raster index inside its box
+// The slot of splat gi's list element in column tx of owned row ky: its offset + the tile's raster index inside its box
 __device__ __forceinline__ uint32_t entry_slot(const uint32_t* offsets, const uint2* extents, uint32_t gi, uint32_t tx,
-                                               uint32_t ty, uint32_t capacity) {
+                                               uint32_t ky, uint32_t capacity) {
     const uint2 ext = extents[gi];
     const uint32_t min_x = ext.x & 0xFFFFu, k0 = ext.x >> 16, max_x = ext.y & 0xFFFFu;
-    const uint64_t slot = (uint64_t)offsets[gi] + (uint64_t)(ty - k0) * (max_x - min_x) + (tx - min_x);
+    const uint64_t slot = (uint64_t)offsets[gi] + (uint64_t)(ky - k0) * (max_x - min_x) + (tx - min_x);
     return slot < capacity ? (uint32_t)slot : kNoSlot;
 }
 
@@ -78,7 +88,7 @@ __device__ __forceinline__ void stage_entries(float (*s_e)[WIDTH], const TilePix
             acc = acc + fp.view[14] * 1.0f;
             z = -acc;
         }
-        const uint32_t slot = entry_slot(a.offsets, a.extents, gi, t.tx, t.ty, a.capacity);
+        const uint32_t slot = entry_slot(a.offsets, a.extents, gi, t.tx, t.ky, a.capacity);
         float* e = s_e[t.tid];
         e[kEntSx] = r0.x; e[kEntSy] = r0.y; e[kEntIx] = r0.z; e[kEntIy] = r0.w; e[kEntIz] = r1.x;
         e[kEntAlpha0] = r2.x;
@@ -119,7 +129,7 @@ __device__ __forceinline__ void zero_rows(const TilePixel& t, const TileListArgs
     for (; i0 < t.end; i0 += BATCH) {
         const uint32_t cnt = t.end - i0 < (uint32_t)BATCH ? t.end - i0 : (uint32_t)BATCH;
         if ((uint32_t)t.tid < cnt) {
-            const uint32_t slot = entry_slot(a.offsets, a.extents, a.sorted_id[i0 + t.tid], t.tx, t.ty, a.capacity);
+            const uint32_t slot = entry_slot(a.offsets, a.extents, a.sorted_id[i0 + t.tid], t.tx, t.ky, a.capacity);
             if (slot != kNoSlot) {
                 Word* row = rows + (size_t)slot * WORDS;
 #pragma unroll

@@ -38,10 +38,13 @@ bool overlap(const Span& a, const Span& b) {
 }
 
 // The context holds a whole frame: not sharded (that refusal ends in sharded_tail), `ready` (else not_ready), all tile rows
-int check_whole_frame(gs_ctx* c, const char* who, const char* sharded_tail, bool ready = true, const char* not_ready = "") {
+// -- or, with band_ok, the rows of a band whose caller has opted in (gs_set_band_gradients)
+int check_whole_frame(gs_ctx* c, const char* who, const char* sharded_tail, bool ready = true, const char* not_ready = "",
+                      bool band_ok = false) {
     if (c->dist_sharded) return refuse(c, who, std::string("a sharded context (gs_dist_shard_rows) ") + sharded_tail);
     if (!ready) return refuse(c, who, not_ready);
-    if (c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u)
+    const bool band = c->row_begin != 0u || c->row_end != c->grid_h || c->row_stride != 1u;
+    if (band && !(band_ok && c->band_gradients))
         return refuse(c, who, "the context owns a subset of the tile rows");
     return GS_OK;
 }
@@ -97,17 +100,18 @@ hipError_t alloc_splat_scan(DeviceOwner& mem, SplatScan& s, uint32_t n, uint32_t
     return e;
 }
 
-// what gs_backward* and gs_contrib_device refuse of the context (nothing enqueued)
-int backward_refusals(gs_ctx* c, const char* who) {
+// what gs_backward* and gs_contrib_device refuse of the context (nothing enqueued); band_ok: the call's result decomposes
+// over the tile rows, so a band context with gs_set_band_gradients on is served
+int backward_refusals(gs_ctx* c, const char* who, bool band_ok = true) {
     if (c->cfg.render_mode != GS_RENDER_EXACT) return refuse(c, who, "only GS_RENDER_EXACT frames can be differentiated");
     const bool frame = c->capacity && c->n && c->last.differentiable;
     const char* no_frame = "no frame since the last gs_set_resolution, gs_set_tile_rows* or upload";
-    return check_whole_frame(c, who, "cannot be differentiated", frame, no_frame);
+    return check_whole_frame(c, who, "cannot be differentiated", frame, no_frame, band_ok);
 }
 
 // the refusals, then the scratch of the first call
-int backward_prepare(gs_ctx* c, const char* who) {
-    if (int r = backward_refusals(c, who)) return r;
+int backward_prepare(gs_ctx* c, const char* who, bool band_ok = true) {
+    if (int r = backward_refusals(c, who, band_ok)) return r;
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->bwd.rows) {
         DeviceOwner& mem = c->bwd_mem;
@@ -459,6 +463,13 @@ int gs_reset_opacity_raw_device(gs_ctx* c, float* raw_dev, float* records_dev, f
     return check_launch(c, __func__);
 }
 
+int gs_set_band_gradients(gs_ctx* c, uint32_t enable) {
+    if (!c) return GS_ERR_INVALID;
+    if (enable > 1u) return refuse(c, __func__, "enable must be 0 or 1");
+    c->band_gradients = enable != 0u;
+    return GS_OK;
+}
+
 int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");
@@ -584,7 +595,7 @@ int gs_contrib_device(gs_ctx* c, uint32_t n, float* wmax_dev, float* wsum_dev, u
     }
     if (e != hipSuccess) return refuse(c, __func__, hipGetErrorString(e), GS_ERR_HIP);
     const SplatScan& scan = own_scan ? c->contrib_scan : c->bwd.scan;
-    launch_slot_offsets(c->scratch.tiles_touched, c->n, scan, c->stream);
+    launch_slot_offsets(splat_counts_of(c->scratch, c->last.fp), c->n, scan, c->stream);
     launch_contrib(backward_frame(c), scan.offsets, c->contrib_rows, wmax_dev, wsum_dev, pixels_dev, c->stream);
     return check_launch(c, __func__);
 }
@@ -625,12 +636,12 @@ int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* 
     if (!c) return GS_ERR_INVALID;
     const char* rows = "ids, count, grad_accum, seen or max_radius";
     if (int r = check_row_arrays(c, __func__, max_rows, {ids_dev, count_dev, grad_accum, seen, max_radius}, rows)) return r;
-    if (int r = backward_prepare(c, __func__)) return r;
+    if (int r = backward_prepare(c, __func__, false)) return r;      // a norm and a count per frame: no sum over bands
     if (!c->last.has_backward) return refuse(c, __func__, "no gs_backward* on this frame");
     if (n != c->n) return refuse(c, __func__, "n differs from the scene's");
     if (!max_rows) return GS_OK;
     const FrameParams& fp = c->last.fp;
-    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, c->scratch.tiles_touched, c->bwd.scan.offsets, c->bwd.rows,
+    const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, splat_counts_of(c->scratch, c->last.fp), c->bwd.scan.offsets, c->bwd.rows,
                              c->scratch.raster, fp.capacity, fp.width, fp.height, grad_accum, seen, max_radius};
     launch_densify_stats(a, c->stream);
     return check_launch(c, __func__);

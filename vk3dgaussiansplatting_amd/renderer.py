@@ -495,6 +495,12 @@ class Renderer:
         rank's strip (owned rows packed) instead of addressing the whole frame."""
         self._ctx.check(_lib.lib().gs_set_tile_rows_interleaved(self._ctx.handle, phase, stride, int(compact_output)))
 
+    def setBandGradients(self, enable: bool = True):
+        """gs_set_band_gradients: with it on, a renderer that owns a band of tile rows (setTileRows*) serves backward*,
+        visibleCount, backwardCamera* and contribDevice with the terms of its own pixels -- partial sums over the frame's tile
+        rows, which the caller adds up over the bands (rowsAccumulateDevice / rowsCollectDevice).  Off (the default): refused."""
+        self._ctx.check(_lib.lib().gs_set_band_gradients(self._ctx.handle, 1 if enable else 0))
+
     @staticmethod
     def _camera_args(cam: Camera):
         """view, proj, pos and sh_mode of a Camera, as _launch takes them."""
