@@ -191,6 +191,10 @@ typedef struct gs_scene_info {
 #define GS_BUF_UNSORTED_DEPTH 8
 #define GS_BUF_UNSORTED_ID 9
 #define GS_BUF_IMAGE 10        /* uint8[H][W][4]             internal framebuffer */
+#define GS_BUF_RASTER_OPACITY 11 /* float[N]                 the opacity RenderGaussians multiplied in the last frame: of every
+                                                             splat that emitted an element its raster opacity (the scene's, 0 where
+                                                             the 2 x 2 determinant vanishes, times the anti-aliasing factor under
+                                                             gs_set_antialias), 0 for every other splat */
 
 /* GS_API_VERSION of the library that is actually loaded: compare with the header's before anything else
  * (gsplat.hpp and the Python binding do). */
@@ -454,7 +458,9 @@ int gs_output_device(gs_ctx* ctx, uint32_t which, void** dev_out, size_t* bytes)
  * every discrete decision held fixed -- the near-plane and NDC culls, tile boxes, depth keys and the sorted order; which
  * entries a pixel blends (f > 0 or alpha < 1/255 skip) and the entry it stops on (nextT < 1e-4, RenderGaussians.comp:127-140);
  * det == 0 (opacity 0: no gradient); max(colour, 0) in getShColor (no derivative where the colour is below 0); the
- * IN_VIEW_LIMIT clamp of x/z and y/z in getCovarianceMatrix (Common.glsl:60-63: a clamped ratio passes no derivative).  A
+ * IN_VIEW_LIMIT clamp of x/z and y/z in getCovarianceMatrix (Common.glsl:60-63: a clamped ratio passes no derivative); in
+ * an anti-aliased frame (gs_set_antialias) the floor under det0 / det and the cap at 1 (there the factor is a constant,
+ * sqrt(2.5e-5) or 1: the opacity gets its share, the covariance nothing).  A
  * frame whose list overflowed (GS_WARN_OVERFLOW) is differentiated as drawn, truncated.  The frame's sorted list, ranges
  * and raster records must still be in HBM (they are until the next frame on the context); the scene's current planes are
  * read.  Bitwise reproducible: no float atomics, the rows of a splat summed in a fixed order -- the same gradients for
@@ -562,6 +568,38 @@ int gs_backward_camera_device(gs_ctx* ctx, float* grad_camera_dev);
  * Moving the lists of the bands between GPUs is the caller's job; gs_rows_accumulate_device / gs_rows_collect_device sum
  * lists over different splat sets, and gs_adam_rows*_device / gs_upload_rows_device take the result unchanged. */
 int gs_set_band_gradients(gs_ctx* ctx, uint32_t enable);
+
+/* Anti-aliased frames (no reference counterpart: the reference adds 0.3 px^2 to the 2-D covariance, Common.glsl:72-75, and
+ * blends the splat at its full opacity; this is the opacity compensation of the INRIA trainer's --antialiasing, gsplat's
+ * rasterize_mode = "antialiased" and Mip-Splatting's 2-D filter.  Callers detect the call by its symbol, GS_API_VERSION is
+ * unchanged).  With the flag on, the opacity RenderGaussians multiplies for a splat that emits an element and whose dilated
+ * determinant is not zero is, in float32 and in this order,
+ *     det0 = a0 * c0 - b0 * b0            a0, b0, c0: the 2-D covariance BEFORE its 0.3 dilation
+ *     r    = det0 / det                   det: the determinant of the dilated covariance, as the frame has it
+ *     rho  = sqrt(r > 2.5e-5 ? min(r, 1) : 2.5e-5)        (the INRIA floor; a NaN r takes the floor)
+ *     raster opacity = opacity * rho
+ * (r <= 1 for every covariance; the cap acts only where both determinants of a needle are float32 cancellation noise below
+ * zero and their ratio comes out above 1, so that no splat is ever blended above its own opacity)
+ * so a splat much smaller than a pixel, which the dilation blows up to about a pixel, is dimmed by the ratio of the areas
+ * instead of being drawn as opaque as before.  Nothing else of a frame changes: covariance (GS_BUF_COV), conic, radius, tile
+ * box, depth key, colour and the det == 0 rule (opacity 0) are the plain frame's, hence so are the sorted list and the
+ * ranges; GS_BUF_COLOR's alpha stays the scene's opacity; GS_BUF_RASTER_OPACITY shows the compensated value.  Both render
+ * modes, every sorter and every launch shape are covered (they read the raster record).
+ * Equivalence: a frame of records R with the flag on equals, in every output, the frame with the flag off of R' = R with
+ * float 15 (the opacity) of every record replaced by its GS_BUF_RASTER_OPACITY.
+ * Gradients (gs_backward*, gs_backward_camera*, bands included) are those of the frame as it was drawn: the record's opacity
+ * receives dL/d(raster opacity) * rho, and above the floor dL/d(raster opacity) * opacity flows through r into the
+ * covariance, i.e. into scale, rotation, position and the view block; dL/dproj and dL/dcam_pos do not depend on rho.  At the
+ * floor rho is a constant (see the boundary convention of gs_backward).  gs_contrib_device replays with the raster opacity.
+ * gs_relocate_device / gs_grow_device correct the opacity and scale of copies so that the plain frame's picture stays; with
+ * the flag on that correction is only approximate (the copies' rho differs from the source's).
+ * A host flag per CONTEXT, not per scene (two contexts that share a scene may differ), 0 by default, legal any time after
+ * gs_create; it survives gs_set_resolution, gs_set_tile_rows*, gs_set_outputs and uploads; nothing is enqueued or waited
+ * for.  It does not invalidate the last frame: gs_backward*, gs_backward_camera* and gs_contrib_device work on the frame as
+ * it was drawn, whatever the flag says by then; the next frame uses the new value.  With the flag off every frame, list and
+ * gradient is bit for bit what it is without this call.  GS_ERR_INVALID for a NULL ctx (the code alone) and for enable > 1
+ * (with a message; the flag stays as it was). */
+int gs_set_antialias(gs_ctx* ctx, uint32_t enable);
 
 /* One optimiser step on the rows gs_backward_visible* lists (no reference counterpart), in two calls that keep no state
  * inside the library: an Adam step on the CALLER's records and moments, and the upload of the changed rows alone.

@@ -172,6 +172,14 @@ public:
         return rc;
     }
 
+    // Anti-aliased frames (gsplat.h, gs_set_antialias): from the next frame on every splat is blended at its opacity times
+    // sqrt(det S / det(S + 0.3 I)), S its 2-D covariance before the dilation.  A host flag of this context.
+    int setAntialias(bool enable) {
+        const int rc = gs_set_antialias(ctx_, enable ? 1u : 0u);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // |V| of the last frame: the splats it rasterised (gsplat.h, gs_visible_count); 0 with error() set on a refusal.
     uint32_t visibleCount() {
         uint32_t count = 0;

@@ -1,0 +1,355 @@
+"""Anti-aliased frames (include/gsplat.h, gs_set_antialias) on the CPU.  The oracle cannot draw one, so everything here leans
+on the equivalence the definition implies: the anti-aliased frame of records R is the plain frame of R' = R with every opacity
+multiplied by rho = sqrt(max(det S / det(S + 0.3 I), 2.5e-5)), S the 2-D covariance before its dilation.  rho64 is the float64
+torch restatement of that factor (differentiable in the records and in the view matrix); the composed reference builds the
+anti-aliased gradient from the plain frame's reference gradient at R' and the chain rule through rho64.  Trusted by: rho64
+against its own central differences, the composed reference against central differences of the oracle-drawn loss, the
+designed scene holding what it claims, and the resolution claim on oracle frames.  tests/test_antialias_gpu.py shares the
+helpers."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from test_outputs_cpu import load_scene, oracle_params, reference_outputs
+from test_backward_cpu import frame_decisions, frozen_of, reference_gradient, screen_splat
+
+torch = pytest.importorskip("torch")
+
+FLOOR = float(np.float32(2.5e-5))          # kAntialiasFloor as the kernels hold it
+GEOMETRY = [0, 1, 2, 4, 5, 6, 8, 9, 10, 11]           # position, scale, rotation: the fields rho depends on
+
+# Largest relative deviation of rho32 (float32 NumPy) from rho64 over the compared splats of subpixel, ragged and ragged@pose,
+# as test_float32_restatement_deviation measures it; the GPU's read-back is allowed four times that (its association of the
+# covariance products differs from NumPy's).
+RHO32_DEVIATION = 3.3e-6
+
+
+def _view_tensor(p):
+    return torch.tensor(np.array(p.view, np.float64))
+
+
+def rho64(rec, view, p):
+    """(rho, r) of every record: forward64's projection of the 3-D covariance (test_backward_cpu.forward64, lines 123-148)
+    without the 0.3, r = det0 / det, rho = sqrt(clamp(r, min=FLOOR)).  rec: torch float64 [N, 84]; view: torch float64 [16],
+    column-major as gs_render takes it, or [N, 16], a copy of its own for every record; both may require grad."""
+    w, h = p.width, p.height
+    V = view.reshape(-1, 4, 4).transpose(1, 2)                            # V[.][r][c] = view[c * 4 + r]
+    pos = rec[:, 0:3]
+    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
+    vp = (V @ torch.cat([pos, ones], 1)[:, :, None])[:, :, 0]
+    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
+    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
+                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
+                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
+    M = R * rec[:, None, 4:7]
+    Sig = M @ M.transpose(1, 2)
+    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
+    tan_x = tan_y * w / h
+    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
+    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
+    tz = vp[:, 2]
+    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
+    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
+    zero = torch.zeros_like(tz)
+    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
+                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
+    T = J @ V[:, :3, :3]
+    S2 = T @ Sig @ T.transpose(1, 2)
+    a0, b0, c0 = S2[:, 0, 0], S2[:, 1, 0], S2[:, 1, 1]
+    det0 = a0 * c0 - b0 * b0
+    det = (a0 + 0.3) * (c0 + 0.3) - b0 * b0
+    ratio = det0 / det
+    return torch.sqrt(torch.clamp(ratio, min=FLOOR)), ratio
+
+
+def rho64_numpy(p, aos):
+    """(rho, r) as float64 arrays."""
+    with torch.no_grad():
+        rho, r = rho64(torch.tensor(np.asarray(aos, np.float64)), _view_tensor(p), p)
+    return rho.numpy(), r.numpy()
+
+
+def rho32(p, aos):
+    """The frame's expressions for rho in float32 NumPy: every intermediate rounded to float32, products summed left to right."""
+    f = np.float32
+    a = np.asarray(aos, np.float32)
+    w, h = f(p.width), f(p.height)
+    view = np.array(p.view, np.float32)
+    W = view.reshape(4, 4).T[:3, :3]                                       # W[r][c]
+    vp = [((view[0 + k] * a[:, 0] + view[4 + k] * a[:, 1]) + view[8 + k] * a[:, 2]) + view[12 + k] * f(1) for k in range(3)]
+    r, x, y, z = a[:, 8], a[:, 9], a[:, 10], a[:, 11]
+    two, one = f(2), f(1)
+    R = [[one - two * y * y - two * z * z, two * x * y + two * r * z, two * x * z - two * r * y],
+         [two * x * y - two * r * z, one - two * x * x - two * z * z, two * y * z + two * r * x],
+         [two * x * z + two * r * y, two * y * z - two * r * x, one - two * x * x - two * y * y]]
+    M = [[R[i][k] * a[:, 4 + k] for k in range(3)] for i in range(3)]
+    Sig = [[(M[i][0] * M[j][0] + M[i][1] * M[j][1]) + M[i][2] * M[j][2] for j in range(3)] for i in range(3)]
+    tan_y = f(np.tan(np.float64(f(p.fov_y) * f(0.5))))
+    tan_x = tan_y * w / h
+    fx, fy = w / (two * tan_x), h / (two * tan_y)
+    lim_x, lim_y = tan_x * f(p.in_view_limit), tan_y * f(p.in_view_limit)
+    with np.errstate(all="ignore"):
+        tz = vp[2]
+        pvx = np.clip(vp[0] / tz, -lim_x, lim_x) * tz
+        pvy = np.clip(vp[1] / tz, -lim_y, lim_y) * tz
+        J = [[fx / tz, None, -(fx * pvx) / (tz * tz)], [None, fy / tz, -(fy * pvy) / (tz * tz)]]
+        T = [[J[0][0] * W[0][c] + J[0][2] * W[2][c] for c in range(3)], [J[1][1] * W[1][c] + J[1][2] * W[2][c] for c in range(3)]]
+        TS = [[(T[i][0] * Sig[0][c] + T[i][1] * Sig[1][c]) + T[i][2] * Sig[2][c] for c in range(3)] for i in range(2)]
+        a0 = (TS[0][0] * T[0][0] + TS[0][1] * T[0][1]) + TS[0][2] * T[0][2]
+        b0 = (TS[1][0] * T[0][0] + TS[1][1] * T[0][1]) + TS[1][2] * T[0][2]
+        c0 = (TS[1][0] * T[1][0] + TS[1][1] * T[1][1]) + TS[1][2] * T[1][2]
+        det0 = a0 * c0 - b0 * b0
+        det = (a0 + f(0.3)) * (c0 + f(0.3)) - b0 * b0
+        ratio = det0 / det
+        rho = np.sqrt(np.where(ratio > f(FLOOR), np.minimum(ratio, f(1)), f(FLOOR)))
+    assert rho.dtype == np.float32
+    return rho
+
+
+def compared(scene, aos, r64):
+    """The splats whose factor the value checks compare: r outside [FLOOR / 2, 2 FLOOR] (inside, float32 and float64 may sit on
+    different sides of the floor), and not a zero_det needle (frozen_of)."""
+    return ~frozen_of(scene, aos) & ~((r64 >= FLOOR / 2) & (r64 <= 2 * FLOOR))
+
+
+# ---- the designed scene ---------------------------------------------------------------------------------------------------
+
+SUBPIXEL_SIGMAS = (0.005, 0.02, 0.05, 0.1, 0.3, 1.0, 3.0, 20.0)
+SUBPIXEL_OPACITIES = (1.0, 0.6, 0.15)
+
+
+def subpixel_scene(oracle):
+    """96 x 64 (6 x 4 tiles): round splats of SUBPIXEL_SIGMAS pixels (before the dilation) in SUBPIXEL_OPACITIES, each size on a
+    tile centre, on a tile corner and within a third of a pixel of the frame's edge; the larger a splat the deeper it lies.
+    Returns (aos, w, h, sigma of every record)."""
+    w, h = 96, 64
+    rec, sig = [], []
+    k = 0
+    for i, s in enumerate(SUBPIXEL_SIGMAS):
+        for j, o in enumerate(SUBPIXEL_OPACITIES):
+            n = i * len(SUBPIXEL_OPACITIES) + j
+            centre = ((n % 6) * 16 + 8.0, ((n // 6) % 4) * 16 + 8.0)
+            corner = ((1 + n % 5) * 16.0, (1 + (n // 5) % 3) * 16.0)
+            edge = [(0.25, 5.0 + 2.3 * n), (w - 0.3, 6.0 + 2.3 * n), (5.0 + 3.6 * n, 0.25), (7.0 + 3.6 * n, h - 0.3)][n % 4]
+            for sx, sy in (centre, corner, edge):
+                z = 2.0 + 0.3 * i + 0.01 * (k % 9)
+                rec.append(screen_splat(oracle, w, h, sx, sy, z, s, o, colour=(0.6 - 0.1 * i, -0.3 + 0.1 * j, 0.2 * (k % 3))))
+                sig.append(s)
+                k += 1
+    return np.stack(rec).astype(np.float32), w, h, np.array(sig)
+
+
+def load_antialias_scene(oracle, name):
+    """load_scene plus 'subpixel' and 'extreme' (test_backward_gpu.extreme_cloud): (aos, w, h, cam)."""
+    if name == "subpixel":
+        return subpixel_scene(oracle)[:3] + ({},)
+    if name == "extreme":
+        from vk3dgaussiansplatting_amd import synth
+        aos = synth.generate(400, 96, 64, -2.0, seed=23)                   # extreme_cloud, restated: that module needs a GPU mark
+        aos[0:40, 15] = 0.0
+        aos[40:80, 15] = 1.0
+        aos[80:100, 8:12] = 0.0
+        aos[100:120, 4:7] = 0.0
+        aos[120:130, 4] = 0.0
+        return aos, 96, 64, {}
+    return load_scene(name)
+
+
+def compensated(aos, rho):
+    """R': the records with float 15 multiplied by rho (float64 product rounded once to float32)."""
+    out = np.array(aos, np.float32, copy=True)
+    out[:, 15] = (np.asarray(aos, np.float64)[:, 15] * rho).astype(np.float32)
+    return out
+
+
+# ---- the composed reference -----------------------------------------------------------------------------------------------
+
+def composed_reference(p, aos, aos_prime, ref_prime, flags_prime, w_rgba, w_depth=None, frozen=None):
+    """dL/d(record) [N, 84] of the anti-aliased frame of `aos`, and every splat's term of dL/dview [N, 16] through rho alone:
+    G' = the plain frame's reference gradient at R' = aos_prime (its frame and decisions: ref_prime, flags_prime); column 15
+    times rho64; G'[:, 15] * opacity * d rho64 / d(record) added to the position, scale and rotation columns; the SH columns
+    as they are.  Frozen splats (zero in G') stay out of rho64 too.  Returns (gradient, view terms, G')."""
+    gp = reference_gradient(p, aos_prime, ref_prime, flags_prime, w_rgba, w_depth, frozen)
+    live = np.flatnonzero(~np.asarray(frozen, bool)) if frozen is not None else np.arange(len(aos))
+    rec = torch.tensor(np.asarray(aos, np.float64)[live], requires_grad=True)
+    views = _view_tensor(p).expand(len(live), 16).clone().requires_grad_(True)
+    rho, _ = rho64(rec, views, p)
+    carry = torch.tensor((gp[:, 15] * np.asarray(aos, np.float64)[:, 15])[live])
+    (carry * rho).sum().backward()
+    out = gp.copy()
+    out[live, 15] = gp[live, 15] * rho.detach().numpy()
+    out[np.ix_(live, GEOMETRY)] += rec.grad.numpy()[:, GEOMETRY]
+    view_terms = np.zeros((len(aos), 16))
+    view_terms[live] = views.grad.numpy()
+    return out, view_terms, gp
+
+
+# ---- tests ----------------------------------------------------------------------------------------------------------------
+
+def test_subpixel_scene_holds_what_it_claims(oracle_mod):
+    """On rho64: a splat with r below a quarter of the floor, one with rho > 0.99, one with opacity * rho < 1 / 255 (never
+    blended) and one with 1 / 255 < opacity * rho < 2 / 255; every size on a tile centre, a tile corner and the frame's edge,
+    all inside the frame and emitting in the oracle's plain frame."""
+    aos, w, h, sig = subpixel_scene(oracle_mod)
+    p = oracle_params(oracle_mod, w, h)
+    rho, r = rho64_numpy(p, aos)
+    orho = aos[:, 15].astype(np.float64) * rho
+    assert np.any(r < FLOOR / 4) and np.any(rho > 0.99)
+    assert np.any(orho < 1 / 255) and np.any((orho > 1 / 255) & (orho < 2 / 255))
+    assert np.all(rho[r < FLOOR] == np.sqrt(FLOOR)) and np.all((rho > 0) & (rho < 1))
+    assert compared("subpixel", aos, r).sum() >= len(aos) - 9         # at most one size sits in the band around the floor
+    ref = oracle_mod.full_pipeline(p, aos)
+    assert np.all(ref["stage1"]["splats"]["visible"] != 0)
+    for s in SUBPIXEL_SIGMAS:
+        assert np.count_nonzero(sig == s) == 3 * len(SUBPIXEL_OPACITIES)
+    # the ideal round splat: rho = sigma^2 / (sigma^2 + 0.3) above the floor
+    big = sig >= 0.05
+    np.testing.assert_allclose(rho[big], sig[big] ** 2 / (sig[big] ** 2 + 0.3), rtol=2e-2)
+
+
+@pytest.mark.parametrize("scene", ["subpixel", "ragged@pose"])
+def test_rho64_matches_its_central_differences(oracle_mod, scene):
+    """autograd of L = sum w_g rho64_g against central differences of the same function, on sampled (splat, field) pairs of
+    position, scale and rotation and on the twelve affine entries of the view matrix; at or below the floor both are zero."""
+    aos, w, h, cam = load_antialias_scene(oracle_mod, scene)
+    p = oracle_params(oracle_mod, w, h, **cam)
+    rng = np.random.default_rng(17)
+    wts = torch.tensor(rng.standard_normal(len(aos)))
+    base = torch.tensor(aos.astype(np.float64))
+    view0 = _view_tensor(p)
+    rec = base.clone().requires_grad_(True)
+    view = view0.clone().requires_grad_(True)
+    rho, r = rho64(rec, view, p)
+    (wts * rho).sum().backward()
+    g_rec, g_view = rec.grad.numpy(), view.grad.numpy()
+    r = r.detach().numpy()
+    assert np.all(g_rec[r < FLOOR] == 0)
+
+    def loss(rc, vw, g=None):
+        with torch.no_grad():
+            if g is not None:                                           # a record moves its own term alone
+                return float(wts[g] * rho64(rc[g:g + 1], vw, p)[0][0])
+            return float((wts * rho64(rc, vw, p)[0]).sum())
+
+    # steps of 1e-6 of the field's natural size (a scale: the splat's largest; else 1); tolerance 1e-4 relative plus the
+    # differences' own rounding, 64 eps |L_g| / step
+    eps = np.finfo(np.float64).eps
+    splats = np.flatnonzero(np.isfinite(r) & ((r < FLOOR * 0.999) | (r > FLOOR * 1.001)))
+    for _ in range(60):
+        g, f = int(rng.choice(splats)), int(rng.choice(GEOMETRY))
+        step = 1e-6 * (float(np.abs(aos[g, 4:7]).max()) if f in (4, 5, 6) else 1.0)
+        rp, rm = base.clone(), base.clone()
+        rp[g, f] += step
+        rm[g, f] -= step
+        fd = (loss(rp, view0, g) - loss(rm, view0, g)) / (2 * step)
+        assert abs(fd - g_rec[g, f]) <= 1e-4 * abs(fd) + 64 * eps * abs(loss(base, view0, g)) / step, (g, f, fd, g_rec[g, f])
+    vscale = np.abs(g_view).max()
+    assert vscale > 0 and np.all(g_view[[3, 7, 11, 15]] == 0)
+    for k in [c * 4 + rr for c in range(4) for rr in range(3)]:
+        step = 1e-6
+        vp_, vm_ = view0.clone(), view0.clone()
+        vp_[k] += step
+        vm_[k] -= step
+        fd = (loss(base, vp_) - loss(base, vm_)) / (2 * step)
+        assert abs(fd - g_view[k]) <= 1e-4 * abs(fd) + 64 * eps * abs(loss(base, view0)) / step, (k, fd, g_view[k])
+
+
+def test_float32_restatement_deviation(oracle_mod):
+    """The yardstick of the GPU's value check: the largest relative deviation of rho32 (float32 NumPy) from rho64 over the
+    compared splats that the oracle's plain frame does not cull, on subpixel, ragged and ragged@pose.  Measured: subpixel
+    1.6e-7, ragged 3.2e-6, ragged@pose 2.7e-6 (elongated splats: det0 = a0 c0 - b0^2 cancels); RHO32_DEVIATION = 3.3e-6 is
+    that measurement rounded up."""
+    worst = 0.0
+    for scene in ("subpixel", "ragged", "ragged@pose"):
+        aos, w, h, cam = load_antialias_scene(oracle_mod, scene)
+        p = oracle_params(oracle_mod, w, h, **cam)
+        rho, r = rho64_numpy(p, aos)
+        vis = oracle_mod.full_pipeline(p, aos)["stage1"]["splats"]["visible"] != 0
+        keep = compared(scene, aos, r) & vis
+        dev = np.abs(rho32(p, aos).astype(np.float64)[keep] - rho[keep]) / rho[keep]
+        print(f"{scene}: {keep.sum()} splats, largest relative deviation of rho32 from rho64 {dev.max():.3e}")
+        worst = max(worst, float(dev.max()))
+    assert worst <= RHO32_DEVIATION, worst
+    assert worst >= RHO32_DEVIATION / 4, worst                        # the constant is the measurement, not a loose cap
+
+
+def test_composed_reference_matches_central_differences_of_the_oracle_frame(oracle_mod, tmp_path):
+    """ragged: L(R) = sum w * RGBA32F of the oracle's float32 frame of R'(R) = R with opacities float32(o * rho64(R)).  The
+    composed reference against central differences of L on sampled (splat, field) pairs of scale, rotation and opacity, the
+    fields the factor changes most (on them the plain gradient at R' alone is off by up to a factor of ten) -- steps h and 2h
+    (h = 1e-3 of the field's scale); of the kept pairs 95 % agree to 5 % + 0.02 (the bar of
+    test_backward_gpu.test_central_differences_of_the_gpu_forward, for the same float32 frame).  A pair is kept when its two
+    differences agree to 2 % + 0.02: a pixel that crosses the alpha < 1 / 255 skip or a stop inside a step moves the loss by
+    about |w| / 255, i.e. the difference by about 2 at these steps, and shows as a disagreement between h and 2h; that file's
+    10 % lets such pairs through, which its 59 mostly smooth SH fields can afford and the eleven geometric ones here cannot.
+    The position is left to
+    test_rho64_matches_its_central_differences: its share of rho is small, and at steps a float32 frame can resolve its
+    differences are dominated by pixels crossing the alpha < 1 / 255 skip, with or without the factor."""
+    aos, w, h, cam = load_scene("ragged")
+    p = oracle_params(oracle_mod, w, h, **cam)
+    rng = np.random.default_rng(29)
+    wr = rng.standard_normal((h, w, 4))
+
+    def prime(rec):
+        return compensated(rec, rho64_numpy(p, rec)[0])
+
+    ap = prime(aos)
+    ref, flags = frame_decisions(tmp_path, p, ap)
+    grad, _, plain = composed_reference(p, aos, ap, ref, flags, wr)
+    assert np.abs(grad[:, GEOMETRY] - plain[:, GEOMETRY]).max() > 1e-3 * np.abs(plain[:, GEOMETRY]).max()   # rho's term counts
+
+    def loss(rec):
+        return float((reference_outputs(tmp_path, p, prime(rec))["rgba32f"].astype(np.float64) * wr).sum())
+
+    blended = np.unique(np.asarray(ref["id"])[:ref["e"]][flags.any(1)])
+    kept = agree = 0
+    for _ in range(24):
+        g, f = int(rng.choice(blended)), int(rng.choice(GEOMETRY[3:] + [15]))
+        hstep = 1e-3 * max(abs(float(aos[g, f])), 0.05)
+        fds = []
+        for s in (hstep, 2 * hstep):
+            rp, rm = aos.copy(), aos.copy()
+            rp[g, f] += np.float32(s)
+            rm[g, f] -= np.float32(s)
+            fds.append((loss(rp) - loss(rm)) / (float(rp[g, f]) - float(rm[g, f])))
+        if abs(fds[0] - fds[1]) > 0.02 * max(abs(fds[0]), abs(fds[1])) + 0.02:
+            continue
+        kept += 1
+        agree += abs(grad[g, f] - fds[0]) <= 0.05 * abs(fds[0]) + 0.02
+    assert kept >= 12, kept
+    assert agree >= 0.95 * kept, (agree, kept)
+
+
+def test_compensation_keeps_the_coverage_across_resolutions(oracle_mod, tmp_path):
+    """A sparse cloud of tiny opaque splats on black (one per 8 x 8 px cell of the small frame, 0.15 px there), drawn by the
+    oracle at 64 x 48 and at 256 x 192 with the same field of view: the summed alpha of the small frame against one sixteenth
+    of the large frame's.  Plain, every splat is blown up to the 0.3 px^2 dilation and drawn opaque at both sizes, so the
+    small frame holds several times too much; with R' the ratio is strictly closer to one."""
+    rng = np.random.default_rng(5)
+    w, h = 64, 48
+    rec = [screen_splat(oracle_mod, w, h, 8 * cx + rng.uniform(2, 6), 8 * cy + rng.uniform(2, 6), 2.0, 0.15, 1.0)
+           for cy in range(h // 8) for cx in range(w // 8)]
+    aos = np.stack(rec).astype(np.float32)
+
+    def alpha_sum(scale, antialias):
+        p = oracle_params(oracle_mod, w * scale, h * scale)
+        a = compensated(aos, rho64_numpy(p, aos)[0]) if antialias else aos
+        return float(reference_outputs(tmp_path, p, a)["rgba32f"][..., 3].astype(np.float64).sum())
+
+    plain = alpha_sum(1, False) / (alpha_sum(4, False) / 16)
+    anti = alpha_sum(1, True) / (alpha_sum(4, True) / 16)
+    print(f"summed alpha, 64 x 48 against 256 x 192 / 16: plain {plain:.3f}, anti-aliased {anti:.3f}")
+    assert plain > 3.0                                                 # the plain frame misses by a wide factor
+    assert abs(anti - 1.0) < abs(plain - 1.0)
+
+
+def test_set_antialias_refuses_a_null_context():
+    """gs_set_antialias(NULL, 1): GS_ERR_INVALID, no crash; the binding carries the new buffer id."""
+    from vk3dgaussiansplatting_amd import _lib
+    L = _lib.lib()
+    assert L.gs_set_antialias(None, 1) == _lib.GS_ERR_INVALID
+    assert L.gs_set_antialias(None, 0) == _lib.GS_ERR_INVALID
+    assert _lib.BUF_RASTER_OPACITY == 11
+    buf = np.zeros(4, np.float32)
+    assert L.gs_debug_read(None, _lib.BUF_RASTER_OPACITY, buf.ctypes.data_as(C.c_void_p), buf.nbytes) == _lib.GS_ERR_INVALID

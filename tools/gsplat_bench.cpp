@@ -4,7 +4,7 @@
 // running averages of the five GPU timing buckets (Renderer.cpp:477-510) printed at the end.
 //
 //   gsplat_bench <scene.ply | --synthetic N [--skew]> [--scene garden|train|bicycle|origin] [--res WxH]
-//                [--warmup F] [--frames F] [--fast] [--sort radix4|splat_first|bucket|radix8|radix8_splat_first]
+//                [--warmup F] [--frames F] [--fast] [--antialias] [--sort radix4|splat_first|bucket|radix8|radix8_splat_first]
 //                [--present] [--out frame.png|frame.ppm]
 //                [--ranks R [--interleaved | --balanced [--rebalance K]] [--sync]]
 //
@@ -169,7 +169,7 @@ int main(int argc, char** argv) {
     std::string ply, scene = "origin", sort = "radix4";   // GPU_SORT_ALGORITHM (Renderer.h:33)
     Options o;
     uint32_t n_syn = 0;
-    bool fast = false, present = false, skew = false;
+    bool fast = false, present = false, skew = false, antialias = false;
     int ranks = 1, rank = 0;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
@@ -180,6 +180,7 @@ int main(int argc, char** argv) {
         else if (a == "--frames" && i + 1 < argc) o.frames = (uint32_t)atol(argv[++i]);
         else if ((a == "--out" || a == "--ppm") && i + 1 < argc) o.out = argv[++i];
         else if (a == "--fast") fast = true;
+        else if (a == "--antialias") antialias = true;
         else if (a == "--present") present = true;
         else if (a == "--skew") skew = true;
         else if (a == "--sort" && i + 1 < argc) sort = argv[++i];
@@ -237,6 +238,7 @@ int main(int argc, char** argv) {
 
     gsplat::Renderer renderer(o.w, o.h, o.warmup, o.frames);    // Renderer.h:142-143, here from the command line
     bool ready = renderer.init(&cfg) == GS_OK;
+    if (ready && antialias) ready = renderer.setAntialias(true) == GS_OK;      // a flag of the context: every rank sets its own
     if (!ready) fprintf(stderr, "[Log Error]: rank %d: %s\n", rank, renderer.lastError().c_str());
     if (ready && !ply.empty()) {                            // Scene::init -> ResourceManager::loadGaussians
         ready = renderer.initForScenePly(ply) == GS_OK;

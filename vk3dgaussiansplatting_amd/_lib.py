@@ -37,6 +37,7 @@ GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read
 
 (BUF_SORTED_TILE, BUF_SORTED_DEPTH, BUF_SORTED_ID, BUF_RANGES, BUF_COLOR, BUF_COV, BUF_COUNT,
  BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE) = range(11)
+BUF_RASTER_OPACITY = 11
 
 RECORD_BYTES = 336
 
@@ -179,6 +180,7 @@ EXPORTS = [
     "gs_contrib_device", "gs_prune_below_device",
     "gs_relocate_device", "gs_grow_device", "gs_position_noise_device",
     "gs_set_band_gradients",
+    "gs_set_antialias",
 ]
 # GS_SH_*: the sh_mode of a frame (0, 1, 2 = the reference's Camera.h modes; 5 and 4 = SH degree 1 and 2; 3 names none)
 GS_SH_ALL_BANDS, GS_SH_SKIP_FIRST_BAND, GS_SH_ONLY_FIRST_BAND, GS_SH_DEGREE_2, GS_SH_DEGREE_1 = 0, 1, 2, 4, 5
@@ -341,6 +343,7 @@ def lib() -> C.CDLL:
     L.gs_grow_device.argtypes = [ctxp, vp, vp, vp, vp, u32, f32, C.c_uint64, u32, vp, vp, vp, vp, u32, vp]
     L.gs_position_noise_device.argtypes = [ctxp, vp, vp, u32, vp, vp, u32, f32, f32, f32, C.c_uint64]
     L.gs_set_band_gradients.argtypes = [ctxp, u32]
+    L.gs_set_antialias.argtypes = [ctxp, u32]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -55,7 +55,7 @@ from .renderer import FLOATS_PER_GAUSSIAN, Renderer, ResourceManager, default_ad
 
 def make_renderer(width: int, height: int, device: int = 0, **kw) -> Renderer:
     """A Renderer for render(): a context on `device` without a scene (the first render uploads one).  kw: Renderer's
-    options (sort_algorithm, render_kernel, ...); render_mode must stay GS_RENDER_EXACT."""
+    options (sort_algorithm, render_kernel, antialias, ...); render_mode must stay GS_RENDER_EXACT."""
     r = Renderer(width, height, device=device, record_timings=False, **kw)
     r.init(ResourceManager())
     return r

@@ -241,9 +241,12 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     f.ordered = c->cfg.tile_order == GS_TILE_ORDER_LONGEST_FIRST;
     f.direct = c->cfg.record_timings >= 2;
     hipEvent_t* const pass_events = f.direct ? c->scatter_ev : nullptr;
+    // k_project -- the one kernel of a frame that reads FrameParams::antialias -- goes to the stream here, on every frame and
+    // outside every capture (the graphs below start behind the scan): gs_set_antialias has no graph to drop
     launch_project(fp, c->scene, c->scratch, st);
     launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, st);
     f.fixed = fp;
+    f.fixed.antialias = 0u;             // nothing behind the scan reads it: the captured arguments do not depend on the flag
     if (splat_first) {
         // Nothing between the first scan and RenderGaussians depends on the camera: those kernels take a FrameParams
         // without it (and with a fixed helper counter, cleared by the first kernel of the chain), so their arguments

@@ -42,7 +42,8 @@ __device__ __forceinline__ void sh_basis_grad(float X, float Y, float Z, float b
 // From the summed row of a splat down the per-splat part of the frame, to dL/d(record) (CAMERA = false: gs_backward*) or
 // to the splat's 35 camera terms (CAMERA = true: gs_backward_camera*).  The branch the forward took is held fixed: the clamp
 // of x/z, y/z in getCovarianceMatrix (a clamped component passes no derivative to the ratio), max(colour, 0) (no derivative
-// below 0), det == 0 (opacity 0: the splat never contributes, all zero).
+// below 0), det == 0 (opacity 0: the splat never contributes, all zero), and in an anti-aliased frame the floor under
+// det0 / det and the cap at 1 above it (there the factor is a constant: the opacity gets dop * rho, the covariance nothing).
 // `row` = the summed row of splat g, `any` = g emitted into the list.  CAMERA = false: o = the quads of its record gradient
 // (cg unused).  CAMERA = true: cg[0..15] receives dL/dview, cg[16..31] dL/dproj, cg[32..34] dL/dcam_pos of this splat
 // (cg[35] arrives zeroed and stays so for a zero row; o unused); the view's bottom row (3, 7, 11, 15) and the
@@ -135,17 +136,36 @@ __device__ __forceinline__ void bwd_chain(const FrameParams& fp, const SceneBuff
     for (int r = 0; r < 2; ++r)
 #pragma unroll
         for (int c = 0; c < 3; ++c) TS[r][c] = Tm[r][0] * Sg[0][c] + Tm[r][1] * Sg[1][c] + Tm[r][2] * Sg[2][c];
-    const float ca = TS[0][0] * Tm[0][0] + TS[0][1] * Tm[0][1] + TS[0][2] * Tm[0][2] + 0.3f;
+    const float a0 = TS[0][0] * Tm[0][0] + TS[0][1] * Tm[0][1] + TS[0][2] * Tm[0][2];      // before the 0.3 dilation
     const float cb = TS[1][0] * Tm[0][0] + TS[1][1] * Tm[0][1] + TS[1][2] * Tm[0][2];
-    const float cc = TS[1][0] * Tm[1][0] + TS[1][1] * Tm[1][1] + TS[1][2] * Tm[1][2] + 0.3f;
+    const float c0 = TS[1][0] * Tm[1][0] + TS[1][1] * Tm[1][1] + TS[1][2] * Tm[1][2];
+    const float ca = a0 + 0.3f, cc = c0 + 0.3f;
     const float det = ca * cc - cb * cb;
 
     float dpos[3] = {0.f, 0.f, 0.f}, dscale[3] = {0.f, 0.f, 0.f}, drot[4] = {0.f, 0.f, 0.f, 0.f};
+    float dop_rec = dop;                                    // dL/d(the record's opacity)
     if (det != 0.0f) {
         const float rd = 1.0f / det;
         const float ix = cc * rd, iy = -cb * rd, iz = ca * rd;
         const float ddet = -(dix * ix + diy * iy + diz * iz) * rd;
-        const float da = diz * rd + ddet * cc, db = -diy * rd - 2.0f * cb * ddet, dcc = dix * rd + ddet * ca;
+        float da = diz * rd + ddet * cc, db = -diy * rd - 2.0f * cb * ddet, dcc = dix * rd + ddet * ca;
+        // an anti-aliased frame (gs_set_antialias) blended opacity * rho, rho = sqrt(max(r, floor)), r = det0 / det: the
+        // record's opacity gets dop * rho, and above the floor dop * opacity flows on through r into the covariance
+        if (fp.antialias) {
+            const float det0 = a0 * c0 - cb * cb;
+            const float r = det0 / det;
+            const bool above = r > kAntialiasFloor;         // false for a NaN r, as in k_project
+            const float rho = sqrtf(above ? (r < 1.0f ? r : 1.0f) : kAntialiasFloor);
+            dop_rec = dop * rho;
+            if (above && r <= 1.0f) {                       // beyond 1 (rounding alone) k_project capped the factor: a constant too
+                const float drho = dop * scene.opacity[g];
+                const float dr = drho / (2.0f * rho);
+                const float ddet0 = dr / det, ddet_r = -dr * r / det;
+                da += ddet0 * c0 + ddet_r * cc;
+                dcc += ddet0 * a0 + ddet_r * ca;
+                db += -2.0f * cb * (ddet0 + ddet_r);
+            }
+        }
         const float Gs[2][2] = {{2.0f * da, db}, {db, 2.0f * dcc}};   // dL/dSigma' + its transpose (upper 2 x 2)
         float GT[2][3];
 #pragma unroll
@@ -260,7 +280,7 @@ __device__ __forceinline__ void bwd_chain(const FrameParams& fp, const SceneBuff
     for (int k = 0; k < 16; ++k) {
         const bool used = k >= k_lo && k < k_hi;
         o[kRecSh / 4 + k] = make_float4(used ? dres[0] * b[k] : 0.0f, used ? dres[1] * b[k] : 0.0f,
-                                        used ? dres[2] * b[k] : 0.0f, k == 0 ? dop : 0.0f);     // .w of k = 0: the opacity
+                                        used ? dres[2] * b[k] : 0.0f, k == 0 ? dop_rec : 0.0f);     // .w of k = 0: the opacity
     }
     o[kRecColor / 4] = zero4;
     o[kRecCov / 4] = zero4;

@@ -111,6 +111,8 @@ struct gs_ctx {
     uint32_t row_begin = 0, row_end = 0, row_stride = 1, first_row = 0, rows_owned = 0;
     bool compact_out = false;
     bool band_gradients = false;      // gs_set_band_gradients: gs_backward* and gs_contrib_device serve a band of tile rows
+    bool antialias = false;           // gs_set_antialias: FrameParams::antialias of the frames enqueued from now on (a host flag of the
+                                      // context, not of the scene; nothing but make_frame_params reads it)
     uint32_t capacity = 0, num_sort_bits = 0;
     // what the sort of the owned tiles runs over: compact tile ids, so ceil((32 + bits(T_owned - 1)) / 4) passes
     // (the reference's formula, RadixSort.cpp:203-204, for the context's own tile count)
@@ -281,6 +283,7 @@ inline FrameParams make_frame_params(const gs_ctx* c, const float* view, const f
     fp.tan_fov_y = (float)std::tan((double)(c->cfg.fov_y * 0.5f));   // Common.glsl:53, host-folded
     fp.hi16 = c->hi16 ? 1u : 0u;
     fp.parity = 0u;       // set by the InitSortList launch sites
+    fp.antialias = c->antialias ? 1u : 0u;
     // |W|_2^2 <= min(trace, largest absolute row sum) of M = W^T W (Gershgorin); exactly 1 (+ rounding) for a rigid view
     double m[3][3], tr = 0.0, gersh = 0.0;
     for (int i = 0; i < 3; ++i)

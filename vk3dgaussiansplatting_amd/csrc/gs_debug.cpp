@@ -145,6 +145,23 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
             std::memcpy(dst, outv.data(), bytes);
             return GS_OK;
         }
+        case GS_BUF_RASTER_OPACITY: {
+            // SplatRaster::a of the splats that emitted an element in the last list: their wave stored its records (wave_wrote; a
+            // block k_band_cull rejected has zeros there and stale counts) and their count is not zero
+            const size_t need = (size_t)c->n * sizeof(float);
+            if (bytes > need) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
+            std::vector<SplatRaster> host(c->n);
+            std::vector<uint32_t> touched(c->n);
+            std::vector<uint8_t> wrote((size_t)c->num_blocks * 4);
+            HIP_TRY(c, hipMemcpy(host.data(), c->scratch.raster, (size_t)c->n * sizeof(SplatRaster), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(touched.data(), c->scratch.tiles_touched, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(wrote.data(), c->scratch.wave_wrote, wrote.size(), hipMemcpyDeviceToHost));
+            std::vector<float> outv(c->n, 0.0f);
+            for (uint32_t i = 0; i < c->n; ++i)
+                if (wrote[i / 64u] && touched[i]) outv[i] = host[i].a;
+            std::memcpy(dst, outv.data(), bytes);
+            return GS_OK;
+        }
         default: return fail(c, GS_ERR_INVALID, "gs_debug_read: unknown buffer id");
     }
     if (bytes > avail) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");

@@ -79,7 +79,12 @@ struct FrameParams {
                           // helper records of k_emit to k_gather_sorted
     uint32_t packed;      // k_emit writes the packed payload (SortRun::packed, gs_sort_words.h): pk32 into the id plane, pk8
                           // into a byte plane in the storage of the tile words
+    uint32_t antialias;   // gs_set_antialias: the raster opacity of an emitting splat is opacity * sqrt(det Sigma' / det(Sigma' +
+                          // 0.3 I)), floored (kAntialiasFloor); k_project picks its instantiation by it, bwd_chain branches on it
 };
+// The floor under r = det Sigma' / det(Sigma' + 0.3 I) of an anti-aliased frame (the INRIA rasteriser's 0.000025): at or
+// below it -- or with a NaN r -- the factor is the constant sqrt(floor) and passes no derivative to the covariance.
+constexpr float kAntialiasFloor = 2.5e-5f;
 
 // Device-side dispatch record: the role of RadixIndirectDispatch (ShaderStructs.h:45-57) +
 // GaussianCullData (77-82).  Written by the scan kernel (IndirectSetup-equivalent), read by every

@@ -38,10 +38,11 @@ __device__ __forceinline__ Mat3 mat3_transpose(const Mat3& a) {
     return t;
 }
 
-// Common/Common.glsl:32-78
+// Common/Common.glsl:32-78.  cov0: the same three entries before the 0.3 dilation (what an anti-aliased frame compares the
+// dilated determinant with; unused otherwise and then not computed: the function is inlined)
 __device__ __forceinline__ void get_covariance(const FrameParams& fp, const float scale[3],
                                                const float rot[4], const float pv_in[4],
-                                               float cov[3]) {
+                                               float cov[3], float cov0[3]) {
     const float width = (float)fp.width, height = (float)fp.height;
     float pv[3] = {pv_in[0], pv_in[1], pv_in[2]};
 
@@ -88,6 +89,7 @@ __device__ __forceinline__ void get_covariance(const FrameParams& fp, const floa
     cov[0] = sp.m[0][0];
     cov[1] = sp.m[0][1];
     cov[2] = sp.m[1][1];
+    cov0[0] = cov[0]; cov0[1] = cov[1]; cov0[2] = cov[2];
     cov[0] += 0.3f;
     cov[2] += 0.3f;
 }
@@ -331,7 +333,11 @@ inline int sh_cut_of_mode(uint32_t sh_mode) { return sh_mode == 5u ? 4 : sh_mode
 // VIEW_Z (GS_OUTPUT_DEPTH on, SplatScratch::view_z allocated): also stores the view depth -viewSpacePos.z of every emitting
 // splat for the depth output -- an instantiation of its own, so that frames without it run the kernel as it was (a branch
 // in this kernel, at its SGPR limit, re-arranged the spills of the whole kernel).  SH_K: splat_colour's K, for the same reason.
-template <bool NT_SH, bool VIEW_Z, int SH_K>
+// AA (gs_set_antialias): the raster opacity of an emitting splat is multiplied by sqrt(det0 / det), det0 the determinant of
+// the 2-D covariance before its 0.3 dilation, floored at kAntialiasFloor -- again an instantiation of its own, so that the
+// frames without it run the kernels they ran (registers of both: profiles/antialias_cost.txt).  Nothing else of a frame
+// changes with it: covariance, conic, radius, tile box, depth key and colour are those of the plain frame.
+template <bool NT_SH, bool VIEW_Z, int SH_K, bool AA>
 __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(const FrameParams fp,
                                                            const SceneBuffers scene,
                                                            const SplatScratch sc, const uint32_t num_blocks) {
@@ -393,12 +399,12 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                     band_skip = misses_owned_rows(fp, sy_b - rmax, sy_b + rmax);
                 }
                 if (!band_skip) {
-                    float scale[3], rot[4], cov[3];
+                    float scale[3], rot[4], cov[3], cov0[3];
 #pragma unroll
                     for (int a = 0; a < 3; ++a) scale[a] = scene.scale[a * (size_t)n + g];
 #pragma unroll
                     for (int a = 0; a < 4; ++a) rot[a] = scene.rot[a * (size_t)n + g];
-                    get_covariance(fp, scale, rot, vp, cov);              // :113-120
+                    get_covariance(fp, scale, rot, vp, cov, cov0);        // :113-120
 
                     // getScreenSpacePosition, Common.glsl:80-89 (same proj*viewPos and division as above)
                     float sx = ndc_x, sy = -ndc_y;
@@ -443,6 +449,13 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                             inv_x = cov[2] * det_inv;                          // :100
                             inv_y = -cov[1] * det_inv;
                             inv_z = cov[0] * det_inv;
+                            if constexpr (AA) {
+                                const float det0 = cov0[0] * cov0[2] - cov0[1] * cov0[1];
+                                const float r = det0 / det;
+                                // a NaN r takes the floor.  r > 1 is rounding alone (a needle whose two determinants are both
+                                // cancellation noise below zero): capped, so that no splat is drawn above its own opacity
+                                opacity = opacity * sqrtf(r > kAntialiasFloor ? (r < 1.0f ? r : 1.0f) : kAntialiasFloor);
+                            }
                         } else {
                             opacity = 0.0f;                                    // :104
                         }
@@ -757,15 +770,15 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
     }
 }
 
-template <int SH_K>
+template <int SH_K, bool AA>
 static void launch_project_cut(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, uint32_t blocks, bool nt_sh,
                                hipStream_t stream) {
     if (sc.view_z) {
-        if (nt_sh) hipLaunchKernelGGL((k_project<true, true, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-        else hipLaunchKernelGGL((k_project<false, true, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, true, SH_K, AA>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, true, SH_K, AA>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
     } else {
-        if (nt_sh) hipLaunchKernelGGL((k_project<true, false, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
-        else hipLaunchKernelGGL((k_project<false, false, SH_K>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        if (nt_sh) hipLaunchKernelGGL((k_project<true, false, SH_K, AA>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
+        else hipLaunchKernelGGL((k_project<false, false, SH_K, AA>), dim3(blocks), dim3(kProjThreads), 0, stream, fp, scene, sc, blocks);
     }
 }
 
@@ -780,10 +793,19 @@ void launch_project(const FrameParams& fp, const SceneBuffers& scene, const Spla
 #define GS_PROJECT_NT_SH_ABOVE ((size_t)256u << 20)       /* scene bytes above which the SH planes are loaded non-temporally */
 #endif
     const bool nt_sh = (size_t)fp.num_gaussians * 236u > GS_PROJECT_NT_SH_ABOVE;
-    switch (sh_cut_of_mode(fp.sh_mode)) {
-        case 4: launch_project_cut<4>(fp, scene, sc, blocks, nt_sh, stream); break;
-        case 9: launch_project_cut<9>(fp, scene, sc, blocks, nt_sh, stream); break;
-        default: launch_project_cut<0>(fp, scene, sc, blocks, nt_sh, stream); break;
+    const int cut = sh_cut_of_mode(fp.sh_mode);
+    if (fp.antialias) {
+        switch (cut) {
+            case 4: launch_project_cut<4, true>(fp, scene, sc, blocks, nt_sh, stream); break;
+            case 9: launch_project_cut<9, true>(fp, scene, sc, blocks, nt_sh, stream); break;
+            default: launch_project_cut<0, true>(fp, scene, sc, blocks, nt_sh, stream); break;
+        }
+    } else {
+        switch (cut) {
+            case 4: launch_project_cut<4, false>(fp, scene, sc, blocks, nt_sh, stream); break;
+            case 9: launch_project_cut<9, false>(fp, scene, sc, blocks, nt_sh, stream); break;
+            default: launch_project_cut<0, false>(fp, scene, sc, blocks, nt_sh, stream); break;
+        }
     }
 }
 

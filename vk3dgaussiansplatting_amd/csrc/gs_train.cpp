@@ -470,6 +470,16 @@ int gs_set_band_gradients(gs_ctx* c, uint32_t enable) {
     return GS_OK;
 }
 
+// A host flag and nothing else: the last frame stays what it was (its FrameParams, flag included, are in c->last.fp, which is what
+// gs_backward*, gs_backward_camera* and gs_contrib_device go by), and no captured graph holds a launch that reads the flag
+// (enqueue_frame launches k_project directly)
+int gs_set_antialias(gs_ctx* c, uint32_t enable) {
+    if (!c) return GS_ERR_INVALID;
+    if (enable > 1u) return refuse(c, __func__, "enable must be 0 or 1");
+    c->antialias = enable != 0u;
+    return GS_OK;
+}
+
 int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");

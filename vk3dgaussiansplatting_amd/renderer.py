@@ -423,8 +423,8 @@ class Renderer:
                  render_kernel: int = _lib.GS_RENDER_KERNEL_AUTO,
                  tile_order: int = _lib.GS_TILE_ORDER_LONGEST_FIRST, count_launches: int = _lib.GS_COUNT_AUTO,
                  near_plane: float | None = None, far_plane: float | None = None, ndc_cull: float | None = None,
-                 in_view_limit: float | None = None, fov_y: float | None = None):
-        """near_plane, far_plane, ndc_cull, in_view_limit, fov_y: the camera constants of gs_config, fixed for the life of
+                 in_view_limit: float | None = None, fov_y: float | None = None, antialias: bool = False):
+        """antialias: setAntialias for the context init() creates.  near_plane, far_plane, ndc_cull, in_view_limit, fov_y: the camera constants of gs_config, fixed for the life of
         the context (None: gs_default_config's, the reference's).  proj drives the screen position, fov_y the covariance's
         focal lengths: INTEGRATION.md, "Real cameras".  self.cfg is the gs_config init() hands to gs_create."""
         given = locals()                                     # _config's options are arguments here under their own names
@@ -436,6 +436,7 @@ class Renderer:
         self.numSortElements = 0
         self.frameSerial = 0        # counts the calls that launched a sort list: what was drawn before the last is gone
         self._outputs_mask = None   # the GS_OUTPUT_* mask setOutputs set last
+        self.antialias = bool(antialias)
         self.warmupFrames = self.WAIT_ELAPSED_WARMUP_FRAMES_FOR_AVG if warmup_frames is None else warmup_frames
         self._reset_avgs()
 
@@ -448,6 +449,8 @@ class Renderer:
     def init(self, resourceManager: ResourceManager):
         self.resourceManager = resourceManager
         self._ctx = _Context(self.cfg)
+        if self.antialias:
+            self.setAntialias(True)
 
     # -- Renderer.cpp:696-710
     def getNumTiles(self) -> int:
@@ -500,6 +503,13 @@ class Renderer:
         visibleCount, backwardCamera* and contribDevice with the terms of its own pixels -- partial sums over the frame's tile
         rows, which the caller adds up over the bands (rowsAccumulateDevice / rowsCollectDevice).  Off (the default): refused."""
         self._ctx.check(_lib.lib().gs_set_band_gradients(self._ctx.handle, 1 if enable else 0))
+
+    def setAntialias(self, enable: bool = True):
+        """gs_set_antialias: the frames drawn from now on blend every splat at opacity * sqrt(det S / det(S + 0.3 I)), S its
+        2-D covariance before the dilation (floored; include/gsplat.h) -- the opacity compensation of anti-aliased training.
+        A host flag of this renderer's context; the last frame and its gradients stay those of the frame as drawn."""
+        self._ctx.check(_lib.lib().gs_set_antialias(self._ctx.handle, 1 if enable else 0))
+        self.antialias = bool(enable)
 
     @staticmethod
     def _camera_args(cam: Camera):
@@ -577,6 +587,8 @@ class Renderer:
             a = np.zeros(1, dtype=np.uint64)
         elif which in (_lib.BUF_COLOR, _lib.BUF_COV):
             a = np.zeros((info.num_gaussians, 4), dtype=np.float32)
+        elif which == _lib.BUF_RASTER_OPACITY:
+            a = np.zeros(info.num_gaussians, dtype=np.float32)
         elif which == _lib.BUF_RANGES:
             a = np.zeros((info.tiles_x * info.tiles_y, 2), dtype=np.uint32)
         elif which == _lib.BUF_IMAGE:
