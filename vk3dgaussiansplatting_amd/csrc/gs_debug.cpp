@@ -102,52 +102,61 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
             // color.a as the reference stores it (InitSortList.comp:126) is the opacity itself; the record's copy is
             // already zeroed where the 2x2 determinant vanishes (RenderGaussians.comp:104), so it comes from the scene
             std::vector<float> opacity;
-            std::vector<uint32_t> touched;
-            // N6 (InitSortList.comp:124-127): the reference stores colour for EVERY splat that passes the culls; the frame
-            // evaluates it for the emitting ones only, so the others are evaluated here, on demand, from the last frame's
-            // camera (k_debug_colour) -- in a context that owns the whole grid.  A context that owns a subset of the tile rows
-            // does not even project the splats that cannot reach its rows: there GS_BUF_COLOR stays what the frame stored.
-            std::vector<float> on_demand;
-            const bool whole_grid = c->row_begin == 0u && c->row_end == c->grid_h && c->row_stride == 1u;
+            std::vector<uint32_t> touched(c->n);
+            HIP_TRY(c, hipMemcpy(touched.data(), c->scratch.tiles_touched, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
             if (which == GS_BUF_COLOR) {
-                opacity.resize(c->n); touched.resize(c->n);
+                opacity.resize(c->n);
                 HIP_TRY(c, hipMemcpy(opacity.data(), c->scene.opacity, (size_t)c->n * sizeof(float), hipMemcpyDeviceToHost));
-                HIP_TRY(c, hipMemcpy(touched.data(), c->scratch.tiles_touched, (size_t)c->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                if (whole_grid) {
-                    float* dev = nullptr;
-                    HIP_TRY(c, hipMalloc((void**)&dev, need));
-                    launch_debug_colour(c->last.fp, c->scene, c->scratch, dev, c->stream);
-                    hipError_t e = hipGetLastError();
-                    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                    on_demand.resize((size_t)c->n * 4);
-                    if (e == hipSuccess) e = hipMemcpy(on_demand.data(), dev, need, hipMemcpyDeviceToHost);
-                    (void)hipFree(dev);
-                    HIP_TRY(c, e);
-                }
             }
-            // records of a wave (64 consecutive splats) that k_project did not store this frame -- wholly culled, or with
-            // nothing to emit into this context's tile rows -- read back as zero, what a culled splat's scratch holds
+            // N6 (InitSortList.comp:124-127): the reference stores colour and covariance for EVERY splat that passes the culls;
+            // the frame stores the records of the chunks with an emitting splat and evaluates the colour of the emitting ones
+            // only, so what the others would hold is computed here, on demand, from the last frame's camera (k_debug_records,
+            // k_debug_colour) -- in a context that owns the whole grid.  A context that owns a subset of the tile rows does not
+            // even project the splats that cannot reach its rows: there both stay what the frame stored.
+            std::vector<float> records, on_demand;      // [n][8] (sx, sy, 0, passed | 0, cx, cy, cz), [n][4]: non-emitting splats
+            const bool whole_grid = c->row_begin == 0u && c->row_end == c->grid_h && c->row_stride == 1u;
+            if (whole_grid) {
+                float* dev = nullptr;                    // the records, then the colours
+                HIP_TRY(c, hipMalloc((void**)&dev, 3 * need));
+                launch_debug_records(c->last.fp, c->scene, c->scratch, dev, c->stream);
+                if (which == GS_BUF_COLOR) launch_debug_colour(c->last.fp, c->scene, dev, dev + (size_t)c->n * 8, c->stream);
+                hipError_t e = hipGetLastError();
+                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+                records.resize((size_t)c->n * 8);
+                if (e == hipSuccess) e = hipMemcpy(records.data(), dev, 2 * need, hipMemcpyDeviceToHost);
+                if (which == GS_BUF_COLOR) {
+                    on_demand.resize((size_t)c->n * 4);
+                    if (e == hipSuccess) e = hipMemcpy(on_demand.data(), dev + (size_t)c->n * 8, need, hipMemcpyDeviceToHost);
+                }
+                (void)hipFree(dev);
+                HIP_TRY(c, e);
+            }
+            // wave_wrote: the quarter waves (16 consecutive splats) whose records k_project stored this frame.  The whole grid:
+            // the record of an emitting splat is this frame's (its chunk was stored), every other splat is recomputed above.  A
+            // band: records of a wave that emits nothing into this context's tile rows read back as zero, what a culled
+            // splat's scratch holds
             std::vector<uint8_t> wrote((size_t)c->num_blocks * 4);
             HIP_TRY(c, hipMemcpy(wrote.data(), c->scratch.wave_wrote, wrote.size(), hipMemcpyDeviceToHost));
             std::vector<float> outv((size_t)c->n * 4, 0.0f);
             for (uint32_t i = 0; i < c->n; ++i) {
-                if (!wrote[i / 64u]) continue;
+                const bool stored = (wrote[i / 64u] >> ((i / 16u) & 3u)) & 1u;
                 const SplatRaster& r = host[i];
                 float* o = &outv[(size_t)i * 4];
-                if (which == GS_BUF_COLOR) {
-                    if (touched[i]) { o[0] = r.r; o[1] = r.g; o[2] = r.b; o[3] = opacity[i]; }       // what the frame stored and blended
-                    else if (!on_demand.empty() && on_demand[(size_t)i * 4 + 3] != 0.0f) {           // passed the culls, touched no tile
-                        o[0] = on_demand[(size_t)i * 4]; o[1] = on_demand[(size_t)i * 4 + 1]; o[2] = on_demand[(size_t)i * 4 + 2]; o[3] = opacity[i];
-                    }
+                if (stored && (touched[i] || !whole_grid)) {
+                    if (which == GS_BUF_COV) { o[0] = r.cx; o[1] = r.cy; o[2] = r.cz; o[3] = 0.0f; }
+                    else if (touched[i]) { o[0] = r.r; o[1] = r.g; o[2] = r.b; o[3] = opacity[i]; }  // what the frame stored and blended
+                } else if (whole_grid && !touched[i] && records[(size_t)i * 8 + 3] != 0.0f) {        // passed the culls, touched no tile
+                    const float* rec = &records[(size_t)i * 8];
+                    if (which == GS_BUF_COV) { o[0] = rec[5]; o[1] = rec[6]; o[2] = rec[7]; o[3] = 0.0f; }
+                    else { o[0] = on_demand[(size_t)i * 4]; o[1] = on_demand[(size_t)i * 4 + 1]; o[2] = on_demand[(size_t)i * 4 + 2]; o[3] = opacity[i]; }
                 }
-                else { o[0] = r.cx; o[1] = r.cy; o[2] = r.cz; o[3] = 0.0f; }
             }
             std::memcpy(dst, outv.data(), bytes);
             return GS_OK;
         }
         case GS_BUF_RASTER_OPACITY: {
-            // SplatRaster::a of the splats that emitted an element in the last list: their wave stored its records (wave_wrote; a
-            // block k_band_cull rejected has zeros there and stale counts) and their count is not zero
+            // SplatRaster::a of the splats that emitted an element in the last list: their quarter wave stored its records
+            // (wave_wrote; a block k_band_cull rejected has zeros there and stale counts) and their count is not zero
             const size_t need = (size_t)c->n * sizeof(float);
             if (bytes > need) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
             std::vector<SplatRaster> host(c->n);
@@ -158,7 +167,7 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
             HIP_TRY(c, hipMemcpy(wrote.data(), c->scratch.wave_wrote, wrote.size(), hipMemcpyDeviceToHost));
             std::vector<float> outv(c->n, 0.0f);
             for (uint32_t i = 0; i < c->n; ++i)
-                if (wrote[i / 64u] && touched[i]) outv[i] = host[i].a;
+                if (((wrote[i / 64u] >> ((i / 16u) & 3u)) & 1u) && touched[i]) outv[i] = host[i].a;
             std::memcpy(dst, outv.data(), bytes);
             return GS_OK;
         }

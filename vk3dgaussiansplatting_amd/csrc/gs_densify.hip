@@ -67,6 +67,9 @@ __global__ __launch_bounds__(256) void k_densify_stats(const DensifyStatsArgs a)
     a.grad_accum[g] = a.grad_accum[g] + norm;
     a.seen[g] += 1u;
 
+    // the frame stores the records of emitting splats (k_project): a listed id that emitted nothing in this frame (a caller's
+    // union of several frames' lists) has a stale or zero record, which counts as the zero one -- radius 0
+    if (a.counts.of(g) == 0u) return;
     const SplatRaster* rec = a.raster + g;
     const float radius = tile_extent_radius(rec->cx, rec->cy, rec->cz);
     const float old = a.max_radius[g];

@@ -131,8 +131,11 @@ struct SplatScratch {
     uint32_t* depth_key;     // [N]
     uint32_t* tiles_touched; // [N]  0 for culled / zero-extent splats
     uint2* extents;          // [N]  packed u16: .x = minx | miny<<16, .y = maxx | maxy<<16 (row-clamped)
-    uint8_t* wave_wrote;     // [4 * ceil(N/kProjThreads)]  1: this frame's k_project stored the raster records of the wave's
-                             //       64 splats (else they are stale / zero: gs_debug_read zero-fills them)
+    uint8_t* wave_wrote;     // [4 * ceil(N/kProjThreads)]  one byte per wave of 64 splats, a mask of its four quarters: bit q
+                             //       set = this frame's k_project stored the raster records of splats 16 q .. 16 q + 15 of the
+                             //       wave (the others are stale -- an earlier frame's -- or zero: nothing behind the frame reads
+                             //       them, gs_debug_read recomputes or zero-fills them).  0xF or 0 where whole waves are stored
+                             //       (a band context, the GS_PROJECT_* tuning builds)
     uint32_t* block_sums;    // [ceil(N/kProjThreads)]  tile counts per project workgroup
     uint32_t* block_offsets; // same size, exclusive scan
     // k_emit load balance: a project workgroup whose 256 splats emit more than kEmitSlice elements registers one
@@ -278,7 +281,11 @@ inline uint32_t sort_pass_bytes(const SortPass& p, bool hi16) {
 void launch_project(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc,
                     hipStream_t stream);
 // sums == nullptr: block_sums -> block_offsets, the frame's clears, the IndirectSetup record in `params`.
-void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, float* out_rgba, hipStream_t stream);
+// gs_debug_read of a full-grid context, on demand from the last frame's camera.  out_records: float[n][8], what k_project
+// computed and did not store for the splats that passed the culls and touched no tile (k_debug_records); out_rgba: float[n][4],
+// their colours, from those records' flags
+void launch_debug_records(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, float* out_records, hipStream_t stream);
+void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const float* records, float* out_rgba, hipStream_t stream);
 void launch_scan_blocks(const FrameParams& fp, const SplatScratch& sc, SortParams* params,
                         uint32_t* ranges, uint32_t* coarse, hipStream_t stream);
 void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb,

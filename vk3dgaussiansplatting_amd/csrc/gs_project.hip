@@ -94,6 +94,16 @@ __device__ __forceinline__ void get_covariance(const FrameParams& fp, const floa
     cov[2] += 0.3f;
 }
 
+// getScreenSpacePosition, Common.glsl:80-89, from the NDC position InitSortList.comp:99 already formed (same proj*viewPos and
+// division)
+__device__ __forceinline__ void screen_position(const FrameParams& fp, const float ndc_x, const float ndc_y, float& sx, float& sy) {
+    sx = ndc_x; sy = -ndc_y;
+    sx = (sx + 1.0f) * 0.5f;
+    sy = (sy + 1.0f) * 0.5f;
+    sx = sx * (float)fp.width;
+    sy = sy * (float)fp.height;
+}
+
 // Common/Common.glsl:94-138
 __device__ __forceinline__ void sh_eval4(float dx, float dy, float dz, float sh[16]) {
     const float fX = -dx, fY = -dy, fZ = dz;
@@ -365,7 +375,7 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
     }
     const uint32_t g = blk * kProjThreads + threadIdx.x;
     uint32_t count = 0;
-    bool kept = false;                                                          // passed both culls: its record is stored (N6)
+    bool kept = false;                                                          // passed both culls (GS_PROJECT_WRITE_KEPT goes by it)
     float4 rec0 = make_float4(0.f, 0.f, 0.f, 0.f), rec1 = rec0, rec2 = rec0;   // culled splats: zero record
 
     if (g < n && !wave_skip) {
@@ -406,12 +416,8 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                     for (int a = 0; a < 4; ++a) rot[a] = scene.rot[a * (size_t)n + g];
                     get_covariance(fp, scale, rot, vp, cov, cov0);        // :113-120
 
-                    // getScreenSpacePosition, Common.glsl:80-89 (same proj*viewPos and division as above)
-                    float sx = ndc_x, sy = -ndc_y;
-                    sx = (sx + 1.0f) * 0.5f;
-                    sy = (sy + 1.0f) * 0.5f;
-                    sx = sx * (float)fp.width;
-                    sy = sy * (float)fp.height;
+                    float sx, sy;
+                    screen_position(fp, ndc_x, ndc_y, sx, sy);
 
                     // getGaussianTileExtents, InitSortList.comp:47-68
                     const float det = cov[0] * cov[2] - cov[1] * cov[1];
@@ -482,22 +488,38 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
     s_raster[threadIdx.x * 3 + 2] = rec2;
     // per-workgroup total -> block_sums (input of the scan that replaces the atomic counter)
     const uint32_t wsum = wave_sum_to_lane63(count);
-    const uint32_t wflags = (uint32_t)__popcll(__ballot(count != 0u));   // emitting splats (GS_SORT_RADIX4_SPLAT_FIRST)
+    const uint64_t emits = __ballot(count != 0u);
+    const uint32_t wflags = (uint32_t)__popcll(emits);                   // emitting splats (GS_SORT_RADIX4_SPLAT_FIRST)
     const bool wave_kept = __ballot(kept) != 0ull;
     if (lane_id() == 63) {
         s_wave_sum[wave_id()] = wsum;
         s_wave_flags[wave_id()] = wflags;
-        // Which waves write their 3 KB of the block.  RenderGaussians reaches records only through the sorted list, i.e.
-        // those of emitting splats; the reference also stores colour + covariance of every splat that passes the culls
-        // (N6), readable here through gs_debug_read.  Full grid: a wave writes when any of its splats passed the culls
-        // -- a wholly culled wave (a quarter of them at the benchmark pose; the arrays are in Morton order, so culled
-        // splats come in runs) has nothing but zero records to store.  A context that owns a tile-row band: when any of
-        // its splats emits into the band (most waves of a narrow band do not).  wave_wrote tells gs_debug_read which
-        // records are this frame's (the others read back as zero, what a culled splat's scratch holds).
+        // Which chunks of its 3 KB of the block a wave writes, as a mask of its four quarters (16 records = 768 bytes =
+        // twelve whole 64-byte lines each).  RenderGaussians -- and every kernel behind the frame -- reaches records only
+        // through the sorted list, i.e. those of emitting splats; the reference also stores colour + covariance of every
+        // splat that passes the culls (N6), which gs_debug_read recomputes on demand (k_debug_records).  Full grid: a
+        // chunk of GS_PROJECT_RECORD_CHUNK records is written when one of its splats emits -- the splats in the margin
+        // between NDC 1.0 and the 1.3 cull pass the culls and touch no tile (a third of the kept ones at the benchmark
+        // pose; the arrays are in Morton order, so they come in runs), and a wholly culled chunk has nothing but zero
+        // records to store.  A context that owns a tile-row band: the whole wave when any of its splats emits into the
+        // band (most waves of a narrow band do not).  wave_wrote tells gs_debug_read which records are this frame's; the
+        // others are stale (an earlier frame's) or zero.
 #ifndef GS_PROJECT_WRITE_ALL
 #define GS_PROJECT_WRITE_ALL 0      /* tuning: 1 = a full-grid frame stores every wave's records, as before round 4 */
 #endif
-        const uint32_t wrote = (band ? wsum != 0u : (GS_PROJECT_WRITE_ALL || wave_kept)) ? 1u : 0u;
+#ifndef GS_PROJECT_WRITE_KEPT
+#define GS_PROJECT_WRITE_KEPT 0     /* tuning: 1 = a full-grid frame stores a wave when any of its splats passed the culls */
+#endif
+#ifndef GS_PROJECT_RECORD_CHUNK
+#define GS_PROJECT_RECORD_CHUNK 16  /* records per stored chunk of a full-grid frame: 16 (a quarter wave) or 64 (a wave) */
+#endif
+        static_assert(GS_PROJECT_RECORD_CHUNK == 16 || GS_PROJECT_RECORD_CHUNK == 64, "a quarter wave or a wave");
+        uint32_t wrote;
+        if (band) wrote = wsum != 0u ? 0xFu : 0u;
+        else if (GS_PROJECT_WRITE_ALL || GS_PROJECT_WRITE_KEPT) wrote = (GS_PROJECT_WRITE_ALL || wave_kept) ? 0xFu : 0u;
+        else if (GS_PROJECT_RECORD_CHUNK == 64) wrote = emits != 0ull ? 0xFu : 0u;
+        else wrote = ((emits & 0xFFFFull) ? 1u : 0u) | ((emits & 0xFFFF0000ull) ? 2u : 0u) |
+                     ((emits & 0xFFFF00000000ull) ? 4u : 0u) | ((emits >> 48) ? 8u : 0u);
         s_wave_emits[wave_id()] = wrote;
         sc.wave_wrote[blk * (kProjThreads / 64) + wave_id()] = (uint8_t)wrote;
     }
@@ -508,8 +530,8 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
         float4* out = reinterpret_cast<float4*>(sc.raster + first);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const uint32_t i = q * kProjThreads + threadIdx.x;
-            if (i < valid * 3u && s_wave_emits[i / 192u]) out[i] = s_raster[i];
+            const uint32_t i = q * kProjThreads + threadIdx.x;          // float4 i of the block: record i / 3, quarter i / 48
+            if (i < valid * 3u && ((s_wave_emits[i / 192u] >> ((i / 48u) & 3u)) & 1u)) out[i] = s_raster[i];
         }
     }
     uint32_t t = 0;
@@ -812,15 +834,15 @@ void launch_project(const FrameParams& fp, const SceneBuffers& scene, const Spla
 // gs_debug_read(GS_BUF_COLOR), full-grid contexts: the reference stores a colour for EVERY splat that passes the two culls
 // (InitSortList.comp:124-127, before it knows whether the splat touches a tile; SURVEY "preserve" item N6); k_project
 // evaluates it only for the splats that emit (nothing else is ever read by a frame).  This fills in the others on demand,
-// from the last frame's camera: out[g] = (r, g, b, 1) for a splat whose record k_project stored (its covariance carries
-// the +0.3 dilation, so .cx != 0 marks it) but which touched no tile, (0, 0, 0, 0) otherwise.
+// from the last frame's camera: out[g] = (r, g, b, 1) for a splat that passed the culls but touched no tile (k_debug_records
+// says which: records[2 g].w), (0, 0, 0, 0) otherwise.
 template <int SH_K>
-__global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, const SceneBuffers scene, const SplatScratch sc, float4* out) {
+__global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, const SceneBuffers scene, const float4* records, float4* out) {
     const uint32_t n = fp.num_gaussians;
     const uint32_t g = blockIdx.x * 256u + threadIdx.x;
     if (g >= n) return;
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (sc.wave_wrote[g >> 6] && sc.raster[g].cx != 0.0f && sc.tiles_touched[g] == 0u) {
+    if (records[2 * (size_t)g].w != 0.0f) {
         float res[3];
         splat_colour<false, SH_K>(fp, scene.sh + g, n, scene.pos[g], scene.pos[(size_t)n + g], scene.pos[2 * (size_t)n + g], res);
         o = make_float4(res[0], res[1], res[2], 1.0f);
@@ -828,15 +850,59 @@ __global__ __launch_bounds__(256) void k_debug_colour(const FrameParams fp, cons
     out[g] = o;
 }
 
-void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, float* out_rgba, hipStream_t stream) {
+void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const float* records, float* out_rgba, hipStream_t stream) {
     const uint32_t blocks = (fp.num_gaussians + 255u) / 256u;
     if (!blocks) return;
     float4* out = reinterpret_cast<float4*>(out_rgba);
+    const float4* recs = reinterpret_cast<const float4*>(records);
     switch (sh_cut_of_mode(fp.sh_mode)) {
-        case 4: hipLaunchKernelGGL(k_debug_colour<4>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
-        case 9: hipLaunchKernelGGL(k_debug_colour<9>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
-        default: hipLaunchKernelGGL(k_debug_colour<0>, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, out); break;
+        case 4: hipLaunchKernelGGL(k_debug_colour<4>, dim3(blocks), dim3(256), 0, stream, fp, scene, recs, out); break;
+        case 9: hipLaunchKernelGGL(k_debug_colour<9>, dim3(blocks), dim3(256), 0, stream, fp, scene, recs, out); break;
+        default: hipLaunchKernelGGL(k_debug_colour<0>, dim3(blocks), dim3(256), 0, stream, fp, scene, recs, out); break;
     }
+}
+
+// gs_debug_read(GS_BUF_COV / GS_BUF_COLOR), full-grid contexts: the frame stores the records of the chunks with an emitting
+// splat only, the reference the covariance of every splat that passes the two culls (N6).  This recomputes, from the last
+// frame's camera, what k_project held in registers for the splats that touched no tile: out[2 g] = (sx, sy, 0, 1) and
+// out[2 g + 1] = (0, cx, cy, cz) for a splat that passes both culls and has tiles_touched == 0, zeros for every other one (a
+// culled splat, and an emitting one: its stored record is this frame's).  The culls are k_project's expressions and the
+// geometry its device functions, compiled with its flags: the same bits as a record the frame would have stored.
+__global__ __launch_bounds__(256) void k_debug_records(const FrameParams fp, const SceneBuffers scene, const SplatScratch sc, float4* out) {
+    const uint32_t n = fp.num_gaussians;
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n) return;
+    float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
+    if (sc.tiles_touched[g] == 0u) {
+        float vp[4];
+        mat4_mul_vec4(fp.view, scene.pos[g], scene.pos[(size_t)n + g], scene.pos[2 * (size_t)n + g], 1.0f, vp);   // InitSortList.comp:93
+        if (!(-vp[2] <= fp.near_plane)) {                                                                       // :94
+            float q[4];
+            mat4_mul_vec4(fp.proj, vp[0], vp[1], vp[2], vp[3], q);                                              // :98
+            const float ndc_x = q[0] / q[3];                                                                    // :99
+            const float ndc_y = q[1] / q[3];
+            if (!(fabsf(ndc_x) > fp.ndc_cull || fabsf(ndc_y) > fp.ndc_cull)) {                                  // :100
+                float scale[3], rot[4], cov[3], cov0[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) scale[a] = scene.scale[a * (size_t)n + g];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) rot[a] = scene.rot[a * (size_t)n + g];
+                get_covariance(fp, scale, rot, vp, cov, cov0);                                                  // :113-120
+                float sx, sy;
+                screen_position(fp, ndc_x, ndc_y, sx, sy);
+                o0 = make_float4(sx, sy, 0.0f, 1.0f);
+                o1 = make_float4(0.0f, cov[0], cov[1], cov[2]);
+            }
+        }
+    }
+    out[2 * (size_t)g] = o0;
+    out[2 * (size_t)g + 1] = o1;
+}
+
+void launch_debug_records(const FrameParams& fp, const SceneBuffers& scene, const SplatScratch& sc, float* out_records, hipStream_t stream) {
+    const uint32_t blocks = (fp.num_gaussians + 255u) / 256u;
+    if (!blocks) return;
+    hipLaunchKernelGGL(k_debug_records, dim3(blocks), dim3(256), 0, stream, fp, scene, sc, reinterpret_cast<float4*>(out_records));
 }
 
 void launch_scan_blocks(const FrameParams& fp, const SplatScratch& sc, SortParams* params,
