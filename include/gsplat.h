@@ -195,6 +195,22 @@ typedef struct gs_scene_info {
                                                              splat that emitted an element its raster opacity (the scene's, 0 where
                                                              the 2 x 2 determinant vanishes, times the anti-aliasing factor under
                                                              gs_set_antialias), 0 for every other splat */
+/* The work the last frame decided NOT to do (values never show it: a frame that skips nothing has the same pixels) */
+#define GS_BUF_WAVE_WROTE 12   /* uint8[ceil(N / 64)]        per wave of 64 splats, a mask of its four quarters (bit q = splats
+                                                             64 w + 16 q ..): InitSortList stored their raster records.  Whole grid
+                                                             or interleaved rows: a quarter with a splat that emits an element.  A
+                                                             contiguous band of tile rows: 0xF when a splat of the wave emits into
+                                                             the band, else 0.  Valid after a frame and after
+                                                             gs_debug_init_sort_list */
+#define GS_BUF_BAND_BLOCKS 13  /* uint32[1 + count]          word 0 = count, then the blocks of 256 splats InitSortList projected,
+                                                             ascending: block | skip mask << 28 (bit w of the mask: wave w of the
+                                                             block was not projected).  A caller reads 4 bytes to learn the count,
+                                                             then 4 * (1 + count).  A contiguous band of tile rows: what the band
+                                                             cull kept.  Every row, or interleaved rows: every block, mask 0 */
+#define GS_BUF_TILE_ORDER 14   /* uint32[owned tiles]        the k-th tile RenderGaussians dispatched, a global tile id: longest
+                                                             list first by bit length of (end - start), any order among equal bit
+                                                             lengths; GS_TILE_ORDER_RASTER: the owned tiles ascending.  Valid after
+                                                             a frame only */
 
 /* GS_API_VERSION of the library that is actually loaded: compare with the header's before anything else
  * (gsplat.hpp and the Python binding do). */

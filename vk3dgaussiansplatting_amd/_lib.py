@@ -38,6 +38,7 @@ GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read
 (BUF_SORTED_TILE, BUF_SORTED_DEPTH, BUF_SORTED_ID, BUF_RANGES, BUF_COLOR, BUF_COV, BUF_COUNT,
  BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE) = range(11)
 BUF_RASTER_OPACITY = 11
+BUF_WAVE_WROTE, BUF_BAND_BLOCKS, BUF_TILE_ORDER = 12, 13, 14   # the work the last frame skipped (include/gsplat.h)
 
 RECORD_BYTES = 336
 

@@ -171,6 +171,51 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
             std::memcpy(dst, outv.data(), bytes);
             return GS_OK;
         }
+        // The three read-backs of work a frame decided NOT to do (nothing of a frame reads them back: host code only)
+        case GS_BUF_WAVE_WROTE:
+            // one byte per wave of 64 splats as k_project / k_band_cull left it; the waves past the last splat are not part
+            src = c->scratch.wave_wrote; avail = ((size_t)c->n + 63u) / 64u; break;
+        case GS_BUF_BAND_BLOCKS: {
+            // word 0 = the count, then the records ascending by block (k_band_cull appends them in atomic arrival order)
+            const FrameParams& fp = c->last.fp;
+            const bool listed = !(fp.row_begin == 0u && fp.row_end == fp.grid_h) && fp.row_stride == 1u;   // launch_project's
+            std::vector<uint32_t> rec(1);
+            if (listed) {
+                uint32_t count = 0;
+                HIP_TRY(c, hipMemcpy(&count, c->scratch.help_count + 2u + fp.parity, sizeof(count), hipMemcpyDeviceToHost));
+                if (count > c->num_blocks) return fail(c, GS_ERR_INVALID, "gs_debug_read: band list count exceeds the project blocks");
+                rec.resize(1u + (size_t)count);
+                if (count) HIP_TRY(c, hipMemcpy(rec.data() + 1, c->scratch.band_list, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                std::sort(rec.begin() + 1, rec.end(), [](uint32_t a, uint32_t b) { return (a & 0x0FFFFFFFu) < (b & 0x0FFFFFFFu); });
+            } else {
+                // every row, or interleaved rows: k_band_cull does not run and k_project takes every block, no wave skipped
+                rec.resize(1u + (size_t)c->num_blocks);
+                for (uint32_t b = 0; b < c->num_blocks; ++b) rec[1u + b] = b;
+            }
+            rec[0] = (uint32_t)(rec.size() - 1u);
+            if (bytes > rec.size() * sizeof(uint32_t)) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
+            std::memcpy(dst, rec.data(), bytes);
+            return GS_OK;
+        }
+        case GS_BUF_TILE_ORDER: {
+            if (c->last.kind != LastFrame::kFrame)
+                return fail(c, GS_ERR_INVALID, "gs_debug_read: the tile order is only valid after a frame");
+            const FrameParams& fp = c->last.fp;
+            const size_t tiles = (size_t)fp.rows_owned * fp.grid_w;
+            if (bytes > tiles * sizeof(uint32_t)) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
+            const size_t cnt = bytes / sizeof(uint32_t);
+            uint32_t* out = static_cast<uint32_t*>(dst);
+            if (c->cfg.tile_order == GS_TILE_ORDER_LONGEST_FIRST) {
+                if (cnt) HIP_TRY(c, hipMemcpy(out, c->tile_order, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            } else {
+                for (size_t i = 0; i < cnt; ++i) out[i] = (uint32_t)i;      // raster order: workgroup k takes compact tile k
+            }
+            for (size_t i = 0; i < cnt; ++i) {                              // compact -> global, as k_render's TileMap does
+                const uint32_t k = out[i] / fp.grid_w, x = out[i] - k * fp.grid_w;
+                out[i] = (fp.first_row + k * fp.row_stride) * fp.grid_w + x;
+            }
+            return GS_OK;
+        }
         default: return fail(c, GS_ERR_INVALID, "gs_debug_read: unknown buffer id");
     }
     if (bytes > avail) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");

@@ -591,6 +591,16 @@ class Renderer:
             a = np.zeros(info.num_gaussians, dtype=np.float32)
         elif which == _lib.BUF_RANGES:
             a = np.zeros((info.tiles_x * info.tiles_y, 2), dtype=np.uint32)
+        elif which == _lib.BUF_WAVE_WROTE:
+            a = np.zeros((info.num_gaussians + 63) // 64, dtype=np.uint8)
+        elif which == _lib.BUF_TILE_ORDER:
+            a = np.zeros(info.rows_owned * info.tiles_x, dtype=np.uint32)
+        elif which == _lib.BUF_BAND_BLOCKS:      # word 0 is the count: read it, then the records behind it
+            cnt = np.zeros(1, dtype=np.uint32)
+            self._ctx.check(L.gs_debug_read(self._ctx.handle, which, _p(cnt), 4))
+            a = np.zeros(1 + int(cnt[0]), dtype=np.uint32)
+            self._ctx.check(L.gs_debug_read(self._ctx.handle, which, _p(a), a.nbytes))
+            return a[1:]
         elif which == _lib.BUF_IMAGE:
             a = np.zeros((info.height, info.width, 4), dtype=np.uint8)
         else:
