@@ -10,10 +10,10 @@ the 59 fields of records, m and v read and written (7 x 236); the upload reads a
 gs_adam_rows_raw_device, runs beside the record-space one on the same rows in the same repetitions (--out-raw): it also
 writes the record's fields and reads its scale, rotation and opacity again (8 x 236 + 32 bytes per row).
 
-    python tools/adam_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/adam_cost.txt] [--out-raw profiles/adam_raw_cost.txt]"""
-import argparse, json, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+    python tools/adam_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/adam_cost.txt] [--out-raw profiles/adam_raw_cost.txt] [--cache DIR]"""
+import argparse, json, os
+import costlib
+from costlib import ROOT, event_ms
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="C")
@@ -21,38 +21,20 @@ ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "adam_cost.txt"))
 ap.add_argument("--out-raw", default=os.path.join(ROOT, "profiles", "adam_raw_cost.txt"))
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
 
+gs, _ = costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import synth
 
 ADAM_BYTES_PER_ROW = 7 * 59 * 4
 ADAM_RAW_BYTES_PER_ROW = 8 * 59 * 4 + (3 + 4 + 1) * 4      # + the record's fields written, its scale, rotation and opacity read
 UPLOAD_BYTES_PER_ROW = 336 + 60 * 4
 
-aos, cfg = synth.generate_config(a.config)
-aos = np.ascontiguousarray(aos, dtype=np.float32)
-n, w, h = len(aos), cfg["width"], cfg["height"]
-rm = gs.ResourceManager(); rm.setGaussians(aos)
-sc = gs.Scene(rm, aspect_ratio=w / h)
-cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
-r = gs.Renderer(w, h, record_timings=False, warmup_frames=0)
-r.init(rm); r.initForScene(sc)
-
+aos, n, w, h, rm, sc, r = costlib.config_scene(a.config, record_timings=False, cache=a.cache)
 dev = torch.device("cuda:0")
-rng = np.random.default_rng(0)
-grad_image = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device=dev)
-r.drawDevice(sc, None, sync=True)
-rows_listed = r.visibleCount()
-ids = torch.zeros(rows_listed, dtype=torch.int32, device=dev)
-rows = torch.zeros(rows_listed, 84, device=dev)
-count = torch.zeros(1, dtype=torch.int32, device=dev)
-torch.cuda.synchronize()
-r.backwardVisibleDevice(grad_image.data_ptr(), None, ids.data_ptr(), rows.data_ptr(), rows_listed, count.data_ptr())
-r.synchronize()
-assert int(count.item()) == rows_listed and bool(torch.isfinite(rows).all())
+rows_listed, ids, rows, count = costlib.visible_list(r, sc, costlib.image_grads(h, w))
 
 records = torch.tensor(aos, device=dev)
 m, v = torch.zeros_like(records), torch.zeros_like(records)
@@ -63,19 +45,6 @@ leaf.grad = torch.sparse_coo_tensor(ids.long()[None], rows, size=(n, 84)).coales
 stream = torch.cuda.Stream(device=dev)
 torch.cuda.synchronize()
 r.setStream(stream.cuda_stream)
-
-
-def timed(calls):
-    """The calls back to back on the stream, an event before each and one behind the last: milliseconds per call."""
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(calls) + 1)]
-    for e, call in zip(ev, calls):
-        e.record(stream)
-        call()
-    ev[-1].record(stream)
-    ev[-1].synchronize()
-    return [ev[k].elapsed_time(ev[k + 1]) for k in range(len(calls))]
-
-
 step = [0]
 
 
@@ -106,7 +75,7 @@ old_route = [opt.step, lambda: r.uploadDevice(leaf.data_ptr(), n)]
 new_ms, old_ms, raw_ms = [], [], []
 with torch.cuda.stream(stream):
     for k in range(a.warmup + a.iters):
-        t_new, t_raw, t_old = timed(new_route), timed([adam_raw]), timed(old_route)
+        t_new, t_raw, t_old = event_ms(stream, new_route), event_ms(stream, [adam_raw]), event_ms(stream, old_route)
         if k >= a.warmup:
             new_ms.append(t_new)
             old_ms.append(t_old)
@@ -116,8 +85,8 @@ r.setStream(None)
 r.cleanup()
 
 new_ms, old_ms = np.array(new_ms), np.array(old_ms)
-mean = lambda x: round(float(np.mean(x)), 4)
-spread = lambda x: [round(float(np.min(x)), 4), round(float(np.max(x)), 4)]
+mean = lambda x: costlib.summary(x)[0]
+spread = lambda x: costlib.summary(x)[2]
 adam_ms, upload_rows_ms = mean(new_ms[:, 0]), mean(new_ms[:, 1])
 new_total, old_total = mean(new_ms.sum(1)), mean(old_ms.sum(1))
 line = {"config": a.config, "width": w, "height": h, "gaussians": n, "rows": rows_listed, "iters": a.iters, "warmup": a.warmup,
@@ -134,14 +103,12 @@ line = {"config": a.config, "width": w, "height": h, "gaussians": n, "rows": row
         "documented_route_over_new_route": round(old_total / new_total, 2),
         "new_route_is_faster": bool(new_total < old_total)}
 print(json.dumps(line), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("# tools/adam_cost.py on one MI355X: gs_adam_rows_device + gs_upload_rows_device against torch.optim.SparseAdam.step() on the\n"
+costlib.write_lines(
+    a.out, "# tools/adam_cost.py on one MI355X: gs_adam_rows_device + gs_upload_rows_device against torch.optim.SparseAdam.step() on the\n"
             "# same sparse gradient + the full in-place gs_upload_gaussians_device; config C under its own camera, the rows of one\n"
             "# gs_backward_visible_device; HIP events around every call on one stream, the routes alternating, means (and min, max) over\n"
             "# `iters` repetitions after `warmup`.  GPU times; the host-side wait for the count that the documented route also needs\n"
-            "# (gs_visible_count, to size the COO tensor) is not in them.  Recorded numbers, not a bound.\n")
-    f.write(json.dumps(line) + "\n")
+            "# (gs_visible_count, to size the COO tensor) is not in them.  Recorded numbers, not a bound.\n", [line])
 
 # the raw step beside the record step, the same rows in the same run
 raw_ms = np.array(raw_ms)
@@ -165,13 +132,10 @@ finding += ("the exps, the division and the square root did not make it VALU-bou
             "well below what the bytes say -- the arithmetic (four exps, a division and a square root per row) shows; "
             "look at its VALU busy before trusting the byte count.\n")
 print(json.dumps(raw_line), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(a.out_raw)), exist_ok=True)
-with open(a.out_raw, "w") as f:
-    f.write("# tools/adam_cost.py on one MI355X: gs_adam_rows_raw_device beside gs_adam_rows_device, the same listed rows in the same run,\n"
+costlib.write_lines(
+    a.out_raw, "# tools/adam_cost.py on one MI355X: gs_adam_rows_raw_device beside gs_adam_rows_device, the same listed rows in the same run,\n"
             "# the calls alternating; HIP events around every call, means (and min, max) over `iters` repetitions after `warmup`.\n"
             "# Bytes per row: the raw kernel reads the gradient's 59 fields, reads and writes the 59 fields of raw, m and v, writes the\n"
             "# record's 59 fields (8 x 236) and reads the record's scale, rotation and opacity again (32); the record kernel moves 7 x 236.\n"
             "# It also evaluates four pinned exps per row.  Recorded numbers, not a bound; both kernels' times and the\n"
-            "# ratios are of this one run.\n")
-    f.write(finding)
-    f.write(json.dumps(raw_line) + "\n")
+            "# ratios are of this one run.\n" + finding, [raw_line])

@@ -7,22 +7,22 @@ the same sequence -- the milliseconds of the scan (the three kernels of gs_splat
 per call.  The first entry is the whole grid on the same build; each dealing ends with its slowest band beside it.  Recorded,
 not gated.  One JSON line per band and per dealing.
 
-    python tools/band_backward_cost.py [--iters 5] [--out profiles/band_backward_cost.txt]"""
-import argparse, csv, glob, json, os, shutil, subprocess, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+    python tools/band_backward_cost.py [--iters 5] [--out profiles/band_backward_cost.txt] [--cache DIR]"""
+import argparse, json, os, shutil, sys
+import costlib
+from costlib import ROOT
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="C")
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "band_backward_cost.txt"))
+costlib.add_cache_argument(ap)
 ap.add_argument("--child", action="store_true", help="run the sequence only (under rocprofv3)")
 a = ap.parse_args()
 
+costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import synth
 
 CALL = ("k_splat_block_sums<gs::BwdSource<true>>", "k_splat_scan_blocks<gs::BwdSource<true>>",
         "k_splat_offsets<gs::BwdSource<true>>", "k_bwd_blend", "k_bwd_rowsum_chain<true>")   # the launches of one call, in order
@@ -38,17 +38,10 @@ def sequence(gh):
 
 
 def run(record):
-    aos, cfg = synth.generate_config(a.config)
-    w, h, n = cfg["width"], cfg["height"], len(aos)
-    rm = gs.ResourceManager(); rm.setGaussians(aos)
-    sc = gs.Scene(rm, aspect_ratio=w / h)
-    cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
-    r = gs.Renderer(w, h, record_timings=1, warmup_frames=0)
-    r.init(rm); r.initForScene(sc)
+    s = costlib.config_scene(a.config, record_timings=1, cache=a.cache)
+    n, w, h, sc, r = s.n, s.w, s.h, s.sc, s.r
     r.setBandGradients(True)
-    rng = np.random.default_rng(0)
-    gr = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device="cuda")
-    gd = torch.tensor(rng.standard_normal((h, w)).astype(np.float32), device="cuda")
+    gr, gd = costlib.image_grads(h, w, depth=True)
     ids, rows = torch.empty(n, dtype=torch.int32, device="cuda"), torch.empty(n, 84, device="cuda")
     count = torch.zeros(1, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
@@ -61,14 +54,10 @@ def run(record):
         else:
             r.setTileRowsInterleaved(spec[1], spec[2], False)
         r.drawDevice(sc, None, sync=True)
-        ms = []
-        for _ in range(a.iters + 1):                            # the first is the warm-up
-            t0 = time.perf_counter()
-            r.backwardVisibleDevice(gr.data_ptr(), gd.data_ptr(), ids.data_ptr(), rows.data_ptr(), n, count.data_ptr())
-            r.synchronize()
-            ms.append((time.perf_counter() - t0) * 1e3)
+        ms = [costlib.host_ms(r, lambda: r.backwardVisibleDevice(gr.data_ptr(), gd.data_ptr(), ids.data_ptr(), rows.data_ptr(), n, count.data_ptr()))
+              for _ in range(a.iters + 1)]                      # the first is the warm-up
         record(dict(dealing=dealing, band=k, rows=None if spec is None else list(spec[1:]), elements=int(r.timings().num_sort_elements),
-                    visible=int(count.item()), visible_backward_ms_median=round(float(np.median(ms[1:])), 4)))
+                    visible=int(count.item()), visible_backward_ms_median=costlib.median(ms[1:])))
     r.cleanup()
     return dict(config=a.config, width=w, height=h, gaussians=n, tiles_y=gh, iters=a.iters)
 
@@ -82,16 +71,8 @@ head = run(bands.append)
 
 # the split: one traced child, its launches in start order, five per call, iters + 1 calls per band
 if shutil.which("rocprofv3"):
-    d = tempfile.mkdtemp(prefix="band_bwd_cost_")
-    rc = subprocess.run(["timeout", "-k", "10", "500", "rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--",
-                         sys.executable, os.path.abspath(__file__), "--child", "--config", a.config, "--iters", str(a.iters)],
-                        capture_output=True, text=True).returncode
-    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-    if rc != 0 or not files:
-        raise SystemExit(f"band_backward_cost: the traced child failed (rc {rc}, {len(files)} trace files)")
-    kname = lambda k: k.replace("void ", "").replace("gs::k_", "k_").split("(")[0].replace(" ", "")
-    trace = sorted(csv.DictReader(open(files[0])), key=lambda row: int(row["Start_Timestamp"]))
-    seq = [(kname(row["Kernel_Name"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e6) for row in trace]
+    seq = costlib.traced_child([os.path.abspath(__file__), "--child", "--config", a.config, "--iters", str(a.iters)], 500,
+                               "band_backward_cost", stats=False, cache=a.cache)
     seq = [(k, ms) for k, ms in seq if k in CALL]
     calls = len(bands) * (a.iters + 1)
     if len(seq) != calls * len(CALL) or any(seq[i][0] != CALL[i % len(CALL)] for i in range(len(seq))):
@@ -100,7 +81,6 @@ if shutil.which("rocprofv3"):
     med = np.median(per_call, axis=1)
     for b, m in zip(bands, med):
         b.update(scan_ms=round(float(m[0] + m[1] + m[2]), 4), blend_ms=round(float(m[3]), 4), rowsum_chain_ms=round(float(m[4]), 4))
-    shutil.rmtree(d, ignore_errors=True)
 
 lines = [json.dumps({**head, **b}) for b in bands]
 whole = bands[0]
@@ -115,6 +95,5 @@ for dealing in dict.fromkeys(b["dealing"] for b in bands[1:]):
 header = ("# tools/band_backward_cost.py on one MI355X: gs_backward_visible_device (max_rows = N) of a context that owns a band of tile rows, gs_set_band_gradients on,\n"
           "# one band after another on one context; host-timed call (enqueue + gs_synchronize), median; scan / blend / rowsum_chain from one rocprofv3 kernel trace of the same\n"
           "# sequence in a child process (medians over the same iterations).  The first line is the whole grid on the same build.  Recorded, not gated.\n")
-with open(a.out, "w") as f:
-    f.write(header + "\n".join(lines) + "\n")
+costlib.write_lines(a.out, header, lines)
 print("\n".join(lines), flush=True)

@@ -13,10 +13,10 @@ from the counts of this run:
 Then, as an observation only, the per-view losses of 20 VisibleAdam.step_batch steps on the dense test scene under the tests' two
 cameras.
 
-    python tools/batch_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/batch_cost.txt]"""
+    python tools/batch_cost.py [--config C] [--iters 20] [--warmup 3] [--out profiles/batch_cost.txt] [--cache DIR]"""
 import argparse, ctypes as C, json, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import costlib
+from costlib import ROOT, event_ms
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 ap = argparse.ArgumentParser()
@@ -24,40 +24,25 @@ ap.add_argument("--config", default="C")
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batch_cost.txt"))
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
 
+gs, _ = costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import _lib, synth
+from vk3dgaussiansplatting_amd import _lib
 
 POSES = (dict(pos=(0.0, 0.0, 0.0), yaw=0.0, pitch=0.0), dict(pos=(0.2, 0.1, -0.5), yaw=0.1, pitch=-0.05))
 WEIGHTS = (0.5, 0.5)
 FIELD_BYTES, ROW_BYTES = 59 * 4, 336
 
-aos, cfg = synth.generate_config(a.config)
-aos = np.ascontiguousarray(aos, dtype=np.float32)
-n, w, h = len(aos), cfg["width"], cfg["height"]
-rm = gs.ResourceManager(); rm.setGaussians(aos)
-sc = gs.Scene(rm, aspect_ratio=w / h)
-r = gs.Renderer(w, h, record_timings=False, warmup_frames=0)
-r.init(rm); r.initForScene(sc)
-
+aos, n, w, h, rm, sc, r = costlib.config_scene(a.config, record_timings=False, cache=a.cache)
 dev = torch.device("cuda:0")
-rng = np.random.default_rng(0)
-grad_image = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device=dev)
+grad_image = costlib.image_grads(h, w)
 views = []
 for pose in POSES:
     cam = sc.getCamera(); cam.setPosition(pose["pos"]); cam.setRotation(pose["yaw"], pose["pitch"]); cam.recalculate()
-    r.drawDevice(sc, None, sync=True)
-    listed = r.visibleCount()
-    ids = torch.zeros(listed, dtype=torch.int32, device=dev)
-    rows = torch.zeros(listed, 84, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    r.backwardVisibleDevice(grad_image.data_ptr(), None, ids.data_ptr(), rows.data_ptr(), listed, count.data_ptr())
-    r.synchronize()
-    assert int(count.item()) == listed and bool(torch.isfinite(rows).all())
+    listed, ids, rows, count = costlib.visible_list(r, sc, grad_image)
     views.append((ids, rows, count, listed))
 
 acc = torch.empty(n, 84, device=dev)
@@ -72,17 +57,6 @@ ids64 = [v[0].long() for v in views]
 stream = torch.cuda.Stream(device=dev)
 torch.cuda.synchronize()
 r.setStream(stream.cuda_stream)
-
-
-def timed(calls):
-    """The calls back to back on the stream, an event before each and one behind the last: milliseconds per call."""
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(calls) + 1)]
-    for e, call in zip(ev, calls):
-        e.record(stream)
-        call()
-    ev[-1].record(stream)
-    ev[-1].synchronize()
-    return [ev[k].elapsed_time(ev[k + 1]) for k in range(len(calls))]
 
 
 def accumulate(b):
@@ -119,7 +93,7 @@ old_route = [torch_clear, torch_add(0), torch_add(1), torch_list]
 new_ms, old_ms = [], []
 with torch.cuda.stream(stream):
     for k in range(a.warmup + a.iters):
-        t_new, t_old = timed(new_route), timed(old_route)
+        t_new, t_old = event_ms(stream, new_route), event_ms(stream, old_route)
         if k >= a.warmup:
             new_ms.append(t_new)
             old_ms.append(t_old)
@@ -141,8 +115,8 @@ for kind, name in ((1, "copy16"), (10, "copy16_x4")):
 r.cleanup()
 
 new_ms, old_ms = np.array(new_ms), np.array(old_ms)
-mean = lambda x: round(float(np.mean(x)), 4)
-spread = lambda x: [round(float(np.min(x)), 4), round(float(np.max(x)), 4)]
+mean = lambda x: costlib.summary(x)[0]
+spread = lambda x: costlib.summary(x)[2]
 listed = [v[3] for v in views]
 common = listed[0] + listed[1] - union
 acc_bytes = [listed[0] * (2 * FIELD_BYTES + 20), listed[1] * (2 * FIELD_BYTES + 20) + common * FIELD_BYTES]
@@ -212,15 +186,12 @@ train = {"scene": "dense (6000 splats, 160 x 96)", "views": 2, "steps": STEPS, "
          "mean_loss_last_step": round(float(np.mean(losses[-1])), 6)}
 print(json.dumps(train), flush=True)
 
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("# tools/batch_cost.py on one MI355X: gs_rows_accumulate_device for each of two views and one gs_rows_collect_device against the\n"
+costlib.write_lines(
+    a.out, ("# tools/batch_cost.py on one MI355X: gs_rows_accumulate_device for each of two views and one gs_rows_collect_device against the\n"
             "# torch route (zero a dense [N, 84] gradient and the touched flags, index_add_ per view, nonzero + index_select), and gs_membench's\n"
             "# device-to-device copy rate (1 GiB buffers) on the same device in the same run.  Config C under its own camera and a nearby\n"
             "# pose, the rows of one gs_backward_visible_device per view; HIP events around every call on one stream, the routes\n"
             "# alternating, means (and min, max) over `iters` repetitions after `warmup`.  Bytes: what each call has to move, from this\n"
             "# run's counts (the tool's docstring has the formulas); rates = those bytes over the GPU time; *_over_copy = that rate over the\n"
-            "# better of the two copy rates.  GPU times: the host wait inside nonzero is not in them.  Recorded numbers, not a bound.\n")
-    f.write(json.dumps(line) + "\n")
-    f.write("# Observation only: the per-view losses of 20 VisibleAdam.step_batch steps (default rates, weights 1/2) on the dense test scene.\n")
-    f.write(json.dumps(train) + "\n")
+            "# better of the two copy rates.  GPU times: the host wait inside nonzero is not in them.  Recorded numbers, not a bound.\n"),
+    [line, "# Observation only: the per-view losses of 20 VisibleAdam.step_batch steps (default rates, weights 1/2) on the dense test scene.", train])

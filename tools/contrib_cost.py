@@ -8,10 +8,10 @@ alternating in one loop so that all see the same neighbours; mean, median and mi
 `rocprofv3 --kernel-trace --stats` (a child process) for the split of gs_contrib_device into its slot-offset scan,
 k_contrib_blend and k_contrib_rowsum, next to k_bwd_blend of the same trace.
 
-    python tools/contrib_cost.py [C Chard ...] [--iters 20] [--warmup 3] [--trace] [--out profiles/contrib_cost.txt]"""
-import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+    python tools/contrib_cost.py [C Chard ...] [--iters 20] [--warmup 3] [--trace] [--out profiles/contrib_cost.txt] [--cache DIR]"""
+import argparse, json, os, shutil, sys
+import costlib
+from costlib import ROOT
 
 ap = argparse.ArgumentParser()
 ap.add_argument("configs", nargs="*", default=["C", "Chard"])
@@ -20,33 +20,21 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--trace", action="store_true", help="also split the calls into kernels with rocprofv3 (a second run)")
 ap.add_argument("--child", action="store_true", help="run the loop only (under rocprofv3)")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "contrib_cost.txt"))
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
 
+gs, _ = costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import synth
 
 dev = torch.device("cuda:0")
 
 
 def measure(name):
-    aos, cfg = synth.generate_config(name)
-    aos = np.ascontiguousarray(aos, dtype=np.float32)
-    n, w, h = len(aos), cfg["width"], cfg["height"]
-    rm = gs.ResourceManager(); rm.setGaussians(aos)
-    sc = gs.Scene(rm, aspect_ratio=w / h)
-    cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
-    r = gs.Renderer(w, h, record_timings=False, warmup_frames=0)
-    r.init(rm); r.initForScene(sc)
-    rng = np.random.default_rng(0)
-    grad_image = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device=dev)
-    r.drawDevice(sc, None, sync=True)
+    aos, n, w, h, rm, sc, r = costlib.config_scene(name, record_timings=False, cache=a.cache)
+    grad_image = costlib.image_grads(h, w)
+    visible, ids, rows, count = costlib.visible_list(r, sc)
     elems = int(r.debugRead(gs.BUF_COUNT)[0])
-    visible = r.visibleCount()
-    ids = torch.zeros(visible, dtype=torch.int32, device=dev)
-    rows = torch.zeros(visible, 84, device=dev)
-    count = torch.zeros(1, dtype=torch.int32, device=dev)
     wmax, wsum = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
     pixels = torch.zeros(n, dtype=torch.int32, device=dev)
     records = torch.tensor(aos, device=dev)
@@ -57,16 +45,7 @@ def measure(name):
     stream = torch.cuda.Stream(device=dev)
     torch.cuda.synchronize()
     r.setStream(stream.cuda_stream)
-    args = gs.Renderer._camera_args(cam)
-
-    def timed(call):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        call()
-        e1.record(stream)
-        e1.synchronize()
-        return e0.elapsed_time(e1)
-
+    args = gs.Renderer._camera_args(sc.getCamera())
     calls = {
         "forward": lambda: r.drawCamera(*args, None, sync=False),
         "backward_visible": lambda: r.backwardVisibleDevice(grad_image.data_ptr(), None, ids.data_ptr(), rows.data_ptr(), visible,
@@ -81,7 +60,7 @@ def measure(name):
     with torch.cuda.stream(stream):
         for it in range(a.warmup + a.iters):
             for k, call in calls.items():
-                t = timed(call)
+                t = costlib.event_ms(stream, [call])[0]
                 if it >= a.warmup:
                     ms[k].append(t)
     torch.cuda.synchronize()
@@ -94,9 +73,7 @@ def measure(name):
     line = {"config": name, "width": w, "height": h, "gaussians": n, "elements": elems, "visible": visible, "blended": blended,
             "iters": a.iters, "warmup": a.warmup}
     for k, x in ms.items():
-        line[k + "_ms_mean"] = round(float(np.mean(x)), 4)
-        line[k + "_ms_median"] = round(float(np.median(x)), 4)
-        line[k + "_ms_min_max"] = [round(float(np.min(x)), 4), round(float(np.max(x)), 4)]
+        line[k + "_ms_mean"], line[k + "_ms_median"], line[k + "_ms_min_max"] = costlib.summary(x)
     prune_bytes = 2 * 3 * 336 * kept + 4 * n
     line.update(contrib_vs_backward_visible=round(line["contrib_ms_median"] / line["backward_visible_ms_median"], 3),
                 prune_kept=kept, prune_bytes=prune_bytes,
@@ -109,32 +86,12 @@ if a.child:
         measure(name)
     sys.exit(0)
 
-def write(lines):
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(HEADER)
-        for line in lines:
-            f.write(json.dumps(line) + "\n")
-
 
 def trace(line):
     """The averages per launch of the kernels behind the calls, from a second run of the loop under rocprofv3."""
-    d = tempfile.mkdtemp(prefix="contrib_cost_")
-    rc = subprocess.run(["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d,
-                         "-o", "p", "--", sys.executable, os.path.abspath(__file__), line["config"], "--child", "--iters",
-                         str(a.iters), "--warmup", str(a.warmup)], capture_output=True, text=True)
-    files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-    if rc.returncode != 0 or not files:
-        raise SystemExit(f"contrib_cost: the traced run failed ({rc.returncode}): {rc.stderr[-2000:]}")
-    us = {re.sub(r"\s+", "", row["Name"]): float(row["AverageNs"]) / 1e3 for row in csv.DictReader(open(files[0]))}
-    shutil.rmtree(d, ignore_errors=True)
-
-    def ms(*words):
-        """the kernels whose name (blanks removed) holds every word"""
-        hits = [v for k, v in us.items() if all(w in k for w in words)]
-        if not hits:
-            raise SystemExit(f"contrib_cost: no kernel with {words} in the trace; it has {sorted(us)}")
-        return sum(hits) / 1e3
+    stats = costlib.traced_child([os.path.abspath(__file__), line["config"], "--child", "--iters", str(a.iters), "--warmup", str(a.warmup)],
+                                 400, "contrib_cost", cache=a.cache)
+    ms = lambda *words: costlib.kernel_us(stats, words, "contrib_cost") / 1e3       # the kernels whose name holds every word
     scan = lambda src: sum(ms(k + "<", src) for k in ("k_splat_block_sums", "k_splat_scan_blocks", "k_splat_offsets"))
     line.update(k_contrib_blend_ms=round(ms("k_contrib_blend"), 4), k_contrib_rowsum_ms=round(ms("k_contrib_rowsum"), 4),
                 slot_offsets_ms=round(scan("BwdSource<false>"), 4), k_bwd_blend_ms=round(ms("k_bwd_blend"), 4),
@@ -152,11 +109,11 @@ HEADER = ("# tools/contrib_cost.py on one MI355X: gs_contrib_device (slot-offset
 lines = [measure(name) for name in a.configs]
 for line in lines:
     print(json.dumps(line), flush=True)
-write(lines)                     # the event timings are on disk before the traced runs start
+costlib.write_lines(a.out, HEADER, lines)                     # the event timings are on disk before the traced runs start
 if a.trace:
     if not shutil.which("rocprofv3"):
         raise SystemExit("contrib_cost: --trace needs rocprofv3")
     for line in lines:
         trace(line)
         print(json.dumps(line), flush=True)
-    write(lines)
+    costlib.write_lines(a.out, HEADER, lines)

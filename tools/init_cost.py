@@ -12,8 +12,8 @@ per-lane point-against-box test), in a child process, since a process holds one 
 
 Without build_variants/lib_init_probe.so the per-launch columns and the counts are left out and the file says so."""
 import argparse, ctypes as C, json, os, subprocess, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import costlib
+from costlib import ROOT
 PROBE_LIB = os.path.join(ROOT, "build_variants", "lib_init_probe.so")
 LAUNCHES = ("bounds", "codes", "sort", "gather_boxes", "search", "rows")
 
@@ -25,10 +25,10 @@ ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "init_cost.txt")
 ap.add_argument("--probe-child", action="store_true", help=argparse.SUPPRESS)
 a = ap.parse_args()
 
+gs, synth = costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import _lib, synth
+from vk3dgaussiansplatting_amd import _lib
 
 sizes = [synth.CONFIGS["C"]["n"] if s == "C" else int(s) for s in a.sizes.split(",")]
 
@@ -51,17 +51,9 @@ stream = torch.cuda.Stream(device=dev)
 r.setStream(stream.cuda_stream)
 
 
-def timed(call):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    call()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
-mean_of = lambda x: round(float(np.mean(x)), 4)
-spread = lambda x: [round(float(np.min(x)), 4), round(float(np.max(x)), 4)]
+timed = lambda call: costlib.event_ms(stream, [call])[0]
+mean_of = lambda x: costlib.summary(x)[0]
+spread = lambda x: costlib.summary(x)[2]
 rows = []
 for kind in ("uniform", "clustered"):
     for n in sizes:
@@ -119,37 +111,35 @@ if os.path.exists(PROBE_LIB):
 for row in rows:
     row.update({k: v for k, v in probe.get((row["cloud"], row["n"]), {}).items() if k not in row})
 
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("# tools/init_cost.py on one MI355X: gs_records_from_points_device (bounds, codes, sort, gather + boxes, search, rows) and\n"
-            "# gs_knn_mean_dist2_device (the same without the rows) on a uniform cube and on the clustered cloud of config Chard; HIP\n"
-            "# events around every call on one stream, means (and min, max) over `iters` repetitions after `warmup`.\n"
-            "# launch_ms_mean and the survivor counts come from the -DGS_INIT_PROBE build (events between the launches, a counting\n"
-            "# search): per wave of 64 query points, coarse_tests = the boxes tested against the wave's box (all others, 64 per\n"
-            "# round), coarse_survivors = those the box-against-box bound kept, lane_survivors = those some lane's own\n"
-            "# point-against-box bound kept, whose 64 points were then staged and tried.  Recorded numbers, not a bound.\n")
-    if not probe:
-        f.write("# build_variants/lib_init_probe.so was not there: no per-launch times and no counts in this run.\n")
-    for row in rows:
-        f.write(json.dumps(row) + "\n")
-    # Do the n^2 / 4096 coarse tests dominate at the largest count?  Everything else in the search is linear in n (the
-    # survivors per wave hardly move), so search_ms = a n + b n^2 through the two largest sizes separates the two.
-    top = sorted(sizes)[-2:]
-    for kind in ("uniform", "clustered"):
-        two = [row for n in top for row in rows if row["cloud"] == kind and row["n"] == n and "launch_ms_mean" in row]
-        if len(two) != 2 or top[0] == top[1]:
-            continue
-        (n1, t1), (n2, t2) = ((row["n"] / 1e6, row["launch_ms_mean"]["search"]) for row in two)
-        b = (t2 - t1 * n2 / n1) / (n2 * n2 - n1 * n2)
-        a_lin = t1 / n1 - b * n1
-        big, ms = two[1], two[1]["launch_ms_mean"]
-        quad = b * n2 * n2
-        verdict = ("the coarse tests DOMINATE here: the next step is a second box level (a box per 64 boxes, tested first), not built"
-                   if quad > 0.5 * t2 else
-                   "the coarse tests do not dominate here; they would equal the linear part near n = "
-                   f"{a_lin / b:.0f} M, where the next step would be a second box level (a box per 64 boxes, tested first), not built"
-                   if b > 0 else "no quadratic part is measurable here; a second box level (a box per 64 boxes), the next step if it ever is, is not built")
-        f.write(f"# {kind} at n = {big['n']}: the search is {100 * ms['search'] / sum(ms.values()):.0f} % of the call; a wave makes "
-                f"{big['coarse_tests_per_wave']} coarse tests (n^2 / 4096 in all) for {big['coarse_survivors_per_wave']} coarse and "
-                f"{big['lane_survivors_per_wave']} per-lane survivors.  search_ms = {a_lin:.3f} n + {b:.4f} n^2 (n in millions, through the two "
-                f"largest sizes): the quadratic part is {quad:.2f} of {t2:.2f} ms -- {verdict}.\n")
+header = ("# tools/init_cost.py on one MI355X: gs_records_from_points_device (bounds, codes, sort, gather + boxes, search, rows) and\n"
+          "# gs_knn_mean_dist2_device (the same without the rows) on a uniform cube and on the clustered cloud of config Chard; HIP\n"
+          "# events around every call on one stream, means (and min, max) over `iters` repetitions after `warmup`.\n"
+          "# launch_ms_mean and the survivor counts come from the -DGS_INIT_PROBE build (events between the launches, a counting\n"
+          "# search): per wave of 64 query points, coarse_tests = the boxes tested against the wave's box (all others, 64 per\n"
+          "# round), coarse_survivors = those the box-against-box bound kept, lane_survivors = those some lane's own\n"
+          "# point-against-box bound kept, whose 64 points were then staged and tried.  Recorded numbers, not a bound.\n")
+if not probe:
+    header += "# build_variants/lib_init_probe.so was not there: no per-launch times and no counts in this run.\n"
+lines = list(rows)
+# Do the n^2 / 4096 coarse tests dominate at the largest count?  Everything else in the search is linear in n (the
+# survivors per wave hardly move), so search_ms = a n + b n^2 through the two largest sizes separates the two.
+top = sorted(sizes)[-2:]
+for kind in ("uniform", "clustered"):
+    two = [row for n in top for row in rows if row["cloud"] == kind and row["n"] == n and "launch_ms_mean" in row]
+    if len(two) != 2 or top[0] == top[1]:
+        continue
+    (n1, t1), (n2, t2) = ((row["n"] / 1e6, row["launch_ms_mean"]["search"]) for row in two)
+    b = (t2 - t1 * n2 / n1) / (n2 * n2 - n1 * n2)
+    a_lin = t1 / n1 - b * n1
+    big, ms = two[1], two[1]["launch_ms_mean"]
+    quad = b * n2 * n2
+    verdict = ("the coarse tests DOMINATE here: the next step is a second box level (a box per 64 boxes, tested first), not built"
+               if quad > 0.5 * t2 else
+               "the coarse tests do not dominate here; they would equal the linear part near n = "
+               f"{a_lin / b:.0f} M, where the next step would be a second box level (a box per 64 boxes, tested first), not built"
+               if b > 0 else "no quadratic part is measurable here; a second box level (a box per 64 boxes), the next step if it ever is, is not built")
+    lines.append(f"# {kind} at n = {big['n']}: the search is {100 * ms['search'] / sum(ms.values()):.0f} % of the call; a wave makes "
+            f"{big['coarse_tests_per_wave']} coarse tests (n^2 / 4096 in all) for {big['coarse_survivors_per_wave']} coarse and "
+            f"{big['lane_survivors_per_wave']} per-lane survivors.  search_ms = {a_lin:.3f} n + {b:.4f} n^2 (n in millions, through the two "
+            f"largest sizes): the quadratic part is {quad:.2f} of {t2:.2f} ms -- {verdict}.")
+costlib.write_lines(a.out, header, lines)

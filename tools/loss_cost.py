@@ -7,10 +7,10 @@ like tools/backward_cost.py, profiles/backward_cost.txt) as the yardstick of a t
 child run under `rocprofv3 --kernel-trace --stats`, and the accuracy figures of tests/test_loss_gpu.py: the kernels' and
 float32 torch's worst error against the float64 reference over the test's shapes, kinds, lambdas and backgrounds.
 
-    python tools/loss_cost.py [--iters 20] [--reps 50] [--out profiles/loss_cost.txt] [--no-backward]"""
-import argparse, csv, glob, json, os, re, shutil, subprocess, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+    python tools/loss_cost.py [--iters 20] [--reps 50] [--out profiles/loss_cost.txt] [--no-backward] [--cache DIR]"""
+import argparse, json, os, shutil, sys
+import costlib
+from costlib import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 ap = argparse.ArgumentParser()
@@ -19,13 +19,13 @@ ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_cost.txt"))
 ap.add_argument("--no-backward", action="store_true", help="skip the config C backward (40 s of cloud generation)")
 ap.add_argument("--child", nargs=2, type=int, metavar=("W", "H"), help="run the loss at W x H only (under rocprofv3)")
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
 
+gs, _ = costlib.use_root()
 import numpy as np
 import torch
 import torch.nn.functional as F
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import synth
 
 SIZES = ((1920, 1080), (3840, 2160))
 LAM, BG = 0.2, (0.2, 0.5, 0.9)
@@ -64,13 +64,7 @@ def torch_loss_and_grad(rgba, target, window, bg):
 
 
 def block_ms(stream, reps, call):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(reps):
-        call()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1) / reps
+    return costlib.event_ms(stream, [lambda: [call() for _ in range(reps)]])[0] / reps
 
 
 def measure(w, h, iters, reps):
@@ -117,48 +111,28 @@ def measure(w, h, iters, reps):
 
 
 def backward_config_c(iters):
-    aos, cfg = synth.generate_config("C")
-    w, h = cfg["width"], cfg["height"]
-    rm = gs.ResourceManager(); rm.setGaussians(aos)
-    sc = gs.Scene(rm, aspect_ratio=w / h)
-    cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
-    r = gs.Renderer(w, h, record_timings=1, warmup_frames=0)
-    r.init(rm); r.initForScene(sc)
-    rng = np.random.default_rng(0)
-    gr = torch.tensor(rng.standard_normal((h, w, 4)).astype(np.float32), device="cuda")
-    out = torch.empty(len(aos), 84, device="cuda")
+    aos, n, w, h, rm, sc, r = costlib.config_scene("C", record_timings=1, cache=a.cache)
+    gr = costlib.image_grads(h, w)
+    out = torch.empty(n, 84, device="cuda")
     torch.cuda.synchronize()
     fwd, bwd = [], []
     for k in range(3 + iters):
         r.drawDevice(sc, None, sync=True)
-        t0 = time.perf_counter()
-        r.backwardDevice(gr.data_ptr(), None, out.data_ptr())
-        r.synchronize()
+        ms = costlib.host_ms(r, lambda: r.backwardDevice(gr.data_ptr(), None, out.data_ptr()))
         if k >= 3:
             fwd.append(r.timings().total_ms)
-            bwd.append((time.perf_counter() - t0) * 1e3)
+            bwd.append(ms)
     r.cleanup()
-    return {"config": "C", "width": w, "height": h, "iters": iters, "forward_total_ms_median": round(float(np.median(fwd)), 4),
-            "backward_ms_median": round(float(np.median(bwd)), 4)}
+    return {"config": "C", "width": w, "height": h, "iters": iters, "forward_total_ms_median": costlib.median(fwd),
+            "backward_ms_median": costlib.median(bwd)}
 
 
 def kernel_split(w, h, iters):
     if not shutil.which("rocprofv3"):
         return {}
-    d = tempfile.mkdtemp(prefix="loss_cost_")
-    rc = subprocess.run(["timeout", "-k", "10", "300", "rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv",
-                         "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__), "--child", str(w), str(h), "--iters", str(iters)],
-                        capture_output=True, text=True).returncode
-    files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-    split = {}
-    if rc == 0 and files:
-        for row in csv.DictReader(open(files[0])):
-            name = re.sub(r"^(void )?(gs::)?", "", row["Name"]).split("(")[0]
-            if name.startswith("k_loss_"):
-                split[name] = {"calls": int(row["Calls"]), "average_us": round(float(row["AverageNs"]) / 1e3, 2),
-                               "min_us": round(float(row["MinNs"]) / 1e3, 2), "max_us": round(float(row["MaxNs"]) / 1e3, 2)}
-    shutil.rmtree(d, ignore_errors=True)
-    return split
+    stats = costlib.traced_child([os.path.abspath(__file__), "--child", str(w), str(h), "--iters", str(iters)], 300, "loss_cost")
+    return {name: {"calls": k.calls, "average_us": round(k.average_us, 2), "min_us": round(k.min_us, 2), "max_us": round(k.max_us, 2)}
+            for name, k in stats.items() if name.startswith("k_loss_")}
 
 
 def accuracy():
@@ -219,11 +193,8 @@ if not a.no_backward:
 for row in accuracy():
     lines.append({"accuracy": row})
     print(json.dumps(lines[-1]), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("# tools/loss_cost.py on one MI355X: gs_photometric_loss_device (loss + gradient; loss only) and the same loss by torch conv2d + autograd,\n"
+costlib.write_lines(
+    a.out, ("# tools/loss_cost.py on one MI355X: gs_photometric_loss_device (loss + gradient; loss only) and the same loss by torch conv2d + autograd,\n"
             "# HIP events around blocks of `reps` calls on one stream, alternating, medians of `iters` blocks after 3 warm-up blocks; the kernels' own\n"
             "# times from a rocprofv3 --kernel-trace --stats child per size; the dense backward of config C (host-timed, as\n"
-            "# profiles/backward_cost.txt); the accuracy figures of tests/test_loss_gpu.py against the float64 reference.\n")
-    for row in lines:
-        f.write(json.dumps(row) + "\n")
+            "# profiles/backward_cost.txt); the accuracy figures of tests/test_loss_gpu.py against the float64 reference.\n"), lines)

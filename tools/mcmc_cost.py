@@ -6,25 +6,25 @@ and no resolution.  Relocation runs in place, so every repetition starts from a 
 the events).  Everything runs on one torch stream handed to gs_set_stream; every repetition is bracketed by HIP events, and
 the means are over --iters repetitions after --warmup.
 
-    python tools/mcmc_cost.py [--config C] [--iters 10] [--warmup 2] [--out profiles/mcmc_cost.txt]"""
-import argparse, ctypes as C, json, os, sys
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+    python tools/mcmc_cost.py [--config C] [--iters 10] [--warmup 2] [--out profiles/mcmc_cost.txt] [--cache DIR]"""
+import argparse, ctypes as C, json, os
+import costlib
+from costlib import ROOT
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", default="C")
 ap.add_argument("--iters", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mcmc_cost.txt"))
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
 
+gs, _ = costlib.use_root()
 import numpy as np
 import torch
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import _lib, synth
+from vk3dgaussiansplatting_amd import _lib
 
-aos, cfg = synth.generate_config(a.config)
-aos = np.ascontiguousarray(aos, dtype=np.float32)
+aos, _ = costlib.cloud(a.config, a.cache)
 n = len(aos)
 r = gs.Renderer(64, 64, record_timings=False, warmup_frames=0)
 r.init(gs.ResourceManager())
@@ -48,18 +48,8 @@ r.setStream(stream.cuda_stream)
 
 
 def timed(call, before=None):
-    ms = []
-    for k in range(a.warmup + a.iters):
-        if before is not None:
-            before()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        call()
-        e1.record(stream)
-        e1.synchronize()
-        if k >= a.warmup:
-            ms.append(e0.elapsed_time(e1))
-    return {"ms_mean": round(float(np.mean(ms)), 4), "ms_min_max": [round(float(np.min(ms)), 4), round(float(np.max(ms)), 4)]}
+    mean, _, spread = costlib.summary([costlib.event_ms(stream, [call], before)[0] for _ in range(a.warmup + a.iters)][a.warmup:])
+    return {"ms_mean": mean, "ms_min_max": spread}
 
 
 line = {"config": a.config, "gaussians": n, "alive_in_the_config": alive0, "iters": a.iters, "warmup": a.warmup, "relocate": []}
@@ -130,11 +120,9 @@ line["membench_copy_tbytes_per_s"] = copy
 r.cleanup()
 
 print(json.dumps(line), flush=True)
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    f.write("# tools/mcmc_cost.py on one MI355X: gs_relocate_device (raw space, with moments, ids listed) with 1 %, 10 % and 50 % of\n"
+costlib.write_lines(
+    a.out, ("# tools/mcmc_cost.py on one MI355X: gs_relocate_device (raw space, with moments, ids listed) with 1 %, 10 % and 50 % of\n"
             "# config C's splats dead, gs_grow_device by 5 % (records, raw, m, v), gs_position_noise_device on every row,\n"
             "# gs_densify_device on the same cloud with every row kept (records, m, v) and gs_membench's copy rate, in one run; HIP events\n"
             "# around every call on one stream, means (and min, max) over `iters` repetitions after `warmup`.  bytes: the rows read and\n"
-            "# written as the tool's text counts them.  Recorded numbers, not a bound.\n")
-    f.write(json.dumps(line) + "\n")
+            "# written as the tool's text counts them.  Recorded numbers, not a bound.\n"), [line])

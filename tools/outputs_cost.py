@@ -3,27 +3,23 @@ record_timings = 1) and the InitSortList bucket (k_project stores the view depth
 / 3, median of --frames synchronous frames after 5 warm-up frames, the masks taken in turn over --rounds rounds (so that
 clock drift spreads over all of them).  One JSON line per (config, mask).
 
-    python tools/outputs_cost.py [C Chard ...] [--frames 25] [--rounds 3]"""
-import argparse, json, os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import numpy as np
-import vk3dgaussiansplatting_amd as gs
-from vk3dgaussiansplatting_amd import synth
+    python tools/outputs_cost.py [C Chard ...] [--frames 25] [--rounds 3] [--cache DIR]"""
+import argparse, json
+import costlib
 
 ap = argparse.ArgumentParser()
 ap.add_argument("configs", nargs="*", default=["C", "Chard"])
 ap.add_argument("--frames", type=int, default=25)
 ap.add_argument("--rounds", type=int, default=3)
+costlib.add_cache_argument(ap)
 a = ap.parse_args()
+
+gs, _ = costlib.use_root(torch=False)
+import numpy as np
+
 MASKS = (0, gs.GS_OUTPUT_RGBA32F, gs.GS_OUTPUT_DEPTH, gs.GS_OUTPUT_RGBA32F | gs.GS_OUTPUT_DEPTH)
 for name in a.configs:
-    aos, cfg = synth.generate_config(name)
-    w, h = cfg["width"], cfg["height"]
-    rm = gs.ResourceManager(); rm.setGaussians(aos)
-    sc = gs.Scene(rm, aspect_ratio=w / h)
-    cam = sc.getCamera(); cam.setPosition((0, 0, 0)); cam.setRotation(0.0, 0.0); cam.recalculate()
-    r = gs.Renderer(w, h, record_timings=1, warmup_frames=0)
-    r.init(rm); r.initForScene(sc)
+    aos, n, w, h, rm, sc, r = costlib.config_scene(name, record_timings=1, cache=a.cache)
     render = {m: [] for m in MASKS}
     init = {m: [] for m in MASKS}
     frame = None
@@ -44,6 +40,6 @@ for name in a.configs:
     for m in MASKS:
         med = float(np.median(render[m]))
         print(json.dumps({"config": name, "width": w, "height": h, "mask": m, "frames": len(render[m]),
-                          "render_ms_median": round(med, 4), "render_vs_mask0": round(med / base - 1.0, 4),
-                          "init_sort_list_ms_median": round(float(np.median(init[m])), 4)}), flush=True)
+                          "render_ms_median": costlib.median(render[m]), "render_vs_mask0": round(med / base - 1.0, 4),
+                          "init_sort_list_ms_median": costlib.median(init[m])}), flush=True)
     r.cleanup()
