@@ -211,6 +211,12 @@ typedef struct gs_scene_info {
                                                              list first by bit length of (end - start), any order among equal bit
                                                              lengths; GS_TILE_ORDER_RASTER: the owned tiles ascending.  Valid after
                                                              a frame only */
+#define GS_BUF_PASS0_OFFSETS 15 /* uint32[blocks + 1][16]    pass 0 of the depth sort as InitSortList ran it (blocks of 256 splats):
+                                                             row b, word d = the elements with depth_key & 15 == d that the splats
+                                                             before block b emit; the last row = the sixteen digit bases (elements
+                                                             of smaller digits).  GS_ERR_INVALID unless the last frame took that
+                                                             path: GS_SORT_RADIX4 with a Count launch per pass, record_timings < 2,
+                                                             every tile row, no overflow */
 
 /* GS_API_VERSION of the library that is actually loaded: compare with the header's before anything else
  * (gsplat.hpp and the Python binding do). */

@@ -39,6 +39,7 @@ GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read
  BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE) = range(11)
 BUF_RASTER_OPACITY = 11
 BUF_WAVE_WROTE, BUF_BAND_BLOCKS, BUF_TILE_ORDER = 12, 13, 14   # the work the last frame skipped (include/gsplat.h)
+BUF_PASS0_OFFSETS = 15      # the scanned digit rows of a frame whose k_emit did pass 0 of the depth sort
 
 RECORD_BYTES = 336
 

@@ -88,8 +88,8 @@ int alloc_sort(gs_ctx* ctx, DeviceOwner& mem, SortBuffers& s, uint32_t capacity)
         s.fed[1] = s.fed[0] + set_words;
         s.fed[2] = s.fed[1] + set_words;
     }
-    HIP_TRY(ctx, mem.alloc(s.params, sizeof(SortParams)));
-    HIP_TRY(ctx, hipMemset(s.params, 0, sizeof(SortParams)));
+    HIP_TRY(ctx, mem.alloc(s.params, 2 * sizeof(SortParams)));
+    HIP_TRY(ctx, hipMemset(s.params, 0, 2 * sizeof(SortParams)));
     HIP_TRY(ctx, mem.alloc(s.coarse, (size_t)kMaxSortPasses * kBins * kCoarse * sizeof(uint32_t)));
     return GS_OK;
 }
@@ -188,7 +188,7 @@ int launch_stage(Frame& f, const Stage& s, bool graphs) {
             launch_gather_sorted(f.fixed, c->scratch, c->sort, f.sorted, st);
             launch_emit_sorted(f.fixed, c->scratch, c->sort, f.sorted, st);
             break;
-        case kStageEmit: launch_emit(f.fp, c->scratch, c->sort, st); break;
+        case kStageEmit: launch_emit(f.fp, c->scratch, c->sort, !sorts_splat_first(c->cfg.sort_algorithm) && c->sort_pass0, st); break;
         case kStagePasses: {
             auto passes = [&] { return launch_radix_sort(c->sort, c->runs[s.run], st); };
             f.sorted = graphs ? capture_or_replay(f, c->run_graph[s.run], passes) : passes();
@@ -282,15 +282,24 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
         // the packed payload of the depth passes (gs_sort_words.h): the contractual sorter over 16-bit tile ids and 24-bit
         // splat indices; sort_pass() checks what the run itself must offer.  Like the fed counts it is part of the capture.
         const bool packed = c->cfg.sort_algorithm == GS_SORT_RADIX4 && frame_packs_payload(c->hi16, c->n, c->cfg.record_timings);
-        if (fed != c->sort_fed || packed != c->sort_packed) {
+        // pass 0 inside InitSortList (k_emit<false, true>): the contractual sorter with a Count launch per pass, over every
+        // tile row, without per-pass timers -- a frame with them is what the per-pass profiles and tests/test_parity_gpu.py
+        // are stated in (eight depth launches).  Part of the capture as well.
+        const bool pass0 = GS_EMIT_PASS0 != 0 && c->cfg.sort_algorithm == GS_SORT_RADIX4 && !fed && c->cfg.record_timings < 2u &&
+                           c->row_begin == 0u && c->row_end == c->grid_h && c->row_stride == 1u;
+        if (fed != c->sort_fed || packed != c->sort_packed || pass0 != c->sort_pass0) {
             if (c->run_graph[0].exec || c->chain_graph.exec) HIP_TRY(c, hipStreamSynchronize(st));   // the graph may still be executing (rare: the mode flips)
             drop_sort_graph(c);
             c->sort_fed = fed;
             c->sort_packed = packed;
+            c->sort_pass0 = pass0;
         }
         fp.packed = packed ? 1u : 0u;
         // the bucket sorter runs the tile-word passes alone and carries the depth words through them
+        // (pass0: the list arrives in half 1, in pass 0's order; that pass's launches stay in the chain for a frame that
+        // overflows, over the record k_scan_blocks leaves in sort.params[1])
         c->runs[0] = {.capacity = c->capacity, .first_bit = bucket ? 32u : 0u, .num_sort_bits = c->band_sort_bits,
+                      .start = pass0 ? 1 : 0, .passes_done = pass0 ? 1u : 0u, .done_params = pass0 ? c->sort.params + 1 : nullptr,
                       .drop_depth_payload = !bucket, .hi16 = c->hi16, .packed = packed, .share = tile_share, .fed = fed,
                       .scatter_events = pass_events};
         c->num_runs = 1;
@@ -320,6 +329,7 @@ int enqueue_frame(gs_ctx* c, const float* view, const float* proj, const float* 
     if (int r = check_launch(c, "RenderGaussians")) return r;
     if (tm) if (int r = mark(c, kBucketRender)) return r;
     frame_enqueued(c, listed, f.sorted);
+    c->last_pass0 = !splat_first && c->sort_pass0;
     return GS_OK;
 }
 
@@ -583,12 +593,19 @@ static int alloc_scratch(gs_ctx* c, uint32_t n) {
     HIP_TRY(c, mem.alloc(sc.extents, N * sizeof(uint2)));
     c->num_blocks = (n + kProjThreads - 1) / kProjThreads;
     // k_scan_blocks reads/writes whole 16-byte groups up to 1024 * per entries: zero-padded
-    const size_t padded = (size_t)c->num_blocks + 8192;
-    HIP_TRY(c, mem.alloc_zeroed(sc.block_sums, padded * sizeof(uint32_t), st));
+    const size_t padded = (size_t)c->num_blocks + kBlockSumsPad;
+    // behind block_sums: pass 0 inside InitSortList -- the rows of the blocks (whole chunks) and the two halves of the chunk
+    // sums, which start from zero
+    const size_t chunks = pass0_chunks(c->num_blocks);
+    HIP_TRY(c, mem.alloc_zeroed(sc.block_sums, (padded + 4 + (chunks * kPass0Chunk + 2 * chunks) * kBins) * sizeof(uint32_t), st));
+    sc.pass0_hist = pass0_hist_of(sc.block_sums, c->num_blocks);
+    sc.pass0_chunk = pass0_chunk_of(sc.block_sums, c->num_blocks);
     HIP_TRY(c, mem.alloc_zeroed(sc.block_offsets, padded * sizeof(uint32_t), st));
     HIP_TRY(c, mem.alloc_zeroed(sc.wave_wrote, (size_t)c->num_blocks * 4, st));
     HIP_TRY(c, mem.alloc_zeroed(sc.help_list, (size_t)kEmitHelpCap * sizeof(uint2), st));
     HIP_TRY(c, mem.alloc_zeroed(sc.help_count, 4 * sizeof(uint32_t), st));
+    // the scanned rows of pass 0 (whole chunks: the totals row lies behind the last block)
+    HIP_TRY(c, mem.alloc_zeroed(sc.pass0_offs, chunks * kPass0Chunk * kBins * sizeof(uint32_t), st));
     sc.elems_note = nullptr;
     if (c->elems_note) {
         void* dev = nullptr;

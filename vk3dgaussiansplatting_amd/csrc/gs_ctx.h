@@ -174,6 +174,8 @@ struct gs_ctx {
                                       // since the rows were set) -- what GS_COUNT_AUTO goes by
     bool sort_fed = false;        // the captured radix passes are the fed kind (k_scatter<.., FED>)
     bool sort_packed = false;     // ... and carry the packed payload through the depth passes (SortRun::packed)
+    bool sort_pass0 = false;      // ... and start behind pass 0, which k_emit does (SortRun::passes_done; GS_EMIT_PASS0)
+    bool last_pass0 = false;      // the last frame was enqueued that way: gs_debug_read(GS_BUF_PASS0_OFFSETS) has its table
 
     gs_timings timings{};
     gs_host_timings host{};           // RECORD_CPU_TIMES (Renderer.cpp:299-456)

@@ -19,7 +19,7 @@ int gs_debug_init_sort_list(gs_ctx* c, const float view[16], const float proj[16
     fp.parity = (c->emit_parity ^= 1u);
     launch_project(fp, c->scene, c->scratch, c->stream);
     launch_scan_blocks(fp, c->scratch, c->sort.params, c->ranges, c->sort.coarse, c->stream);
-    launch_emit(fp, c->scratch, c->sort, c->stream);
+    launch_emit(fp, c->scratch, c->sort, false, c->stream);      // the canonical unsorted list, whatever frames do
     if (int r = check_launch(c, "InitSortList")) return r;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     unsorted_list_ready(c, fp, outputs_valid);
@@ -214,6 +214,20 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
                 const uint32_t k = out[i] / fp.grid_w, x = out[i] - k * fp.grid_w;
                 out[i] = (fp.first_row + k * fp.row_stride) * fp.grid_w + x;
             }
+            return GS_OK;
+        }
+        case GS_BUF_PASS0_OFFSETS: {
+            // the scanned rows k_emit went by, then the sixteen digit bases, from the totals row behind them; only a frame
+            // that took the path has them (a frame that overflowed wrote the plain list: its pass 0 ran as launches)
+            if (c->last.kind != LastFrame::kFrame || !c->last_pass0 || sp.overflow)
+                return fail(c, GS_ERR_INVALID, "gs_debug_read: the last frame did not run pass 0 inside InitSortList");
+            std::vector<uint32_t> rows(((size_t)c->num_blocks + 1u) * kBins);
+            if (bytes > rows.size() * sizeof(uint32_t)) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
+            HIP_TRY(c, hipMemcpy(rows.data(), c->scratch.pass0_offs, rows.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            uint32_t* totals = rows.data() + (size_t)c->num_blocks * kBins;
+            uint32_t smaller = 0u;
+            for (int d = 0; d < kBins; ++d) { const uint32_t t = totals[d]; totals[d] = smaller; smaller += t; }
+            std::memcpy(dst, rows.data(), bytes);
             return GS_OK;
         }
         default: return fail(c, GS_ERR_INVALID, "gs_debug_read: unknown buffer id");

@@ -46,6 +46,15 @@ __device__ __forceinline__ uint32_t wave_inclusive_max(uint32_t v) {
     return v;
 }
 
+// inclusive prefix sum inside each row of 16 lanes (DPP row_shr 1/2/4/8; lanes shifted in from outside the row add 0)
+__device__ __forceinline__ uint32_t row16_inclusive_scan(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xe, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xc, false);   // row_shr:8
+    return v;
+}
+
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {   // all 64 lanes active
     return wave_sum_to_lane63(v);
 }

@@ -47,6 +47,24 @@ static_assert(kBins8 <= kBins * kCoarse, "a pass's 256 digit totals live in its 
 
 // ---- InitSortList tiling -----------------------------------------------------------------
 constexpr int kProjThreads = 256;      // splats per workgroup in project + emit
+// Pass 0 of the frame's depth sort inside InitSortList (k_emit<false, true>, gs_project.hip): k_project leaves the digit
+// counts of its 256 splats (depth_key & 15, weighted by the tile count) as a row of sixteen, k_scan_blocks scans the sixteen
+// columns over the blocks, and k_emit stores every element where the stable counting sort on that digit would put it.
+#ifndef GS_EMIT_PASS0
+#define GS_EMIT_PASS0 1             /* tuning: 0 = k_emit always writes the plain list and the sort runs its pass 0 */
+#endif
+constexpr uint32_t kPass0Chunk = 64;   // project blocks per chunk of the column scan: one workgroup of k_scan_blocks each
+// chunks that cover the rows 0 .. blocks of SplatScratch::pass0_offs (row `blocks` holds the column totals)
+__host__ __device__ inline uint32_t pass0_chunks(uint32_t blocks) { return blocks / kPass0Chunk + 1u; }
+// SplatScratch::block_sums is zero-padded by this many words (k_scan_blocks reads whole 16-byte groups per thread); behind
+// the padding, in the same allocation, lie pass0_hist (whole chunks of rows) and the two halves of pass0_chunk
+constexpr uint32_t kBlockSumsPad = 8192;
+__host__ __device__ inline uint32_t* pass0_hist_of(uint32_t* block_sums, uint32_t blocks) {
+    return block_sums + ((blocks + kBlockSumsPad + 3u) & ~3u);      // rows are stored and cleared as 16-byte groups
+}
+__host__ __device__ inline uint32_t* pass0_chunk_of(uint32_t* block_sums, uint32_t blocks) {
+    return pass0_hist_of(block_sums, blocks) + (size_t)pass0_chunks(blocks) * kPass0Chunk * kBins;
+}
 
 // Per-frame constants: CamUBO (ShaderStructs.h:37-41) + InitSortListPCD (7-12) + the shader
 // #defines of Common.glsl:2-15.  Passed by value as a kernel argument.
@@ -154,6 +172,12 @@ struct SplatScratch {
     SortParams* aux_params;  // [2]: the splat list's dispatch record; scratch for the second scan
     uint32_t* elems_note;    // device alias of a pinned host word (or null): k_scan_blocks leaves the frame's element count + 1
                              // there, so that the host knows the length of recent lists without waiting for a frame
+    // Pass 0 of the depth sort inside InitSortList (GS_EMIT_PASS0).  Rows of sixteen words, one per value of depth_key & 15:
+    // (pass0_hist and pass0_chunk live behind block_sums: pass0_hist_of / pass0_chunk_of, which k_project reaches them by)
+    uint32_t* pass0_hist;    // [blocks][16]      elements of each digit the block's splats emit (k_project; zero row: k_band_cull)
+    uint32_t* pass0_offs;    // [blocks + 1][16]  column d summed over the blocks before (k_scan_blocks); row `blocks` = the totals
+    uint32_t* pass0_chunk;   // [2][chunks][16]   the rows summed per kPass0Chunk blocks, added by the k_project launch of
+                             //       parity p into half p; k_scan_blocks clears the half of the next launch
     float* view_z;           // [N] while GS_OUTPUT_DEPTH is on (null otherwise): -viewSpacePos.z of the emitting splats, the
                              //       value getDepthKey quantises (InitSortList.comp:70-80); what the depth output blends
 };
@@ -179,7 +203,8 @@ struct SortBuffers {
                                      // (8-bit digits: the first 256 words of a pass's slab = its digit totals)
     uint32_t* fed[3];                // 4-bit digits: [G_max][16] digit counts per group, three rotating sets of the fed
                                      // sort (k_scatter<.., FED>); null for 8-bit digits
-    SortParams* params;
+    SortParams* params;              // [2]: the list's dispatch record; the same for the launches of a pass k_emit has done
+                                     // already (SortRun::done_params): no elements unless the frame overflows
     uint32_t digit_bits;             // what alloc_sort sized table / seg_sum for (4 or 8): the digit width of every run over these buffers
 };
 
@@ -193,6 +218,12 @@ struct SortRun {
     int start = 0;
     uint32_t coarse_pass = 0;          // first slab of SortBuffers::coarse (one per pass; two runs of a frame must not share slabs)
     const SortParams* params = nullptr;   // dispatch record of this list (null: SortBuffers::params)
+    uint32_t passes_done = 0;          // the list in half `start` is already in the order of this many leading passes (k_emit
+                                       // stores a frame's list where pass 0 would: 1); the run goes on with pass passes_done,
+                                       // whose word layout, coarse slab and key bit are those of that pass of the whole run
+    const SortParams* done_params = nullptr;   // with passes_done: the leading passes are launched all the same, over this
+                                       // dispatch record, from the half they would have started in.  It holds no elements
+                                       // (the launches return at once) unless the producer had to leave the plain list there
     bool drop_depth_payload = false;   // frame path: a pass carries only the depth bytes that later passes still read
     bool hi16 = false;                 // frame path: the hi arrays hold 16-bit tile ids (at most 65535 owned tiles)
     bool packed = false;               // frame path, 4-bit digits, hi16, first_bit == 0, at least 32 sort bits, at most 2^24
@@ -288,7 +319,9 @@ void launch_debug_records(const FrameParams& fp, const SceneBuffers& scene, cons
 void launch_debug_colour(const FrameParams& fp, const SceneBuffers& scene, const float* records, float* out_rgba, hipStream_t stream);
 void launch_scan_blocks(const FrameParams& fp, const SplatScratch& sc, SortParams* params,
                         uint32_t* ranges, uint32_t* coarse, hipStream_t stream);
-void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb,
+// pass0: the list goes to half 1, in the order pass 0 of the depth sort would leave it (GS_EMIT_PASS0; an overflowing
+// frame writes the plain list into half 0 all the same, and sb.params[1] says so to the sort)
+void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, bool pass0,
                  hipStream_t stream);
 // GS_SORT_RADIX4_SPLAT_FIRST (gs_project.hip): the (depth word | tile count | splat) list of the emitting splats into
 // sort buffers [1] (lo, hi, id), with its dispatch record in sc.aux_params[0]; then, once that list is sorted by depth

@@ -12,6 +12,7 @@
 // against oracle/gs_oracle.c.  Paths are relative to /root/reference/vkGaussianSplatting/Resources/Shaders/.
 #include <cstdlib>
 #include "gs_splat_math.h"
+#include "gs_sort_words.h"
 
 namespace gs {
 
@@ -263,6 +264,11 @@ __global__ __launch_bounds__(kCullThreads) void k_band_cull(const FrameParams fp
         sc.block_sums[b] = 0u;
         if (fp.splat_first) sc.block_flags[b] = 0u;
         reinterpret_cast<uint32_t*>(sc.wave_wrote)[b] = 0u;           // none of its four waves writes records this frame
+#if GS_EMIT_PASS0
+        uint4* row = reinterpret_cast<uint4*>(sc.pass0_hist + (size_t)b * kBins);   // ... and it emits no digit
+#pragma unroll
+        for (int q = 0; q < 4; ++q) row[q] = make_uint4(0u, 0u, 0u, 0u);
+#endif
     }
     // one returning atomic per workgroup (on one address they complete at about 90 per microsecond)
     const uint64_t vote = __ballot(survives);
@@ -467,22 +473,42 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
                         }
                         rec0.z = inv_x; rec0.w = inv_y;
                         rec2.x = opacity;
+                        // (a frame with the depth output stores its per-splat words before the 48 SH loads, the others behind
+                        // them, as ever: with the digit histogram below, <*, true, 0, *> needed 72 VGPRs and 8 to 12 bytes of scratch)
+                        if constexpr (VIEW_Z) {
+                            sc.view_z[g] = -vp[2];     // GS_OUTPUT_DEPTH: the z getDepthKey used
+                            sc.depth_key[g] = depth_key;
+                            sc.extents[g] = make_uint2((uint32_t)min_x | ((uint32_t)k0 << 16), (uint32_t)max_x | ((uint32_t)k1 << 16));
+                        }
                         float res[3];
                         splat_colour<NT_SH, SH_K>(fp, scene.sh + g, n, px, py, pz, res);
                         rec1 = make_float4(inv_z, res[0], res[1], res[2]);
-                        sc.depth_key[g] = depth_key;
-                        if constexpr (VIEW_Z) sc.view_z[g] = -vp[2];     // GS_OUTPUT_DEPTH: the z getDepthKey used
-                        sc.extents[g] = make_uint2((uint32_t)min_x | ((uint32_t)k0 << 16),
-                                                   (uint32_t)max_x | ((uint32_t)k1 << 16));
+                        if constexpr (!VIEW_Z) sc.depth_key[g] = depth_key;
+#if GS_EMIT_PASS0
+                        // the lowest depth digit rides in the top four bits of the count to the histogram below (a count is at
+                        // most the frame's tiles, far below 2^28): as a value of its own it stayed live across the 48 SH loads
+                        // and every instantiation spilled eight VGPRs (36 bytes of scratch)
+                        count |= (depth_key & (uint32_t)(kBins - 1)) << 28;
+#endif
+                        if constexpr (!VIEW_Z) sc.extents[g] = make_uint2((uint32_t)min_x | ((uint32_t)k0 << 16),
+                                                                          (uint32_t)max_x | ((uint32_t)k1 << 16));
                     }
                 }   // !band_skip
             }
         }
+#if GS_EMIT_PASS0
+        sc.tiles_touched[g] = count & 0x0FFFFFFFu;
+#else
         sc.tiles_touched[g] = count;
+#endif
     } else if (g < n) {
         sc.tiles_touched[g] = 0u;     // skipped wave: k_emit reads the counts of every splat of a workgroup that emits
     }
 
+#if GS_EMIT_PASS0
+    const uint32_t digit = count >> 28;                     // depth_key & 15 of a splat that emits
+    count &= 0x0FFFFFFFu;
+#endif
     s_raster[threadIdx.x * 3 + 0] = rec0;
     s_raster[threadIdx.x * 3 + 1] = rec1;
     s_raster[threadIdx.x * 3 + 2] = rec2;
@@ -491,6 +517,22 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
     const uint64_t emits = __ballot(count != 0u);
     const uint32_t wflags = (uint32_t)__popcll(emits);                   // emitting splats (GS_SORT_RADIX4_SPLAT_FIRST)
     const bool wave_kept = __ballot(kept) != 0ull;
+#if GS_EMIT_PASS0
+    // The block's row of pass0_hist: elements per value of the lowest depth digit.  Most splats of a wave share a digit (the
+    // low bits of uint(nd * 2^32) are zero unless nd is small), so the wave sums one value at a time, those present only, and
+    // lane 63 leaves each sum in the wave's own LDS row: no LDS atomics, and 64 lanes never add into one word.  (One wave
+    // writes and reads its row before the barrier, DS operations of a wave execute in order.)
+    __shared__ uint32_t s_hist[kProjThreads / 64][kBins];
+    if (lane_id() < kBins) s_hist[wave_id()][lane_id()] = 0u;
+    __builtin_amdgcn_wave_barrier();
+    for (uint64_t todo = emits; todo != 0ull;) {
+        const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)digit, (int)__builtin_ctzll(todo));
+        const bool mine = count != 0u && digit == d;
+        const uint32_t dsum = wave_sum_to_lane63(mine ? count : 0u);
+        if (lane_id() == 63) s_hist[wave_id()][d] = dsum;
+        todo &= ~__ballot(mine);
+    }
+#endif
     if (lane_id() == 63) {
         s_wave_sum[wave_id()] = wsum;
         s_wave_flags[wave_id()] = wflags;
@@ -541,6 +583,23 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
         sc.block_sums[blk] = t;
         if (fp.splat_first) sc.block_flags[blk] = s_wave_flags[0] + s_wave_flags[1] + s_wave_flags[2] + s_wave_flags[3];
     }
+#if GS_EMIT_PASS0
+    if (threadIdx.x < kBins) {
+        // one 64-byte row; and the same sixteen sums into the row of the block's chunk, the first level of k_scan_blocks'
+        // column scan (agent-scope adds nobody waits for; most are zero and are not sent).  Both arrays are reached from
+        // block_sums, n and the parity, which the lines around use anyway (pass0_hist_of): as sc.pass0_hist, sc.pass0_chunk
+        // and num_blocks -- five more scalars held from the kernel's entry, at its SGPR limit -- 24 of the 24 instantiations
+        // spilled 9 to 11 VGPRs to scratch (profiles/emit_pass0_cost.txt)
+        const uint32_t v = (s_hist[0][threadIdx.x] + s_hist[1][threadIdx.x]) + (s_hist[2][threadIdx.x] + s_hist[3][threadIdx.x]);
+        const uint32_t nb = (n + (uint32_t)kProjThreads - 1u) / (uint32_t)kProjThreads;
+        uint32_t* hist = pass0_hist_of(sc.block_sums, nb);
+        uint32_t* chunk = pass0_chunk_of(sc.block_sums, nb);
+        hist[(size_t)blk * kBins + threadIdx.x] = v;
+        if (v != 0u)
+            (void)__hip_atomic_fetch_add(&chunk[((size_t)fp.parity * pass0_chunks(nb) + blk / kPass0Chunk) * kBins + threadIdx.x],
+                                         v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#endif
     // k_emit walks a workgroup's output range kEmitSlice elements per workgroup: a block that emits more (a few
     // hundred near splats hold half of a tile-row band's elements) registers the slices after the first as helper
     // records.  The order of the records depends on atomic arrival; what each one writes does not.  (With
@@ -555,17 +614,55 @@ __global__ __launch_bounds__(kProjThreads, GS_PROJECT_MINBLOCKS) void k_project(
 // It also does the frame's clears (computeInitSortList's fills, Subrenderer.cpp:42-60): the tile ranges and the
 // per-pass coarse digit totals of the sort -- two fill launches less per frame.
 struct ScanJob { const uint32_t* sums; uint32_t* offsets; SortParams* params; uint32_t capacity;
-                 uint32_t* host_note; };   // host-mapped word (or null): the element count + 1, for the host to read when it likes
+                 uint32_t* host_note;      // host-mapped word (or null): the element count + 1, for the host to read when it likes
+                 SortParams* done_params; };   // (or null) SortRun::done_params: the record again if the list overflows, else an empty one
 constexpr uint32_t kScanClearWgs = 8;   // workgroups behind the scanning ones: the frame's clears, beside the scan
+// The column scan of pass 0 inside InitSortList (GS_EMIT_PASS0): offs[b][d] = hist[0 .. b)[d] for the rows b <= num_blocks,
+// `chunks` workgroups behind the clearing ones, one per kPass0Chunk rows.  chunk_in: the rows summed per chunk, which this
+// launch's k_project left; chunk_zero: those the next launch's k_project adds to, cleared here.  chunks == 0: none of it.
+struct Pass0Scan { const uint32_t* hist; uint32_t* offs; const uint32_t* chunk_in; uint4* chunk_zero; uint32_t chunks; };
+
+// Workgroup c of the column scan: 64 rows x 16 digits, one word per thread, nothing from any other workgroup of the launch.
+// The rows of the chunks before come from chunk_in, 64 chunks at a stride per thread, so that every global load of the
+// workgroup is issued before its one barrier.
+__device__ __forceinline__ void scan_pass0_chunk(const Pass0Scan& p0, uint32_t c, uint32_t num_blocks) {
+    __shared__ uint32_t s_part[16][kBins], s_rows[16][kBins];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, d = tid & 15u;
+    const uint32_t row = c * kPass0Chunk + (tid >> 4);
+    const uint32_t v = row < num_blocks ? p0.hist[(size_t)row * kBins + d] : 0u;
+    uint32_t before = 0u;
+    for (uint32_t k = tid >> 4; k < c; k += 64u) before += p0.chunk_in[(size_t)k * kBins + d];
+    before += (uint32_t)__shfl_xor((int)before, 16, 64);
+    before += (uint32_t)__shfl_xor((int)before, 32, 64);
+    // the four rows of a wave: inclusive over the rows, per digit
+    uint32_t inc = v;
+    uint32_t up = (uint32_t)__shfl_up((int)inc, 16, 64);
+    inc += lane >= 16u ? up : 0u;
+    up = (uint32_t)__shfl_up((int)inc, 32, 64);
+    inc += lane >= 32u ? up : 0u;
+    if (lane < (uint32_t)kBins) s_part[wave][d] = before;
+    if (lane >= 48u) s_rows[wave][d] = inc;
+    __syncthreads();
+    uint32_t base = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < 16u; ++w) base += s_part[w][d] + (w < wave ? s_rows[w][d] : 0u);
+    if (row <= num_blocks) p0.offs[(size_t)row * kBins + d] = base + inc - v;
+}
+
 __global__ __launch_bounds__(1024) void k_scan_blocks(const ScanJob job0, const ScanJob job1, uint32_t jobs, uint32_t num_blocks,
                                                        uint4* __restrict__ zero_a, uint32_t n16_a,
                                                        uint4* __restrict__ zero_b, uint32_t n16_b,
-                                                       uint32_t* __restrict__ next_help_count) {
+                                                       uint32_t* __restrict__ next_help_count, const Pass0Scan p0) {
+    if (blockIdx.x >= jobs + kScanClearWgs) {
+        scan_pass0_chunk(p0, blockIdx.x - jobs - kScanClearWgs, num_blocks);
+        return;
+    }
     if (blockIdx.x >= jobs) {
         const uint32_t k = blockIdx.x - jobs;
         if (k == 0u && threadIdx.x == 0 && next_help_count) { next_help_count[0] = 0u; next_help_count[2] = 0u; }   // what the NEXT InitSortList launch adds to
         for (uint32_t i = k * 1024u + threadIdx.x; i < n16_a; i += kScanClearWgs * 1024u) zero_a[i] = make_uint4(0u, 0u, 0u, 0u);
         for (uint32_t i = k * 1024u + threadIdx.x; i < n16_b; i += kScanClearWgs * 1024u) zero_b[i] = make_uint4(0u, 0u, 0u, 0u);
+        for (uint32_t i = k * 1024u + threadIdx.x; i < p0.chunks * 4u; i += kScanClearWgs * 1024u) p0.chunk_zero[i] = make_uint4(0u, 0u, 0u, 0u);
         return;
     }
     // workgroup 0: the list of elements; workgroup 1, when asked for: a second, independent scan
@@ -609,6 +706,16 @@ __global__ __launch_bounds__(1024) void k_scan_blocks(const ScanJob job0, const 
         params->num_groups = (e + kSortTile - 1) / kSortTile;
         params->groups_per_seg = (params->num_groups + kSegments - 1) / kSegments;
         params->overflow = counter > capacity ? 1u : 0u;
+        if (job.done_params) {
+            // the launches of the pass k_emit does itself: nothing to do, unless the list overflows and k_emit leaves the
+            // plain list in their input half (k_emit<false, true>)
+            const bool redo = counter > capacity;
+            job.done_params->counter = counter;
+            job.done_params->num_elems = redo ? e : 0u;
+            job.done_params->num_groups = redo ? params->num_groups : 0u;
+            job.done_params->groups_per_seg = redo ? params->groups_per_seg : 0u;
+            job.done_params->overflow = redo ? 1u : 0u;
+        }
         // what GS_COUNT_AUTO goes by (gs_api.cpp): a fire-and-forget store into pinned host memory, nobody waits for it
         if (job.host_note) __hip_atomic_store(job.host_note, e + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -650,14 +757,37 @@ static_assert(kEmitSlice % kEmitChunk == 0, "a slice is a whole number of rounds
 // through the depth passes as the payload, the splat index too, the extents are gathered through it -- and no depth
 // word is written: the list is already in depth order, the tile-word passes that follow are stable and nothing later
 // reads depth words.
-template <bool SORTED>
+//
+// P0 (GS_EMIT_PASS0; the contractual sorter with a Count launch per pass, over every tile row): pass 0 of the depth sort, a
+// stable counting sort on depth_key & 15, happens here.  All elements of a splat share that digit, so the place of element
+// j of splat s behind the pass is D[d] + (elements of digit d of the splats before s) + j, D[d] = the elements of smaller
+// digits: the workgroup ranks its 256 splats stably by digit (the match mask of scatter_group, once), lets everything
+// below run over that order -- the scan of the counts, the start marks, the slices and their helpers -- and stores element
+// j of the ranked order at gofs[d] + j, gofs[d] = D[d] + pass0_offs[blk][d] - (first ranked element of digit d), into the
+// ping-pong half and in the layout pass 0 would have written.  Count, Reduce and Scan of that pass are k_project's rows
+// and k_scan_blocks' column scan.  The workgroups take the blocks in launch order: in the XCD-contiguous order of Scatter
+// (xcd_group; GS_EMIT_XCD_ORDER=1), where blocks b and b + 1 meet in one L2, the launch wrote the same 118.7 MB at config C
+// (no partial lines either way) and the step was 0.7 % longer (profiles/emit_pass0_cost.txt).  A list that overflows its capacity is truncated by LIST index
+// (InitSortList.comp:143), which the rows do not know: `done` (the record k_scan_blocks leaves for the launches of pass 0)
+// says so, the plain list goes to half 0 as ever and those launches, otherwise empty, sort it.
+#ifndef GS_EMIT_XCD_ORDER
+#define GS_EMIT_XCD_ORDER 0         /* tuning: 1 = k_emit<false, true> takes the blocks in the XCD-contiguous order of Scatter */
+#endif
+template <bool SORTED, bool P0 = false>
 __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, const SplatScratch sc,
                                                         uint32_t* __restrict__ out_lo,
                                                         uint32_t* __restrict__ out_hi,
                                                         uint32_t* __restrict__ out_id, uint32_t num_blocks,
                                                         uint32_t helpers, const uint32_t* __restrict__ sorted_ids,
-                                                        const uint32_t* __restrict__ sorted_counts) {
+                                                        const uint32_t* __restrict__ sorted_counts,
+                                                        uint32_t* __restrict__ p0_lo = nullptr, uint32_t* __restrict__ p0_hi = nullptr,
+                                                        uint32_t* __restrict__ p0_id = nullptr, const SortParams* __restrict__ done = nullptr) {
+    static_assert(!(SORTED && P0), "the splat-first list is in depth order already");
     const uint32_t* __restrict__ sums = SORTED ? sc.sorted_sums : sc.block_sums;
+    __shared__ __attribute__((aligned(16))) uint32_t s_dig[P0 ? kBins : 1][kProjThreads / 64];   // splats per digit and wave
+    __shared__ uint32_t s_gofs[P0 ? kBins : 1];
+    __shared__ uint32_t s_tot[P0 ? kBins : 1];
+    __shared__ uint8_t s_idx[P0 ? kProjThreads : 1];             // splat of a ranked slot
     __shared__ uint32_t s_incl[kProjThreads];   // inclusive scan of tile counts
     __shared__ uint32_t s_wave_tot[kProjThreads / 64];
     __shared__ uint2 s_ext[kProjThreads];
@@ -681,6 +811,9 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
         if (first == kEmitNoHelp || h - first + 1u != slice) return;
         const uint32_t t = sums[blk];
         if (t <= kEmitSlice || slice > (t - 1u) / kEmitSlice) return;
+    } else if constexpr (P0 && GS_EMIT_XCD_ORDER != 0) {
+        blk = xcd_group(blk, (num_blocks + 7u) / 8u);
+        if (blk >= num_blocks) return;
     }
     const uint32_t g = blk * kProjThreads + tid;
     // every global read of the workgroup is issued up front (one memory latency instead of a chain);
@@ -705,10 +838,62 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
             my_depth = sc.depth_key[g];
         }
     }
+    bool fused = false;
+    uint32_t my_offs = 0u, dstart16 = 0u;
+    if constexpr (P0) {
+        fused = done->overflow == 0u;            // kernel-uniform
+        if (tid < kBins) {
+            my_offs = sc.pass0_offs[(size_t)blk * kBins + tid];
+            s_tot[tid] = sc.pass0_offs[(size_t)num_blocks * kBins + tid];
+        }
+    }
     if (total == 0) return;
     if (base >= fp.capacity) return;             // whole block dropped (overflow, :143)
-    s_ext[tid] = my_ext;
-    s_depth[tid] = my_depth;
+    if (P0 && fused) {
+        // stable rank of the 256 splats by digit (a splat without elements: digit 0; it owns nothing): inside the wave by the
+        // mask of the lanes with the same digit, across the waves through the counts in LDS
+        const uint32_t dg = cnt != 0u ? my_depth & (uint32_t)(kBins - 1) : 0u;
+        uint32_t m_lo = 0xFFFFFFFFu, m_hi = 0xFFFFFFFFu;
+#pragma unroll
+        for (int b = 0; b < kRadixBits; ++b) {
+            const int32_t sbit = __builtin_amdgcn_sbfe((int32_t)dg, (uint32_t)b, 1u);
+            const uint64_t bal = __ballot(sbit != 0);
+            m_lo &= ~((uint32_t)bal ^ (uint32_t)sbit);
+            m_hi &= ~((uint32_t)(bal >> 32) ^ (uint32_t)sbit);
+        }
+        const uint64_t same = ((uint64_t)m_hi << 32) | m_lo;
+        const uint32_t in_wave = mbcnt(same);
+        if (lane_id() < kBins) s_dig[lane_id()][wave_id()] = 0u;
+        __builtin_amdgcn_wave_barrier();         // one wave writes both, DS operations of a wave execute in order
+        if (in_wave == 0u) s_dig[dg][wave_id()] = (uint32_t)__popcll(same);
+        __syncthreads();
+        // lane d of every row of 16 (all four rows alike, as in scatter_group): the block's splats of digit d, the first ranked
+        // slot of the digit (threads 0..15 keep it for gofs) and this wave's base inside it
+        static_assert(kProjThreads / 64 == 4, "one 16-byte LDS read per digit");
+        const uint4 c = *reinterpret_cast<const uint4*>(&s_dig[lane_id() & 15][0]);
+        const uint32_t tot = c.x + c.y + c.z + c.w;
+        dstart16 = row16_inclusive_scan(tot) - tot;
+        const uint32_t wb = dstart16 + (wave_id() > 0 ? c.x : 0u) + (wave_id() > 1 ? c.y : 0u) + (wave_id() > 2 ? c.z : 0u);
+        const uint32_t slot = (uint32_t)__shfl((int)wb, (int)dg, 64) + in_wave;
+        if ((uint32_t)__shfl((int)tot, (int)dg, 64) == (uint32_t)kProjThreads) {
+            // every splat of the block has this digit (block-uniform; most blocks of a frame: far splats have digit 0): the
+            // ranked order is the splat order
+            s_ext[tid] = my_ext;
+            s_depth[tid] = my_depth;
+            s_idx[tid] = (uint8_t)tid;
+        } else {
+            s_incl[slot] = cnt;
+            s_ext[slot] = my_ext;
+            s_depth[slot] = my_depth;
+            s_idx[slot] = (uint8_t)tid;
+            __syncthreads();
+            cnt = s_incl[tid];                   // from here on "splat tid" is ranked slot tid
+        }
+    } else {
+        s_ext[tid] = my_ext;
+        s_depth[tid] = my_depth;
+        if constexpr (P0) s_idx[tid] = (uint8_t)tid;
+    }
     const uint32_t inc = wave_inclusive_scan(cnt);
     if (lane_id() == 63) s_wave_tot[wave_id()] = inc;
     __syncthreads();
@@ -716,6 +901,18 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
     for (int w = 0; w < wave_id(); ++w) wbase += s_wave_tot[w];
     s_incl[tid] = wbase + inc;
     __syncthreads();
+    if constexpr (P0) {
+        if (tid < kBins) {          // read in the loop below, behind its first barrier
+            uint32_t gofs = base;
+            if (fused) {
+                uint32_t smaller = 0u;                              // D[tid]
+                for (int d = 0; d < tid; ++d) smaller += s_tot[d];
+                gofs = smaller + my_offs - (dstart16 > 0u ? s_incl[dstart16 - 1u] : 0u);
+            }
+            s_gofs[tid] = gofs;
+        }
+        if (fused) { out_lo = p0_lo; out_hi = p0_hi; out_id = p0_id; }
+    }
 
     const uint32_t g0 = blk * kProjThreads;
     const uint32_t my_excl = s_incl[tid] - cnt;
@@ -770,12 +967,13 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
                 else if ((uint32_t)rx >= wdt) { ++ry; rx -= (int32_t)wdt; }
                 // :137 with y = the y0-th + ry owned row: compact tile id (FrameParams), the global one on one GPU
                 const uint32_t tile_key = (y0 + ry) * fp.grid_w + (min_x + (uint32_t)rx);
-                const uint64_t out = (uint64_t)base + j;
+                // P0: where pass 0 puts element j of the ranked order (the plain list of an overflowing frame: gofs = base)
+                const uint64_t out = P0 ? (uint64_t)(s_gofs[s_depth[s] & (uint32_t)(kBins - 1)] + j) : (uint64_t)base + j;
+                const uint32_t id = g0 + (P0 ? (uint32_t)s_idx[s] : s);
                 if (out < fp.capacity) {                                  // :143
                     if (!SORTED && fp.packed) {
                         // the packed payload of the depth passes (gs_sort_words.h): pk32, and pk8 into the byte plane
                         // that uses the storage of the tile words
-                        const uint32_t id = g0 + s;
                         out_lo[out] = s_depth[s];
                         out_id[out] = (tile_key << 16) | (id & 0xFFFFu);
                         reinterpret_cast<uint8_t*>(out_hi)[out] = (uint8_t)(id >> 16);
@@ -783,7 +981,7 @@ __global__ __launch_bounds__(kProjThreads) void k_emit(const FrameParams fp, con
                         if (fp.hi16) reinterpret_cast<uint16_t*>(out_hi)[out] = (uint16_t)tile_key;
                         else out_hi[out] = tile_key;
                         if constexpr (SORTED) out_id[out] = s_depth[s];
-                        else { out_lo[out] = s_depth[s]; out_id[out] = g0 + s; }
+                        else { out_lo[out] = s_depth[s]; out_id[out] = id; }
                     }
                 }
             }
@@ -911,20 +1109,33 @@ void launch_scan_blocks(const FrameParams& fp, const SplatScratch& sc, SortParam
     // ranges: [grid_w * grid_h][2] uint32 (hipMalloc'd, so 16-byte aligned; padded to a multiple of 16 bytes by the caller)
     const uint32_t n16_ranges = (fp.grid_w * fp.grid_h * 2u + 3u) / 4u;
     const uint32_t n16_coarse = (uint32_t)(kMaxSortPasses * kBins * kCoarse) / 4u;
-    const ScanJob elements{sc.block_sums, sc.block_offsets, params, fp.capacity, sc.elems_note};
+    // params[1]: the dispatch record of the pass a k_emit<false, true> does itself (SortBuffers::params)
+    const ScanJob elements{sc.block_sums, sc.block_offsets, params, fp.capacity, sc.elems_note, GS_EMIT_PASS0 ? params + 1 : nullptr};
     // GS_SORT_RADIX4_SPLAT_FIRST: the emitting splats are scanned beside the elements (a second workgroup)
-    const ScanJob splats{sc.block_flags, sc.flag_offsets, sc.aux_params, fp.num_gaussians, nullptr};
+    const ScanJob splats{sc.block_flags, sc.flag_offsets, sc.aux_params, fp.num_gaussians, nullptr, nullptr};
     const uint32_t jobs = fp.splat_first ? 2u : 1u;
-    hipLaunchKernelGGL(k_scan_blocks, dim3(jobs + kScanClearWgs), dim3(1024), 0, stream, elements, splats, jobs, blocks,
+    // the column scan of pass 0 beside them: k_project has left its rows whatever the frame goes on to do
+    const uint32_t chunks = GS_EMIT_PASS0 ? pass0_chunks(blocks) : 0u;
+    const size_t half = (size_t)chunks * kBins;
+    const Pass0Scan p0{sc.pass0_hist, sc.pass0_offs, sc.pass0_chunk + fp.parity * half,
+                       reinterpret_cast<uint4*>(sc.pass0_chunk + (fp.parity ^ 1u) * half), chunks};
+    hipLaunchKernelGGL(k_scan_blocks, dim3(jobs + kScanClearWgs + chunks), dim3(1024), 0, stream, elements, splats, jobs, blocks,
                        reinterpret_cast<uint4*>(ranges), n16_ranges, reinterpret_cast<uint4*>(coarse), n16_coarse,
-                       sc.help_count + (fp.parity ^ 1u));
+                       sc.help_count + (fp.parity ^ 1u), p0);
 }
 
-void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb,
+void launch_emit(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, bool pass0,
                  hipStream_t stream) {
     const uint32_t blocks = (fp.num_gaussians + kProjThreads - 1) / kProjThreads;
     if (blocks == 0) return;
     const uint32_t helpers = emit_helpers(fp.capacity);
+    if (pass0) {
+        const uint32_t owners = GS_EMIT_XCD_ORDER != 0 ? 8u * ((blocks + 7u) / 8u) : blocks;
+        hipLaunchKernelGGL((k_emit<false, true>), dim3(helpers + owners), dim3(kProjThreads), 0, stream, fp, sc, sb.lo[0],
+                           sb.hi[0], sb.id[0], blocks, helpers, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                           sb.lo[1], sb.hi[1], sb.id[1], (const SortParams*)(sb.params + 1));
+        return;
+    }
     hipLaunchKernelGGL((k_emit<false>), dim3(helpers + blocks), dim3(kProjThreads), 0, stream, fp, sc, sb.lo[0],
                        sb.hi[0], sb.id[0], blocks, helpers, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
 }
@@ -1025,7 +1236,7 @@ void launch_gather_sorted(const FrameParams& fp, const SplatScratch& sc, const S
     // scan's: same length, and it knows about an overflow)
     const ScanJob sorted_blocks{sc.sorted_sums, sc.block_offsets, sc.aux_params + 1, fp.capacity};
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, stream, sorted_blocks, sorted_blocks, 1u, blocks,
-                       (uint4*)nullptr, 0u, (uint4*)nullptr, 0u, (uint32_t*)nullptr);
+                       (uint4*)nullptr, 0u, (uint4*)nullptr, 0u, (uint32_t*)nullptr, Pass0Scan{});
 }
 
 void launch_emit_sorted(const FrameParams& fp, const SplatScratch& sc, const SortBuffers& sb, int sorted, hipStream_t stream) {

@@ -17,6 +17,11 @@
 //                       of ScanAdd); there is no Scan launch.
 //              Scatter: one 256-thread workgroup per group (5-6 resident per CU): wave64 match-mask ranking (stable),
 //                       LDS-staged local sort, run-wise coalesced stores (RadixSortScatter.comp:58-171).
+// In a frame of this sorter with a Count launch per pass, pass 0 happens inside InitSortList (GS_EMIT_PASS0, gs_project.hip):
+//   Count = the rows of sixteen element counts k_project leaves per block of 256 splats, Reduce / Scan = their column scan
+//   in k_scan_blocks, ScanAdd + Scatter = k_emit<false, true>, which stores every element where this pass would; the run
+//   starts behind it (SortRun::passes_done).  The pass's two launches stay in the chain over a dispatch record that is
+//   empty unless the list overflowed its capacity (SortRun::done_params): then k_emit left the plain list and they sort it.
 // Short lists (at most kFedMaxGroups groups; gs_config.count_launches) sort with ONE k_count launch: every Scatter counts the next
 // pass's digit of the keys it stores and feeds the next pass's per-group count rows (k_scatter<.., FED>, "fed counts").
 // Inside a frame the words are narrower than the reference's: 16-bit compact tile ids when they fit, and depth words
@@ -42,14 +47,6 @@ constexpr int kSortWaves = kSortThreads / 64;
 // widened into 16-bit fields and summed over the wave with DPP adds; no LDS atomics.
 // W16: the word the digit lives in is stored as 16 bits (tile ids of a frame; the upper depth half in passes 4-7).
 // ---------------------------------------------------------------------------------------------
-// inclusive prefix sum inside each row of 16 lanes (DPP row_shr 1/2/4/8; lanes shifted in from outside the row add 0)
-__device__ __forceinline__ uint32_t row16_inclusive_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xe, false);   // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xc, false);   // row_shr:8
-    return v;
-}
 
 static_assert(kCountChunk == kSortTile, "a Count wave takes a whole group per step");
 constexpr int kCountMaxK = 128;                     // groups per segment whose counts are kept in LDS (8 KB)
@@ -508,6 +505,7 @@ void k_scatter(const SortParams* __restrict__ params, const uint32_t* __restrict
 int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t stream) {
     if (sb.digit_bits == 8u) return launch_radix_sort8(sb, run, stream);
     if (sb.digit_bits != (uint32_t)kRadixBits || (run.fed && !sb.fed[0])) return -1;   // table / seg_sum are sized per digit width
+    if (run.passes_done != 0u && run.fed) return -1;    // the rows of a fed run start with pass 0's Count launch
     const bool fed = run.fed, hi16 = run.hi16;
     const SortParams* params = run.params ? run.params : sb.params;
     uint32_t max_groups = scatter_grid(run, kSortTile);
@@ -516,11 +514,18 @@ int launch_radix_sort(const SortBuffers& sb, const SortRun& run, hipStream_t str
     if (fed && max_groups > 2u * kFedMaxGroups) max_groups = 2u * kFedMaxGroups;
     // sb.coarse (the coarse digit totals of every pass; Count adds into them with atomics) must be zero on entry:
     // k_scan_blocks clears it in a frame, k_set_sort_params for the stand-alone sorter
+    // A run whose list is already in the order of its first passes_done passes (a frame's k_emit does pass 0) goes on with
+    // the pass behind them; with done_params it launches those passes all the same, from the half they would have read, over
+    // a record that is empty unless the producer left the plain list there.
     int src = run.start;
+    uint32_t first = run.passes_done;
+    if (run.done_params) { src ^= (int)(run.passes_done & 1u); first = 0u; }
+    const SortParams* const run_params = params;
     const uint32_t passes = sort_pass_count(run, kRadixBits);
-    for (uint32_t pass = 0; pass < passes; ++pass) {
+    for (uint32_t pass = first; pass < passes; ++pass) {
         const SortPass p = sort_pass(run, kRadixBits, pass);
         const int dst = src ^ 1;
+        params = pass < run.passes_done ? run.done_params : run_params;
         const uint32_t* word = p.tile_word ? sb.hi[src] : sb.lo[src];
         uint32_t* coarse = sb.coarse + (size_t)(run.coarse_pass + pass) * kBins * kCoarse;   // zeroed above; this pass's Count adds into it
         // fed counts: one Count launch per SORT (the rows of pass 0); pass p reads set p % 3, adds into (p + 1) % 3

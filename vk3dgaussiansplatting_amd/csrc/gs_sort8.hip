@@ -307,6 +307,7 @@ void k_scatter8(const SortParams* __restrict__ params, const uint32_t* __restric
 
 int launch_radix_sort8(const SortBuffers& sb, const SortRun& run, hipStream_t stream) {
     if (sb.digit_bits != 8u) return -1;           // 4-bit buffers hold 16 x 512 segment words, not 2 x 256 x 512
+    if (run.passes_done != 0u) return -1;         // only the 4-bit sorter of a frame starts behind its first pass
     const bool hi16 = run.hi16;
     const SortParams* params = run.params ? run.params : sb.params;
     // Group size by what the list can be expected to hold (the host never reads the element count back): 2048-key groups for
