@@ -817,6 +817,60 @@ int gs_densify_device(gs_ctx* ctx, const float* records, const float* m, const f
                       const gs_densify_params* p,
                       float* records_out, float* m_out, float* v_out, uint32_t max_out, uint32_t* counts_out);
 
+/* Absolute screen gradients (no reference counterpart; the growth statistic of AbsGS, gsplat's absgrad = True.  Callers
+ * detect the three calls by their symbols, GS_API_VERSION is unchanged).  The screen gradient dL/d(sx, sy) of a splat is the
+ * sum of one term per pixel that blends it.  Over a large, blurry splat on fine texture the terms pull in opposite directions
+ * and cancel, so the norm gs_densify_stats_device accumulates stays below the threshold exactly where a split is needed.  The
+ * statistic here is the sum of the ABSOLUTE values of the same terms, per component:
+ *     abs_x(g) = sum over (pixel p, list element of g that p blends) of |dL_p/dsx|,    abs_y(g) likewise with dsy
+ * where dL_p/dsx is the float32 term the backward adds into dsx for that pair -- not a recomputation.
+ *
+ * gs_set_abs_gradients(ctx, 1): every gs_backward* form (gs_backward, gs_backward_device, gs_backward_visible,
+ * gs_backward_visible_device; on a band context too) also leaves the absolute pairs in the context's scratch, one pair per
+ * list element in its slot.  Per element the 256 pixels of its tile are summed in the fixed order of the signed columns
+ * (per wave a balanced tree over the lanes, then ((W0 + W1) + W2) + W3; a pixel that does not blend the entry adds +0.0f);
+ * an element no pixel of its tile reaches gets (0, 0), never what an earlier frame left; an element at or past the list
+ * capacity has no slot and no pair.  Everything those calls return is bit for bit what it is with the switch off, and so is
+ * whatever gs_backward_camera* and gs_densify_stats_device read afterwards.  Frames are not affected.  Scratch: 8 bytes per
+ * list element of capacity, allocated by the first gs_backward* form that runs with the switch on, freed with the resolution.
+ * A host flag per context, 0 by default, legal any time after gs_create; it survives gs_set_resolution, gs_set_tile_rows* and
+ * uploads; nothing is enqueued or waited for.  With the switch off gs_backward* runs the kernel it ran before this call existed.
+ * GS_ERR_INVALID for a NULL ctx (the code alone) and for enable > 1 (with a message; the flag stays as it was).
+ *
+ * gs_abs_screen_gradient_device: for i < min(*count_dev, max_rows), g = ids_dev[i]:
+ *     abs_out[i] = (abs_x(g), abs_y(g)), in pixel units like dsx, dsy: per component S = 0.0f; S = S + pair over the
+ *     splat's list elements in slot order (tile raster order inside its box), over the slots below the list capacity;
+ *     (0, 0) for a splat with no element in this frame and for an id >= n of the scene (compared, never dereferenced).
+ * Rows at or past the count are not touched.  abs_out: float[max_rows][2], DEVICE.  abs_x(g) >= |dsx(g)| and abs_y(g) >=
+ * |dsy(g)| as float32 (the same terms in the same tree; rounding is monotone).  Served on a band context while
+ * gs_set_band_gradients is on: the band's pairs are the partial sums over its own pixels, and -- unlike the norm -- they add
+ * up over the bands of a frame (up to the association of a float32 sum of non-negative numbers).
+ *
+ * gs_densify_stats_abs_device: gs_densify_stats_device's grad_accum on the absolute pair.  Per listed g < n (an id >= n is
+ * skipped), in float32, not contracted:
+ *     ax = abs_x(g) * 0.5f * W,  ay = abs_y(g) * 0.5f * H
+ *     grad_accum_abs[g] = grad_accum_abs[g] + sqrtf(ax * ax + ay * ay)
+ * and nothing else: seen and max_radius stay with gs_densify_stats_device, which is called beside it on the same ids.
+ * grad_accum_abs: float[n].  Like that call it is refused on a band.  A caller applies the AbsGS rule with gs_densify_device
+ * as it stands by handing it, per splat, grad_accum_abs * (grad_threshold / abs_threshold) where the largest scale exceeds
+ * split_scale and grad_accum elsewhere: large splats split by the absolute mean against abs_threshold, small ones clone by
+ * the signed mean against grad_threshold.  AbsGS and gsplat's documentation publish abs_threshold = 8e-4; this library has
+ * not measured a value.
+ *
+ * Both read calls: enqueued on the context's stream, no host sync; count_dev is never read by the host, the grid is sized
+ * from max_rows; ids are distinct (for the accumulating call), there are no atomics and the result is bitwise reproducible,
+ * the same for every sorter.  max_rows == 0: GS_OK, nothing launched.
+ * GS_ERR_INVALID (message in gs_last_error, nothing enqueued; a NULL ctx: the code alone): a NULL pointer with max_rows > 0;
+ * everything gs_densify_stats_device refuses, with its messages (for gs_abs_screen_gradient_device a band is refused only
+ * while gs_set_band_gradients is off, and there is no n to compare); and "no gs_backward* on this frame with
+ * gs_set_abs_gradients on": the last blend of a gs_backward* form on this frame did not run with the switch on.  Turning the
+ * switch on after the backward does not count; a new frame, an upload, a new resolution or tile rows clear the state. */
+int gs_set_abs_gradients(gs_ctx* ctx, uint32_t enable);
+int gs_abs_screen_gradient_device(gs_ctx* ctx, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows,
+                                  float* abs_out);
+int gs_densify_stats_abs_device(gs_ctx* ctx, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows,
+                                uint32_t n, float* grad_accum_abs);
+
 /* Pruning by contribution (no reference counterpart): which splats does any picture ever show?  The blend weight
  * w = T * alpha is known to the blend alone; a splat behind an opaque surface in every view passes the opacity, scale and
  * radius tests of gs_densify_device and is still projected, sorted and walked in every frame.  Two calls: the per-splat blend

@@ -301,6 +301,25 @@ public:
         return rc;
     }
 
+    // Absolute screen gradients (gsplat.h, gs_set_abs_gradients): with the switch on every backward also leaves the sums of
+    // |dL_p/dsx|, |dL_p/dsy| per list element; absScreenGradient writes the pair of ids[i] to abs_out[i] (DEVICE
+    // [max_rows][2]), densifyStatsAbs adds its norm in NDC units into grad_accum_abs (DEVICE [n]) beside densifyStats.
+    int setAbsGradients(bool enable) {
+        const int rc = gs_set_abs_gradients(ctx_, enable ? 1u : 0u);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int absScreenGradient(const uint32_t* ids, const uint32_t* count, uint32_t max_rows, float* abs_out) {
+        const int rc = gs_abs_screen_gradient_device(ctx_, ids, count, max_rows, abs_out);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+    int densifyStatsAbs(const uint32_t* ids, const uint32_t* count, uint32_t max_rows, uint32_t n, float* grad_accum_abs) {
+        const int rc = gs_densify_stats_abs_device(ctx_, ids, count, max_rows, n, grad_accum_abs);
+        if (rc < 0) error_ = gs_last_error(ctx_);
+        return rc;
+    }
+
     // Pruning by contribution (gsplat.h, gs_contrib_device and gs_prune_below_device): the blend weights of the last frame
     // accumulated per splat into the caller's DEVICE arrays wmax / wsum / pixels [n] (wsum and pixels may be null), and the
     // rows whose score reaches the threshold copied, in order, into records_out / raw_out / m_out / v_out [max_out][84] (raw,

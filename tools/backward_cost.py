@@ -5,7 +5,7 @@ the blend backward (k_bwd_blend, with the three small kernels of the per-splat s
 (k_bwd_rowsum_chain).  The visible form (gs_backward_visible_device with max_rows = |V|) is timed in the same window, dense
 and visible iterations alternating in one process so that both see the same neighbours; it runs the <true> instantiations
 of the same kernels, which the trace tells from the dense <false> ones by the template argument in the kernel name
-(k_splat_offsets<gs::BwdSource<true>>; k_bwd_blend is one kernel for both).  A traced child that fails, or a trace in which a
+(k_splat_offsets<gs::BwdSource<true>>; k_bwd_blend<false> is one kernel for both; <true> adds the absolute columns, tools/absgrad_cost.py).  A traced child that fails, or a trace in which a
 part of the split matches no kernel, is an error, not a zero.  camera_ms is gs_backward_camera_device + gs_synchronize behind
 the visible backward of the same iteration (it re-reads that backward's rows), in the same alternating loop; the trace splits
 it into k_bwd_camera_blocks and k_bwd_camera_reduce.  One JSON line per config.
@@ -69,7 +69,7 @@ for name in a.configs:
         # the template argument tells the dense instantiation from the visible one
         ms = lambda key: costlib.kernel_us(stats, key, "backward_cost") / 1e3
         scan = lambda vis: sum(ms(f"{k}<gs::BwdSource<{vis}>>") for k in ("k_splat_block_sums", "k_splat_scan_blocks", "k_splat_offsets"))
-        split = {"blend_backward_ms": round(ms("k_bwd_blend") + scan("false"), 4),
+        split = {"blend_backward_ms": round(ms("k_bwd_blend<false>") + scan("false"), 4),
                  "rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<false>"), 4),
                  "slot_offsets_ms": round(scan("false"), 4), "visible_scan_ms": round(scan("true"), 4),
                  "visible_rowsum_chain_ms": round(ms("k_bwd_rowsum_chain<true>"), 4),

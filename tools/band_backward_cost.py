@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 CALL = ("k_splat_block_sums<gs::BwdSource<true>>", "k_splat_scan_blocks<gs::BwdSource<true>>",
-        "k_splat_offsets<gs::BwdSource<true>>", "k_bwd_blend", "k_bwd_rowsum_chain<true>")   # the launches of one call, in order
+        "k_splat_offsets<gs::BwdSource<true>>", "k_bwd_blend<false>", "k_bwd_rowsum_chain<true>")   # the launches of one call, in order
 
 
 def sequence(gh):

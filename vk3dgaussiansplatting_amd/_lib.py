@@ -183,6 +183,7 @@ EXPORTS = [
     "gs_relocate_device", "gs_grow_device", "gs_position_noise_device",
     "gs_set_band_gradients",
     "gs_set_antialias",
+    "gs_set_abs_gradients", "gs_abs_screen_gradient_device", "gs_densify_stats_abs_device",
 ]
 # GS_SH_*: the sh_mode of a frame (0, 1, 2 = the reference's Camera.h modes; 5 and 4 = SH degree 1 and 2; 3 names none)
 GS_SH_ALL_BANDS, GS_SH_SKIP_FIRST_BAND, GS_SH_ONLY_FIRST_BAND, GS_SH_DEGREE_2, GS_SH_DEGREE_1 = 0, 1, 2, 4, 5
@@ -346,6 +347,9 @@ def lib() -> C.CDLL:
     L.gs_position_noise_device.argtypes = [ctxp, vp, vp, u32, vp, vp, u32, f32, f32, f32, C.c_uint64]
     L.gs_set_band_gradients.argtypes = [ctxp, u32]
     L.gs_set_antialias.argtypes = [ctxp, u32]
+    L.gs_set_abs_gradients.argtypes = [ctxp, u32]
+    L.gs_abs_screen_gradient_device.argtypes = [ctxp, vp, vp, u32, vp]
+    L.gs_densify_stats_abs_device.argtypes = [ctxp, vp, vp, u32, u32, vp]
     _lib = L
     _check_hip_runtime(L)
     return L

@@ -263,6 +263,11 @@ class VisibleAdam:
     track_density=True: the optimiser also owns grad_accum, seen and max_radius (zeros of N), step() enqueues
     gs_densify_stats_device right behind the backward, and densify() replaces the cloud.
 
+    abs_density=True (needs track_density): the AbsGS statistic beside the signed one.  The optimiser also owns
+    grad_accum_abs (zeros of N), turns the renderer's setAbsGradients on, and enqueues gs_densify_stats_abs_device right
+    behind gs_densify_stats_device, in step() and in every view of step_batch(); densify(abs_threshold=...) then splits by
+    it.  Off (the default), the calls of a step are exactly those without it.
+
     space="raw": the optimiser moves self.raw -- log-scales, the logit of the opacity, the rotation before normalisation:
     the parameters a .ply stores, made from records by gs_raw_from_records_device -- and keeps records == act(raw) bit for
     bit (records is rewritten once, here, as act(raw): its scales and opacity move by the rounding of one log and one
@@ -278,16 +283,18 @@ class VisibleAdam:
     (gs_rows_accumulate_device) and one Adam step on the union of their lists (gs_rows_collect_device)."""
 
     def __init__(self, records: torch.Tensor, *, renderer: Renderer, max_rows: int | None = None, track_density: bool = False,
-                 space: str = "records", **params):
+                 space: str = "records", abs_density: bool = False, **params):
         _check_records(records, plain=True)
         if space not in ("records", "raw"):
             raise ValueError(f"space must be 'records' or 'raw', not {space!r}")
+        if abs_density and not track_density:
+            raise ValueError("abs_density=True needs track_density=True")
         self.records, self.renderer, self.space = records, renderer, space
         self.params = default_adam_params(space=space, **params)
         dev, n = records.device, records.shape[0]
         self.max_rows = n if max_rows is None else int(max_rows)
         self._rows_follow_n = max_rows is None
-        self.track_density = bool(track_density)
+        self.track_density, self.abs_density = bool(track_density), bool(abs_density)
         if self.track_density:
             self._zero_stats(n, dev)
         self.m, self.v = torch.zeros_like(records), torch.zeros_like(records)
@@ -300,6 +307,8 @@ class VisibleAdam:
         self.raw = torch.zeros_like(records) if space == "raw" else None
         torch.cuda.synchronize(dev)                       # the zeros above; gs_set_stream waits for the context's stream itself
         renderer.setStream(self.stream.cuda_stream)
+        if self.abs_density:
+            renderer.setAbsGradients(True)
         if space == "raw":
             self._raw_from_records()
             self.stream.synchronize()                     # once: records were rewritten, and the caller may read them anywhere
@@ -321,6 +330,7 @@ class VisibleAdam:
         self.grad_accum = torch.zeros(n, dtype=torch.float32, device=dev)
         self.seen = _u32(n, dev)
         self.max_radius = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.grad_accum_abs = torch.zeros(n, dtype=torch.float32, device=dev) if self.abs_density else None
 
     def _alloc_batch(self, dev):
         """What step_batch sums into: the accumulator (never initialised: a first touch is a store) and the zero marks."""
@@ -363,6 +373,9 @@ class VisibleAdam:
         if self.track_density:
             r.densifyStatsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, self.records.shape[0],
                                  self.grad_accum.data_ptr(), self.seen.data_ptr(), self.max_radius.data_ptr())
+            if self.abs_density:
+                r.densifyStatsAbsDevice(self.ids.data_ptr(), self.count.data_ptr(), self.max_rows, self.records.shape[0],
+                                        self.grad_accum_abs.data_ptr())
 
     def _adam(self):
         """t advanced once, then gs_adam_rows_device, or gs_adam_rows_raw_device in raw space, on self.ids / rows / count."""
@@ -392,9 +405,14 @@ class VisibleAdam:
         # another n is another scene: the next step uploads everything and sets the resolution again (the output mask stays)
         self._full_upload = True
 
-    def densify(self, **params):
+    def densify(self, abs_threshold: float | None = None, **params):
         """Clone, split and prune by the statistics gathered since the last call (gs_densify_device, params:
-        default_densify_params()'s overrides) -> (n_out, cloned, split, pruned).  self.records, self.m and self.v become new
+        default_densify_params()'s overrides) -> (n_out, cloned, split, pruned).
+        abs_density=True: the AbsGS rule through the same call.  The accumulator handed to it is, per splat and in float32
+        on the stream, smax > split_scale ? grad_accum_abs * (grad_threshold / abs_threshold) : grad_accum (smax: the
+        largest of the record's three scales): large splats split by the mean ABSOLUTE screen gradient against
+        abs_threshold, small ones clone by the signed mean against grad_threshold.  abs_threshold=None is 8e-4, the value
+        AbsGS and gsplat's documentation publish: a hyper-parameter that nothing here has measured.  self.records, self.m and self.v become new
         tensors of n_out rows, the children beside their parents; the statistics start again from zero; ids, rows and max_rows
         follow the new size (a max_rows given to the constructor stays); the next step uploads the whole cloud as a new scene.
         t and the hyper-parameters stay.  Reading the four counts is the one host wait of this rare event.
@@ -403,12 +421,19 @@ class VisibleAdam:
         rare event -- and a split child starts from log(s / split_shrink)."""
         if not self.track_density:
             raise RuntimeError("VisibleAdam(track_density=True) gathers the statistics densify() goes by")
+        if abs_threshold is not None and not self.abs_density:
+            raise RuntimeError("VisibleAdam(abs_density=True) gathers the statistic abs_threshold goes by")
         p = _lib.default_densify_params(**params)
         r, dev, n = self.renderer, self.records.device, self.records.shape[0]
         with self._enqueue():
+            accum = self.grad_accum
+            if self.abs_density:
+                ratio = float(np.float32(p.grad_threshold) / np.float32(8e-4 if abs_threshold is None else abs_threshold))
+                large = self.records[:, 4:7].amax(dim=1) > float(p.split_scale)
+                accum = torch.where(large, self.grad_accum_abs * ratio, self.grad_accum)
             out = [torch.empty(2 * n, FLOATS_PER_GAUSSIAN, dtype=torch.float32, device=dev) for _ in range(3)]
             counts = _u32(4, dev)
-            r.densifyDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, self.grad_accum.data_ptr(),
+            r.densifyDevice(self.records.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), n, accum.data_ptr(),
                             self.seen.data_ptr(), self.max_radius.data_ptr(), p, out[0].data_ptr(), out[1].data_ptr(),
                             out[2].data_ptr(), 2 * n, counts.data_ptr())
             n_out, cloned, split, pruned = (int(x) for x in counts.cpu().numpy().view(np.uint32))      # waits for the stream

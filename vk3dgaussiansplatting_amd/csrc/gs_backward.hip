@@ -15,7 +15,9 @@
 //                   of gs_contrib.hip: the same entries contribute and each pixel stops on the same entry K with the same
 //                   T_K).  What this kernel adds: the walk back to front with the colour behind every entry as a running
 //                   sum; the 256 pixels' derivatives of each list entry are reduced on chip in a fixed tree and stored as
-//                   one 10-float row in the slot of the entry, with plain stores;
+//                   one 10-float row in the slot of the entry, with plain stores.  A template on ABS (gs_set_abs_gradients):
+//                   <true> also reduces |d/dsx| and |d/dsy| of every (entry, pixel) and stores the pair in the entry's slot of
+//                   abs_rows, which gs_abs_screen_gradient_device / gs_densify_stats_abs_device sum (gs_densify.hip);
 //   k_bwd_rowsum_chain<VIS> : per splat, its rows summed in slot order (= tile raster order inside its box), then the sum
 //                   through the per-splat part of the frame (conic <- 2-D covariance <- scale, rotation; screen position
 //                   and depth <- position; colour <- SH coefficients and position: bwd_chain<false> of gs_bwd_chain.h, which
@@ -29,6 +31,8 @@
 #include "gs_bwd_chain.h"
 #include "gs_splat_scan.h"
 #include "gs_tile_replay.h"
+
+#include <type_traits>
 
 namespace gs {
 
@@ -66,11 +70,20 @@ struct BwdBlendArgs : TileListArgs {
     const float* grad_depth;        // [H][W] dL/dDEPTH or null
     float* rows;                    // [capacity][kRowFloats]
 };
+struct BwdBlendAbsArgs : BwdBlendArgs {
+    float* abs_rows;                // [capacity][kAbsRowFloats]  BackwardBuffers::abs_rows
+};
 
-// One 256-thread workgroup per owned tile, one pixel per lane: the replay of gs_tile_replay.h, then its walk back
-__global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const BwdBlendArgs a) {
+// One 256-thread workgroup per owned tile, one pixel per lane: the replay of gs_tile_replay.h, then its walk back.
+// ABS (gs_set_abs_gradients): two more columns per (entry, pixel), |v[0]| and |v[1]| of the very terms the signed columns
+// add, through the same tree and the same combination of the four waves, stored as a pair in the entry's slot of abs_rows.
+// Without ABS the columns, their LDS and their stores are compiled out: the kernel is the one it was, argument block included.
+template <bool ABS>
+__global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp,
+                                                   const std::conditional_t<ABS, BwdBlendAbsArgs, BwdBlendArgs> a) {
+    constexpr int kPartFloats = ABS ? kRowFloats + kAbsRowFloats : kRowFloats;
     __shared__ float s_e[kBwdBatch][12];                 // staged entries, with colour and depth
-    __shared__ float s_part[4][kBwdBatch][kRowFloats];   // per-wave sums of an entry's row
+    __shared__ float s_part[4][kBwdBatch][kPartFloats];  // per-wave sums of an entry's row (ABS: and of its absolute pair)
     __shared__ uint32_t s_kend;
 
     const TilePixel t = tile_pixel(fp, a.ranges);
@@ -125,9 +138,9 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
             bool contributes;
             const float alpha = entry_alpha(e, t, ex, ey, ef, contributes);
             contributes = contributes && last != 0xFFFFFFFFu && i <= last;
-            float v[kRowFloats];
+            float v[kPartFloats];
 #pragma unroll
-            for (int k = 0; k < kRowFloats; ++k) v[k] = 0.0f;
+            for (int k = 0; k < kPartFloats; ++k) v[k] = 0.0f;
             if (contributes) {
                 const float one_m = 1.0f - alpha;                              // the forward's own (1 - alpha)
                 const float Ti = i == last ? TK : Tcur / one_m;                // T_{i+1} >= 1e-4 here: no early-out before K
@@ -145,6 +158,7 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
                 v[5] = gc.x * w; v[6] = gc.y * w; v[7] = gc.z * w;
                 v[8] = dalpha * ef;
                 v[9] = gd * w;
+                if constexpr (ABS) { v[kRowFloats] = fabsf(v[0]); v[kRowFloats + 1] = fabsf(v[1]); }
                 Sr = alpha * cr + one_m * Sr;
                 Sg = alpha * cg + one_m * Sg;
                 Sb = alpha * cb + one_m * Sb;
@@ -155,33 +169,44 @@ __global__ __launch_bounds__(256) void k_bwd_blend(const FrameParams fp, const B
             // the wave's sum in a fixed butterfly (every lane ends with the same bits), then one lane parks it
             if (__ballot(contributes) != 0ull) {
 #pragma unroll
-                for (int k = 0; k < kRowFloats; ++k) v[k] = wave_tree(v[k], [](float x, float y) { return x + y; });
+                for (int k = 0; k < kPartFloats; ++k) v[k] = wave_tree(v[k], [](float x, float y) { return x + y; });
             }
             if (t.lane == 0) {
 #pragma unroll
-                for (int k = 0; k < kRowFloats; ++k) s_part[t.wave][j][k] = v[k];
+                for (int k = 0; k < kPartFloats; ++k) s_part[t.wave][j][k] = v[k];
             }
         }
         __syncthreads();
         // the four waves' sums -> the entry's row, in its slot
-        for (uint32_t q = (uint32_t)t.tid; q < cnt * kRowFloats; q += 256u) {
-            const uint32_t j = q / kRowFloats, k = q % kRowFloats;
+        for (uint32_t q = (uint32_t)t.tid; q < cnt * kPartFloats; q += 256u) {
+            const uint32_t j = q / kPartFloats, k = q % kPartFloats;
             const uint32_t slot = __float_as_uint(s_e[j][kEntSlot<true>]);
             const float sum = ((s_part[0][j][k] + s_part[1][j][k]) + s_part[2][j][k]) + s_part[3][j][k];
-            if (slot != kNoSlot) a.rows[(size_t)slot * kRowFloats + k] = sum;
+            if constexpr (ABS) {
+                if (slot != kNoSlot) {
+                    if (k < (uint32_t)kRowFloats) a.rows[(size_t)slot * kRowFloats + k] = sum;
+                    else a.abs_rows[(size_t)slot * kAbsRowFloats + (k - kRowFloats)] = sum;
+                }
+            } else {
+                if (slot != kNoSlot) a.rows[(size_t)slot * kRowFloats + k] = sum;
+            }
         }
         __syncthreads();
         i1 = i0;
     }
     // 3. entries no pixel of the tile reaches
     zero_rows<kRowFloats, kBwdBatch>(t, a, kend, a.rows);
+    if constexpr (ABS) zero_rows<kAbsRowFloats, kBwdBatch>(t, a, kend, a.abs_rows);     // a stale pair must never be summed
 }
 
 static void launch_blend(const BackwardFrame& f, const float* grad_rgba, const float* grad_depth, hipStream_t stream) {
     const BwdBlendArgs args{{f.sc.raster, f.sorted_id, f.ranges, f.bb.scan.offsets, f.sc.extents, f.fp.capacity},
                             grad_depth ? f.scene.pos : nullptr, reinterpret_cast<const float4*>(grad_rgba), grad_depth, f.bb.rows};
     if (!f.fp.rows_owned) return;                     // an empty band: no tile, no element, no row
-    hipLaunchKernelGGL(k_bwd_blend, replay_grid(f.fp), dim3(256), 0, stream, f.fp, args);
+    if (f.bb.abs_rows)                                // the switch is on (backward_frame): the absolute pairs beside the rows
+        hipLaunchKernelGGL(k_bwd_blend<true>, replay_grid(f.fp), dim3(256), 0, stream, f.fp, BwdBlendAbsArgs{args, f.bb.abs_rows});
+    else
+        hipLaunchKernelGGL(k_bwd_blend<false>, replay_grid(f.fp), dim3(256), 0, stream, f.fp, args);
 }
 
 // ---- per splat ----------------------------------------------------------------------------------------------------

@@ -66,6 +66,8 @@ struct LastFrame {
     bool differentiable = false;  // kFrame, and no upload or tile-row change since: gs_backward* may run
     bool has_backward = false;    // bwd.rows holds a backward of this frame (a gs_backward* form ran the blend): what
                                   // gs_densify_stats_device and gs_backward_camera* sum
+    bool has_abs_backward = false;  // ... and that blend ran with gs_set_abs_gradients on: bwd.abs_rows holds the absolute pairs
+                                  // of this frame, what gs_abs_screen_gradient_device and gs_densify_stats_abs_device sum
     int sorted_index = 0;         // kFrame: which ping-pong half holds the sorted list
     gs::FrameParams fp{};         // of the InitSortList launch (gs_debug_read(GS_BUF_COLOR) evaluates colours on demand)
 };
@@ -111,6 +113,7 @@ struct gs_ctx {
     uint32_t row_begin = 0, row_end = 0, row_stride = 1, first_row = 0, rows_owned = 0;
     bool compact_out = false;
     bool band_gradients = false;      // gs_set_band_gradients: gs_backward* and gs_contrib_device serve a band of tile rows
+    bool abs_gradients = false;       // gs_set_abs_gradients: the gs_backward* forms run k_bwd_blend<true> and leave bwd.abs_rows
     bool antialias = false;           // gs_set_antialias: FrameParams::antialias of the frames enqueued from now on (a host flag of the
                                       // context, not of the scene; nothing but make_frame_params reads it)
     uint32_t capacity = 0, num_sort_bits = 0;
@@ -126,7 +129,8 @@ struct gs_ctx {
     float* out_rgba32f = nullptr;     // [H][W][4] while GS_OUTPUT_RGBA32F is on and a resolution is set
     float* out_depth = nullptr;       // [H][W] while GS_OUTPUT_DEPTH is on and a resolution is set
     bool outputs_valid = false;       // a frame has been enqueued since the mask or the resolution last changed
-    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity), freed with the resolution
+    // gs_backward*: scratch allocated on the first call (rows sized by the list capacity; abs_rows, 8 bytes per list element,
+    // on the first call with gs_set_abs_gradients on), freed with the resolution
     gs::BackwardBuffers bwd{};
     DeviceOwner bwd_mem;              // of bwd and bwd_host_in / _out / bwd_vis_out / bwd_cam_partials / bwd_cam_out
     float* bwd_host_in = nullptr;     // gs_backward (host pointers): dL/dRGBA32F [H][W][4] + dL/dDEPTH [H][W] on the device
@@ -228,10 +232,10 @@ inline int fail(gs_ctx* ctx, int code, const std::string& msg) {
 // First statement of a call that launches a sort list: until it succeeds nothing is readable or differentiable
 GS_HIDDEN inline void list_launching(gs_ctx* c) {
     c->last.kind = LastFrame::kNone;
-    c->last.differentiable = c->last.has_backward = c->outputs_valid = false;
+    c->last.differentiable = c->last.has_backward = c->last.has_abs_backward = c->outputs_valid = false;
 }
 GS_HIDDEN inline void frame_enqueued(gs_ctx* c, const gs::FrameParams& fp, int sorted_index) {
-    c->last = {LastFrame::kFrame, true, false, sorted_index, fp};
+    c->last = {LastFrame::kFrame, true, false, false, sorted_index, fp};
     c->outputs_valid = c->outputs != 0u;
 }
 // gs_debug_init_sort_list succeeded; the list touches no output buffer: those are as valid as they were before it
@@ -241,8 +245,15 @@ GS_HIDDEN inline void unsorted_list_ready(gs_ctx* c, const gs::FrameParams& fp, 
     c->outputs_valid = outputs_valid;
 }
 // An in-place upload or a change of the tile rows: the lists stay readable, the frame is no longer the scene's
-GS_HIDDEN inline void scene_or_rows_changed(gs_ctx* c) { c->last.differentiable = c->last.has_backward = false; }
-GS_HIDDEN inline void backward_ran(gs_ctx* c) { c->last.has_backward = true; }
+GS_HIDDEN inline void scene_or_rows_changed(gs_ctx* c) {
+    c->last.differentiable = c->last.has_backward = c->last.has_abs_backward = false;
+}
+// The blend of a gs_backward* form was enqueued: bwd.rows is this frame's, and bwd.abs_rows with the switch on (a blend with
+// the switch off leaves the pairs of an earlier one, which belong to other image gradients: they no longer count)
+GS_HIDDEN inline void backward_ran(gs_ctx* c) {
+    c->last.has_backward = true;
+    c->last.has_abs_backward = c->abs_gradients;
+}
 GS_HIDDEN inline void resolution_freed(gs_ctx* c) { list_launching(c); }      // (its output buffers are gone with it)
 
 // gs_dist.cpp: frees the buffers of a sharded frame (they are sized by the resolution).

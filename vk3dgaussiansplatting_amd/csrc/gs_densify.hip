@@ -81,6 +81,39 @@ void launch_densify_stats(const DensifyStatsArgs& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_densify_stats, dim3(backward_blocks(a.max_rows)), dim3(256), 0, stream, a);
 }
 
+// ---- absolute screen gradients (gs_set_abs_gradients) -------------------------------------------------------------
+
+// Thread i < min(*count, max_rows) handles g = ids[i]: the pairs of BackwardBuffers::abs_rows of splat g summed in slot
+// order (splat_row_sum over rows of two floats).  ACCUM: out[g] += the norm of the pair in NDC units, an id >= n is skipped
+// (k_densify_stats' expression on the absolute sums); else out[i] = the pair, (0, 0) for an id >= n.
+template <bool ACCUM>
+__global__ __launch_bounds__(256) void k_abs_gradient(const AbsGradArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t listed = *a.count, rows = listed < a.max_rows ? listed : a.max_rows;
+    if (i >= rows) return;
+    const uint32_t g = a.ids[i];
+    float s[kAbsRowFloats] = {0.0f, 0.0f};
+    if (g < a.n) splat_row_sum<kAbsRowFloats>(a.counts, a.offsets, a.abs_rows, g, a.capacity, s);
+    if constexpr (ACCUM) {
+        if (g >= a.n) return;
+        const float ax = s[0] * 0.5f * (float)a.width, ay = s[1] * 0.5f * (float)a.height;
+        a.out[g] = a.out[g] + sqrtf(ax * ax + ay * ay);
+    } else {
+        a.out[(size_t)i * kAbsRowFloats] = s[0];
+        a.out[(size_t)i * kAbsRowFloats + 1] = s[1];
+    }
+}
+
+void launch_abs_screen_gradient(const AbsGradArgs& a, hipStream_t stream) {
+    if (a.max_rows == 0) return;
+    hipLaunchKernelGGL(k_abs_gradient<false>, dim3(backward_blocks(a.max_rows)), dim3(256), 0, stream, a);
+}
+
+void launch_densify_stats_abs(const AbsGradArgs& a, hipStream_t stream) {
+    if (a.max_rows == 0) return;
+    hipLaunchKernelGGL(k_abs_gradient<true>, dim3(backward_blocks(a.max_rows)), dim3(256), 0, stream, a);
+}
+
 // ---- the new cloud ------------------------------------------------------------------------------------------------
 
 // A lane per (input splat g, group q of four floats): consecutive lanes read consecutive 16 bytes of records, m and v.  The

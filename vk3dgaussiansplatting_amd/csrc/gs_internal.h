@@ -365,8 +365,11 @@ struct SplatScan {
 // gs_backward* (gs_backward.hip): scratch of a backward pass, allocated on the first call
 constexpr int kRowFloats = 10;    // a row of BackwardBuffers::rows: dL/d{sx, sy, ix, iy, iz, r, g, b, a, z} of one list element, in
                                   // that order (screen position, inverse 2-D covariance, colour, opacity, view depth)
+constexpr int kAbsRowFloats = 2;  // a row of BackwardBuffers::abs_rows: the sums over the tile's pixels of |dL_p/dsx| and |dL_p/dsy|
 struct BackwardBuffers {
     float* rows;              // [capacity][kRowFloats]  per element, in its slot
+    float* abs_rows;          // [capacity][kAbsRowFloats]  gs_set_abs_gradients: null until the first backward with the switch on;
+                              // in a BackwardFrame: null unless THIS backward runs with the switch on (k_bwd_blend<true>)
     // row 0: tiles_touched, so offsets[g] = the first slot of splat g; row 1 (gs_backward_visible* only): the flag
     // tiles_touched != 0, whose scan is the position of g in V = the splats with tiles_touched != 0, ascending
     SplatScan scan;           // K = 2
@@ -477,6 +480,21 @@ struct DensifyStatsArgs {
     float* max_radius;
 };
 void launch_densify_stats(const DensifyStatsArgs& a, hipStream_t stream);
+// gs_abs_screen_gradient_device / gs_densify_stats_abs_device (gs_densify.hip): the listed ids of the frame and the absolute
+// pairs its backward left (BackwardBuffers::abs_rows).  out: the pairs [max_rows][2] by list position, or the accumulator [n]
+struct AbsGradArgs {
+    const uint32_t* ids;
+    const uint32_t* count;
+    uint32_t max_rows, n;
+    SplatCounts counts;               // splat_counts_of(the frame's scratch)
+    const uint32_t* offsets;          // BackwardBuffers::scan.offsets
+    const float* abs_rows;
+    uint32_t capacity, width, height;
+    float* out;
+};
+void launch_abs_screen_gradient(const AbsGradArgs& a, hipStream_t stream);
+void launch_densify_stats_abs(const AbsGradArgs& a, hipStream_t stream);
+inline size_t backward_abs_row_bytes(uint32_t capacity) { return (size_t)capacity * kAbsRowFloats * sizeof(float); }
 // gs_densify_device: the thresholds of gs_densify_params, the caller's arrays and the context's scratch
 struct DensifyRule {
     float grad_threshold, split_scale, prune_opacity, prune_scale, prune_radius;

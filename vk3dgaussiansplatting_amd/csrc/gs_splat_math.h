@@ -102,7 +102,8 @@ __device__ __forceinline__ float logit_opacity(float o) {
 
 // The first COLS columns of splat g's rows (BackwardBuffers::rows) summed in slot order, from 0.0f, over the slots below the
 // capacity; zero for a splat that emits nothing in this frame (SplatCounts::of).  Only the summed columns are read.
-template <int COLS>
+// STRIDE: the floats of a row -- kRowFloats, or kAbsRowFloats for the pairs of BackwardBuffers::abs_rows.
+template <int STRIDE = kRowFloats, int COLS>
 __device__ __forceinline__ void splat_row_sum(const SplatCounts& counts, const uint32_t* __restrict__ offsets,
                                               const float* __restrict__ rows, uint32_t g, uint32_t capacity,
                                               float (&acc)[COLS]) {
@@ -112,7 +113,7 @@ __device__ __forceinline__ void splat_row_sum(const SplatCounts& counts, const u
     const uint64_t e = o + counts.of(g);
     const uint64_t stop = e < capacity ? e : capacity;
     for (uint64_t s = o; s < stop; ++s) {
-        const float* r = rows + s * kRowFloats;
+        const float* r = rows + s * STRIDE;
 #pragma unroll
         for (int k = 0; k < COLS; ++k) acc[k] += r[k];
     }

@@ -127,9 +127,18 @@ int backward_prepare(gs_ctx* c, const char* who, bool band_ok = true) {
     return GS_OK;
 }
 
-// The last frame as the backward launchers take it
+// gs_set_abs_gradients is on and a gs_backward* form is about to run its blend: the pairs' scratch of the first such call
+int abs_rows_prepare(gs_ctx* c, const char* who) {
+    if (!c->abs_gradients || c->bwd.abs_rows) return GS_OK;
+    const hipError_t e = c->bwd_mem.alloc(c->bwd.abs_rows, backward_abs_row_bytes(c->capacity));
+    return e == hipSuccess ? GS_OK : refuse(c, who, hipGetErrorString(e), GS_ERR_HIP);
+}
+
+// The last frame as the backward launchers take it; bb.abs_rows only while the switch is on (launch_blend goes by it)
 BackwardFrame backward_frame(const gs_ctx* c) {
-    return BackwardFrame{c->last.fp, c->scene, c->scratch, c->sort.id[c->last.sorted_index], c->ranges, c->bwd};
+    BackwardFrame f{c->last.fp, c->scene, c->scratch, c->sort.id[c->last.sorted_index], c->ranges, c->bwd};
+    if (!c->abs_gradients) f.bb.abs_rows = nullptr;
+    return f;
 }
 
 // Host gradients onto the device (bwd_host_in, allocated on first use), enqueued on the context's stream: the two host
@@ -192,7 +201,23 @@ int backward_visible_refusals(gs_ctx* c, const char* who, const float* grad_rgba
     if (!grad_rgba32f) return refuse(c, who, "null gradient pointer");
     if (!count_out) return refuse(c, who, "null count_out");
     if (int r = check_row_arrays(c, who, max_rows, {ids_out, grad_rows_out}, "ids_out or grad_rows_out")) return r;
-    return backward_prepare(c, who);
+    if (int r = backward_prepare(c, who)) return r;
+    return abs_rows_prepare(c, who);
+}
+
+// gs_abs_screen_gradient_device / gs_densify_stats_abs_device: what gs_densify_stats_device refuses of the context, in its
+// order and words, then the blend that left the pairs
+int abs_gradient_refusals(gs_ctx* c, const char* who, bool band_ok) {
+    if (int r = backward_prepare(c, who, band_ok)) return r;
+    if (!c->last.has_backward) return refuse(c, who, "no gs_backward* on this frame");
+    if (!c->last.has_abs_backward) return refuse(c, who, "no gs_backward* on this frame with gs_set_abs_gradients on");
+    return GS_OK;
+}
+
+AbsGradArgs abs_gradient_args(const gs_ctx* c, const uint32_t* ids, const uint32_t* count, uint32_t max_rows, float* out) {
+    const FrameParams& fp = c->last.fp;
+    return AbsGradArgs{ids, count, max_rows, c->n, splat_counts_of(c->scratch, fp), c->bwd.scan.offsets, c->bwd.abs_rows,
+                       fp.capacity, fp.width, fp.height, out};
 }
 
 // ---- gs_photometric_loss*
@@ -480,10 +505,20 @@ int gs_set_antialias(gs_ctx* c, uint32_t enable) {
     return GS_OK;
 }
 
+// A host flag and nothing else: what a gs_backward* form enqueues from now on.  The pairs a blend has left stay those of
+// their frame (LastFrame::has_abs_backward); a frame is not touched.
+int gs_set_abs_gradients(gs_ctx* c, uint32_t enable) {
+    if (!c) return GS_ERR_INVALID;
+    if (enable > 1u) return refuse(c, __func__, "enable must be 0 or 1");
+    c->abs_gradients = enable != 0u;
+    return GS_OK;
+}
+
 int gs_backward_device(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, float* grad_records) {
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");
     if (int r = backward_prepare(c, __func__)) return r;
+    if (int r = abs_rows_prepare(c, __func__)) return r;
     return enqueue_backward(c, __func__, grad_rgba32f, grad_depth, grad_records);
 }
 
@@ -491,6 +526,7 @@ int gs_backward(gs_ctx* c, const float* grad_rgba32f, const float* grad_depth, f
     if (!c) return GS_ERR_INVALID;
     if (!grad_rgba32f || !grad_records) return refuse(c, __func__, "null gradient pointer");
     if (int r = backward_prepare(c, __func__)) return r;
+    if (int r = abs_rows_prepare(c, __func__)) return r;
     const size_t bytes = (size_t)c->n * GS_GAUSSIAN_RECORD_BYTES;
     if (!c->bwd_host_out) HIP_TRY(c, c->bwd_mem.alloc(c->bwd_host_out, bytes));
     if (int r = stage_host_grads(c, grad_rgba32f, grad_depth)) return r;
@@ -654,6 +690,27 @@ int gs_densify_stats_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* 
     const DensifyStatsArgs a{ids_dev, count_dev, max_rows, n, splat_counts_of(c->scratch, c->last.fp), c->bwd.scan.offsets, c->bwd.rows,
                              c->scratch.raster, fp.capacity, fp.width, fp.height, grad_accum, seen, max_radius};
     launch_densify_stats(a, c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_abs_screen_gradient_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows,
+                                  float* abs_out) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = check_row_arrays(c, __func__, max_rows, {ids_dev, count_dev, abs_out}, "ids, count or abs_out")) return r;
+    if (int r = abs_gradient_refusals(c, __func__, true)) return r;      // a sum of absolute terms over pixels: it adds up over bands
+    if (!max_rows) return GS_OK;
+    launch_abs_screen_gradient(abs_gradient_args(c, ids_dev, count_dev, max_rows, abs_out), c->stream);
+    return check_launch(c, __func__);
+}
+
+int gs_densify_stats_abs_device(gs_ctx* c, const uint32_t* ids_dev, const uint32_t* count_dev, uint32_t max_rows, uint32_t n,
+                                float* grad_accum_abs) {
+    if (!c) return GS_ERR_INVALID;
+    if (int r = check_row_arrays(c, __func__, max_rows, {ids_dev, count_dev, grad_accum_abs}, "ids, count or grad_accum_abs")) return r;
+    if (int r = abs_gradient_refusals(c, __func__, false)) return r;     // a norm per frame: no sum over bands
+    if (n != c->n) return refuse(c, __func__, "n differs from the scene's");
+    if (!max_rows) return GS_OK;
+    launch_densify_stats_abs(abs_gradient_args(c, ids_dev, count_dev, max_rows, grad_accum_abs), c->stream);
     return check_launch(c, __func__);
 }
 

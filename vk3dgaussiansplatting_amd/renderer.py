@@ -511,6 +511,12 @@ class Renderer:
         self._ctx.check(_lib.lib().gs_set_antialias(self._ctx.handle, 1 if enable else 0))
         self.antialias = bool(enable)
 
+    def setAbsGradients(self, enable: bool = True):
+        """gs_set_abs_gradients: with it on, every backward* also leaves, per list element, the sums over its tile's pixels
+        of |dL_p/dsx| and |dL_p/dsy| (the AbsGS statistic) in the context's scratch, 8 bytes per list element of capacity;
+        absScreenGradientDevice and densifyStatsAbsDevice read them.  What backward* returns does not change by a bit."""
+        self._ctx.check(_lib.lib().gs_set_abs_gradients(self._ctx.handle, 1 if enable else 0))
+
     @staticmethod
     def _camera_args(cam: Camera):
         """view, proj, pos and sh_mode of a Camera, as _launch takes them."""
@@ -824,6 +830,21 @@ class Renderer:
         Enqueued on the context's stream without waiting."""
         self._ctx.check(_lib.lib().gs_densify_stats_device(self._ctx.handle, _vp(ids_ptr), _vp(count_ptr), int(max_rows), int(n),
                                                            _vp(grad_accum_ptr), _vp(seen_ptr), _vp(max_radius_ptr)))
+
+    def absScreenGradientDevice(self, ids_ptr: int, count_ptr: int, max_rows: int, abs_out_ptr: int):
+        """abs_out[i] (float32 (max_rows, 2) on the device) = the sums of |dL_p/dsx| and |dL_p/dsy| over the pixels that blend
+        splat ids[i], i < min(count, max_rows), in pixel units, from the last backward* run with setAbsGradients on; (0, 0)
+        for an id >= n.  A band renderer with setBandGradients on gives the partial sums of its pixels, which add up over
+        bands.  Enqueued on the context's stream without waiting."""
+        self._ctx.check(_lib.lib().gs_abs_screen_gradient_device(self._ctx.handle, _vp(ids_ptr), _vp(count_ptr), int(max_rows),
+                                                                 _vp(abs_out_ptr)))
+
+    def densifyStatsAbsDevice(self, ids_ptr: int, count_ptr: int, max_rows: int, n: int, grad_accum_abs_ptr: int):
+        """grad_accum_abs (float32 of n, the caller's) += the norm of the absolute pair in NDC units, for the ids
+        densifyStatsDevice takes and beside it (seen and max_radius stay with that call).  Enqueued on the context's stream
+        without waiting."""
+        self._ctx.check(_lib.lib().gs_densify_stats_abs_device(self._ctx.handle, _vp(ids_ptr), _vp(count_ptr), int(max_rows), int(n),
+                                                               _vp(grad_accum_abs_ptr)))
 
     def densifyDevice(self, records_ptr: int, m_ptr: int | None, v_ptr: int | None, n: int, grad_accum_ptr: int, seen_ptr: int,
                       max_radius_ptr: int, params: GsDensifyParams, records_out_ptr: int, m_out_ptr: int | None,
