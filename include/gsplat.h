@@ -217,6 +217,15 @@ typedef struct gs_scene_info {
                                                              of smaller digits).  GS_ERR_INVALID unless the last frame took that
                                                              path: GS_SORT_RADIX4 with a Count launch per pass, record_timings < 2,
                                                              every tile row, no overflow */
+#define GS_BUF_BACKWARD_ROWS 16 /* float[N][10]              what the per-splat chain of the last gs_backward* / gs_backward_visible*
+                                                             on this context consumed: per splat the sum over its list elements of
+                                                             the blend's derivatives, in the order and with the bits the chain
+                                                             added them.  Columns: dL/d of the screen position (sx, sy), of the
+                                                             inverse 2-D covariance (ix, iy, iz), of the colour (r, g, b), of the
+                                                             raster opacity and of the view depth.  All zero for a splat that is
+                                                             not in the list.  A band context (gs_set_band_gradients): the band's
+                                                             partial sums.  GS_ERR_INVALID ("no gs_backward* on this frame") until
+                                                             a gs_backward* form has run on the last frame */
 
 /* GS_API_VERSION of the library that is actually loaded: compare with the header's before anything else
  * (gsplat.hpp and the Python binding do). */

@@ -18,7 +18,8 @@ from ._lib import (GS_OK, GS_WARN_OVERFLOW, GS_RENDER_EXACT, GS_RENDER_FAST, GS_
                    GsInitParams, default_init_params,
                    BUF_SORTED_TILE, BUF_SORTED_DEPTH, BUF_SORTED_ID, BUF_RANGES, BUF_COLOR, BUF_COV,
                    BUF_COUNT, BUF_UNSORTED_TILE, BUF_UNSORTED_DEPTH, BUF_UNSORTED_ID, BUF_IMAGE,
-                   BUF_RASTER_OPACITY, BUF_WAVE_WROTE, BUF_BAND_BLOCKS, BUF_TILE_ORDER, BUF_PASS0_OFFSETS)
+                   BUF_RASTER_OPACITY, BUF_WAVE_WROTE, BUF_BAND_BLOCKS, BUF_TILE_ORDER, BUF_PASS0_OFFSETS,
+                   BUF_BACKWARD_ROWS)
 from .renderer import (Camera, GpuSort, GsplatError, PlyScene, RadixSort, RadixSort8, Renderer, ResourceManager,
                        Scene, SimpleTestGaussiansScene, SphericalHarmonicsMode, TestSortScene,
                        default_adam_params, makeGaussian, saveImage, savePpm, write_ply)

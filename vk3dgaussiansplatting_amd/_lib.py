@@ -40,6 +40,7 @@ GS_OUTPUT_RGBA32F, GS_OUTPUT_DEPTH = 1, 2   # gs_set_outputs mask bits / gs_read
 BUF_RASTER_OPACITY = 11
 BUF_WAVE_WROTE, BUF_BAND_BLOCKS, BUF_TILE_ORDER = 12, 13, 14   # the work the last frame skipped (include/gsplat.h)
 BUF_PASS0_OFFSETS = 15      # the scanned digit rows of a frame whose k_emit did pass 0 of the depth sort
+BUF_BACKWARD_ROWS = 16      # float[N][10]: the summed rows the per-splat chain of the last gs_backward* consumed
 
 RECORD_BYTES = 336
 

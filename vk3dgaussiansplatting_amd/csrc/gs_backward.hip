@@ -238,6 +238,27 @@ __global__ __launch_bounds__(256) void k_bwd_rowsum_chain(const FrameParams fp, 
     bwd_chain<false>(fp, scene, g, any, row, reinterpret_cast<float4*>(out + (size_t)i * kRecordFloats), nullptr);
 }
 
+// gs_debug_read(GS_BUF_BACKWARD_ROWS): the row k_bwd_rowsum_chain handed bwd_chain for splat g (the same splat_row_sum, hence
+// the same bits), as out[g][kRowFloats]; zeros for a splat that is not in the list.  Nothing of a backward launches it.
+__global__ __launch_bounds__(256) void k_bwd_row_sums(uint32_t n, uint32_t capacity, const SplatCounts counts,
+                                                       const uint32_t* __restrict__ offsets,
+                                                       const float* __restrict__ rows, float* __restrict__ out) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= n) return;
+    float row[kRowFloats];
+#pragma unroll
+    for (int k = 0; k < kRowFloats; ++k) row[k] = 0.0f;
+    if (counts.of(g) != 0u) splat_row_sum(counts, offsets, rows, g, capacity, row);
+#pragma unroll
+    for (int k = 0; k < kRowFloats; ++k) out[(size_t)g * kRowFloats + k] = row[k];
+}
+
+void launch_backward_row_sums(const BackwardFrame& f, float* out, hipStream_t stream) {
+    const uint32_t n = f.fp.num_gaussians;
+    hipLaunchKernelGGL(k_bwd_row_sums, dim3(backward_blocks(n)), dim3(256), 0, stream, n, f.fp.capacity,
+                       splat_counts_of(f.sc, f.fp), f.bb.scan.offsets, f.bb.rows, out);
+}
+
 void launch_slot_offsets(const SplatCounts& counts, uint32_t n, const SplatScan& scan, hipStream_t stream) {
     launch_splat_scan(BwdSource<false>{counts, nullptr, nullptr, 0u}, n, scan, nullptr, stream);
 }

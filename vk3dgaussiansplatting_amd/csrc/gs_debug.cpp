@@ -230,6 +230,24 @@ int gs_debug_read(gs_ctx* c, int which, void* dst, size_t bytes) {
             std::memcpy(dst, rows.data(), bytes);
             return GS_OK;
         }
+        case GS_BUF_BACKWARD_ROWS: {
+            // what the chain of the last gs_backward* consumed: the rows of the blend summed per splat by the chain's own
+            // splat_row_sum (k_bwd_row_sums, gs_backward.hip), launched here and nowhere else.  has_backward: bwd.rows and
+            // bwd.scan.offsets are this frame's (a new frame, an upload or a change of the tile rows clears it)
+            if (!c->last.has_backward) return fail(c, GS_ERR_INVALID, "gs_debug_read: no gs_backward* on this frame");
+            const size_t need = (size_t)c->n * kRowFloats * sizeof(float);
+            if (bytes > need) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");
+            float* dev = nullptr;
+            HIP_TRY(c, hipMalloc((void**)&dev, need));
+            const BackwardFrame f{c->last.fp, c->scene, c->scratch, c->sort.id[si], c->ranges, c->bwd};
+            launch_backward_row_sums(f, dev, c->stream);
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess && bytes) e = hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost);
+            (void)hipFree(dev);
+            HIP_TRY(c, e);
+            return GS_OK;
+        }
         default: return fail(c, GS_ERR_INVALID, "gs_debug_read: unknown buffer id");
     }
     if (bytes > avail) return fail(c, GS_ERR_INVALID, "gs_debug_read: size exceeds buffer");

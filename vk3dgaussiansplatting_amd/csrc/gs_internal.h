@@ -419,6 +419,10 @@ void launch_backward_visible_rows(const BackwardFrame& f, const float* grad_rgba
 // The slot offsets alone (row 0 of the scan, what launch_backward runs first): scan.offsets[g] = the first slot of splat g.
 // Over the buffers of a backward's scan it rewrites the values that are there and leaves V and |V| alone.
 void launch_slot_offsets(const SplatCounts& counts, uint32_t n, const SplatScan& scan, hipStream_t stream);
+// gs_debug_read(GS_BUF_BACKWARD_ROWS): out[N][kRowFloats] (device) = per splat the sum of its rows in bb.rows exactly as
+// k_bwd_rowsum_chain adds them (the input of bwd_chain), zeros for a splat outside the list.  Needs bb.scan.offsets and
+// bb.rows of a launch_backward* on this frame.
+void launch_backward_row_sums(const BackwardFrame& f, float* out, hipStream_t stream);
 // gs_contrib_device (gs_contrib.hip): a row {sum, max, count} of the blend weights of one list element, in its slot
 constexpr int kContribRowWords = 3;
 inline size_t contrib_row_bytes(uint32_t capacity) { return (size_t)capacity * kContribRowWords * sizeof(uint32_t); }

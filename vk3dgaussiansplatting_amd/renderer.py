@@ -603,6 +603,8 @@ class Renderer:
             a = np.zeros(info.rows_owned * info.tiles_x, dtype=np.uint32)
         elif which == _lib.BUF_PASS0_OFFSETS:    # the rows of the blocks, then the sixteen digit bases
             a = np.zeros(((info.num_gaussians + 255) // 256 + 1, 16), dtype=np.uint32)
+        elif which == _lib.BUF_BACKWARD_ROWS:    # dsx, dsy, dix, diy, diz, dcol[3], dop, dz per splat (bwd_chain's row)
+            a = np.zeros((info.num_gaussians, 10), dtype=np.float32)
         elif which == _lib.BUF_BAND_BLOCKS:      # word 0 is the count: read it, then the records behind it
             cnt = np.zeros(1, dtype=np.uint32)
             self._ctx.check(L.gs_debug_read(self._ctx.handle, which, _p(cnt), 4))
