@@ -1,8 +1,8 @@
 """Absolute screen gradients (include/gsplat.h, gs_set_abs_gradients), on the CPU: the float64 reference of the AbsGS pair
--- forward64_screen of tests/test_densify_cpu.py with one zero offset per (list element, pixel) instead of one per splat, so
-that the gradient of the offsets holds the per-pixel terms -- the proof that this reference may be trusted, and the designed
-scenes tests/test_absgrad_gpu.py runs on the MI355X (cancellation, one pixel, the staging batch edges, the early-out over
-stale scratch, a truncated list), each checked here for being what it claims."""
+-- the tile walk and blend of tests/frame64.py with one zero offset per (list element, pixel) instead of test_densify_cpu's
+one per splat, so that the gradient of the offsets holds the per-pixel terms -- the proof that this reference may be trusted,
+and the designed scenes tests/test_absgrad_gpu.py runs on the MI355X (cancellation, one pixel, the staging batch edges, the
+early-out over stale scratch, a truncated list), each checked here for being what it claims."""
 import ctypes as C
 import functools
 
@@ -11,8 +11,8 @@ import pytest
 
 import vk3dgaussiansplatting_amd as gs
 from test_outputs_cpu import known_answer_scene, load_scene, oracle_params
-from test_backward_cpu import (_sh_basis, check_truncated, frame_decisions, frozen_of, list_offsets, raster32, screen_splat,
-                               truncated_scene)
+from test_backward_cpu import check_truncated, frozen_of, list_offsets, screen_splat, truncated_scene
+from frame64 import frame_decisions, live_of, pair_terms, raster32, splat_values, weights
 from test_densify_cpu import screen_gradient, screen_norm
 
 torch = pytest.importorskip("torch")
@@ -21,121 +21,29 @@ F = np.float32
 BATCH_COUNTS = (1, 63, 64, 65, 128, 129)          # kBwdBatch = 64: one batch part and full, two and three with a rest of 1
 
 
-def grads(h, w, seed=1):
-    """dL/dRGBA32F [h, w, 4] and dL/dDEPTH [h, w], float32 (weights of tests/test_backward_gpu.py)."""
-    rng = np.random.default_rng(seed)
-    return rng.standard_normal((h, w, 4)).astype(F), (0.1 * rng.standard_normal((h, w))).astype(F)
-
-
 # ---- the reference ----------------------------------------------------------------------------------------------------------
 
 def splat_values64(p, rec, ref, frozen=None, r32=None):
-    """The per-splat part of forward64_screen, restated: (sx, sy, ix, iy, iz, col [N, 3], opac, zview) in float64, the same
-    expressions in the same order (frozen splats: the float32 frame's values)."""
-    w, h = p.width, p.height
-    V = torch.tensor(np.array(p.view, np.float64).reshape(4, 4).T)
-    P = torch.tensor(np.array(p.proj, np.float64).reshape(4, 4).T)
-    cam = torch.tensor(np.array(p.cam_pos, np.float64))
-    pos = rec[:, 0:3]
-    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
-    vp = torch.cat([pos, ones], 1) @ V.T
-    q = vp @ P.T
-    ndc_x, ndc_y = q[:, 0] / q[:, 3], q[:, 1] / q[:, 3]
-    sx, sy = (ndc_x + 1.0) * 0.5 * w, (-ndc_y + 1.0) * 0.5 * h
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
-    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    Tm = J @ V[:3, :3]
-    S2 = Tm @ Sig @ Tm.transpose(1, 2)
-    a, b, c = S2[:, 0, 0] + 0.3, S2[:, 1, 0], S2[:, 1, 1] + 0.3
-    det = a * c - b * b
-    cov32 = ref["stage1"]["cov"]
-    live = torch.tensor((cov32[:, 0] * cov32[:, 2] - cov32[:, 1] * cov32[:, 1]) != 0)
-    det = torch.where(live, det, torch.ones_like(det))
-    ix, iy, iz = c / det, -b / det, a / det
-    dvec = pos - cam
-    dirs = dvec / torch.sqrt((dvec * dvec).sum(1, keepdim=True))
-    basis = _sh_basis(dirs)
-    sh = rec[:, 12:76].reshape(-1, 16, 4)[:, :, :3]
-    if p.sh_mode == 0:
-        col = (sh * basis[:, :, None]).sum(1) + 0.5
-    elif p.sh_mode == 1:
-        col = (sh[:, 1:] * basis[:, 1:, None]).sum(1) - 0.5 + 0.5
-    else:
-        col = sh[:, 0] * basis[:, 0:1] + 0.5
-    col = torch.clamp(col, min=0.0)
-    opac = torch.where(live, rec[:, 15], torch.zeros_like(det))
-    zview = -vp[:, 2]
-    if frozen is not None:
-        fz = torch.tensor(np.asarray(frozen, bool))
-        k = lambda name, t: torch.where(fz, torch.tensor(r32[name]), t)
-        sx, sy, ix, iy, iz, opac, zview = (k("sx", sx), k("sy", sy), k("ix", ix), k("iy", iy), k("iz", iz), k("op", opac),
-                                          k("z", zview))
-        col = torch.where(fz[:, None], torch.tensor(np.stack([r32["r"], r32["g"], r32["b"]], 1)), col)
-    return sx, sy, ix, iy, iz, col, opac, zview
+    """The per-splat part of forward64: (sx, sy, ix, iy, iz, col [N, 3], opac, zview) in float64, the columns of
+    frame64.splat_values (frozen splats: the float32 frame's values)."""
+    v, _ = splat_values(p, rec, live_of(ref), frozen=frozen, r32=r32)
+    return v[:, 0], v[:, 1], v[:, 2], v[:, 3], v[:, 4], v[:, 5:8], v[:, 8], v[:, 9]
 
 
 def abs_screen_gradient(p, aos, ref, flags, w_rgba, w_depth=None, frozen=None):
-    """(abs [N, 2], signed [N, 2]) in float64 of L = sum w_rgba * RGBA32F + sum w_depth * depth: the tile loop of
-    forward64_screen with a zero offset per (list element, pixel), a tensor [E, 256, 2] added to (sx, sy) of that element at
-    that pixel only.  Its gradient holds the per-pixel terms of dL/d(sx, sy); abs() of it, or the terms as they are, summed
-    over the 256 pixels and then over the elements of each splat.  A tile's pixels read the offsets of its own elements
-    alone, so the gradient is taken tile by tile (the rows of one [E, 256, 2] tensor, never held whole)."""
-    w, h = p.width, p.height
+    """(abs [N, 2], signed [N, 2]) in float64 of L = sum w_rgba * RGBA32F + sum w_depth * depth: frame64.pair_terms of width
+    2, a zero offset per (list element, pixel) added to (sx, sy) of that element at that pixel only.  Its gradient holds the
+    per-pixel terms of dL/d(sx, sy); abs() of it, or the terms as they are, summed over the 256 pixels and then over the
+    elements of each splat."""
     n = len(aos)
-    rec = torch.tensor(np.asarray(aos, np.float64))
     with torch.no_grad():
-        sx, sy, ix, iy, iz, col, opac, zview = splat_values64(p, rec, ref, frozen,
-                                                               raster32(p, aos, ref) if frozen is not None else None)
-    gw, gh = (w + 15) // 16, (h + 15) // 16
-    wimg = torch.zeros(gh * 16, gw * 16, 5, dtype=torch.float64)
-    wimg[:h, :w, :4] = torch.tensor(np.asarray(w_rgba, np.float64))
-    if w_depth is not None:
-        wimg[:h, :w, 4] = torch.tensor(np.asarray(w_depth, np.float64))
-    wtile = wimg.reshape(gh, 16, gw, 16, 5).permute(0, 2, 1, 3, 4).reshape(gh * gw, 256, 5)
-    ids = np.asarray(ref["id"], np.int64)
-    ranges = np.asarray(ref["ranges"]).reshape(-1, 2)
-    ly, lx = np.divmod(np.arange(256), 16)
+        vals, _ = splat_values(p, torch.tensor(np.asarray(aos, np.float64)), live_of(ref), frozen=frozen,
+                               r32=raster32(p, aos, ref) if frozen is not None else None)
     absum = torch.zeros(n, 2, dtype=torch.float64)
     signed = torch.zeros(n, 2, dtype=torch.float64)
-    for t in range(gw * gh):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        ty, tx = divmod(t, gw)
-        blended = np.flatnonzero(flags[s:e].any(1))
-        if not len(blended):
-            continue
-        e = s + int(blended[-1]) + 1
-        m = torch.tensor(flags[s:e].astype(bool))
-        g = torch.tensor(ids[s:e])
-        off = torch.zeros(e - s, 256, 2, dtype=torch.float64, requires_grad=True)
-        fpx = torch.tensor((tx * 16 + lx).astype(np.float64))[None, :]
-        fpy = torch.tensor((ty * 16 + ly).astype(np.float64))[None, :]
-        ex = (sx[g][:, None] + off[:, :, 0]) - fpx
-        ey = fpy - (sy[g][:, None] + off[:, :, 1])
-        f = -0.5 * (ix[g][:, None] * ex * ex + iz[g][:, None] * ey * ey) - iy[g][:, None] * ex * ey
-        f = torch.where(m, f, torch.zeros_like(f))
-        alpha = torch.where(m, opac[g][:, None] * torch.exp(f), torch.zeros_like(f))
-        Tx = torch.cumprod(torch.cat([torch.ones(1, 256, dtype=rec.dtype), 1.0 - alpha[:-1]], 0), 0)
-        wgt = Tx * alpha
-        chans = torch.cat([col[g], torch.ones(len(g), 1, dtype=rec.dtype), zview[g][:, None]], 1)
-        ((wgt.T @ chans) * wtile[t]).sum().backward()
-        absum.index_add_(0, g, off.grad.abs().sum(1))
-        signed.index_add_(0, g, off.grad.sum(1))
+    for g, grad in pair_terms(p, vals, ref, flags, w_rgba, w_depth, width=2):
+        absum.index_add_(0, g, grad.abs().sum(1))
+        signed.index_add_(0, g, grad.sum(1))
     return absum.numpy(), signed.numpy()
 
 
@@ -154,7 +62,7 @@ def test_the_reference_is_trusted(oracle_mod, tmp_path, scene):
     it exceeds twice the signed norm for more than 100 splats: the statistic is not the old one in disguise."""
     aos, w, h, p = _scene_reference(scene)
     ref, flags = frame_decisions(tmp_path, p, aos)
-    wr, wd = grads(h, w)
+    wr, wd = weights(h, w, 1)
     fz = frozen_of(scene.partition("@")[0], aos)
     frozen = fz if fz.any() else None
     ab, sg = abs_screen_gradient(p, aos, ref, flags, wr, wd, frozen)
@@ -188,14 +96,14 @@ def one_pixel_case(oracle):
     pixel (20, 14) alone (0.0077 there, 0.0036 at the nearest neighbour)."""
     w, h = 64, 48
     aos = np.stack([screen_splat(oracle, w, h, ONE_PIXEL_AT[0], ONE_PIXEL_AT[1], 2.0, 0.3, 0.008)]).astype(F)
-    return aos, w, h, grads(h, w, 3)
+    return aos, w, h, weights(h, w, 3)
 
 
 def batch_case(count):
     """`count` splats of opacity 0.02 on the camera axis, front to back: the two tiles along the centre's edge hold `count`
     entries each and no pixel stops early (0.98^129 = 0.074)."""
     aos, w, h = known_answer_scene([2.0 + 0.02 * k for k in range(count)], opacity=0.02)
-    return aos, w, h, grads(h, w, 4)
+    return aos, w, h, weights(h, w, 4)
 
 
 STOP_FRONT = 20
@@ -208,7 +116,7 @@ def early_out_case():
     aos, w, h = known_answer_scene([2.0 + 0.02 * k for k in range(129)], opacity=0.5)
     aos[:STOP_FRONT, 4:7] *= F(8.0)
     aos[STOP_FRONT:, 4:7] *= F(0.25)
-    return aos, w, h, grads(h, w, 5)
+    return aos, w, h, weights(h, w, 5)
 
 
 def case_reference(oracle, tmp_dir, aos, w, h, g):
@@ -263,7 +171,7 @@ def test_truncated_case(oracle_mod, tmp_path):
     """truncated_scene of tests/test_backward_cpu.py (64 x 64, 2500 splats, 34207 elements against a capacity of 32768): the
     splats wholly past the capacity have a zero pair in the reference, the straddling one a non-zero pair."""
     aos, w, h = truncated_scene()
-    p, ref, flags, ab, sg = case_reference(oracle_mod, tmp_path, aos, w, h, grads(h, w, 6))
+    p, ref, flags, ab, sg = case_reference(oracle_mod, tmp_path, aos, w, h, weights(h, w, 6))
     across, past = check_truncated(ref, flags)
     assert not ab[past].any() and ab[across].any() and np.count_nonzero(ab.any(1)) > 100
 

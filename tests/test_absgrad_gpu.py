@@ -12,13 +12,14 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, camera_params, load_scene
-from test_backward_cpu import check_truncated, frame_decisions, frozen_of, list_offsets, truncated_scene
+from test_backward_cpu import check_truncated, frozen_of, list_offsets, truncated_scene
 from test_train_chain_gpu import LAMBDA, bits, new_renderer
 from test_densify_cpu import screen_norm
 from test_densify_gpu import DEV, Frame, assert_norm, down, sentinels, up, zeros
 from test_band_backward_gpu import band_renderer, draw_band
 from test_absgrad_cpu import (BATCH_COUNTS, STOP_FRONT, abs_screen_gradient, batch_case, cancellation_case, case_reference,
-                              early_out_case, grads, one_pixel_case)
+                              early_out_case, one_pixel_case)
+from frame64 import frame_decisions, weights
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -205,7 +206,7 @@ def test_truncated_list(oracle_mod, tmp_path):
     """truncated_scene (34207 elements against a capacity of 32768): rows at or past the capacity contribute nothing -- the
     splats wholly past it have (0, 0) exactly and are listed all the same, the straddling splat sums its surviving rows."""
     aos, w, h = truncated_scene()
-    g = grads(h, w, 6)
+    g = weights(h, w, 6)
     f = designed_frame(aos, w, h, g)
     assert f.r.lastStatus == gs.GS_WARN_OVERFLOW
     got = f.per_splat()

@@ -1,22 +1,22 @@
 """Anti-aliased frames (include/gsplat.h, gs_set_antialias) on the CPU.  The oracle cannot draw one, so everything here leans
 on the equivalence the definition implies: the anti-aliased frame of records R is the plain frame of R' = R with every opacity
-multiplied by rho = sqrt(max(det S / det(S + 0.3 I), 2.5e-5)), S the 2-D covariance before its dilation.  rho64 is the float64
-torch restatement of that factor (differentiable in the records and in the view matrix); the composed reference builds the
-anti-aliased gradient from the plain frame's reference gradient at R' and the chain rule through rho64.  Trusted by: rho64
-against its own central differences, the composed reference against central differences of the oracle-drawn loss, the
-designed scene holding what it claims, and the resolution claim on oracle frames.  tests/test_antialias_gpu.py shares the
-helpers."""
+multiplied by rho = sqrt(max(det S / det(S + 0.3 I), 2.5e-5)), S the 2-D covariance before its dilation.  rho64 is that factor
+in float64 from the per-splat stage of tests/frame64.py (differentiable in the records and in the view matrix); the composed
+reference builds the anti-aliased gradient from the plain frame's reference gradient at R' and the chain rule through rho64.
+Trusted by: rho64 against its own central differences, the composed reference against central differences of the oracle-drawn
+loss, the designed scene holding what it claims, and the resolution claim on oracle frames.  tests/test_antialias_gpu.py
+shares the helpers."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from test_outputs_cpu import load_scene, oracle_params, reference_outputs
-from test_backward_cpu import frame_decisions, frozen_of, reference_gradient, screen_splat
+from test_backward_cpu import extreme_cloud, frozen_of, screen_splat
+from frame64 import FLOOR, camera_leaves, frame_decisions, reference_gradient, splat_values
 
 torch = pytest.importorskip("torch")
 
-FLOOR = float(np.float32(2.5e-5))          # kAntialiasFloor as the kernels hold it
 GEOMETRY = [0, 1, 2, 4, 5, 6, 8, 9, 10, 11]           # position, scale, rotation: the fields rho depends on
 
 # Largest relative deviation of rho32 (float32 NumPy) from rho64 over the compared splats of subpixel, ragged and ragged@pose,
@@ -30,37 +30,13 @@ def _view_tensor(p):
 
 
 def rho64(rec, view, p):
-    """(rho, r) of every record: forward64's projection of the 3-D covariance (test_backward_cpu.forward64, lines 123-148)
-    without the 0.3, r = det0 / det, rho = sqrt(clamp(r, min=FLOOR)).  rec: torch float64 [N, 84]; view: torch float64 [16],
-    column-major as gs_render takes it, or [N, 16], a copy of its own for every record; both may require grad."""
-    w, h = p.width, p.height
-    V = view.reshape(-1, 4, 4).transpose(1, 2)                            # V[.][r][c] = view[c * 4 + r]
-    pos = rec[:, 0:3]
-    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
-    vp = (V @ torch.cat([pos, ones], 1)[:, :, None])[:, :, 0]
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
-    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    T = J @ V[:, :3, :3]
-    S2 = T @ Sig @ T.transpose(1, 2)
-    a0, b0, c0 = S2[:, 0, 0], S2[:, 1, 0], S2[:, 1, 1]
-    det0 = a0 * c0 - b0 * b0
-    det = (a0 + 0.3) * (c0 + 0.3) - b0 * b0
-    ratio = det0 / det
-    return torch.sqrt(torch.clamp(ratio, min=FLOOR)), ratio
+    """(rho, r) of every record: r = det0 / det of frame64.splat_values, the 2-D covariance before its dilation against the
+    dilated one (no det == 0 rule, no cap), rho = sqrt(clamp(r, min=FLOOR)).  rec: torch float64 [N, 84]; view: torch float64
+    [16], column-major as gs_render takes it, or [N, 16], a copy of its own for every record; both may require grad."""
+    n = rec.shape[0]
+    V = view.reshape(-1, 4, 4).transpose(1, 2).expand(n, 4, 4)            # V[.][r][c] = view[c * 4 + r]
+    _, aux = splat_values(p, rec, np.ones(n, bool), cams=(V,) + camera_leaves(p, n)[1:])
+    return torch.sqrt(torch.clamp(aux["ratio_t"], min=FLOOR)), aux["ratio_t"]
 
 
 def rho64_numpy(p, aos):
@@ -141,18 +117,11 @@ def subpixel_scene(oracle):
 
 
 def load_antialias_scene(oracle, name):
-    """load_scene plus 'subpixel' and 'extreme' (test_backward_gpu.extreme_cloud): (aos, w, h, cam)."""
+    """load_scene plus 'subpixel' and 'extreme' (test_backward_cpu.extreme_cloud): (aos, w, h, cam)."""
     if name == "subpixel":
         return subpixel_scene(oracle)[:3] + ({},)
     if name == "extreme":
-        from vk3dgaussiansplatting_amd import synth
-        aos = synth.generate(400, 96, 64, -2.0, seed=23)                   # extreme_cloud, restated: that module needs a GPU mark
-        aos[0:40, 15] = 0.0
-        aos[40:80, 15] = 1.0
-        aos[80:100, 8:12] = 0.0
-        aos[100:120, 4:7] = 0.0
-        aos[120:130, 4] = 0.0
-        return aos, 96, 64, {}
+        return extreme_cloud() + ({},)
     return load_scene(name)
 
 

@@ -12,12 +12,13 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, assert_posed, camera_params
-from test_backward_cpu import frame_decisions, frozen_of
-from test_backward_gpu import CASES as BACKWARD_CASES, READ_FIELDS, UNREAD, compare_with_reference, weights
+from test_backward_cpu import frozen_of
+from test_backward_gpu import CASES as BACKWARD_CASES, READ_FIELDS, UNREAD, compare_with_reference
 from test_backward_camera_cpu import PROJ_CLIP_Z, VIEW_BOTTOM_ROW, camera_reference, masked as camera_masked
 from test_backward_camera_gpu import check_against
 from test_band_backward_gpu import contrib_into, set_band
-from test_antialias_cpu import (FLOOR, RHO32_DEVIATION, compared, composed_reference, load_antialias_scene, rho64_numpy)
+from test_antialias_cpu import RHO32_DEVIATION, compared, composed_reference, load_antialias_scene, rho64_numpy
+from frame64 import FLOOR, frame_decisions, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -74,8 +75,8 @@ def drawn_pair(oracle_mod, scene, sh_mode=0, **kw):
 
 
 def test_extreme_scene_is_the_one_of_test_backward_gpu(oracle_mod):
-    """'extreme' of load_antialias_scene (restated there for the CPU tests) is test_backward_gpu.extreme_cloud, bit for bit."""
-    from test_backward_gpu import extreme_cloud
+    """'extreme' of load_antialias_scene is the extreme_cloud test_backward_gpu draws, bit for bit."""
+    from test_backward_cpu import extreme_cloud
     aos, w, h, cam = load_antialias_scene(oracle_mod, "extreme")
     want, w2, h2 = extreme_cloud()
     assert (w, h, cam) == (w2, h2, {}) and np.array_equal(bits(aos), bits(want))

@@ -1,7 +1,7 @@
 """The float64 reference of the frame's camera gradients (include/gsplat.h, gs_backward_camera), on the CPU.
 
-forward64_cam is forward64 of tests/test_backward_cpu.py restated with per-splat camera leaves: every splat gets its own
-copy of the view matrix, the projection and the camera position.  The gradient of those leaves is then the per-splat
+forward64_cam is forward64 of tests/frame64.py on per-splat camera leaves (its `cams`): every splat gets its own copy of
+the view matrix, the projection and the camera position.  The gradient of those leaves is then the per-splat
 contribution C[g][35] to dL/dcamera; its column sums are the reference `want`, and S[k] = sum_g |C[g][k]| is the scale
 the GPU tests measure against (tests/test_backward_camera_gpu.py).  It is trusted by three checks here: its outputs equal
 forward64's, its gradient equals central differences of its own loss, and the translation identity ties it to the
@@ -17,7 +17,7 @@ import pytest
 from conftest import ROOT
 
 from test_outputs_cpu import assert_posed, load_scene, oracle_params
-from test_backward_cpu import _sh_basis, forward64, frame_decisions, reference_gradient
+from frame64 import camera_leaves, forward64, frame_decisions, loss_of, reference_gradient, weights
 
 torch = pytest.importorskip("torch")
 
@@ -26,114 +26,16 @@ VIEW_BOTTOM_ROW = [3, 7, 11, 15]          # of the 35 floats: the view matrix is
 PROJ_CLIP_Z = [18, 22, 26, 30]            # ... and no frame reads clip z
 
 
-def weights(h, w, seed=0):
-    """The loss weights of test_backward_gpu.weights (the same numbers for the same seed)."""
-    rng = np.random.default_rng(seed)
-    return rng.standard_normal((h, w, 4)).astype(np.float32), (0.1 * rng.standard_normal((h, w))).astype(np.float32)
-
-
-def camera_leaves(p, n):
-    """The frame's camera copied per splat: Vn [n, 4, 4] with Vn[g][r][c] = view[c * 4 + r], Pn likewise, camn [n, 3]."""
-    V = torch.tensor(np.array(p.view, np.float64).reshape(4, 4).T)
-    P = torch.tensor(np.array(p.proj, np.float64).reshape(4, 4).T)
-    cam = torch.tensor(np.array(p.cam_pos, np.float64))
-    return V.expand(n, 4, 4).clone(), P.expand(n, 4, 4).clone(), cam.expand(n, 3).clone()
-
-
 def forward64_cam(p, rec, ref, flags, Vn, Pn, camn):
-    """forward64 (tests/test_backward_cpu.py) with the camera of splat g taken from Vn[g], Pn[g], camn[g]: rgba32f
-    [H, W, 4] and depth [H, W] in float64, with the float32 frame's decisions."""
-    w, h = p.width, p.height
-    pos = rec[:, 0:3]
-    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
-    vp = torch.einsum("nrc,nc->nr", Vn, torch.cat([pos, ones], 1))
-    q = torch.einsum("nrc,nc->nr", Pn, vp)
-    ndc_x, ndc_y = q[:, 0] / q[:, 3], q[:, 1] / q[:, 3]
-    sx, sy = (ndc_x + 1.0) * 0.5 * w, (-ndc_y + 1.0) * 0.5 * h
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
-    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    T = J @ Vn[:, :3, :3]
-    S2 = T @ Sig @ T.transpose(1, 2)
-    a, b, c = S2[:, 0, 0] + 0.3, S2[:, 1, 0], S2[:, 1, 1] + 0.3
-    det = a * c - b * b
-    cov32 = ref["stage1"]["cov"]
-    live = torch.tensor((cov32[:, 0] * cov32[:, 2] - cov32[:, 1] * cov32[:, 1]) != 0)
-    det = torch.where(live, det, torch.ones_like(det))
-    ix, iy, iz = c / det, -b / det, a / det
-    dvec = pos - camn
-    dirs = dvec / torch.sqrt((dvec * dvec).sum(1, keepdim=True))
-    basis = _sh_basis(dirs)
-    sh = rec[:, 12:76].reshape(-1, 16, 4)[:, :, :3]
-    if p.sh_mode == 0:
-        col = (sh * basis[:, :, None]).sum(1) + 0.5
-    elif p.sh_mode == 1:
-        col = (sh[:, 1:] * basis[:, 1:, None]).sum(1) - 0.5 + 0.5
-    else:
-        col = sh[:, 0] * basis[:, 0:1] + 0.5
-    col = torch.clamp(col, min=0.0)
-    opac = torch.where(live, rec[:, 15], torch.zeros_like(det))
-    zview = -vp[:, 2]
-    gw, gh = (w + 15) // 16, (h + 15) // 16
-    drawn, outs = [], []
-    ids = np.asarray(ref["id"], np.int64)
-    ranges = np.asarray(ref["ranges"]).reshape(-1, 2)
-    ly, lx = np.divmod(np.arange(256), 16)
-    for t in range(gw * gh):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        ty, tx = divmod(t, gw)
-        blended = np.flatnonzero(flags[s:e].any(1))
-        if not len(blended):
-            continue
-        e = s + int(blended[-1]) + 1
-        m = torch.tensor(flags[s:e].astype(bool))
-        g = torch.tensor(ids[s:e])
-        fpx = torch.tensor((tx * 16 + lx).astype(np.float64))[None, :]
-        fpy = torch.tensor((ty * 16 + ly).astype(np.float64))[None, :]
-        ex = sx[g][:, None] - fpx
-        ey = fpy - sy[g][:, None]
-        f = -0.5 * (ix[g][:, None] * ex * ex + iz[g][:, None] * ey * ey) - iy[g][:, None] * ex * ey
-        f = torch.where(m, f, torch.zeros_like(f))
-        alpha = torch.where(m, opac[g][:, None] * torch.exp(f), torch.zeros_like(f))
-        Tx = torch.cumprod(torch.cat([torch.ones(1, 256, dtype=rec.dtype), 1.0 - alpha[:-1]], 0), 0)
-        wgt = Tx * alpha
-        chans = torch.cat([col[g], torch.ones(len(g), 1, dtype=rec.dtype), zview[g][:, None]], 1)
-        drawn.append(t)
-        outs.append(wgt.T @ chans)
-    img = torch.zeros(gw * gh, 256, 5, dtype=rec.dtype)
-    if drawn:
-        img = img.index_copy(0, torch.tensor(drawn, dtype=torch.int64), torch.stack(outs))
-    img = img.reshape(gh, gw, 16, 16, 5).permute(0, 2, 1, 3, 4).reshape(gh * 16, gw * 16, 5)[:h, :w]
-    return img[..., :4], img[..., 4]
-
-
-def loss_of(rgba, dep, w_rgba, w_depth):
-    loss = (rgba * torch.tensor(np.asarray(w_rgba, np.float64))).sum()
-    if w_depth is not None:
-        loss = loss + (dep * torch.tensor(np.asarray(w_depth, np.float64))).sum()
-    return loss
+    """forward64 with the camera of splat g taken from Vn[g], Pn[g], camn[g] (laid out as camera_leaves)."""
+    return forward64(p, rec, ref, flags, cams=(Vn, Pn, camn))
 
 
 def camera_contributions(p, aos, ref, flags, w_rgba, w_depth=None):
     """C [N, 35] (float64): the contribution of every splat to dL/dview (column-major, as gs_render* takes the matrix),
     dL/dproj and dL/dcam_pos of L = sum w_rgba * RGBA32F + sum w_depth * depth, unmasked."""
     rec = torch.tensor(np.asarray(aos, np.float64))
-    Vn, Pn, camn = (t.requires_grad_(True) for t in camera_leaves(p, len(aos)))
+    Vn, Pn, camn = camera_leaves(p, len(aos), grad=True)
     rgba, dep = forward64_cam(p, rec, ref, flags, Vn, Pn, camn)
     loss_of(rgba, dep, w_rgba, w_depth).backward()
     n = len(aos)

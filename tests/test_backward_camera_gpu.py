@@ -23,7 +23,9 @@ from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, assert_posed, camera_params, known_answer_scene, load_scene
 from test_backward_cpu import batch_edge_scene, padded_cloud, truncated_scene
-from test_backward_gpu import KERNELS, extreme_cloud, weights
+from test_backward_gpu import KERNELS
+from test_backward_cpu import extreme_cloud
+from frame64 import weights
 from test_backward_camera_cpu import CAMERA_FLOATS, PROJ_CLIP_Z, VIEW_BOTTOM_ROW, camera_reference
 from test_loss_cpu import BG
 

@@ -1,9 +1,8 @@
-"""The float64 reference of the frame's gradients (include/gsplat.h, gs_backward), on the CPU: the EXACT frame restated in
-torch -- projection, 2-D covariance and its inverse, SH colour, the blend -- with the discrete decisions of the float32 frame
-held fixed (which entries each pixel blends and where it stops: tests/host/blend_trace_ref.c, the loop of
-blend_outputs_ref.c that reproduces the oracle's frame byte for byte), differentiated by torch.autograd.  It is trusted by
-two checks here: its RGBA32F and depth match the float32 C restatement to 1e-5, and its gradients match its own central
-differences.  tests/test_backward_gpu.py compares the GPU's gradients with it.  Helpers are shared with that file.
+"""The float64 reference of the frame's gradients (include/gsplat.h, gs_backward), on the CPU: what makes tests/frame64.py
+trusted, and the scenes of the gradient tests.  frame64.forward64 is the EXACT frame restated in torch with the float32
+frame's decisions held fixed; two checks here stand behind it: its RGBA32F and depth match the float32 C restatement to
+1e-5, and its gradients match its own central differences.  tests/test_backward_gpu.py compares the GPU's gradients with it.
+Helpers are shared with that file.
 
 At full size (13 M to 33 M list elements) the reference is evaluated on sampled tiles: with loss weights that are zero
 outside a set of tiles the gradient follows from those tiles' lists alone, so sampled_reference_gradient runs forward64
@@ -22,203 +21,9 @@ import pytest
 from conftest import ROOT
 
 from test_outputs_cpu import SCENES, POSES, assert_posed, in_front_of, load_scene, oracle_params, reference_outputs
+from frame64 import forward64, frame_decisions, ptr, raster32, reference_gradient, trace_lib
 
 torch = pytest.importorskip("torch")
-
-_TRACE = {}
-
-
-def trace_lib(tmp_dir):
-    if "lib" not in _TRACE:
-        import oracle
-        oracle.lib()
-        so = os.path.join(str(tmp_dir), "libblend_trace_ref.so")
-        odir = os.path.join(ROOT, "oracle")
-        build = subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-I", odir, "-o", so,
-                                os.path.join(ROOT, "tests", "host", "blend_trace_ref.c"), "-L", odir, "-lgs_oracle",
-                                f"-Wl,-rpath,{odir}", "-lm"], capture_output=True, text=True)
-        assert build.returncode == 0, build.stderr[-2000:]
-        R = C.CDLL(so)
-        R.gsb_blend_trace.restype = None
-        _TRACE["lib"] = R
-    return _TRACE["lib"]
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def frame_decisions(tmp_dir, p, aos, ref=None):
-    """The oracle's frame and the blend decisions of the float32 frame: flags [E, 256] (entry e adds its colour to tile
-    pixel ly * 16 + lx: 1, or 2 where the pixel stops on it, nextT < 1e-4)."""
-    import oracle
-    aos = np.ascontiguousarray(aos, dtype=np.float32)
-    if ref is None:
-        ref = oracle.full_pipeline(p, aos)
-    e = int(ref["e"])
-    flags = np.zeros((max(e, 1), 256), np.uint8)
-    trace_lib(tmp_dir).gsb_blend_trace(C.byref(p), _ptr(aos), _ptr(np.ascontiguousarray(ref["stage1"]["color"])),
-                                       _ptr(np.ascontiguousarray(ref["stage1"]["cov"])),
-                                       _ptr(np.ascontiguousarray(ref["id"], dtype=np.uint32)),
-                                       _ptr(np.ascontiguousarray(ref["ranges"], dtype=np.uint32)), _ptr(flags))
-    return ref, flags[:e]
-
-
-def _sh_basis(d):
-    """Common.glsl:94-138 on directions d [M, 3] (float64 torch)."""
-    X, Y, Z = -d[:, 0], -d[:, 1], d[:, 2]
-    S1, C1 = 2.0 * X * Y, X * X - Y * Y
-    S2, C2 = X * S1 + Y * C1, X * C1 - Y * S1
-    Z2 = Z * Z
-    tc = -2.285228997322329 * Z2 + 0.4570457994644658
-    b = [torch.full_like(X, 0.2820947917738781), -0.48860251190292 * Y, 0.4886025119029199 * Z, -0.48860251190292 * X,
-         0.5462742152960395 * S1, -1.092548430592079 * Z * Y, 0.9461746957575601 * Z2 - 0.31539156525252,
-         -1.092548430592079 * Z * X, 0.5462742152960395 * C1, -0.5900435899266435 * S2, 1.445305721320277 * Z * S1,
-         tc * Y, Z * (1.865881662950577 * Z2 - 1.119528997770346), tc * X, 1.445305721320277 * Z * C1,
-         -0.5900435899266435 * C2]
-    return torch.stack(b, dim=1)
-
-
-def raster32(p, aos, ref):
-    """Per splat, the float32 values the frame blends (as the C restatement computes them): sx, sy, ix, iy, iz, colour,
-    alpha factor, z -- float64 arrays of float32 values."""
-    f = np.float32
-    a = np.asarray(aos, np.float32)
-    view, proj = np.array(p.view, np.float32), np.array(p.proj, np.float32)
-
-    def mul(m, v):
-        out = []
-        for r in range(4):
-            acc = m[r] * v[0]
-            for k in range(1, 4):
-                acc = acc + m[k * 4 + r] * v[k]
-            out.append(acc)
-        return out
-
-    one = np.ones(len(a), np.float32)
-    pv = mul(view, [a[:, 0], a[:, 1], a[:, 2], one])
-    q = mul(proj, pv)
-    x, y = q[0] / q[3], -(q[1] / q[3])
-    sx, sy = ((x + f(1)) * f(0.5)) * f(p.width), ((y + f(1)) * f(0.5)) * f(p.height)
-    cov = np.asarray(ref["stage1"]["cov"], np.float32)
-    det = cov[:, 0] * cov[:, 2] - cov[:, 1] * cov[:, 1]
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        inv = np.where(det != 0, f(1) / det, f(0)).astype(np.float32)
-    ix, iy, iz = cov[:, 2] * inv, -cov[:, 1] * inv, cov[:, 0] * inv
-    col = np.asarray(ref["stage1"]["color"], np.float32)
-    op = np.where(det != 0, col[:, 3], f(0))
-    return {k: v.astype(np.float64) for k, v in dict(sx=sx, sy=sy, ix=ix, iy=iy, iz=iz, r=col[:, 0], g=col[:, 1], b=col[:, 2],
-                                                       op=op, z=-pv[2]).items()}
-
-
-def forward64(p, rec, ref, flags, frozen=None, r32=None):
-    """The frame of the records rec (torch float64 [N, 84]) with the float32 frame's decisions: rgba32f [H, W, 4] and depth
-    [H, W] in float64.  frozen (bool [N], optional): splats that enter with the float32 values of raster32 r32, as constants
-    -- for splats whose float32 2-D covariance is dominated by rounding (the needles of the zero_det scene: a float64
-    restatement of them is another function)."""
-    w, h = p.width, p.height
-    V = torch.tensor(np.array(p.view, np.float64).reshape(4, 4).T)        # V[r][c] = view[c * 4 + r]
-    P = torch.tensor(np.array(p.proj, np.float64).reshape(4, 4).T)
-    cam = torch.tensor(np.array(p.cam_pos, np.float64))
-    pos = rec[:, 0:3]
-    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
-    vp = torch.cat([pos, ones], 1) @ V.T
-    q = vp @ P.T
-    ndc_x, ndc_y = q[:, 0] / q[:, 3], q[:, 1] / q[:, 3]
-    sx, sy = (ndc_x + 1.0) * 0.5 * w, (-ndc_y + 1.0) * 0.5 * h
-    # getCovarianceMatrix (Common.glsl:32-78)
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
-    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    T = J @ V[:3, :3]
-    S2 = T @ Sig @ T.transpose(1, 2)
-    a, b, c = S2[:, 0, 0] + 0.3, S2[:, 1, 0], S2[:, 1, 1] + 0.3
-    det = a * c - b * b
-    # the det == 0 rule of the float32 frame (RenderGaussians.comp:104): such a splat never contributes
-    cov32 = ref["stage1"]["cov"]
-    live = torch.tensor((cov32[:, 0] * cov32[:, 2] - cov32[:, 1] * cov32[:, 1]) != 0)
-    det = torch.where(live, det, torch.ones_like(det))
-    ix, iy, iz = c / det, -b / det, a / det
-    # colour (Common.glsl:141-170)
-    dvec = pos - cam
-    dirs = dvec / torch.sqrt((dvec * dvec).sum(1, keepdim=True))
-    basis = _sh_basis(dirs)
-    sh = rec[:, 12:76].reshape(-1, 16, 4)[:, :, :3]
-    if p.sh_mode == 0:
-        col = (sh * basis[:, :, None]).sum(1) + 0.5
-    elif p.sh_mode == 1:
-        col = (sh[:, 1:] * basis[:, 1:, None]).sum(1) - 0.5 + 0.5
-    else:
-        col = sh[:, 0] * basis[:, 0:1] + 0.5
-    col = torch.clamp(col, min=0.0)
-    opac = torch.where(live, rec[:, 15], torch.zeros_like(det))
-    zview = -vp[:, 2]
-    if frozen is not None:
-        fz = torch.tensor(np.asarray(frozen, bool))
-        k = lambda name, v: torch.where(fz, torch.tensor(r32[name]), v)
-        sx, sy, ix, iy, iz, opac, zview = (k("sx", sx), k("sy", sy), k("ix", ix), k("iy", iy), k("iz", iz), k("op", opac),
-                                          k("z", zview))
-        col = torch.where(fz[:, None], torch.tensor(np.stack([r32["r"], r32["g"], r32["b"]], 1)), col)
-    # the blend, tile by tile, with the decisions fixed
-    gw, gh = (w + 15) // 16, (h + 15) // 16
-    drawn, outs = [], []                    # the tiles that blend something and their [256, 5] pixels
-    ids = np.asarray(ref["id"], np.int64)
-    ranges = np.asarray(ref["ranges"]).reshape(-1, 2)
-    ly, lx = np.divmod(np.arange(256), 16)
-    for t in range(gw * gh):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        ty, tx = divmod(t, gw)
-        blended = np.flatnonzero(flags[s:e].any(1))
-        if not len(blended):
-            continue
-        e = s + int(blended[-1]) + 1        # the entries behind every pixel's last one add nothing and get nothing
-        m = torch.tensor(flags[s:e].astype(bool))
-        g = torch.tensor(ids[s:e])
-        fpx = torch.tensor((tx * 16 + lx).astype(np.float64))[None, :]
-        fpy = torch.tensor((ty * 16 + ly).astype(np.float64))[None, :]
-        ex = sx[g][:, None] - fpx
-        ey = fpy - sy[g][:, None]
-        f = -0.5 * (ix[g][:, None] * ex * ex + iz[g][:, None] * ey * ey) - iy[g][:, None] * ex * ey
-        f = torch.where(m, f, torch.zeros_like(f))
-        alpha = torch.where(m, opac[g][:, None] * torch.exp(f), torch.zeros_like(f))
-        Tx = torch.cumprod(torch.cat([torch.ones(1, 256, dtype=rec.dtype), 1.0 - alpha[:-1]], 0), 0)
-        wgt = Tx * alpha
-        chans = torch.cat([col[g], torch.ones(len(g), 1, dtype=rec.dtype), zview[g][:, None]], 1)   # r, g, b, 1, z
-        drawn.append(t)
-        outs.append(wgt.T @ chans)                                                                     # [256, 5]
-    # one out-of-place scatter for the whole frame (a slice assignment per tile costs autograd a copy of the frame each:
-    # hours on a 65 k-tile grid), then [gh, gw, 16, 16] -> [gh * 16, gw * 16]
-    img = torch.zeros(gw * gh, 256, 5, dtype=rec.dtype)
-    if drawn:
-        img = img.index_copy(0, torch.tensor(drawn, dtype=torch.int64), torch.stack(outs))
-    img = img.reshape(gh, gw, 16, 16, 5).permute(0, 2, 1, 3, 4).reshape(gh * 16, gw * 16, 5)[:h, :w]
-    return img[..., :4], img[..., 4]
-
-
-def reference_gradient(p, aos, ref, flags, w_rgba, w_depth=None, frozen=None):
-    """dL/d(record) [N, 84] (float64) of L = sum w_rgba * RGBA32F + sum w_depth * depth (zero for frozen splats)."""
-    rec = torch.tensor(np.asarray(aos, np.float64), requires_grad=True)
-    rgba, dep = forward64(p, rec, ref, flags, frozen, raster32(p, aos, ref) if frozen is not None else None)
-    loss = (rgba * torch.tensor(np.asarray(w_rgba, np.float64))).sum()
-    if w_depth is not None:
-        loss = loss + (dep * torch.tensor(np.asarray(w_depth, np.float64))).sum()
-    loss.backward()
-    return rec.grad.numpy()
 
 
 def frozen_of(scene, aos):
@@ -233,6 +38,18 @@ def small_scene():
     from vk3dgaussiansplatting_amd import synth
     aos = synth.generate(300, 64, 48, -2.5, seed=11)
     return aos, 64, 48
+
+
+def extreme_cloud():
+    """96 x 64, 400 splats with opacity exactly 0 and 1, zero quaternions and zero scales among them."""
+    from vk3dgaussiansplatting_amd import synth
+    aos = synth.generate(400, 96, 64, -2.0, seed=23)
+    aos[0:40, 15] = 0.0
+    aos[40:80, 15] = 1.0
+    aos[80:100, 8:12] = 0.0
+    aos[100:120, 4:7] = 0.0
+    aos[120:130, 4] = 0.0
+    return aos, 96, 64
 
 
 def screen_splat(oracle, w, h, sx, sy, z, sigma_px, opacity, colour=(0.3, -0.2, 0.5)):
@@ -428,9 +245,9 @@ def sampled_decisions(tmp_dir, p, aos, stage1, ids, ranges, tiles):
     aos = np.ascontiguousarray(aos, dtype=np.float32)
     sub_ids, sub_ranges = sampled_list(ids, ranges, tiles)
     flags = np.zeros((max(len(sub_ids), 1), 256), np.uint8)
-    trace_lib(tmp_dir).gsb_blend_trace(C.byref(p), _ptr(aos), _ptr(np.ascontiguousarray(stage1["color"])),
-                                       _ptr(np.ascontiguousarray(stage1["cov"])), _ptr(sub_ids), _ptr(sub_ranges),
-                                       _ptr(flags))
+    trace_lib(tmp_dir).gsb_blend_trace(C.byref(p), ptr(aos), ptr(np.ascontiguousarray(stage1["color"])),
+                                       ptr(np.ascontiguousarray(stage1["cov"])), ptr(sub_ids), ptr(sub_ranges),
+                                       ptr(flags))
     return sub_ids, sub_ranges, flags[:len(sub_ids)]
 
 
@@ -723,9 +540,9 @@ def test_backward_entry_points_refuse_a_null_context():
     from vk3dgaussiansplatting_amd import _lib
     L = _lib.lib()
     buf = np.zeros(84, np.float32)
-    assert L.gs_backward(None, _ptr(buf), None, _ptr(buf)) == _lib.GS_ERR_INVALID
-    assert L.gs_backward_device(None, _ptr(buf), None, _ptr(buf)) == _lib.GS_ERR_INVALID
-    assert L.gs_upload_gaussians_device(None, _ptr(buf), 1) == _lib.GS_ERR_INVALID
+    assert L.gs_backward(None, ptr(buf), None, ptr(buf)) == _lib.GS_ERR_INVALID
+    assert L.gs_backward_device(None, ptr(buf), None, ptr(buf)) == _lib.GS_ERR_INVALID
+    assert L.gs_upload_gaussians_device(None, ptr(buf), 1) == _lib.GS_ERR_INVALID
     assert _lib.API_VERSION == 7
 
 

@@ -22,10 +22,10 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib, synth
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, assert_posed, camera_params
-from test_backward_cpu import (check_overflowing, frame_decisions, overflow_tiles, overflowing_scene, padded_cloud,
-                               pick_tiles, read_fields_of, reference_gradient, sampled_decisions,
-                               sampled_reference_gradient, tile_lengths, tile_weights)
-from test_backward_gpu import READ_FIELDS, UNREAD, compare_with_reference, frame_and_grad, weights
+from test_backward_cpu import (check_overflowing, overflow_tiles, overflowing_scene, padded_cloud, pick_tiles,
+                               read_fields_of, sampled_decisions, sampled_reference_gradient, tile_lengths, tile_weights)
+from test_backward_gpu import READ_FIELDS, UNREAD, compare_with_reference, frame_and_grad
+from frame64 import frame_decisions, reference_gradient, weights
 
 pytestmark = pytest.mark.gpu
 

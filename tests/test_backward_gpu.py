@@ -13,8 +13,9 @@ from vk3dgaussiansplatting_amd import _lib, synth
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import (POSES, SCENES, assert_posed, camera, camera_params, in_front_of, known_answer_scene,
                               load_scene, oracle_params)
-from test_backward_cpu import (_sh_basis, batch_edge_scene, check_batch_edges, check_truncated, frame_decisions,
-                               frozen_of, reference_gradient, truncated_scene)
+from test_backward_cpu import (batch_edge_scene, check_batch_edges, check_truncated, extreme_cloud, frozen_of,
+                               truncated_scene)
+from frame64 import frame_decisions, reference_gradient, sh_basis, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +24,6 @@ KERNELS = (gs.GS_RENDER_KERNEL_AUTO, gs.GS_RENDER_KERNEL_WAVE_1PX, gs.GS_RENDER_
 # the 59 fields a frame reads: position.xyz, scale.xyz, rot, shCoeffs[k].rgb, shCoeffs[0].a
 READ_FIELDS = [0, 1, 2, 4, 5, 6, 8, 9, 10, 11, 15] + [12 + 4 * k + c for k in range(16) for c in range(3)]
 UNREAD = np.setdiff1d(np.arange(84), READ_FIELDS)
-
-
-def weights(h, w, seed=0):
-    rng = np.random.default_rng(seed)
-    return rng.standard_normal((h, w, 4)).astype(np.float32), (0.1 * rng.standard_normal((h, w))).astype(np.float32)
 
 
 def frame_and_grad(aos, w, h, sh_mode=0, seed=0, cam=None, **kw):
@@ -105,23 +101,12 @@ def test_known_answer_posed(oracle_mod, pose):
 
     gr = zero_rgba.copy(); gr[cy, cx, 0] = 1.0
     g = r.backward(gr)[0]
-    basis = _sh_basis(torch.tensor(forward[None] / np.linalg.norm(forward)))[0].numpy()
+    basis = sh_basis(torch.tensor(forward[None] / np.linalg.norm(forward)))[0].numpy()
     assert np.all(np.abs(basis) > 1e-3), basis
     np.testing.assert_allclose(g[12:76:4], 0.5 * basis, rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(g[15], col[0], rtol=1e-5)
     assert np.all(g[13:76:4] == 0) and np.all(g[14:76:4] == 0) and np.all(g[19:76:4] == 0) and np.all(g[UNREAD] == 0)
     r.cleanup()
-
-
-def extreme_cloud():
-    """96 x 64, 400 splats with opacity exactly 0 and 1, zero quaternions and zero scales among them."""
-    aos = synth.generate(400, 96, 64, -2.0, seed=23)
-    aos[0:40, 15] = 0.0
-    aos[40:80, 15] = 1.0
-    aos[80:100, 8:12] = 0.0
-    aos[100:120, 4:7] = 0.0
-    aos[120:130, 4] = 0.0
-    return aos, 96, 64
 
 
 CASES = [("ragged", 0), ("ragged", 1), ("ragged", 2), ("dense", 0), ("zero_det", 0), ("extreme", 0), ("extreme", 1),
@@ -300,7 +285,7 @@ def test_api_refusals():
     aos, w, h = SCENES["ragged"]()
     sc = make_scene(aos, w, h)
     L = _lib.lib()
-    wr, wd = weights(h, w)
+    wr, wd = weights(h, w, 0)
     out = np.zeros((len(aos), 84), np.float32)
     p = lambda a: a.ctypes.data_as(C.c_void_p)
 

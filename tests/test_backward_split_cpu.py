@@ -2,17 +2,18 @@
 the CPU; tests/test_backward_split_gpu.py runs the kernels against them).
 
   rows   k_bwd_blend leaves one 10-float row per list element; gs_debug_read(GS_BUF_BACKWARD_ROWS) returns their sum per
-         splat (dsx, dsy, dix, diy, diz, dcol[3], dop, dz: the input of bwd_chain).  rows_reference is the tile loop of
-         test_absgrad_cpu.abs_screen_gradient with its zero offset per (list element, pixel) widened from the screen position
-         to all ten splat values, evaluated on the float32 frame's own values (raster32, constants): `signed` is the row sum,
-         `absolute` the same per-pixel terms summed as abs(), the scale an error of the blend is measured against.
+         splat (dsx, dsy, dix, diy, diz, dcol[3], dop, dz: the input of bwd_chain).  rows_reference is the tile walk and blend
+         of tests/frame64.py (pair_terms) with a zero offset per (list element, pixel) on all ten splat values -- where
+         test_absgrad_cpu.abs_screen_gradient has it on the screen position alone -- evaluated on the float32 frame's own
+         values (raster32, constants): `signed` is the row sum, `absolute` the same per-pixel terms summed as abs(), the scale
+         an error of the blend is measured against.
   chain  bwd_chain takes a splat's row through the per-splat part of the frame.  chain64 is the vector-Jacobian product of
-         the ten splat values against given rows, by autograd through splat_values (splat_values64 of test_absgrad_cpu.py
-         restated with the camera per splat, the five SH modes, the anti-aliasing factor and the number format as
-         arguments); chain_scale is S = sum_j |d value_j / d field| |row_j|, the majorant of the rounding of a float32
-         matrix-vector product, with the sum of the absolute monomials of b_k in place of |b_k| for the SH coefficient
-         fields (a basis function that cancels to nearly zero would understate the scale).  camera=True gives both the twin for
-         the 35 camera floats, per splat (the tests sum them over the splats), and its scale.
+         the ten splat values against given rows, by autograd through frame64.splat_values, the per-splat stage every
+         reference shares (here with the camera per splat, any of the five SH modes, the anti-aliasing factor, the number
+         format and the branches as arguments); chain_scale is S = sum_j |d value_j / d field| |row_j|, the majorant of the
+         rounding of a float32 matrix-vector product, with the sum of the absolute monomials of b_k in place of |b_k| for the
+         SH coefficient fields (a basis function that cancels to nearly zero would understate the scale).  camera=True gives
+         both the twin for the 35 camera floats, per splat (the tests sum them over the splats), and its scale.
 
 Calibration: both references run once more in torch float32 on the same inputs with the same decisions; the worst
 |ref32 - ref64| / scale over the designed scenes is recorded below and each GPU tier is asserted to be at least twice it, so
@@ -53,16 +54,16 @@ import numpy as np
 import pytest
 
 from test_outputs_cpu import oracle_params
-from test_backward_cpu import (_sh_basis, batch_edge_scene, frame_decisions, frozen_of, raster32, reference_gradient,
-                               truncated_scene)
-from test_absgrad_cpu import abs_screen_gradient, grads, splat_values64
-from test_antialias_cpu import FLOOR, load_antialias_scene
+from test_backward_cpu import batch_edge_scene, frozen_of, truncated_scene
+from frame64 import (DECISIONS, FLOOR, WRONG_TERMS, camera_leaves, frame_decisions, frame_values32, live_of, pair_terms,
+                     reference_gradient, sh_basis, sh_monomials, sh_range, splat_values, weights)
+from test_absgrad_cpu import abs_screen_gradient, splat_values64
+from test_antialias_cpu import load_antialias_scene
 from test_camera_constants_cpu import clamp_masks, with_constants
 from test_backward_camera_cpu import PROJ_CLIP_Z, VIEW_BOTTOM_ROW
 
 torch = pytest.importorskip("torch")
 
-ROW_NAMES = ("sx", "sy", "ix", "iy", "iz", "r", "g", "b", "op", "z")          # bwd_chain's row, raster32's keys
 GEOMETRY = [0, 1, 2, 4, 5, 6, 8, 9, 10, 11]
 
 # ---- the calibrated constants (test_calibration re-measures them and fails when one no longer covers its measurement) ------
@@ -76,125 +77,9 @@ CHAIN_TIER = 8.0 * CHAIN_REF32_MAX
 CHAIN_P999_TIER = 8.0 * CHAIN_REF32_P999          # ... and at most 0.1 % of the compared entries above this one
 
 
-def sh_range(sh_mode):
-    """[k_lo, k_hi): the SH coefficients a frame of this GS_SH_* mode evaluates (bwd_chain)."""
-    return (1 if sh_mode == 1 else 0), {2: 1, 5: 4, 4: 9}.get(sh_mode, 16)
-
-
 def read_fields(sh_mode):
     k_lo, k_hi = sh_range(sh_mode)
     return GEOMETRY + [15] + [12 + 4 * k + c for k in range(k_lo, k_hi) for c in range(3)]
-
-
-def live_of(ref):
-    """The det != 0 rule of the float32 frame (RenderGaussians.comp:104) from its stage-1 covariance."""
-    cov = np.asarray(ref["stage1"]["cov"], np.float32)
-    return (cov[:, 0] * cov[:, 2] - cov[:, 1] * cov[:, 1]) != 0
-
-
-# ---- the per-splat values ----------------------------------------------------------------------------------------------------
-
-def camera_leaves(p, n, dtype=torch.float64, grad=False):
-    """The frame's camera copied per splat: V [n, 4, 4] with V[g][r][c] = view[c * 4 + r], P likewise, cam [n, 3]."""
-    V = torch.tensor(np.array(p.view, np.float64).reshape(4, 4).T, dtype=dtype).expand(n, 4, 4).clone()
-    P = torch.tensor(np.array(p.proj, np.float64).reshape(4, 4).T, dtype=dtype).expand(n, 4, 4).clone()
-    cam = torch.tensor(np.array(p.cam_pos, np.float64), dtype=dtype).expand(n, 3).clone()
-    if grad:
-        for t in (V, P, cam):
-            t.requires_grad_(True)
-    return V, P, cam
-
-
-def _scaled_derivative(x, k):
-    """x with its derivative scaled by k (the value is x exactly: x - x.detach() is an exact zero)."""
-    return x if k == 1.0 else x.detach() + k * (x - x.detach())
-
-
-WRONG_TERMS = ("sh_direction", "whole_J", "J02", "view_depth")
-
-
-def splat_values(p, rec, live, cams=None, dec=None, antialias=False, wrong=None):
-    """(values [N, 10] in the order of ROW_NAMES, aux) of the records rec [N, 84] in rec's number format: splat_values64 of
-    tests/test_absgrad_cpu.py restated -- the same expressions -- with the camera per splat (cams = camera_leaves, so that a
-    camera gradient comes out per splat), the SH coefficients of all five modes, opacity * rho under antialias (rho of
-    tests/test_antialias_cpu.py with the cap at 1 bwd_chain holds fixed), and the branches as `dec` names them (clamp_x,
-    clamp_y [N]; colour [N, 3]: not on max(colour, 0); floored, capped [N]) or, without dec, as the values themselves decide.
-    wrong = (one of WRONG_TERMS, k): that term's derivative scaled by k.  aux: the decisions taken, the unit direction."""
-    dtype, n = rec.dtype, rec.shape[0]
-    w, h = p.width, p.height
-    V, P, cam = cams if cams is not None else camera_leaves(p, n, dtype)
-    k_of = lambda name: wrong[1] if wrong is not None and wrong[0] == name else 1.0
-    live = torch.as_tensor(np.asarray(live, bool))
-    pos = rec[:, 0:3]
-    ones = torch.ones(n, 1, dtype=dtype)
-    vp = torch.einsum("nrc,nc->nr", V, torch.cat([pos, ones], 1))
-    q = torch.einsum("nrc,nc->nr", P, vp)
-    ndc_x, ndc_y = q[:, 0] / q[:, 3], q[:, 1] / q[:, 3]
-    sx, sy = (ndc_x + 1.0) * 0.5 * w, (-ndc_y + 1.0) * 0.5 * h
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    rx, ry = vp[:, 0] / tz, vp[:, 1] / tz
-    clamp_x = torch.as_tensor(dec["clamp_x"]) if dec is not None else (rx < -lim_x) | (rx > lim_x)
-    clamp_y = torch.as_tensor(dec["clamp_y"]) if dec is not None else (ry < -lim_y) | (ry > lim_y)
-    pvx = torch.where(clamp_x, torch.clamp(rx.detach(), -lim_x, lim_x), rx) * tz
-    pvy = torch.where(clamp_y, torch.clamp(ry.detach(), -lim_y, lim_y), ry) * tz
-    zero = torch.zeros_like(tz)
-    J02 = _scaled_derivative(-(fx * pvx) / (tz * tz), k_of("J02"))
-    J = torch.stack([torch.stack([fx / tz, zero, J02], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    J = _scaled_derivative(J, k_of("whole_J"))
-    Tm = J @ V[:, :3, :3]
-    S2 = Tm @ Sig @ Tm.transpose(1, 2)
-    a0, b, c0 = S2[:, 0, 0], S2[:, 1, 0], S2[:, 1, 1]
-    a, c = a0 + 0.3, c0 + 0.3
-    det = a * c - b * b
-    det = torch.where(live, det, torch.ones_like(det))
-    ix, iy, iz = c / det, -b / det, a / det
-    dvec = pos - cam
-    dirs = dvec / torch.sqrt((dvec * dvec).sum(1, keepdim=True))
-    basis = _sh_basis(_scaled_derivative(dirs, k_of("sh_direction")))
-    sh = rec[:, 12:76].reshape(-1, 16, 4)[:, :, :3]
-    k_lo, k_hi = sh_range(p.sh_mode)
-    res = (sh[:, k_lo:k_hi] * basis[:, k_lo:k_hi, None]).sum(1)
-    if p.sh_mode == 1:
-        res = res - 0.5
-    res = res + 0.5
-    colour = torch.as_tensor(dec["colour"]) if dec is not None else res >= 0
-    col = torch.where(colour, res, torch.zeros_like(res))
-    opac = torch.where(live, rec[:, 15], torch.zeros_like(det))
-    aux = dict(clamp_x=clamp_x.numpy(), clamp_y=clamp_y.numpy(), colour=colour.numpy(), dirs=dirs.detach())
-    if antialias:
-        ratio = (a0 * c0 - b * b) / det
-        floored = torch.as_tensor(dec["floored"]) if dec is not None else ~(ratio > FLOOR)
-        capped = torch.as_tensor(dec["capped"]) if dec is not None else ratio > 1.0
-        const = torch.where(floored, torch.full_like(ratio, FLOOR), torch.ones_like(ratio))
-        opac = opac * torch.sqrt(torch.where(floored | capped, const, ratio))
-        aux.update(floored=floored.numpy(), capped=capped.numpy(), ratio=ratio.detach().numpy())
-    zview = _scaled_derivative(-vp[:, 2], k_of("view_depth"))
-    return torch.stack([sx, sy, ix, iy, iz, col[:, 0], col[:, 1], col[:, 2], opac, zview], 1), aux
-
-
-def sh_monomials(dirs):
-    """Per basis function b_k of Common.glsl:94-138 the sum of the absolute values of its monomials in (X, Y, Z) = (-dx, -dy,
-    dz), as bwd_chain's sh_basis_grad adds them: [M, 16] >= |b_k|, equal where b_k is a single monomial."""
-    X, Y, Z = dirs[:, 0].abs(), dirs[:, 1].abs(), dirs[:, 2].abs()
-    X2, Y2, Z2 = X * X, Y * Y, Z * Z
-    tc = 2.285228997322329 * Z2 + 0.4570457994644658
-    m = [torch.full_like(X, 0.2820947917738781), 0.48860251190292 * Y, 0.4886025119029199 * Z, 0.48860251190292 * X,
-         0.5462742152960395 * 2.0 * X * Y, 1.092548430592079 * Z * Y, 0.9461746957575601 * Z2 + 0.31539156525252,
-         1.092548430592079 * Z * X, 0.5462742152960395 * (X2 + Y2), 0.5900435899266435 * (3.0 * X2 * Y + Y2 * Y),
-         1.445305721320277 * Z * 2.0 * X * Y, tc * Y, Z * (1.865881662950577 * Z2 + 1.119528997770346), tc * X,
-         1.445305721320277 * Z * (X2 + Y2), 0.5900435899266435 * (X2 * X + 3.0 * X * Y2)]
-    return torch.stack(m, 1)
 
 
 # ---- the chain -----------------------------------------------------------------------------------------------------------------
@@ -268,62 +153,23 @@ def decisions64(p, aos, ref, antialias=False):
     """The branches splat_values takes in float64, as `dec` for a run in another number format."""
     with torch.no_grad():
         _, aux = splat_values(p, torch.tensor(np.asarray(aos, np.float64)), live_of(ref), antialias=antialias)
-    return {k: v for k, v in aux.items() if k not in ("dirs", "ratio")}
+    return {k: aux[k] for k in DECISIONS if k in aux}
 
 
 # ---- the rows ------------------------------------------------------------------------------------------------------------------
 
-def frame_values32(p, aos, ref):
-    """[N, 10] float64 array of the float32 values the frame blends (raster32), in the order of ROW_NAMES."""
-    r32 = raster32(p, aos, ref)
-    return np.stack([r32[k] for k in ROW_NAMES], 1)
-
-
 def rows_reference(p, aos, ref, flags, w_rgba, w_depth=None, dtype=torch.float64, values=None, leaves=False):
-    """(signed [N, 10], absolute [N, 10]) in float64 of L = sum w_rgba * RGBA32F + sum w_depth * depth: the tile loop of
-    abs_screen_gradient with its zero offset per (list element, pixel) widened to all ten splat values, on `values` [N, 10]
-    (default: frame_values32, the float32 frame's own, as constants), computed in `dtype`.  leaves=True: a third array, the
-    plain autograd gradient of L w.r.t. `values` as one leaf."""
-    w, h = p.width, p.height
+    """(signed [N, 10], absolute [N, 10]) in float64 of L = sum w_rgba * RGBA32F + sum w_depth * depth: frame64.pair_terms
+    with the zero offset per (list element, pixel) on all ten splat values, on `values` [N, 10] (default: frame_values32, the
+    float32 frame's own, as constants), computed in `dtype`.  leaves=True: a third array, the plain autograd gradient of L
+    w.r.t. `values` as one leaf."""
     n = len(aos)
     vals = torch.tensor(frame_values32(p, aos, ref) if values is None else np.asarray(values, np.float64), dtype=dtype,
                         requires_grad=leaves)
-    gw, gh = (w + 15) // 16, (h + 15) // 16
-    wimg = torch.zeros(gh * 16, gw * 16, 5, dtype=dtype)
-    wimg[:h, :w, :4] = torch.tensor(np.asarray(w_rgba, np.float64), dtype=dtype)
-    if w_depth is not None:
-        wimg[:h, :w, 4] = torch.tensor(np.asarray(w_depth, np.float64), dtype=dtype)
-    wtile = wimg.reshape(gh, 16, gw, 16, 5).permute(0, 2, 1, 3, 4).reshape(gh * gw, 256, 5)
-    ids = np.asarray(ref["id"], np.int64)
-    ranges = np.asarray(ref["ranges"]).reshape(-1, 2)
-    ly, lx = np.divmod(np.arange(256), 16)
     absolute = torch.zeros(n, 10, dtype=torch.float64)
     signed = torch.zeros(n, 10, dtype=torch.float64)
-    for t in range(gw * gh):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        ty, tx = divmod(t, gw)
-        blended = np.flatnonzero(flags[s:e].any(1))
-        if not len(blended):
-            continue
-        e = s + int(blended[-1]) + 1
-        m = torch.tensor(flags[s:e].astype(bool))
-        g = torch.tensor(ids[s:e])
-        off = torch.zeros(e - s, 256, 10, dtype=dtype, requires_grad=True)
-        v = vals[g][:, None, :] + off
-        fpx = torch.tensor((tx * 16 + lx).astype(np.float64), dtype=dtype)[None, :]
-        fpy = torch.tensor((ty * 16 + ly).astype(np.float64), dtype=dtype)[None, :]
-        ex = v[:, :, 0] - fpx
-        ey = fpy - v[:, :, 1]
-        f = -0.5 * (v[:, :, 2] * ex * ex + v[:, :, 4] * ey * ey) - v[:, :, 3] * ex * ey
-        f = torch.where(m, f, torch.zeros_like(f))
-        alpha = torch.where(m, v[:, :, 8] * torch.exp(f), torch.zeros_like(f))
-        Tx = torch.cumprod(torch.cat([torch.ones(1, 256, dtype=dtype), 1.0 - alpha[:-1]], 0), 0)
-        wgt = Tx * alpha
-        chans = torch.cat([v[:, :, 5:8], torch.ones(e - s, 256, 1, dtype=dtype), v[:, :, 9:10]], 2)     # r, g, b, 1, z
-        ((wgt[:, :, None] * chans).sum(0) * wtile[t]).sum().backward()
-        grad = off.grad.to(torch.float64)
+    for g, grad in pair_terms(p, vals, ref, flags, w_rgba, w_depth):
+        grad = grad.to(torch.float64)
         absolute.index_add_(0, g, grad.abs().sum(1))
         signed.index_add_(0, g, grad.sum(1))
     out = (signed.numpy(), absolute.numpy())
@@ -367,7 +213,7 @@ def split_frame(oracle, tmp_dir, name, sh_mode=0, seed=1, with_depth=True):
         aos, w, h, cam, constants = load_split_scene(oracle, name)
         p = with_constants(oracle_params(oracle, w, h, sh_mode, **cam), constants)
         ref, flags = frame_decisions(tmp_dir, p, aos)
-        wr, wd = grads(h, w, seed)
+        wr, wd = weights(h, w, seed)
         wd = wd if with_depth else None
         signed, absolute = rows_reference(p, aos, ref, flags, wr, wd)
         _FRAMES[key] = dict(aos=aos, w=w, h=h, cam=cam, constants=constants, p=p, ref=ref, flags=flags, wr=wr, wd=wd,
@@ -426,7 +272,7 @@ def test_monomial_scale_bounds_the_basis():
     rng = np.random.default_rng(3)
     d = torch.tensor(rng.standard_normal((20000, 3)))
     d = d / torch.sqrt((d * d).sum(1, keepdim=True))
-    b, m = _sh_basis(d).abs().numpy(), sh_monomials(d).numpy()
+    b, m = sh_basis(d).abs().numpy(), sh_monomials(d).numpy()
     assert np.all(m >= b * (1 - 1e-12))
     single = [0, 1, 2, 3, 4, 5, 7, 10]
     assert np.allclose(m[:, single], b[:, single], rtol=1e-12, atol=0)

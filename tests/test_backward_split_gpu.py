@@ -22,12 +22,10 @@ from vk3dgaussiansplatting_amd import _lib
 from vk3dgaussiansplatting_amd.renderer import GsplatError
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import camera_params
-from test_absgrad_cpu import grads
-from test_antialias_cpu import FLOOR
 from test_camera_constants_cpu import clamp_masks, with_constants
 from test_backward_split_cpu import (CAMERA_REF32_MAX, CAMERA_UNWRITTEN, CHAIN_P999_TIER, CHAIN_TIER, ROWS_TIER, chain64,
-                                     chain_scale, decisions64, load_split_scene, read_fields, split_frame, splat_values,
-                                     live_of)
+                                     chain_scale, decisions64, load_split_scene, read_fields, split_frame)
+from frame64 import FLOOR, live_of, splat_values, weights
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -47,7 +45,7 @@ def drawn(oracle, name, sh_mode=0, antialias=False, band=None, seed=1, with_dept
         r.setBandGradients(True)
         r.setTileRows(*band)
     r.draw(sc)
-    wr, wd = grads(h, w, seed)
+    wr, wd = weights(h, w, seed)
     wd = wd if with_depth else None
     grad = r.backward(wr, wd)
     rows = r.debugRead(gs.BUF_BACKWARD_ROWS)
@@ -228,7 +226,7 @@ def test_read_back_behaviour(oracle_mod):
     refused()
     with pytest.raises(GsplatError):
         r.debugRead(gs.BUF_BACKWARD_ROWS)
-    wr, wd = grads(h, w, 1)
+    wr, wd = weights(h, w, 1)
     first = r.backward(wr, wd)
     assert L.gs_debug_read(r._ctx.handle, gs.BUF_BACKWARD_ROWS, ptr, n * 40 + 4) == _lib.GS_ERR_INVALID
     assert np.all(buf == guard)

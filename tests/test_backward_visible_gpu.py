@@ -14,7 +14,7 @@ from vk3dgaussiansplatting_amd import _lib, synth
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, camera_params, oracle_params
 from test_backward_cpu import list_offsets, padded_cloud, small_scene, truncated_scene
-from test_backward_gpu import weights
+from frame64 import weights
 
 pytestmark = pytest.mark.gpu
 

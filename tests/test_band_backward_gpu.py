@@ -17,9 +17,9 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, assert_posed, camera_params, load_scene
-from test_backward_cpu import (frame_decisions, overflowing_scene, pick_tiles, reference_gradient, sampled_reference_gradient,
-                               tile_weights)
-from test_backward_gpu import compare_with_reference, weights
+from test_backward_cpu import overflowing_scene, pick_tiles, sampled_reference_gradient, tile_weights
+from test_backward_gpu import compare_with_reference
+from frame64 import frame_decisions, reference_gradient, weights
 from test_backward_fullsize_gpu import assert_sampled_gradient, oracle_list
 from test_band_cull_cpu import C_BAND, H, W, cameras, cloud_c
 from test_band_backward_cpu import DEALINGS, rows_of, v_band

@@ -469,7 +469,7 @@ def test_reference_forward_matches_the_restatement(oracle_mod, tmp_path, name, s
     relative + 2e-5 absolute): the float64 frame reads fov_y, in_view_limit and proj as the float32 frame does, before the
     GPU's gradients are judged by it.  The culls and the depth key reach it through the frame's decisions."""
     torch = pytest.importorskip("torch")
-    from test_backward_cpu import forward64, frame_decisions
+    from frame64 import forward64, frame_decisions
     c = case(name, scene, pose)
     ref, flags = frame_decisions(tmp_path, c["p"], c["aos"], ref=oracle_frame(name, scene, pose))
     out = reference_outputs(tmp_path, c["p"], c["aos"], ref=ref)

@@ -25,8 +25,9 @@ from test_outputs_cpu import reference_outputs
 from test_outputs_gpu import bits, outputs
 from test_band_cull_cpu import GW, H, W
 from test_band_cull_gpu import assert_band, assert_rows, scene_of
-from test_backward_cpu import frame_decisions, list_offsets, reference_gradient
-from test_backward_gpu import UNREAD, compare_with_reference, weights
+from test_backward_cpu import list_offsets
+from test_backward_gpu import UNREAD, compare_with_reference
+from frame64 import frame_decisions, reference_gradient, weights
 from test_backward_camera_cpu import PROJ_CLIP_Z, VIEW_BOTTOM_ROW, camera_reference
 from test_backward_camera_gpu import check_against, check_cam_pos_central_differences
 from test_camera_constants_cpu import (BAND_ROWS, BAND_RUNS, CONFIGS, CONSTANTS, DEFAULTS, FRAME_CASES, GRAD_CASES, band_cloud,

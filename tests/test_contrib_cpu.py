@@ -16,8 +16,8 @@ from conftest import ROOT
 import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_outputs_cpu import known_answer_scene, load_scene, oracle_params, reference_outputs, assert_posed
-from test_backward_cpu import (batch_edge_scene, check_batch_edges, check_truncated, frame_decisions, list_offsets,
-                               truncated_scene)
+from test_backward_cpu import batch_edge_scene, check_batch_edges, check_truncated, list_offsets, truncated_scene
+from frame64 import frame_decisions
 
 F = np.float32
 _CONTRIB = {}

@@ -19,7 +19,7 @@ from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, camera_params, load_scene
 from test_backward_cpu import batch_edge_scene, check_batch_edges, check_truncated, padded_cloud, small_scene, truncated_scene
-from test_backward_gpu import weights
+from frame64 import weights
 from test_train_chain_gpu import LAMBDA, new_renderer
 from test_contrib_cpu import bits, contrib_reference, prune_mask, prune_ref, scene_reference
 

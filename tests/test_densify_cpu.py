@@ -1,14 +1,15 @@
 """Adaptive density control (include/gsplat.h, gs_densify_stats_device / gs_densify_device), on the CPU: the NumPy restatement
 of the rule and of the counter-based normals, a designed statistics array in which every comparison of the rule decides
-alone, and the float64 reference of dL/d(screen position) -- forward64 of tests/test_backward_cpu.py with one added zero
-tensor on (sx, sy).  tests/test_densify_gpu.py compares the GPU with them.  Helpers are shared with that file."""
+alone, and the float64 reference of dL/d(screen position) -- the gradient of forward64's (tests/frame64.py) screen_offset, a
+zero tensor added to (sx, sy).  tests/test_densify_gpu.py compares the GPU with them.  Helpers are shared with that file."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from test_outputs_cpu import load_scene, oracle_params
-from test_backward_cpu import (_sh_basis, frame_decisions, frozen_of, forward64, raster32, reference_gradient)
+from test_backward_cpu import frozen_of
+from frame64 import forward64, frame_decisions, loss_of, raster32, reference_gradient
 
 torch = pytest.importorskip("torch")
 
@@ -269,96 +270,9 @@ def test_the_normals_are_standard_normal():
 # ---- the float64 reference of dL/d(sx, sy) ----------------------------------------------------------------------------------
 
 def forward64_screen(p, rec, off, ref, flags, frozen=None, r32=None):
-    """forward64 of tests/test_backward_cpu.py with `off` (torch float64 [N, 2]) added to the screen position (sx, sy) of
-    every splat, frozen ones included: the same expressions in the same order, so that with off == 0 the images are those
-    of forward64 exactly."""
-    w, h = p.width, p.height
-    V = torch.tensor(np.array(p.view, np.float64).reshape(4, 4).T)
-    P = torch.tensor(np.array(p.proj, np.float64).reshape(4, 4).T)
-    cam = torch.tensor(np.array(p.cam_pos, np.float64))
-    pos = rec[:, 0:3]
-    ones = torch.ones(rec.shape[0], 1, dtype=rec.dtype)
-    vp = torch.cat([pos, ones], 1) @ V.T
-    q = vp @ P.T
-    ndc_x, ndc_y = q[:, 0] / q[:, 3], q[:, 1] / q[:, 3]
-    sx, sy = (ndc_x + 1.0) * 0.5 * w, (-ndc_y + 1.0) * 0.5 * h
-    r, x, y, z = rec[:, 8], rec[:, 9], rec[:, 10], rec[:, 11]
-    R = torch.stack([torch.stack([1 - 2 * y * y - 2 * z * z, 2 * x * y + 2 * r * z, 2 * x * z - 2 * r * y], 1),
-                     torch.stack([2 * x * y - 2 * r * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z + 2 * r * x], 1),
-                     torch.stack([2 * x * z + 2 * r * y, 2 * y * z - 2 * r * x, 1 - 2 * x * x - 2 * y * y], 1)], 1)
-    M = R * rec[:, None, 4:7]
-    Sig = M @ M.transpose(1, 2)
-    tan_y = float(np.float32(np.tan(np.float64(np.float32(p.fov_y) * np.float32(0.5)))))
-    tan_x = tan_y * w / h
-    fx, fy = w / (2.0 * tan_x), h / (2.0 * tan_y)
-    lim_x, lim_y = tan_x * p.in_view_limit, tan_y * p.in_view_limit
-    tz = vp[:, 2]
-    pvx = torch.clamp(vp[:, 0] / tz, -lim_x, lim_x) * tz
-    pvy = torch.clamp(vp[:, 1] / tz, -lim_y, lim_y) * tz
-    zero = torch.zeros_like(tz)
-    J = torch.stack([torch.stack([fx / tz, zero, -(fx * pvx) / (tz * tz)], 1),
-                     torch.stack([zero, fy / tz, -(fy * pvy) / (tz * tz)], 1)], 1)
-    Tm = J @ V[:3, :3]
-    S2 = Tm @ Sig @ Tm.transpose(1, 2)
-    a, b, c = S2[:, 0, 0] + 0.3, S2[:, 1, 0], S2[:, 1, 1] + 0.3
-    det = a * c - b * b
-    cov32 = ref["stage1"]["cov"]
-    live = torch.tensor((cov32[:, 0] * cov32[:, 2] - cov32[:, 1] * cov32[:, 1]) != 0)
-    det = torch.where(live, det, torch.ones_like(det))
-    ix, iy, iz = c / det, -b / det, a / det
-    dvec = pos - cam
-    dirs = dvec / torch.sqrt((dvec * dvec).sum(1, keepdim=True))
-    basis = _sh_basis(dirs)
-    sh = rec[:, 12:76].reshape(-1, 16, 4)[:, :, :3]
-    if p.sh_mode == 0:
-        col = (sh * basis[:, :, None]).sum(1) + 0.5
-    elif p.sh_mode == 1:
-        col = (sh[:, 1:] * basis[:, 1:, None]).sum(1) - 0.5 + 0.5
-    else:
-        col = sh[:, 0] * basis[:, 0:1] + 0.5
-    col = torch.clamp(col, min=0.0)
-    opac = torch.where(live, rec[:, 15], torch.zeros_like(det))
-    zview = -vp[:, 2]
-    if frozen is not None:
-        fz = torch.tensor(np.asarray(frozen, bool))
-        k = lambda name, t: torch.where(fz, torch.tensor(r32[name]), t)
-        sx, sy, ix, iy, iz, opac, zview = (k("sx", sx), k("sy", sy), k("ix", ix), k("iy", iy), k("iz", iz), k("op", opac),
-                                          k("z", zview))
-        col = torch.where(fz[:, None], torch.tensor(np.stack([r32["r"], r32["g"], r32["b"]], 1)), col)
-    sx, sy = sx + off[:, 0], sy + off[:, 1]                 # the one addition
-    gw, gh = (w + 15) // 16, (h + 15) // 16
-    drawn, outs = [], []
-    ids = np.asarray(ref["id"], np.int64)
-    ranges = np.asarray(ref["ranges"]).reshape(-1, 2)
-    ly, lx = np.divmod(np.arange(256), 16)
-    for t in range(gw * gh):
-        s, e = int(ranges[t, 0]), int(ranges[t, 1])
-        if e <= s:
-            continue
-        ty, tx = divmod(t, gw)
-        blended = np.flatnonzero(flags[s:e].any(1))
-        if not len(blended):
-            continue
-        e = s + int(blended[-1]) + 1
-        m = torch.tensor(flags[s:e].astype(bool))
-        g = torch.tensor(ids[s:e])
-        fpx = torch.tensor((tx * 16 + lx).astype(np.float64))[None, :]
-        fpy = torch.tensor((ty * 16 + ly).astype(np.float64))[None, :]
-        ex = sx[g][:, None] - fpx
-        ey = fpy - sy[g][:, None]
-        f = -0.5 * (ix[g][:, None] * ex * ex + iz[g][:, None] * ey * ey) - iy[g][:, None] * ex * ey
-        f = torch.where(m, f, torch.zeros_like(f))
-        alpha = torch.where(m, opac[g][:, None] * torch.exp(f), torch.zeros_like(f))
-        Tx = torch.cumprod(torch.cat([torch.ones(1, 256, dtype=rec.dtype), 1.0 - alpha[:-1]], 0), 0)
-        wgt = Tx * alpha
-        chans = torch.cat([col[g], torch.ones(len(g), 1, dtype=rec.dtype), zview[g][:, None]], 1)
-        drawn.append(t)
-        outs.append(wgt.T @ chans)
-    img = torch.zeros(gw * gh, 256, 5, dtype=rec.dtype)
-    if drawn:
-        img = img.index_copy(0, torch.tensor(drawn, dtype=torch.int64), torch.stack(outs))
-    img = img.reshape(gh, gw, 16, 16, 5).permute(0, 2, 1, 3, 4).reshape(gh * 16, gw * 16, 5)[:h, :w]
-    return img[..., :4], img[..., 4]
+    """forward64 with `off` (torch float64 [N, 2]) added to the screen position (sx, sy) of every splat, frozen ones
+    included (its `screen_offset`): with off == 0 the images are those of forward64 exactly."""
+    return forward64(p, rec, ref, flags, frozen, r32, screen_offset=off)
 
 
 def screen_gradient(p, aos, ref, flags, w_rgba, w_depth=None, frozen=None):
@@ -366,10 +280,7 @@ def screen_gradient(p, aos, ref, flags, w_rgba, w_depth=None, frozen=None):
     rec = torch.tensor(np.asarray(aos, np.float64), requires_grad=True)
     off = torch.zeros(len(aos), 2, dtype=torch.float64, requires_grad=True)
     rgba, dep = forward64_screen(p, rec, off, ref, flags, frozen, raster32(p, aos, ref) if frozen is not None else None)
-    loss = (rgba * torch.tensor(np.asarray(w_rgba, np.float64))).sum()
-    if w_depth is not None:
-        loss = loss + (dep * torch.tensor(np.asarray(w_depth, np.float64))).sum()
-    loss.backward()
+    loss_of(rgba, dep, w_rgba, w_depth).backward()
     return off.grad.numpy(), rec.grad.numpy()
 
 

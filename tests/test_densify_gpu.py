@@ -12,9 +12,9 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import SCENES, camera_params, load_scene
-from test_backward_cpu import (check_overflowing, frame_decisions, frozen_of, list_offsets, overflow_tiles, overflowing_scene,
+from test_backward_cpu import (check_overflowing, frozen_of, list_offsets, overflow_tiles, overflowing_scene,
                                sampled_decisions, tile_weights)
-from test_backward_gpu import weights
+from frame64 import frame_decisions, weights
 from test_backward_fullsize_gpu import oracle_list
 from test_adam_gpu import frame_state
 from test_train_chain_gpu import LAMBDA, bits, new_renderer

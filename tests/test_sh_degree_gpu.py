@@ -17,8 +17,7 @@ import vk3dgaussiansplatting_amd as gs
 from vk3dgaussiansplatting_amd import _lib, synth
 from test_parity_gpu import ALL_SORTS, make_renderer, make_scene
 from test_outputs_cpu import POSES, SCENES, in_front_of, known_answer_scene
-from test_backward_cpu import _sh_basis
-from test_backward_gpu import weights
+from frame64 import sh_basis, weights
 
 pytestmark = pytest.mark.gpu
 
@@ -208,7 +207,7 @@ def test_known_answer_one_coefficient_per_band(k):
     aos, w, h = known_answer_scene((2.0,))
     aos[0, SH_RGB] = 0.0
     aos[0, 12 + 4 * k:15 + 4 * k] = c
-    basis = _sh_basis(torch.tensor([[0.0, 0.0, 1.0]], dtype=torch.float32))[0].numpy()
+    basis = sh_basis(torch.tensor([[0.0, 0.0, 1.0]], dtype=torch.float32))[0].numpy()
     assert basis.dtype == np.float32 and basis[k] != 0
     for sh_mode, K in ((2, 1), (DEG1, 4), (DEG2, 9), (0, 16)):
         sc = make_scene(aos, w, h, sh_mode=sh_mode)
